@@ -2,7 +2,7 @@
 """Headline benchmark: FM (k=32) training examples/s on the KuaiRec-big-shaped
 synthetic log (BASELINE.json config 3), one process per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 A *step* is one mini-batch pass of the hot path over rows already resident in
 HBM: gather by row id -> forward -> IPS residual -> batch-sum gradients -> SGD
@@ -11,7 +11,9 @@ batches (the reference's resample(..., random_state=epoch)) are produced by the
 exact host sampler before the timed region and uploaded: they are inputs.
 For N > 1 the global batch of N*B rows is sharded over the ranks, gradients are
 exchanged over RCCL and every rank applies the same update (weak scaling: B rows
-per GPU).  Rank 0 prints ONE JSON line.
+per GPU).  Rank 0 prints ONE JSON line.  ``--dump-outputs DIR`` also writes the parameters
+the last timed step left, W + reps x K steps from the seeded initial model (``DIR/w0.npy``,
+``w.npy``, ``V.npy``), for build-to-build comparison.
 
 What the line carries besides the contract's fields:
  * the timed region (exactly K steps between barrier + synchronize) is repeated
@@ -584,10 +586,31 @@ def mf_config(rt, only: str | None = None) -> dict:
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict, limit: int = DUMP_LIMIT_BYTES) -> None:
+    """``--dump-outputs``: each array as ``out_dir/<name>.npy`` in float64.  Inputs are seeded, so
+    two builds run with the same arguments can be compared output for output (the default plan
+    sums the frequent columns with float atomics: runs agree to rounding, not bit for bit).  When
+    the arrays exceed ``limit`` bytes in all, every array keeps the same fixed, seeded sample of
+    its rows (leading axis, ascending order), scaled so that the files stay under the limit."""
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float64) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if total > limit and a.ndim >= 1 and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * 0.95 * limit / total))
+            rows = np.sort(np.random.default_rng(12345).choice(a.shape[0], keep, replace=False))
+            print(f"--dump-outputs: {name} sampled to {keep} of {a.shape[0]} rows (seed 12345)", file=sys.stderr)
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="steps K of each timed region")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=5,
                     help="repetitions of the K-step timed region; the median is reported")
@@ -616,9 +639,17 @@ def main() -> None:
     ap.add_argument("--published-only", default=None, metavar="NAME|all",
                     help="run only extra.published_config (kuairec_fm_ips, coat_fm_ips or all) and print it: "
                          "the command the rocprofv3 profiles of the published operating point are taken from")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the parameters the last timed step left (w0, w, V: "
+                         "what a caller of the step receives) as DIR/<name>.npy, float64; see dump_outputs")
     args = ap.parse_args()
     if args.pmc_child:
         args.no_cpu_baseline = args.no_extra = args.no_pmc = True
+    if args.steps < 1:
+        raise SystemExit(f"--steps {args.steps}: at least one timed step is needed")
+    if args.dump_outputs and (args.mf_only or args.published_only):
+        raise SystemExit("--dump-outputs writes the headline step's outputs; it does not combine with "
+                         "--mf-only / --published-only")
 
     if args.mf_only:
         from relevance_factorizationmachine_amd.runtime import Runtime
@@ -791,6 +822,9 @@ def main() -> None:
         in_sync = bool(torch.equal(lo, hi)) and bool(torch.isfinite(chk).all())
         if not in_sync:
             print(f"[rank {rank}] replicas diverged: {lo.tolist()} vs {hi.tolist()}", file=sys.stderr)
+    if args.dump_outputs and rank == 0:
+        # outside the timed region, before the profiled and extra regions below train further
+        dump_outputs(args.dump_outputs, {"w0": model.w0(), "w": model.w(), "V": model.V()})
 
     out = {
         "metric": "training examples/sec (FM, k=32)",

@@ -215,34 +215,38 @@ def test_csr_cache_fingerprint_follows_in_place_edits():
     assert b != CsrCache._fingerprint(X)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/utils"), reason="the reference tree is only in the build container")
 def test_host_tie_resolution_equals_reference_val_evaluator():
-    """The host half of the device evaluator against the reference's own ValEvaluator
-    (imported from /root/reference, build container only): with 10 % of the scores tied at
-    1.0 -- the case whose ranking NumPy's unstable sort decides -- redoing users with
-    ``ValFrame.host_user_value`` gives the reference's value exactly, the evaluator is
-    recognised, and its frame is not touched."""
-    import sys
-
+    """The host half of the device evaluator against the value the reference's own
+    ValEvaluator returned on fixture G7 (stored by tests/golden/make_golden.py): with 10 % of
+    the scores tied at 1.0 -- the case whose ranking NumPy's unstable sort decides -- redoing
+    users with ``ValFrame.host_user_value`` gives the reference's value exactly, and so does
+    the oracle's restatement of that evaluator; an evaluator under the reference's class and
+    module names is recognised, and its frame is not touched."""
     import pandas as pd
 
+    from oracle import cpu_ref
     from relevance_factorizationmachine_amd import evaluate
 
-    saved = {k: v for k, v in sys.modules.items() if k == "utils" or k.startswith("utils.")}
-    for k in saved:
-        del sys.modules[k]
-    sys.path.insert(0, "/root/reference")
-    try:
-        from utils.evaluate import ValEvaluator
-    finally:
-        sys.path.remove("/root/reference")
-        for k in [m for m in sys.modules if m == "utils" or m.startswith("utils.")]:
-            del sys.modules[k]
-        sys.modules.update(saved)
+    names = ("user", "item", "label", "pscore", "ones_pscore")
+
+    class ValEvaluator:
+        """The reference's ValEvaluator as ``recognise`` sees it (``utils/evaluate.py``:
+        class and module name, constructor arguments), the oracle's restatement as evaluate()."""
+
+        __module__ = "utils.evaluate"
+        __qualname__ = "ValEvaluator"
+
+        def __init__(self, interaction_df, features, k, metric_name):
+            self.interaction_df, self.features, self.k, self.metric_name = interaction_df, features, k, metric_name
+
+        def evaluate(self, y_scores, estimator):
+            frame = {c: self.interaction_df[c].to_numpy() for c in names}
+            return cpu_ref.val_dcg(frame, y_scores, estimator, k=self.k)
 
     g = np.load(os.path.join(os.path.dirname(__file__), "golden", "val_dcg.npz"))
-    cols = {c: g[c] for c in ("user", "item", "label", "pscore", "ones_pscore")}
+    cols = {c: g[c] for c in names}
     ev = ValEvaluator(interaction_df=pd.DataFrame(cols), features={}, k=5, metric_name="DCG")
+    assert evaluate.known_implementation(ev)
     before = ev.interaction_df.copy()
     for est, pcol in (("IPS", "pscore"), ("Naive", "ones_pscore")):
         users, labels, pscores, k = evaluate.recognise(ev, est)
@@ -254,7 +258,7 @@ def test_host_tie_resolution_equals_reference_val_evaluator():
         scratch = np.concatenate([np.zeros(n), counted.astype(np.float64), counted.astype(np.float64)])
         got = frame.resolve(g["scores"], scratch)
         assert got == ev.evaluate(y_scores=g["scores"], estimator=est) == float(g[f"val_dcg_{est}"])
-    pd.testing.assert_frame_equal(ev.interaction_df.drop(columns=["y_score"]), before)
+    pd.testing.assert_frame_equal(ev.interaction_df, before)
 
 
 def test_content_hash_reads_every_byte_and_ignores_the_thread_count():
