@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Timing experiments on the GPU box (not part of the product or the tests).
 
-Runs the FM training step of config 3 under different launch geometries /
-ablation masks, each in a fresh process, and prints per-kernel average times
-(HIP events, rfm_profile_*).  Usage (through gpurun):
-    python profiles/ablate.py [--batch 65536] NAME=ENV1=v,ENV2=v ...
+Runs the FM training step of config 3 under different environments, each in a
+fresh process, and prints per-kernel average times (HIP events, rfm_profile_*).
+Usage (on the GPU box):
+    python profiles/fm_step_timing.py [--batch 65536] NAME=ENV1=v,ENV2=v ...
+    python profiles/fm_step_timing.py --child   # one measurement in this process (profiles/run_pmc.sh)
 """
 import json
 import os
@@ -48,7 +49,7 @@ print(json.dumps({"wall_us": 1e6 * wall, "fwd_us": 1e3 * ms[0] / cnt[0], "cons_u
 
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--child":  # measure in this process (for rocprofv3 -- python3 ...)
-        exec(compile(CHILD % {"root": ROOT}, "ablate_child", "exec"), {"__name__": "__main__"})
+        exec(compile(CHILD % {"root": ROOT}, "fm_step_timing_child", "exec"), {"__name__": "__main__"})
         return
     argv = sys.argv[1:]
     if "--batch" in argv:  # same as ABL_BATCH in the environment

@@ -14,12 +14,12 @@
 //                          combines columns that run over several tasks of the workgroup in
 //                          LDS; trailing workgroups reduce the hot columns' slabs and w0.
 //  (3. fm_finalize_kernel  only for columns longer than a whole workgroup's tasks.)
-// No global float atomics.  Sparse-class sums have a fixed order (bitwise reproducible);
+// The only global float atomics are the no-return f64 adds to w[col] and w0 by the value's only
+// writer of the step.  Sparse-class sums have a fixed order (bitwise reproducible);
 // hot-class sums inside one workgroup are LDS atomics, so their last bits may vary from run
 // to run (hot_min_count < 0 turns the class off).
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <memory>
@@ -30,7 +30,6 @@
 #include "rfm_common.h"
 #include "rfm_fm_kernels.hpp"
 #include "rfm_fm_plan.h"
-#include "rfm_fm_prep.hpp"
 #include "rfm_fm_rows.hpp"
 #include "rfm_fm_sliced.hpp"
 
@@ -40,20 +39,15 @@ namespace rfm {
 
 // forward launch geometry: 1024-thread workgroups whose lane groups keep several
 // rows in flight once the batch fills the chip with them (one per CU: as few
-// hot-sum slabs as possible), 256-thread / one-row ones otherwise.  RFM_FWD_PER_CU
-// overrides the workgroups per CU of the big shape (tuning experiments only).
+// hot-sum slabs as possible), 256-thread / one-row ones otherwise.
 struct FwdGeom {
   int block, grid;
 };
-#ifndef RFM_FWD_SMALL_BLOCK
-#define RFM_FWD_SMALL_BLOCK 256
-#endif
-constexpr int kSmallBlock = RFM_FWD_SMALL_BLOCK;  // threads of the one-row-per-group shape
+constexpr int kSmallBlock = 256;  // threads of the one-row-per-group shape
 constexpr int kMaxDevices = 64;  // devices of one process whose launch attributes are remembered
 
 inline FwdGeom forward_geom(const rfm_ctx* ctx, int64_t n_rows, const Shape& s, bool records) {
-  static const int per_cu = std::max(1, env_int("RFM_FWD_PER_CU", kBigBlock >= 1024 ? 1 : 2));
-  static const int force = env_int("RFM_FWD_BLOCK", 0);
+  constexpr int per_cu = kBigBlock >= 1024 ? 1 : 2;
   FwdGeom g;
   // (the plain forward -- the caller's CSR arrays: predict, validation loss -- takes the same two
   // shapes with its own number of rows per lane group)
@@ -61,7 +55,7 @@ inline FwdGeom forward_geom(const rfm_ctx* ctx, int64_t n_rows, const Shape& s, 
   const int64_t blocks_big = (n_rows + rows_big - 1) / rows_big;
   // (measured on config 3: the many-rows shape wins from about a third of a chip of such
   // workgroups: 16 384 rows 26 vs 30 us, 8 192 rows 21 vs 20 us)
-  if (force != 256 && (force == 512 || blocks_big * 2 >= int64_t(ctx->n_cu) * per_cu)) {
+  if (blocks_big * 2 >= int64_t(ctx->n_cu) * per_cu) {
     g.block = kBigBlock;
     g.grid = int(std::max<int64_t>(1, std::min<int64_t>(blocks_big, int64_t(ctx->n_cu) * per_cu)));
   } else {
@@ -298,15 +292,6 @@ void validate_ids(rfm_ctx* ctx, rfm_fm_plan* plan, const int32_t* d_ids, int64_t
   RFM_REQUIRE(!flags[1], "a row id occurs twice in one batch: the ids of a step must be distinct");
 }
 
-// a prepared step's inputs (rfm_fm_prep.hpp): the batch's row blocks in batch order and the
-// tasks' records of this iteration
-struct PrepView {
-  const Entry* E;
-  const double2* YP;
-  const PrepRec* rec;
-  const int32_t* cnt;
-};
-
 // the three launches of one step; grad == nullptr -> update in place
 // rows of the plan's log that a step's forward launch scores on the side (fm_forward_kernel, XTRA)
 struct XtraRows {
@@ -329,7 +314,7 @@ void enqueue_step(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr,
                   const int32_t* d_indices, const double* d_values, const double* d_y,
                   const double* d_pscore, const int32_t* d_row_ids, int64_t batch, double* d_w0,
                   double* d_w, double* d_V, double lr, double* d_grad, int32_t* d_touch = nullptr,
-                  int32_t touch_id = 0, const PrepView* prep = nullptr, const XtraRows* xtra = nullptr) {
+                  int32_t touch_id = 0, const XtraRows* xtra = nullptr) {
   const int k = plan->k;
   const Shape s = shape_for(k);
   (void)d_indptr;
@@ -349,7 +334,6 @@ void enqueue_step(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr,
   f.w = d_w;
   f.V = d_V;
   f.k = k;
-  f.out_err = plan->err.as<double>();
   f.out_Q = plan->Q.as<double>();
   f.slot_mark = plan->slot_t.as<SlotMark>();
   // more than one chunk per lane: the slot bitmap alternates between two buffers by step
@@ -360,29 +344,15 @@ void enqueue_step(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr,
   unsigned long long* bits_other =
       plan->slot_bits.as<unsigned long long>() + (1 - parity) * plan->bits_words;
   f.slot_bits = bits;
-  if (prep) {  // nothing to mark ...
-    f.slot_mark = nullptr;
-    f.slot_bits = nullptr;
-    if (prep->E) {  // ... and the rows at their batch position
-      f.ent = nullptr;
-      f.rows = nullptr;
-      f.ell = reinterpret_cast<const char*>(prep->E);
-      f.ell_yp = prep->YP;
-      f.row_ids = nullptr;
-    }
-  }
   f.n_hot = plan->n_hot;
   f.hot_rounds = plan->hot_rounds;
   f.hot_fixed = plan->hot_fixed ? 1 : 0;
   f.hot_slab = plan->hot_slab.as<double>();
   f.err_partial = plan->err_partial.as<double>();
-#ifdef RFM_ABLATE
-  f.ablate = env_int("RFM_ABLATE_MASK", 0);
-#endif
   const FwdGeom geom = forward_geom(ctx, batch, s, true);  // (the step's own workgroups: geom.grid slabs)
   FwdGeom launch = geom;
   if (xtra && xtra->n > 0) {
-    RFM_REQUIRE(geom.block == kSmallBlock && !(f.hot_fixed && f.n_hot > 0) && !(prep && prep->E),
+    RFM_REQUIRE(geom.block == kSmallBlock && !(f.hot_fixed && f.n_hot > 0),
                 "this step cannot score extra rows");
     const FwdGeom gx = forward_geom(ctx, xtra->n, s, true);
     RFM_REQUIRE(gx.block == kSmallBlock, "extra rows: unexpected geometry");
@@ -402,49 +372,9 @@ void enqueue_step(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr,
       launch.grid += gy.grid;
     }
   }
-#ifdef RFM_FWD_STAMPS
-  // timing builds: clock readings of the many-rows forward, printed for the 60th step of the plan
-  static DevBuf fwd_stamps;
-  const size_t stamp_count = size_t(launch.grid) * (launch.block / kWave) * 2 * 8;
-  if (env_int("RFM_FWD_STAMPS", 0)) {
-    fwd_stamps.ensure(stamp_count * 8);
-    RFM_HIP_CHECK(hipMemsetAsync(fwd_stamps.p, 0, stamp_count * 8, ctx->stream));
-    f.stamps = static_cast<long long*>(fwd_stamps.p);
-  }
-#endif
   ctx->prof_mark();
-#ifdef RFM_ABLATE
-  if (!(f.ablate & 64))
-#endif
-    launch_forward(ctx, f, launch);
+  launch_forward(ctx, f, launch);
   ctx->prof_mark();
-#ifdef RFM_FWD_STAMPS
-  if (f.stamps && plan->step == 59) {
-    std::vector<long long> h(stamp_count);
-    RFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    RFM_HIP_CHECK(hipMemcpy(h.data(), fwd_stamps.p, stamp_count * 8, hipMemcpyDeviceToHost));
-    const int waves = launch.block / kWave;
-    for (int wv : {0, waves / 2, waves - 1}) {
-      double d[2][8] = {{0}}, n = 0;
-      for (int b = 0; b < launch.grid; ++b) {
-        const long long* t0 = &h[((size_t(b) * waves + wv) * 2 + 0) * 8];
-        const long long* t1 = t0 + 8;
-        if (!t0[0] || !t1[6]) continue;
-        for (int i = 0; i < 8; ++i) {
-          d[0][i] += t0[i] ? double(t0[i] - t0[0]) : 0.0;
-          d[1][i] += t1[i] ? double(t1[i] - t0[0]) : 0.0;
-        }
-        n += 1;
-      }
-      if (n > 0)
-        fprintf(stderr, "[forward stamps] wave %2d over %.0f workgroups, clocks since entry -- trip 0: rows in %.0f, gathers summed %.0f, "
-                        "scores out %.0f, marks + hot adds %.0f | trip 1: start %.0f, rows in %.0f, gathers %.0f, scores %.0f, hot %.0f | "
-                        "trips done %.0f, end %.0f\n",
-                wv, n, d[0][1] / n, d[0][2] / n, d[0][3] / n, d[0][4] / n, d[1][0] / n, d[1][1] / n, d[1][2] / n, d[1][3] / n,
-                d[1][4] / n, d[1][5] / n, d[1][6] / n);
-    }
-  }
-#endif
 
   if (d_grad && !d_touch) {  // dense gradient: every element is written
     const size_t bytes = (size_t(plan->n_features) * (k + 1) + 1) * sizeof(double);
@@ -477,106 +407,32 @@ void enqueue_step(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr,
     c.hot_slab = plan->hot_slab.as<double>();
     c.n_slabs = geom.grid;
     c.err_partial = plan->err_partial.as<double>();
-    if (prep) {
-      c.prep_rec = prep->rec;
-      c.prep_cnt = prep->cnt;
-      c.err = plan->err.as<double>();
-    }
     const int grid = c.nb_tasks + c.n_hot + 1;  // tasks, then the hot columns, then w0
-#ifdef RFM_CONS_STAMPS
-    static DevBuf cons_stamps;
-    const size_t cstamp_count = size_t(grid) * 8 * (kBlock / kWave) * 8;  // (x chunks at most 8)
-    if (env_int("RFM_CONS_STAMPS", 0)) {
-      cons_stamps.ensure(cstamp_count * 8);
-      RFM_HIP_CHECK(hipMemsetAsync(cons_stamps.p, 0, cstamp_count * 8, ctx->stream));
-      c.stamps = static_cast<long long*>(cons_stamps.p);
-    }
-#endif
     // LDS: the groups' lists + parked records + head rows, or the hot workgroups' scratch
     const int gpb = kBlock / s.lpr;
     const int win = s.lpr >= 32 ? 64 : 4 * s.lpr;  // WinShape<LPR>::WIN
     const size_t lds = std::max<size_t>(size_t(gpb) * size_t(win) * (sizeof(WinRec) + 8) +
                                             size_t(gpb) * size_t(k + 3) * 8,
                                         size_t(kBlock + 1024 + 2) * 8);
-#ifdef RFM_ABLATE
-    if (!(f.ablate & 128))
-#endif
-    {
-      if (chunked) {
-        // one workgroup per (four tasks, chunk of 64 lanes x vec factors)
-        const int n_chunks = ((k + s.vec - 1) / s.vec + 63) / 64;
-        c.n_chunks = n_chunks;
-        // chunks dealt to XCDs (see the kernel): every chunk gets at least 8 / n_chunks XCDs
-        static const bool xcd_on = env_int("RFM_XCD_CHUNKS", 1) != 0;
-        c.xcd_chunks = xcd_on && n_chunks <= 8 ? 1 : 0;
-        const int per_chunk = 8 / n_chunks;  // (the fewest XCDs a chunk gets)
-        const dim3 g2 = c.xcd_chunks ? dim3(8 * ((grid + per_chunk - 1) / per_chunk)) : dim3(grid, n_chunks);
-        if (s.vec == 2 && prep)
-          hipLaunchKernelGGL((fm_consume_kernel<64, 2, 1, true, true>), g2, dim3(kBlock), lds, ctx->stream, c);
-        else if (s.vec == 2)
-          hipLaunchKernelGGL((fm_consume_kernel<64, 2, 1, true, false>), g2, dim3(kBlock), lds, ctx->stream, c);
-        else if (prep)
-          hipLaunchKernelGGL((fm_consume_kernel<64, 1, 1, true, true>), g2, dim3(kBlock), lds, ctx->stream, c);
-        else
-          hipLaunchKernelGGL((fm_consume_kernel<64, 1, 1, true, false>), g2, dim3(kBlock), lds, ctx->stream, c);
-      } else if (prep) {
-#define RFM_CALL_CONS(L, Vv, N)                                                                      \
-  hipLaunchKernelGGL((fm_consume_kernel<L, Vv, N, false, true>), dim3(grid), dim3(kBlock), lds, \
-                     ctx->stream, c)
-        RFM_FOR_SINGLE_CHUNK_SHAPE(s, RFM_CALL_CONS);
-#undef RFM_CALL_CONS
-      } else {
+    if (chunked) {
+      // one workgroup per (four tasks, chunk of 64 lanes x vec factors)
+      const int n_chunks = ((k + s.vec - 1) / s.vec + 63) / 64;
+      c.n_chunks = n_chunks;
+      // chunks dealt to XCDs (see the kernel): every chunk gets at least 8 / n_chunks XCDs
+      c.xcd_chunks = n_chunks <= 8 ? 1 : 0;
+      const int per_chunk = 8 / n_chunks;  // (the fewest XCDs a chunk gets)
+      const dim3 g2 = c.xcd_chunks ? dim3(8 * ((grid + per_chunk - 1) / per_chunk)) : dim3(grid, n_chunks);
+      if (s.vec == 2)
+        hipLaunchKernelGGL((fm_consume_kernel<64, 2, 1, true>), g2, dim3(kBlock), lds, ctx->stream, c);
+      else
+        hipLaunchKernelGGL((fm_consume_kernel<64, 1, 1, true>), g2, dim3(kBlock), lds, ctx->stream, c);
+    } else {
 #define RFM_CALL_CONS(L, Vv, N) \
   hipLaunchKernelGGL((fm_consume_kernel<L, Vv, N>), dim3(grid), dim3(kBlock), lds, ctx->stream, c)
-        RFM_FOR_SINGLE_CHUNK_SHAPE(s, RFM_CALL_CONS);
+      RFM_FOR_SINGLE_CHUNK_SHAPE(s, RFM_CALL_CONS);
 #undef RFM_CALL_CONS
-      }
-      RFM_HIP_CHECK(hipGetLastError());
     }
-#ifdef RFM_CONS_STAMPS
-    if (c.stamps && plan->step == 60) {  // timing builds: the task workgroups' clock readings of the 60th step
-      std::vector<long long> h(cstamp_count);
-      RFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-      RFM_HIP_CHECK(hipMemcpy(h.data(), cons_stamps.p, cstamp_count * 8, hipMemcpyDeviceToHost));
-      const int waves = kBlock / kWave;
-      double d[8] = {0}, n = 0, life_max = 0;
-      long long t_first = 0, t_last = 0;
-      for (size_t b = 0; b < cstamp_count / 8 / waves; ++b) {
-        for (int wv = 0; wv < waves; ++wv) {
-          const long long* t = &h[(b * waves + wv) * 8];
-          if (!t[0] || !t[4]) continue;
-          for (int i = 1; i < 5; ++i) d[i] += double(t[i] - t[0]);
-          life_max = std::max(life_max, double(t[4] - t[0]));
-          t_first = t_first ? std::min(t_first, t[0]) : t[0];
-          t_last = std::max(t_last, t[4]);
-          n += 1;
-        }
-      }
-      if (n > 0)
-        fprintf(stderr, "[consume stamps] %.0f task wavefronts, clocks since their entry: slots listed %.0f, chain run %.0f, "
-                        "barrier %.0f, combined %.0f (longest life %.0f)\n",
-                n, d[1] / n, d[2] / n, d[3] / n, d[4] / n, life_max);
-      (void)t_first;
-      (void)t_last;
-      // ... and of the wavefronts that live longer than 0.7 of the longest: which workgroups, which phase
-      double e[8] = {0}, m = 0, bsum = 0, bmin = 1e18, bmax = 0;
-      for (size_t b = 0; b < cstamp_count / 8 / waves; ++b) {
-        for (int wv = 0; wv < waves; ++wv) {
-          const long long* t = &h[(b * waves + wv) * 8];
-          if (!t[0] || !t[4] || double(t[4] - t[0]) < 0.7 * life_max) continue;
-          for (int i = 1; i < 5; ++i) e[i] += double(t[i] - t[0]);
-          bsum += double(b);
-          bmin = std::min(bmin, double(b));
-          bmax = std::max(bmax, double(b));
-          m += 1;
-        }
-      }
-      if (m > 0)
-        fprintf(stderr, "[consume stamps]   the %.0f longest-lived: listed %.0f, chain run %.0f, barrier %.0f, combined %.0f; "
-                        "workgroups %.0f .. %.0f (mean %.0f) of %d\n",
-                m, e[1] / m, e[2] / m, e[3] / m, e[4] / m, bmin, bmax, bsum / m, grid);
-    }
-#endif
+    RFM_HIP_CHECK(hipGetLastError());
   }
   ctx->prof_mark();
   // columns cut into several tasks (none on most plans): their partial rows
@@ -598,9 +454,6 @@ void enqueue_step(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr,
     const int gpb = kBlock / s.lpr;
     const int nb_short = (plan->n_split_short + gpb - 1) / gpb;
     const int grid = nb_short + plan->n_split_long;
-#ifdef RFM_ABLATE
-    if (f.ablate & 256) return;
-#endif
     if (chunked) {
       const dim3 g2(grid, ((k + s.vec - 1) / s.vec + 63) / 64);
       if (s.vec == 2)
@@ -619,161 +472,6 @@ void enqueue_step(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr,
   ctx->prof_mark();
 }
 
-// The prepared steps of one rfm_fm_train call: chunks of plan->prep_iters iterations, two
-// chunk buffers alive (the chunk being trained on, the next one already laid out).
-struct PrepRun {
-  rfm_ctx* ctx;
-  rfm_fm_plan* plan;
-  const int32_t* d_ids;
-  int64_t batch, n_iters;
-  int per_chunk = 0, n_chunks = 0;
-  bool on = false, records_only = false;
-
-  PrepRun(rfm_ctx* c, rfm_fm_plan* p, const int32_t* ids, int64_t b, int64_t n, bool allowed)
-      : ctx(c), plan(p), d_ids(ids), batch(b), n_iters(n) {
-    // (a short call -- an evaluator between iterations -- would pay the three launches of a
-    // chunk for a handful of steps)
-    records_only = plan->prep_records_only;
-    on = allowed && plan->prep_ok && n_iters >= 8 && (records_only ? plan->rows.p != nullptr : plan->ell.p != nullptr);
-    if (!on) return;
-    per_chunk = plan->prep_iters;
-    n_chunks = int((n_iters + per_chunk - 1) / per_chunk);
-    enqueue(0);
-    if (n_chunks > 1) enqueue(1);
-  }
-
-  void enqueue(int c) {
-    auto& ch = plan->prep[c % 2];
-    const size_t cap_it = size_t(plan->prep_iters), nt = size_t(plan->n_tasks), mb = size_t(plan->max_batch);
-    if (!ch.tmp.p) {
-      if (!records_only) {
-        ch.E.alloc(cap_it * mb * size_t(plan->ell_stride));
-        ch.YP.alloc(cap_it * mb * 16);
-      }
-      ch.tmp.alloc(cap_it * nt * kPrepCap * sizeof(PrepTmp));
-      ch.rec.alloc(cap_it * nt * kPrepCap * sizeof(PrepRec));
-      ch.cnt.alloc(cap_it * nt * 4);
-      ch.flags.alloc(cap_it * 4);
-      RFM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&ch.h_flags), cap_it * 4, hipHostMallocDefault));
-      RFM_HIP_CHECK(hipEventCreateWithFlags(&ch.ready, hipEventDisableTiming));
-    }
-    const int64_t first = int64_t(c) * per_chunk;
-    const int n_it = int(std::min<int64_t>(per_chunk, n_iters - first));
-    hipStream_t st = ctx->stream;
-    RFM_HIP_CHECK(hipMemsetAsync(ch.cnt.p, 0, size_t(n_it) * nt * 4, st));
-    RFM_HIP_CHECK(hipMemsetAsync(ch.flags.p, 0, size_t(n_it) * 4, st));
-    const Shape s = shape_for(plan->k);
-    if (records_only) {
-      const int64_t waves = int64_t(n_it) * batch;
-      const int grid_a = int(std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, int64_t(ctx->n_cu) * 32)));
-      hipLaunchKernelGGL(fm_prep_bucket_kernel, dim3(grid_a), dim3(kBlock), 0, st, plan->rows.as<RowRec>(),
-                         plan->ent.as<Entry>(), d_ids + first * batch, batch, batch, n_it,
-                         int32_t(plan->task_words * 64), plan->n_tasks, ch.tmp.as<PrepTmp>(),
-                         ch.cnt.as<int32_t>());
-    } else {
-      const int64_t items = int64_t(n_it) * batch * s.lpr;
-      const int grid_a = int(std::max<int64_t>(1, std::min<int64_t>((items + kBlock - 1) / kBlock, int64_t(ctx->n_cu) * 32)));
-      hipLaunchKernelGGL(fm_prep_gather_kernel, dim3(grid_a), dim3(kBlock), 0, st, plan->ell.as<char>(),
-                         plan->ell_stride, plan->ell_yp.as<double2>(), s.lpr, d_ids + first * batch, batch,
-                         batch, n_it, int32_t(plan->task_words * 64), plan->n_tasks, ch.E.as<Entry>(),
-                         ch.YP.as<double2>(), ch.tmp.as<PrepTmp>(), ch.cnt.as<int32_t>());
-    }
-    const int64_t buckets = int64_t(n_it) * plan->n_tasks;
-    const int grid_b = int(std::max<int64_t>(1, std::min<int64_t>((buckets + 15) / 16, int64_t(ctx->n_cu) * 32)));
-    hipLaunchKernelGGL(fm_prep_sort_kernel, dim3(grid_b), dim3(kBlock), 0, st, ch.tmp.as<PrepTmp>(),
-                       ch.cnt.as<int32_t>(), plan->slots.as<SlotRec>(), plan->n_tasks, n_it,
-                       ch.rec.as<PrepRec>(), ch.flags.as<int32_t>());
-    RFM_HIP_CHECK(hipGetLastError());
-    RFM_HIP_CHECK(hipMemcpyAsync(ch.h_flags, ch.flags.p, size_t(n_it) * 4, hipMemcpyDeviceToHost, st));
-    RFM_HIP_CHECK(hipEventRecord(ch.ready, st));
-  }
-
-  // the view of iteration `it`, or false when the iteration is not prepared (a task with more
-  // than kPrepCap marks: it takes the bitmap path)
-  bool view(int64_t it, PrepView& v) {
-    if (!on) return false;
-    const int c = int(it / per_chunk), j = int(it % per_chunk);
-    auto& ch = plan->prep[c % 2];
-    if (j == 0) RFM_HIP_CHECK(hipEventSynchronize(ch.ready));  // its flags are on the host
-    if (ch.h_flags[j]) return false;
-    const size_t nt = size_t(plan->n_tasks);
-    v.E = records_only ? nullptr
-                       : reinterpret_cast<const Entry*>(ch.E.as<char>() + size_t(j) * size_t(batch) * size_t(plan->ell_stride));
-    v.YP = records_only ? nullptr : ch.YP.as<double2>() + size_t(j) * size_t(batch);
-    v.rec = ch.rec.as<PrepRec>() + size_t(j) * nt * kPrepCap;
-    v.cnt = ch.cnt.as<int32_t>() + size_t(j) * nt;
-    return true;
-  }
-
-  // after the last step of chunk c has been enqueued: its buffer is free for chunk c + 2
-  void done(int64_t it) {
-    if (!on) return;
-    const int c = int(it / per_chunk);
-    if ((it + 1) % per_chunk == 0 && c + 2 < n_chunks) enqueue(c + 2);
-  }
-};
-
-// Timing experiment (RFM_TRAIN_GRAPH): everything enqueued on the context's stream while this
-// object lives is captured into one hipGraph on a stream of its own (the legacy default stream
-// cannot be captured) and run by replay().  Whatever happens in between -- an RFM_REQUIRE, a HIP
-// error -- the destructor ends the capture, restores ctx->stream and frees the stream.
-struct GraphCapture {
-  rfm_ctx* ctx;
-  hipStream_t user_stream = nullptr, cap_stream = nullptr;
-  bool capturing = false;
-  GraphCapture(rfm_ctx* c, bool on) : ctx(c) {
-    if (!on) return;
-    user_stream = ctx->stream;
-    RFM_HIP_CHECK(hipStreamSynchronize(user_stream));
-    RFM_HIP_CHECK(hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking));
-    if (hipStreamBeginCapture(cap_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-      (void)hipStreamDestroy(cap_stream);
-      cap_stream = nullptr;
-      fail(RFM_ERR_HIP, "hipStreamBeginCapture failed");
-    }
-    ctx->stream = cap_stream;
-    capturing = true;
-  }
-  GraphCapture(const GraphCapture&) = delete;
-  GraphCapture& operator=(const GraphCapture&) = delete;
-  hipGraph_t end() {
-    hipGraph_t graph = nullptr;
-    if (capturing) {
-      capturing = false;
-      ctx->stream = user_stream;
-      if (hipStreamEndCapture(cap_stream, &graph) != hipSuccess) graph = nullptr;
-    }
-    return graph;
-  }
-  void replay(int64_t n_iters) {
-    if (!cap_stream) return;
-    hipGraph_t graph = end();
-    RFM_REQUIRE(graph, "hipStreamEndCapture failed");
-    hipGraphExec_t exec = nullptr;
-    const hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    if (e != hipSuccess) {
-      (void)hipGraphDestroy(graph);
-      fail(RFM_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(e));
-    }
-    const bool timed = env_int("RFM_TRAIN_GRAPH", 0) > 1;
-    const auto t0 = std::chrono::steady_clock::now();
-    hipError_t run = hipGraphLaunch(exec, cap_stream);
-    if (run == hipSuccess) run = hipStreamSynchronize(cap_stream);
-    if (timed && run == hipSuccess)
-      fprintf(stderr, "[rfm] graph of %lld iterations: %.2f us per iteration (launch to drain)\n",
-              (long long)n_iters,
-              std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() /
-                  double(std::max<int64_t>(n_iters, 1)));
-    (void)hipGraphExecDestroy(exec);
-    (void)hipGraphDestroy(graph);
-    RFM_HIP_CHECK(run);
-  }
-  ~GraphCapture() {
-    if (hipGraph_t graph = end()) (void)hipGraphDestroy(graph);
-    if (cap_stream) (void)hipStreamDestroy(cap_stream);
-  }
-};
-
 FwdArgs forward_args(const int64_t* d_indptr, const int32_t* d_indices, const double* d_values,
                      const int32_t* d_row_ids, int64_t n_rows, const double* d_w0,
                      const double* d_w, const double* d_V, int32_t k) {
@@ -787,9 +485,6 @@ FwdArgs forward_args(const int64_t* d_indptr, const int32_t* d_indices, const do
   f.w = d_w;
   f.V = d_V;
   f.k = k;
-#ifdef RFM_ABLATE
-  f.ablate = env_int("RFM_ABLATE_MASK", 0);  // (timing experiments: bit 4 = every gather reads row 0 of V)
-#endif
   return f;
 }
 
@@ -1168,11 +863,6 @@ void train_loop(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr, const 
     // iterations are then computed together (rfm_fm_sliced.hpp)
     const int64_t sl_a = d_out_train_loss ? batch : 0, sl_b = d_out_val_loss ? n_val : 0;
     const SlicedGeom sliced = sliced_geom(ctx, plan, sl_a + sl_b);
-    // RFM_TRAIN_GRAPH=1 (timing experiment): the run's launches captured into one hipGraph
-    // and replayed once (GraphCapture restores the context's stream on every way out)
-    static const bool as_graph = env_int("RFM_TRAIN_GRAPH", 0) != 0;
-    // (prepared steps wait for an event on the host at every chunk: not inside a capture)
-    PrepRun prepared(ctx, plan, d_ids, batch, n_iters, !as_graph);
     // one decision for the whole call (the partials of a run are finished together).  Only for
     // factor counts of several chunks per lane: there it saves a launch (k = 400, B = 2 000:
     // 0.098 -> 0.090 ms per iteration of fit()); at one chunk per lane the batch's rows are
@@ -1180,7 +870,7 @@ void train_loop(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr, const 
     // 104.7 vs 111.6 us per iteration at B = 65 536).  RFM_MERGE_LOSS=0 / 2: never / always.
     const int merge_mode = env_int("RFM_MERGE_LOSS", 1);
     const bool merge_call = !sliced.ok && merge_mode != 0 && (merge_mode == 2 || shape_for(plan->k).nc > 1) &&
-                            d_out_train_loss && d_out_val_loss && (!prepared.on || prepared.records_only) &&
+                            d_out_train_loss && d_out_val_loss &&
                             forward_geom(ctx, batch + n_val, shape_for(plan->k), false).block == kBigBlock;
     // The plain loss forwards (neither sliced nor merged) leave their rows' SCORES and take no
     // logarithms: the two logs of a row's term are ~200 dependent f64 instructions, and a whole
@@ -1205,13 +895,6 @@ void train_loop(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr, const 
         sliced_translate(ctx, plan, d_val_indptr, d_val_indices, d_val_values, sl_b, plan->sl_log[0].tr);
       }
     }
-#ifdef RFM_SLICED_STAMPS
-    DevBuf stamps;
-    if (sliced.ok && env_int("RFM_SLICED_STAMPS", 0)) {
-      stamps.alloc(size_t(sliced.grid) * kSlWaves * 8 * 8);
-      RFM_HIP_CHECK(hipMemsetAsync(stamps.p, 0, stamps.bytes, ctx->stream));
-    }
-#endif
     const auto finish = [&](int64_t first, int64_t count) {
       if (count <= 0) return;
       if (deferred) {
@@ -1240,13 +923,12 @@ void train_loop(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr, const 
                            val_rows, int64_t(kMaxFwdGrid), val_parts, n_val, d_out_val_loss + first);
       RFM_HIP_CHECK(hipGetLastError());
     };
-    GraphCapture capture(ctx, as_graph && !ctx->profiling);
     // Small batches: the train-loss forward of iteration it - 1 reads the parameters that step
     // it's forward reads -- it RIDES in that launch (extra workgroups that only score the previous
     // batch's rows; fm_forward_kernel's XTRA form), and only the last iteration's is a launch of
     // its own.  A run's logarithms then wait for the next step's launch.  (RFM_RIDE_LOSS=0: never.)
     const bool ride = scores_only && d_out_train_loss && step_takes_extra_rows(ctx, plan, batch) &&
-                      !(prepared.on && !prepared.records_only) && env_int("RFM_RIDE_LOSS", 1) != 0;
+                      env_int("RFM_RIDE_LOSS", 1) != 0;
     // ... and so may the validation rows (the same parameters again), when the caller has registered
     // the log (rfm_fm_plan_register_log keeps it as records), it takes the one-row shape too, and the
     // plan holds plain records (RFM_RIDE_VAL=0: never)
@@ -1259,8 +941,6 @@ void train_loop(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr, const 
     for (int64_t it = 0; it < n_iters; ++it) {
       const int32_t* ids = d_ids + it * batch;
       const int64_t slot = it - run_first;
-      PrepView pv{};
-      const bool is_prepared = prepared.view(it, pv);
       XtraRows prev{};
       if (ride && it > 0) {
         const int64_t prev_slot = pending_count > 0 ? pending_count - 1 : slot - 1;
@@ -1271,8 +951,7 @@ void train_loop(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr, const 
                           n_val, zs + sl_a};
       }
       enqueue_step(ctx, plan, d_indptr, d_indices, d_values, d_y, d_pscore, ids, batch, d_w0,
-                   d_w, d_V, lr, nullptr, nullptr, 0, is_prepared ? &pv : nullptr,
-                   prev.n > 0 ? &prev : nullptr);
+                   d_w, d_V, lr, nullptr, nullptr, 0, prev.n > 0 ? &prev : nullptr);
       if (pending_count > 0) {  // (before this iteration's forwards reuse the run's first slots)
         finish(pending_first, pending_count);
         pending_count = 0;
@@ -1298,9 +977,6 @@ void train_loop(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr, const 
         f.w = d_w;
         f.V = d_V;
         f.zpart = plan->sl_z.as<double>() + slot * z_per_iter;
-#ifdef RFM_SLICED_STAMPS
-        f.stamps = static_cast<long long*>(stamps.p);
-#endif
         launch_sliced(ctx, plan, sliced, f);
         merged = true;
       } else if (merge_call) {
@@ -1325,11 +1001,10 @@ void train_loop(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr, const 
         FwdArgs f{};
         f.ent = plan->ent.as<Entry>();
         f.rows = plan->rows.as<RowRec>();
-        const bool rows_prepared = is_prepared && pv.E != nullptr;
-        f.ell = rows_prepared ? reinterpret_cast<const char*>(pv.E) : plan->ell.as<char>();
+        f.ell = plan->ell.as<char>();
         f.ell_stride = plan->ell_stride;
-        f.ell_yp = rows_prepared ? pv.YP : plan->ell_yp.as<double2>();
-        f.row_ids = rows_prepared ? nullptr : ids;
+        f.ell_yp = plan->ell_yp.as<double2>();
+        f.row_ids = ids;
         f.n_rows = batch;
         f.w0 = d_w0;
         f.w = d_w;
@@ -1374,28 +1049,8 @@ void train_loop(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr, const 
         }
         run_first = it + 1;
       }
-      prepared.done(it);
     }
     finish(run_first, n_iters - run_first);
-    capture.replay(n_iters);
-#ifdef RFM_SLICED_STAMPS
-    if (sliced.ok && stamps.p) {  // the LAST iteration's clock readings, averaged over the workgroups
-      std::vector<long long> h(size_t(sliced.grid) * kSlWaves * 8);
-      RFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-      RFM_HIP_CHECK(hipMemcpy(h.data(), stamps.p, h.size() * 8, hipMemcpyDeviceToHost));
-      for (int wv : {0, kSlWaves - 1}) {
-        double d[7] = {0}, n = 0;
-        for (int b = 0; b < sliced.grid; ++b) {
-          const long long* t = &h[(size_t(b) * kSlWaves + wv) * 8];
-          if (!t[0] || !t[6]) continue;
-          for (int i = 1; i < 7; ++i) d[i] += double(t[i] - t[0]);
-          n += 1;
-        }
-        fprintf(stderr, "[sliced stamps] wave %d over %.0f workgroups (clocks since entry): fill issued+summed %.0f, barrier %.0f, prologue %.0f, row 1 %.0f, row 8 %.0f, end %.0f\n",
-                wv, n, d[1] / n, d[2] / n, d[3] / n, d[4] / n, d[5] / n, d[6] / n);
-      }
-    }
-#endif
   }
 }
 

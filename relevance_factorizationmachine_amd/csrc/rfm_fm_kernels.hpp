@@ -37,43 +37,26 @@ __device__ inline double logloss_term(double y, double p, double pred, double ep
   return r * log(pred + eps) + (1.0 - r) * log(1.0 - pred + eps);
 }
 
+constexpr int kBigBlock = 1024;  // threads of the forward's many-rows-in-flight shape
 // waves per SIMD the big forward shape is compiled for (register budget 512/N)
-#ifndef RFM_FWD_BIG_BLOCK
-#define RFM_FWD_BIG_BLOCK 1024
-#endif
-constexpr int kBigBlock = RFM_FWD_BIG_BLOCK;  // threads of the forward's many-rows-in-flight shape
-#ifndef RFM_FWD_BIG_WAVES
-#define RFM_FWD_BIG_WAVES 4
-#endif
+constexpr int kBigWaves = 4;
 // rows per lane group of the big forward shape (single-chunk factor counts)
-#ifndef RFM_FWD_ROWS
-#define RFM_FWD_ROWS 2
-#endif
+constexpr int kFwdRows = 2;
 
 // entries of a row whose V gathers the one-row forward shape keeps in flight
-#ifndef RFM_FWD_BIG_UNROLL
-#define RFM_FWD_BIG_UNROLL 3
-#endif
-#ifndef RFM_FWD_SMALL_UNROLL
-#define RFM_FWD_SMALL_UNROLL 8
-#endif
+constexpr int kBigUnroll = 3;
+constexpr int kSmallUnroll = 8;
 // ... of the one-row shape at two to four chunks of factors per lane (k = 300 / 400: an entry is
 // NC gathers per lane; the shape runs about two waves per SIMD, so registers are not the limit)
-#ifndef RFM_FWD_SMALL_WIDE_UNROLL
-#define RFM_FWD_SMALL_WIDE_UNROLL 2
-#endif
+constexpr int kSmallWideUnroll = 2;
 
 // rows a lane group works on concurrently (independent load chains in flight)
-constexpr int rows_in_flight(int nc) { return nc == 1 ? RFM_FWD_ROWS : 1; }
+constexpr int rows_in_flight(int nc) { return nc == 1 ? kFwdRows : 1; }
 // ... of the PLAIN forward (the caller's CSR arrays: predict, validation loss), which keeps no Q
-// row, leaves no marks and sums no hot class, so its registers hold more rows
-#ifndef RFM_FWD_ROWS_PLAIN
-#define RFM_FWD_ROWS_PLAIN RFM_FWD_ROWS
-#endif
-#ifndef RFM_FWD_PLAIN_UNROLL
-#define RFM_FWD_PLAIN_UNROLL RFM_FWD_BIG_UNROLL
-#endif
-constexpr int rows_in_flight_plain(int nc) { return nc == 1 ? RFM_FWD_ROWS_PLAIN : 1; }
+// row, leaves no marks and sums no hot class
+constexpr int kFwdRowsPlain = kFwdRows;
+constexpr int kPlainUnroll = kBigUnroll;
+constexpr int rows_in_flight_plain(int nc) { return nc == 1 ? kFwdRowsPlain : 1; }
 
 // Hot-class sums in a fixed order (training forward): the rows a workgroup holds in one trip
 // leave their Q rows and per-entry coefficients in LDS, every hot column gets the set of those
@@ -83,9 +66,7 @@ constexpr int rows_in_flight_plain(int nc) { return nc == 1 ? RFM_FWD_ROWS_PLAIN
 constexpr bool hot_fixed_order(int lpr, int nc, int block, int rows) {
   return nc == 1 && (block / lpr) * rows <= 128;
 }
-#ifndef RFM_HOT_U
-#define RFM_HOT_U 2
-#endif
+constexpr int kHotUnroll = 2;  // rows of a fixed-order hot sum whose LDS reads are in flight together
 constexpr int kHotPosPad = 4;  // bytes between the position rows of two columns (bank spread)
 // LDS bytes of the forward kernel (what a launch asks for)
 inline size_t forward_lds_bytes(int block, int lpr, int vec, int nc, int rows, int n_hot, int k,
@@ -149,7 +130,6 @@ struct FwdArgs {
   double* err_partial;   // nullable: [gridDim.x] per-workgroup sums of the residual (for w0)
   double* loss_partial;  // nullable: [gridDim.x]
   double eps;
-  int32_t ablate;  // -DRFM_ABLATE builds only: bit mask of parts to skip (timing experiments)
   // XTRA form (with REC, one-row shape): workgroups grid_main .. gridDim.x - 1 only SCORE the rows
   // row_ids_x[0 .. n_rows_x) of the same plan (-> out_pred_x) -- no Q rows, marks, hot sums or
   // residuals: the train-loss forward of the previous batch, which reads the same parameters as
@@ -165,18 +145,7 @@ struct FwdArgs {
   const Entry* ent_y;
   int64_t n_rows_y;
   double* out_pred_y;
-#ifdef RFM_FWD_STAMPS
-  long long* stamps;  // -DRFM_FWD_STAMPS builds only: [workgroup][wave][trip 0/1][8] clock readings
-#endif
 };
-
-#ifdef RFM_ABLATE
-#define RFM_KEEP(a, bit) (((a).ablate & (bit)) == 0)
-#else
-#define RFM_KEEP(a, bit) true
-#endif
-// bits: 1 slot marks, 2 Q store, 4 V gathers, 8 hot LDS adds, 16 slab store, 32 hot pass,
-// 512 no adds of the five most frequent columns after a workgroup's first trip
 
 // A row is handled by LPR consecutive lanes; lane l holds factors
 // (c*LPR + l)*VEC .. +VEC-1 for c < NC.  k=32 -> LPR=16, VEC=2: one 16-byte
@@ -199,7 +168,7 @@ struct FwdArgs {
 // SEG (without REC, many-rows shape): two logs in one launch, see FwdArgs.
 template <int LPR, int VEC, int NC, int BLOCK, int R, bool REC, bool ELL = false, bool DET = false,
           bool SEG = false, bool XTRA = false>
-__global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? RFM_FWD_BIG_WAVES : 1)) void fm_forward_kernel(
+__global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? kBigWaves : 1)) void fm_forward_kernel(
     FwdArgs a) {
   constexpr int GPB = BLOCK / LPR;  // lane groups per block
   // workgroup index and count among the workgroups of its kind (XTRA: the step's, or the ones
@@ -276,30 +245,8 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? RFM_FWD_BIG_WAVES : 1)
       for (int i = tid; i < H * NW; i += BLOCK) hbits[i] = 0u;
     __syncthreads();
   }
-  // The wavefronts of a workgroup run their trips in lockstep: all sixteen gather (memory latency,
-  // LDS idle), then all sixteen add their hot entries (LDS atomics saturated, nobody gathers).  Half
-  // of them starting one gather phase late puts the two kinds of work side by side
-  // (RFM_FWD_STAGGER = the delay in units of 64 clocks; 0: none).
-#ifndef RFM_FWD_STAGGER
-#define RFM_FWD_STAGGER 0
-#endif
-  if constexpr (RFM_FWD_STAGGER > 0 && REC && BLOCK == kBigBlock) {
-    if (H > 0 && tid / kWave >= BLOCK / kWave / 2) {
-#pragma unroll
-      for (int i = 0; i < (RFM_FWD_STAGGER + 126) / 127; ++i)
-        __builtin_amdgcn_s_sleep(RFM_FWD_STAGGER < 127 ? RFM_FWD_STAGGER : 127);
-    }
-  }
-
-#ifdef RFM_FWD_STAMPS
-  int trip_no = 0;
-#define RFM_FSTAMP(i) do { if (a.stamps && (tid & (kWave - 1)) == 0 && trip_no < 2) a.stamps[((int64_t(blockIdx.x) * (BLOCK / kWave) + tid / kWave) * 2 + trip_no) * 8 + (i)] = __builtin_readcyclecounter(); } while (0)
-#else
-#define RFM_FSTAMP(i) do { } while (0)
-#endif
   for (int64_t base = int64_t(bx) * (GPB * R); base < a.n_rows;
        base += int64_t(gx) * (GPB * R)) {
-    RFM_FSTAMP(0);
     int64_t t[R];
     int32_t r[R];  // rows of a log (or of a batch) fit 31 bits
     // entry offsets: the plan checks that they fit 31 bits; the caller's CSR is taken as it is
@@ -396,7 +343,6 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? RFM_FWD_BIG_WAVES : 1)
         if (l == 0) parked[i * GPB + g] = nxt[i];
     }
 
-    RFM_FSTAMP(1);  // (row blocks have arrived: maxlen is known)
     double q[R][NC][VEC];
     double s2[R], lin[R], err[R];
 #pragma unroll
@@ -443,14 +389,14 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? RFM_FWD_BIG_WAVES : 1)
       const int cnt = (maxlen - pb) < LPR ? (maxlen - pb) : LPR;
       // entries whose gathers are in flight together: the many-rows shape is at its register
       // budget with two (x R rows); the one-row shape has registers to spare
-#pragma unroll(BLOCK == kBigBlock || NC > 1 ? (NC == 1 && !DET && (ELL || !REC) ? (REC ? RFM_FWD_BIG_UNROLL : RFM_FWD_PLAIN_UNROLL) : (BLOCK == kBigBlock || NC > 4 ? 2 : RFM_FWD_SMALL_WIDE_UNROLL)) : RFM_FWD_SMALL_UNROLL)
+#pragma unroll(BLOCK == kBigBlock || NC > 1 ? (NC == 1 && !DET && (ELL || !REC) ? (REC ? kBigUnroll : kPlainUnroll) : (BLOCK == kBigBlock || NC > 4 ? 2 : kSmallWideUnroll)) : kSmallUnroll)
       for (int j = 0; j < cnt; ++j) {
         Entry ej[R];
         Pack<VEC> pv[R][NC];
 #pragma unroll
         for (int i = 0; i < R; ++i) {
           ej[i] = ebuf[i * LPR + j];  // same address in the lane group: broadcast
-          const double* vrow = a.V + (RFM_KEEP(a, 4) ? int64_t(ej[i].col) * k : 0);
+          const double* vrow = a.V + int64_t(ej[i].col) * k;
 #pragma unroll
           for (int c = 0; c < NC; ++c) pv[i][c].load(vrow + fo[c]);
         }
@@ -473,7 +419,6 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? RFM_FWD_BIG_WAVES : 1)
       }
     }
 
-    RFM_FSTAMP(2);  // (gathers summed)
     if (warm) {  // back from LDS (same wave wrote them): the gathers' registers are free again
 #pragma unroll
       for (int i = 0; i < R; ++i) nxt[i] = parked[i * GPB + g];
@@ -498,7 +443,7 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? RFM_FWD_BIG_WAVES : 1)
       const double pred = sigmoid_clipped(w0 + linsum + 0.5 * pair);
       err[i] = valid[i] ? yy[i] / pp[i] - pred : 0.0;
       if (valid[i]) {
-        if (a.out_Q && RFM_KEEP(a, 2)) {
+        if (a.out_Q) {
           // (Q belongs to a plan: max_batch * k fits 31 bits, checked where it is made)
           const uint32_t qoff = uint32_t(t[i]) * uint32_t(k);
 #pragma unroll
@@ -549,7 +494,6 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? RFM_FWD_BIG_WAVES : 1)
       }
     }
     ++trip;
-    RFM_FSTAMP(3);  // (scores, residuals, Q rows out)
 
     int32_t touched[R];
     if (warm) {
@@ -558,13 +502,13 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? RFM_FWD_BIG_WAVES : 1)
         touched[i] = *reinterpret_cast<const int32_t*>(a.ell + int64_t(nxt[i]) * a.ell_stride +
                                                       16 * l);
     }
-    if (REC && (a.slot_mark || (H > 0 && RFM_KEEP(a, 32)))) {
+    if (REC && (a.slot_mark || H > 0)) {
       // after the residual is known: marks of the sparse-class entries, and the hot
       // entries' err * x * [q, 1, x] into the workgroup's LDS sums.  A single round (rows
       // of at most LPR entries) still has its entries parked in LDS.
       // (fixed-order hot sums meet at workgroup barriers: every group then makes the rounds
       // of the plan's longest row, whatever its own rows need)
-      const bool fix_hot = FIX && H > 0 && RFM_KEEP(a, 32);
+      const bool fix_hot = FIX && H > 0;
       const int rounds_len = fix_hot ? a.hot_rounds * LPR : maxlen;
       for (int pb = 0; pb < rounds_len; pb += LPR) {
         Entry em[R];
@@ -578,7 +522,7 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? RFM_FWD_BIG_WAVES : 1)
             em[i] = ebuf[i * LPR + l];
           }
         }
-        if (a.slot_mark && RFM_KEEP(a, 1)) {
+        if (a.slot_mark) {
 #pragma unroll
           for (int i = 0; i < R; ++i) {
             if (pb + l < len[i] && em[i].slot >= 0) {
@@ -590,7 +534,7 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? RFM_FWD_BIG_WAVES : 1)
             }
           }
         }
-        if (!(H > 0 && RFM_KEEP(a, 32))) continue;
+        if (!(H > 0)) continue;
         if constexpr (FIX) {
           // ---- park: Q rows (once), err * x * [1, x] in place of the entries, row sets ----
 #pragma unroll
@@ -615,101 +559,99 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? RFM_FWD_BIG_WAVES : 1)
             pc.store(reinterpret_cast<double*>(ebuf + i * LPR + l));
           }
           __syncthreads();
-          if (RFM_KEEP(a, 8)) {
-            const Entry* ebase = reinterpret_cast<const Entry*>(dyn_lds + BLOCK);
-            // sum of err * x * [q, 1, x] over the rows of a set (lo: rows base.., hi: rows
-            // base + 64..), ascending; U rows' LDS reads are in flight together
-            double acc[VEC], accw, accx;
-            const auto add_rows = [&](int h, unsigned long long lo, unsigned long long hi, int base) {
-              while (lo | hi) {
-                constexpr int U = RFM_HOT_U;
-                int rowu[U];
-                bool ok[U];
+          const Entry* ebase = reinterpret_cast<const Entry*>(dyn_lds + BLOCK);
+          // sum of err * x * [q, 1, x] over the rows of a set (lo: rows base.., hi: rows
+          // base + 64..), ascending; U rows' LDS reads are in flight together
+          double acc[VEC], accw, accx;
+          const auto add_rows = [&](int h, unsigned long long lo, unsigned long long hi, int base) {
+            while (lo | hi) {
+              constexpr int U = kHotUnroll;
+              int rowu[U];
+              bool ok[U];
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
-                  ok[u] = (lo | hi) != 0;
-                  int bit = 0;
-                  if (lo) {
-                    bit = __builtin_ctzll(lo);
-                    lo &= lo - 1;
-                  } else if (hi) {
-                    bit = 64 + __builtin_ctzll(hi);
-                    hi &= hi - 1;
-                  }
-                  rowu[u] = base + bit;
+              for (int u = 0; u < U; ++u) {
+                ok[u] = (lo | hi) != 0;
+                int bit = 0;
+                if (lo) {
+                  bit = __builtin_ctzll(lo);
+                  lo &= lo - 1;
+                } else if (hi) {
+                  bit = 64 + __builtin_ctzll(hi);
+                  hi &= hi - 1;
                 }
-                int ju[U];
+                rowu[u] = base + bit;
+              }
+              int ju[U];
 #pragma unroll
-                for (int u = 0; u < U; ++u) ju[u] = hpos[h * PS + rowu[u]] & (LPR - 1);
-                Pack<2> cf[U];
-                Pack<VEC> qv[U];
+              for (int u = 0; u < U; ++u) ju[u] = hpos[h * PS + rowu[u]] & (LPR - 1);
+              Pack<2> cf[U];
+              Pack<VEC> qv[U];
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
-                  const int gg = rowu[u] % GPB, ii = rowu[u] / GPB;
-                  cf[u].load(reinterpret_cast<const double*>(ebase + gg * (R * LPR + 1) + ii * LPR + ju[u]));
-                  qv[u].load(Qs + rowu[u] * KS + fo[0]);
-                }
+              for (int u = 0; u < U; ++u) {
+                const int gg = rowu[u] % GPB, ii = rowu[u] / GPB;
+                cf[u].load(reinterpret_cast<const double*>(ebase + gg * (R * LPR + 1) + ii * LPR + ju[u]));
+                qv[u].load(Qs + rowu[u] * KS + fo[0]);
+              }
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
-                  if (ok[u]) {
+              for (int u = 0; u < U; ++u) {
+                if (ok[u]) {
 #pragma unroll
-                    for (int v = 0; v < VEC; ++v) acc[v] += cf[u].v[0] * qv[u].v[v];
-                    accw += cf[u].v[0];
-                    accx += cf[u].v[1];
-                  }
+                  for (int v = 0; v < VEC; ++v) acc[v] += cf[u].v[0] * qv[u].v[v];
+                  accw += cf[u].v[0];
+                  accx += cf[u].v[1];
                 }
               }
-            };
-            const auto clear_acc = [&] {
-#pragma unroll
-              for (int v = 0; v < VEC; ++v) acc[v] = 0.0;
-              accw = 0.0;
-              accx = 0.0;
-            };
-            const auto add_to = [&](double* row_out, bool overwrite) {
-              if (fok[0]) {
-#pragma unroll
-                for (int v = 0; v < VEC; ++v)
-                  row_out[fo[0] + v] = overwrite ? acc[v] : row_out[fo[0] + v] + acc[v];
-              }
-              if (l == 0) {
-                row_out[k] = overwrite ? accw : row_out[k] + accw;
-                row_out[k + 1] = overwrite ? accx : row_out[k + 1] + accx;
-              }
-            };
-            // the NHV most frequent columns are cut into cells of 32 rows, one per lane group:
-            // a cell's sum goes to its own row of `part`, combined in cell order below
-            if (NCELL > 1 && g / NCELL < H) {
-              const int h = g / NCELL, cell = g % NCELL;
-              const unsigned int word = hbits[h * NW + cell];
-              if (l == 0) hbits[h * NW + cell] = 0u;  // (the group has read it: one wave)
-              clear_acc();
-              add_rows(h, word, 0ull, cell * 32);
-              add_to(part + g * hot_w, true);
             }
-            // the other columns: one lane group each, dealt boustrophedon over the ranks (which
-            // descend by frequency), starting opposite to the cells' order
-            for (int s2 = 0; NHV + s2 * GPB < H; ++s2) {
-              const int h = NHV + s2 * GPB + ((s2 & 1) ? g : GPB - 1 - g);
-              if (h >= H) continue;
-              unsigned long long lo = 0, hi = 0;
+          };
+          const auto clear_acc = [&] {
 #pragma unroll
-              for (int wi = 0; wi < NW; ++wi) {
-                const unsigned long long word = hbits[h * NW + wi];
-                if (wi < 2)
-                  lo |= word << (32 * wi);
-                else
-                  hi |= word << (32 * (wi - 2));
-              }
-              if ((lo | hi) == 0) continue;
-              if (l < NW) hbits[h * NW + l] = 0u;
-              clear_acc();
-              add_rows(h, lo, hi, 0);
-              add_to(hot + h * hot_w, false);
+            for (int v = 0; v < VEC; ++v) acc[v] = 0.0;
+            accw = 0.0;
+            accx = 0.0;
+          };
+          const auto add_to = [&](double* row_out, bool overwrite) {
+            if (fok[0]) {
+#pragma unroll
+              for (int v = 0; v < VEC; ++v)
+                row_out[fo[0] + v] = overwrite ? acc[v] : row_out[fo[0] + v] + acc[v];
             }
+            if (l == 0) {
+              row_out[k] = overwrite ? accw : row_out[k] + accw;
+              row_out[k + 1] = overwrite ? accx : row_out[k + 1] + accx;
+            }
+          };
+          // the NHV most frequent columns are cut into cells of 32 rows, one per lane group:
+          // a cell's sum goes to its own row of `part`, combined in cell order below
+          if (NCELL > 1 && g / NCELL < H) {
+            const int h = g / NCELL, cell = g % NCELL;
+            const unsigned int word = hbits[h * NW + cell];
+            if (l == 0) hbits[h * NW + cell] = 0u;  // (the group has read it: one wave)
+            clear_acc();
+            add_rows(h, word, 0ull, cell * 32);
+            add_to(part + g * hot_w, true);
+          }
+          // the other columns: one lane group each, dealt boustrophedon over the ranks (which
+          // descend by frequency), starting opposite to the cells' order
+          for (int s2 = 0; NHV + s2 * GPB < H; ++s2) {
+            const int h = NHV + s2 * GPB + ((s2 & 1) ? g : GPB - 1 - g);
+            if (h >= H) continue;
+            unsigned long long lo = 0, hi = 0;
+#pragma unroll
+            for (int wi = 0; wi < NW; ++wi) {
+              const unsigned long long word = hbits[h * NW + wi];
+              if (wi < 2)
+                lo |= word << (32 * wi);
+              else
+                hi |= word << (32 * (wi - 2));
+            }
+            if ((lo | hi) == 0) continue;
+            if (l < NW) hbits[h * NW + l] = 0u;
+            clear_acc();
+            add_rows(h, lo, hi, 0);
+            add_to(hot + h * hot_w, false);
           }
           __syncthreads();  // the next round / trip rewrites the entries
-          if (NCELL > 1 && RFM_KEEP(a, 8)) {
+          if (NCELL > 1) {
             // cells of a column, in cell order (lane group h: nobody else touches hot[h])
             if (g < NHV && g < H) {
               double* hrow = hot + g * hot_w;
@@ -745,26 +687,18 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? RFM_FWD_BIG_WAVES : 1)
             const double coef = err[i] * eh[i].x;
             const double coef2 = pair01 ? err[R - 1] * eh[R - 1].x : 0.0;
             double* hrow = hot + (-1 - eh[i].slot) * hot_w;
-#ifdef RFM_ABLATE
-            // bit 512: what carrying the five most frequent columns (present in every row of the
-            // KuaiRec-shaped log) in registers across a workgroup's trips would save at best --
-            // their adds vanish on every trip after a workgroup's first
-            if ((a.ablate & 512) && -1 - eh[i].slot < 5 && base >= int64_t(gx) * (GPB * R)) continue;
-#endif
-            if (RFM_KEEP(a, 8)) {
 #pragma unroll
-              for (int c = 0; c < NC; ++c) {
-                if (fok[c]) {
+            for (int c = 0; c < NC; ++c) {
+              if (fok[c]) {
 #pragma unroll
-                  for (int v = 0; v < VEC; ++v)
-                    unsafeAtomicAdd(hrow + fo[c] + v, coef * q[i][c][v] + coef2 * q[R - 1][c][v]);
-                }
+                for (int v = 0; v < VEC; ++v)
+                  unsafeAtomicAdd(hrow + fo[c] + v, coef * q[i][c][v] + coef2 * q[R - 1][c][v]);
               }
-              // sum coef (lane 0) and sum coef*x (lane 1) in one instruction
-              if (l < 2)
-                unsafeAtomicAdd(hrow + k + l, l == 0 ? coef + coef2
-                                                     : coef * eh[i].x + coef2 * eh[R - 1].x);
             }
+            // sum coef (lane 0) and sum coef*x (lane 1) in one instruction
+            if (l < 2)
+              unsafeAtomicAdd(hrow + k + l, l == 0 ? coef + coef2
+                                                   : coef * eh[i].x + coef2 * eh[R - 1].x);
           }
         }
       }
@@ -773,17 +707,9 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? RFM_FWD_BIG_WAVES : 1)
 #pragma unroll
       for (int i = 0; i < R; ++i) asm volatile("" ::"v"(touched[i]));  // keep the touches alive
     }
-    RFM_FSTAMP(4);  // (marks left, hot entries added)
-#ifdef RFM_FWD_STAMPS
-    ++trip_no;
-#endif
   }
-#ifdef RFM_FWD_STAMPS
-  trip_no = 1;
-#endif
-  RFM_FSTAMP(5);  // (all trips done)
 
-  if (H > 0 && RFM_KEEP(a, 16)) {
+  if (H > 0) {
     __syncthreads();
     // slab layout [H][gridDim.x][k+2]: the slabs of one column are contiguous
     for (int i = tid; i < H * hot_w; i += BLOCK) {
@@ -803,7 +729,6 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? RFM_FWD_BIG_WAVES : 1)
     const double s = block_sum<BLOCK>(loss_acc2, red);
     if (tid == 0) a.loss_partial2[bx] = s;
   }
-  RFM_FSTAMP(6);  // (slab and partial sums stored)
 }
 
 // loss = -(sum of partials)/n, fixed order
@@ -970,13 +895,6 @@ struct ConsArgs {
   const double* err_partial;  // [n_slabs] per-workgroup sums of the residual
   int32_t n_chunks;           // CH form: chunks of 64 lanes x VEC factors
   int32_t xcd_chunks;         // CH form: 1 = chunks dealt to XCDs (1-D grid), 0 = blockIdx.y
-  // PREP form: the task's records and their number, the rows' residuals by batch position
-  const PrepRec* prep_rec;    // [tasks][kPrepCap]
-  const int32_t* prep_cnt;    // [tasks]
-  const double* err;          // [batch]
-#ifdef RFM_CONS_STAMPS
-  long long* stamps;  // -DRFM_CONS_STAMPS builds only: [workgroup][wave][8] clock readings of the task workgroups
-#endif
 };
 
 template <int VEC, int NC>
@@ -1000,14 +918,8 @@ struct ColAcc {
 // *p += x by its only writer of the step.  As `*p += x` the wavefront stands still for the load of *p
 // (nothing else waits for it) -- once per finished column in the gradient launch, eight times per task
 // where columns are short, and one dependent level in the finalize; the no-return atomic add gives the
-// same sum without the wait (-DRFM_W_RMW=1: the read-modify-write, for timing).
-__device__ inline void add_by_only_writer(double* p, double x) {
-#if defined(RFM_W_RMW) && RFM_W_RMW
-  *p += x;
-#else
-  unsafeAtomicAdd(p, x);
-#endif
-}
+// same sum without the wait.
+__device__ inline void add_by_only_writer(double* p, double x) { unsafeAtomicAdd(p, x); }
 
 template <int LPR, int VEC, int NC>
 __device__ inline void apply_column(const ColAcc<VEC, NC>& acc, const Pack<VEC> (&vold)[NC],
@@ -1106,9 +1018,6 @@ __device__ inline int group_scan(int v, int l) {
 // launch follows the batch (marked slots): an untouched task reads its bitmap words and
 // waits at the barrier.
 // (The lane groups of a wave run in lock step: ballots and shuffles are wave-wide.)
-#ifndef RFM_CONS_CH_BATCH
-#define RFM_CONS_CH_BATCH 4
-#endif
 // CH (factor counts of more than one chunk per lane): the chunks of a row are dealt to
 // DIFFERENT workgroups -- blockIdx.y = chunk, LPR x VEC factors each, NC = 1 in registers -- so
 // that a task's chain is one 16-byte load per lane and entry instead of NC of them, NC times as
@@ -1118,23 +1027,14 @@ __device__ inline int group_scan(int v, int l) {
 // chunk lists the task's marks itself (same bitmap words: they hit in L2), so the words cannot be
 // cleared while a sibling may still read them: the bitmap is double-buffered by step parity and
 // chunk 0 clears the task's words of the OTHER buffer (the step before, long consumed).
-// PREP: the task's marked entries come as records in slot order at a fixed place (prepared
-// ahead of the loop from the row ids, see PrepRec) instead of being discovered from the bitmap:
-// first load = the records, second level = residuals + Q / V rows, third = the stores.  Sums
-// and their order are those of the bitmap form, bit for bit.
-// (waves per SIMD the chunk-per-workgroup form is compiled for: its grid is task workgroups x
-// chunks -- 1 400 workgroups at the published point -- and how many of them are resident sets
-// the launch's length; RFM_CONS_CH_WAVES=0: no cap)
-#ifndef RFM_CONS_CH_WAVES
-#define RFM_CONS_CH_WAVES 0
-#endif
-template <int LPR, int VEC, int NC, bool CH = false, bool PREP = false>
-__global__ __launch_bounds__(kBlock, (CH && RFM_CONS_CH_WAVES > 0 ? RFM_CONS_CH_WAVES : 1)) void fm_consume_kernel(ConsArgs a) {
+constexpr int kConsChBatch = 4;  // CH form: entries whose Q and V rows are in flight together
+template <int LPR, int VEC, int NC, bool CH = false>
+__global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
   static_assert(!CH || NC == 1, "the chunked form holds one chunk per lane group");
   constexpr int GPB = kBlock / LPR;  // tasks of a workgroup
   constexpr int PLANES = WinShape<LPR>::PLANES;
   constexpr int WIN = WinShape<LPR>::WIN;  // marked slots a group lists before it runs the chain
-  constexpr int BATCH = CH ? RFM_CONS_CH_BATCH : 4;  // entries whose Q and V rows are in flight together
+  constexpr int BATCH = CH ? kConsChBatch : 4;  // entries whose Q and V rows are in flight together
   // CH: which chunk and which group of tasks this workgroup takes.  Workgroups go to the eight
   // XCDs round robin by their linear id, and every XCD has an L2 of its own: with the chunks
   // dealt to XCDs (chunk c = the XCDs [8c / n, 8(c+1) / n)) an XCD only ever touches ITS slice of
@@ -1195,43 +1095,24 @@ __global__ __launch_bounds__(kBlock, (CH && RFM_CONS_CH_WAVES > 0 ? RFM_CONS_CH_
   (void)kHotBytes;
   const int lane = threadIdx.x % kWave;
   const int l = lane % LPR;
-#ifdef RFM_CONS_STAMPS
-#define RFM_CSTAMP(i) do { if (a.stamps && (threadIdx.x & (kWave - 1)) == 0) a.stamps[(int64_t(blockIdx.x) * (kBlock / kWave) + threadIdx.x / kWave) * 8 + (i)] = __builtin_readcyclecounter(); } while (0)
-#else
-#define RFM_CSTAMP(i) do { } while (0)
-#endif
-  RFM_CSTAMP(0);
   const int gb = threadIdx.x / LPR;  // group in the workgroup
   const int task = bx * GPB + gb;
   const int W = a.task_words;
   const int32_t slot0 = task * W * 64;  // first slot of the task
-  // first loads: the task's bitmap words (one per lane and trip) -- or, PREP, its records --
-  // and its description
+  // first loads: the task's bitmap words (one per lane and trip) and its description
   unsigned long long wd[TRIPS];
-  PrepRec pr[PLANES];
-  int prep_n = 0;
-  if constexpr (PREP) {
 #pragma unroll
-    for (int pl = 0; pl < PLANES; ++pl) pr[pl] = a.prep_rec[int64_t(task) * kPrepCap + pl * LPR + l];
-    prep_n = a.prep_cnt[task];
-#pragma unroll
-    for (int u = 0; u < TRIPS; ++u) wd[u] = 0ull;
-  } else {
-#pragma unroll
-    for (int u = 0; u < TRIPS; ++u) {
-      const int idx = u * LPR + l;
-      wd[u] = idx < W ? a.slot_bits[int64_t(task) * W + idx] : 0ull;
-    }
+  for (int u = 0; u < TRIPS; ++u) {
+    const int idx = u * LPR + l;
+    wd[u] = idx < W ? a.slot_bits[int64_t(task) * W + idx] : 0ull;
   }
   const TaskRec tk = a.tasks[task];
-  if constexpr (!PREP) {
 #pragma unroll
-    for (int u = 0; u < TRIPS; ++u) {
-      if (CH) {
-        if (fb == 0 && u * LPR + l < W) a.slot_bits_other[int64_t(task) * W + u * LPR + l] = 0ull;
-      } else if (wd[u]) {
-        a.slot_bits[int64_t(task) * W + u * LPR + l] = 0ull;  // consumed: cleared at once
-      }
+  for (int u = 0; u < TRIPS; ++u) {
+    if (CH) {
+      if (fb == 0 && u * LPR + l < W) a.slot_bits_other[int64_t(task) * W + u * LPR + l] = 0ull;
+    } else if (wd[u]) {
+      a.slot_bits[int64_t(task) * W + u * LPR + l] = 0ull;  // consumed: cleared at once
     }
   }
 
@@ -1276,23 +1157,21 @@ __global__ __launch_bounds__(kBlock, (CH && RFM_CONS_CH_WAVES > 0 ? RFM_CONS_CH_
   // the chain over the group's list of `fill` marked slots
   const auto run_list = [&]() {
     // records and marks of the listed slots, parked in LDS by list position
-    if constexpr (!PREP) {
-      SlotRec sr[PLANES];
-      SlotMark mk[PLANES];
+    SlotRec sr[PLANES];
+    SlotMark mk[PLANES];
 #pragma unroll
-      for (int pl = 0; pl < PLANES; ++pl) {
-        const int e = pl * LPR + l;
-        const int32_t s = e < fill ? list[e] : slot0;
-        mk[pl] = a.slot_mark[s];
-        sr[pl] = a.slots[s];
-      }
+    for (int pl = 0; pl < PLANES; ++pl) {
+      const int e = pl * LPR + l;
+      const int32_t s = e < fill ? list[e] : slot0;
+      mk[pl] = a.slot_mark[s];
+      sr[pl] = a.slots[s];
+    }
 #pragma unroll
-      for (int pl = 0; pl < PLANES; ++pl) {
-        const int e = pl * LPR + l;
-        if (e < fill) {
-          const double coef = mk[pl].err * sr[pl].x;
-          wrec[e] = WinRec{mk[pl].t, sr[pl].col, coef, coef * sr[pl].x};
-        }
+    for (int pl = 0; pl < PLANES; ++pl) {
+      const int e = pl * LPR + l;
+      if (e < fill) {
+        const double coef = mk[pl].err * sr[pl].x;
+        wrec[e] = WinRec{mk[pl].t, sr[pl].col, coef, coef * sr[pl].x};
       }
     }
     // every group of the wave loops as long as any of them has entries left
@@ -1301,7 +1180,6 @@ __global__ __launch_bounds__(kBlock, (CH && RFM_CONS_CH_WAVES > 0 ? RFM_CONS_CH_
       const int nb = max(min(BATCH, fill - at), 0);
       WinRec rec[BATCH];
       Pack<VEC> qq[BATCH][NC], vv[BATCH][NC];
-      double ee[BATCH];
 #pragma unroll
       for (int u = 0; u < BATCH; ++u) {
         rec[u] = wrec[u < nb ? at + u : 0];
@@ -1309,7 +1187,6 @@ __global__ __launch_bounds__(kBlock, (CH && RFM_CONS_CH_WAVES > 0 ? RFM_CONS_CH_
           rec[u].t = 0;
           rec[u].col = 0;
         }
-        if constexpr (PREP) ee[u] = a.err[rec[u].t];  // the row's residual, with its Q row
         // the entry's Q row, and the V row of its column in case the entry starts a new
         // column: fetched together, so that a run of one-entry columns (one-hot users and
         // items in a small batch) costs one round trip, not one per column
@@ -1337,15 +1214,7 @@ __global__ __launch_bounds__(kBlock, (CH && RFM_CONS_CH_WAVES > 0 ? RFM_CONS_CH_
 #pragma unroll
             for (int ch = 0; ch < NC; ++ch) vold[ch] = vv[u][ch];
           }
-          // (PREP: the record holds x; coef = err * x and cx = coef * x as the bitmap form parks them)
-          // (the two products are rounded on their own -- no contraction into the sums below --
-          // so that both forms add the same numbers)
-          double coef = rec[u].coef, cx = rec[u].cx;
-          if constexpr (PREP) {
-#pragma clang fp contract(off)
-            coef = ee[u] * rec[u].coef;
-            cx = coef * rec[u].coef;
-          }
+          const double coef = rec[u].coef, cx = rec[u].cx;
 #pragma unroll
           for (int ch = 0; ch < NC; ++ch)
 #pragma unroll
@@ -1359,27 +1228,8 @@ __global__ __launch_bounds__(kBlock, (CH && RFM_CONS_CH_WAVES > 0 ? RFM_CONS_CH_
     fill = 0;
   };
 
-  if constexpr (PREP) {
-    // passes of WIN records (one, but for a task with unusually many marks): park, run the chain
-    for (int base = 0; __ballot(base < prep_n); base += WIN) {
-      if (base > 0) {
 #pragma unroll
-        for (int pl = 0; pl < PLANES; ++pl) {
-          const int e = base + pl * LPR + l;
-          pr[pl] = a.prep_rec[int64_t(task) * kPrepCap + (e < kPrepCap ? e : 0)];
-        }
-      }
-      fill = max(min(prep_n - base, WIN), 0);
-#pragma unroll
-      for (int pl = 0; pl < PLANES; ++pl) {
-        const int e = pl * LPR + l;
-        if (e < fill) wrec[e] = WinRec{pr[pl].t, pr[pl].col, pr[pl].x, 0.0};
-      }
-      if (__ballot(fill > 0)) run_list();
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < (PREP ? 0 : TRIPS); ++u) {
+  for (int u = 0; u < TRIPS; ++u) {
     unsigned long long word = wd[u];
     const int32_t s0 = slot0 + (u * LPR + l) * 64;  // first slot of this lane's word
     // move the trip's marked slots into the list in lane (= slot) order, as many as the list
@@ -1401,9 +1251,7 @@ __global__ __launch_bounds__(kBlock, (CH && RFM_CONS_CH_WAVES > 0 ? RFM_CONS_CH_
       if (__ballot(word != 0ull)) run_list();
     }
   }
-  RFM_CSTAMP(1);  // (bitmap words in, marked slots listed)
-  if (!PREP && __ballot(fill > 0)) run_list();
-  RFM_CSTAMP(2);  // (chain run: records, Q / V rows, sums, columns inside the task updated)
+  if (__ballot(fill > 0)) run_list();
 
   // ---- columns that run over several tasks of this workgroup -----------------------------
   // the last column of a tail-open task is still in `acc` (if it got any entry here); a
@@ -1423,7 +1271,6 @@ __global__ __launch_bounds__(kBlock, (CH && RFM_CONS_CH_WAVES > 0 ? RFM_CONS_CH_
   if (head_open && l == 0) head[k + 2] = (head_done ? 1.0 : 0.0) + (through ? 2.0 : 0.0);
   if (!head_open && l == 0) head[k + 2] = 0.0;
   __syncthreads();
-  RFM_CSTAMP(3);
   if (own) {
     if (!own_acc) {
       acc.clear();
@@ -1473,7 +1320,6 @@ __global__ __launch_bounds__(kBlock, (CH && RFM_CONS_CH_WAVES > 0 ? RFM_CONS_CH_
                                  a.touch, a.touch_id, fb);
     }
   }
-  RFM_CSTAMP(4);  // (columns that run over several tasks combined)
 }
 
 // ---------------------------------------------------------------------------

@@ -17,7 +17,6 @@
 // The slot order inside a column is the row order, as in the host builder this replaces,
 // so the fixed-order sums of fm_consume_kernel are bit-identical to what they were.
 #include <algorithm>
-#include <chrono>
 #include <climits>
 #include <cstring>
 #include <memory>
@@ -195,17 +194,6 @@ rfm_fm_plan* build_plan(rfm_ctx* ctx, const int64_t* d_indptr, const int32_t* d_
   RFM_HIP_CHECK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
 
-  const bool timing = env_int("RFM_PLAN_TIMING", 0) != 0;
-  auto t_prev = std::chrono::steady_clock::now();
-  const auto lap = [&](const char* what) {
-    if (!timing) return;
-    RFM_HIP_CHECK(hipStreamSynchronize(st));
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[plan] %s: %.2f ms\n", what,
-            std::chrono::duration<double, std::milli>(now - t_prev).count());
-    t_prev = now;
-  };
-
   int64_t nnz = 0;
   RFM_HIP_CHECK(hipMemcpyAsync(&nnz, d_indptr + n_rows, 8, hipMemcpyDeviceToHost, st));
   RFM_HIP_CHECK(hipStreamSynchronize(st));
@@ -237,7 +225,6 @@ rfm_fm_plan* build_plan(rfm_ctx* ctx, const int64_t* d_indptr, const int32_t* d_
   RFM_HIP_CHECK(hipStreamSynchronize(st));
   RFM_REQUIRE(!h_flags[0], "indptr not monotone / out of range (nnz %lld)", (long long)nnz);
   RFM_REQUIRE(!h_flags[1], "a column index lies outside 0..%lld", (long long)n_features - 1);
-  lap("row records + checks");
 
   key.alloc(std::max<size_t>(nz, 1) * 4);
   pos.alloc(std::max<size_t>(nz, 1) * 4);
@@ -255,7 +242,6 @@ rfm_fm_plan* build_plan(rfm_ctx* ctx, const int64_t* d_indptr, const int32_t* d_
                                             positions, pos.as<int32_t>(), nz, 0u, unsigned(bits),
                                             st));
   }
-  lap("sort by column");
   hipLaunchKernelGGL(plan_starts_kernel, dim3(grid_for(ctx, nnz + 1)), dim3(kBlock), 0, st,
                      key.as<int32_t>(), pos.as<int32_t>(), row_of.as<int32_t>(), nnz, n_features,
                      cstart.as<int32_t>(), flags.as<int32_t>());
@@ -265,7 +251,6 @@ rfm_fm_plan* build_plan(rfm_ctx* ctx, const int64_t* d_indptr, const int32_t* d_
   RFM_HIP_CHECK(hipMemcpyAsync(h_flags, flags.p, 16, hipMemcpyDeviceToHost, st));
   RFM_HIP_CHECK(hipStreamSynchronize(st));
   RFM_REQUIRE(!h_flags[2], "a row names a column twice: sum duplicate entries first");
-  lap("column starts");
 
   // ---- host: classes, slot bases, windows, crossing columns (O(n_features + windows)) --
   const auto len = [&](size_t c) { return int64_t(h_start[c + 1]) - int64_t(h_start[c]); };
@@ -274,15 +259,14 @@ rfm_fm_plan* build_plan(rfm_ctx* ctx, const int64_t* d_indptr, const int32_t* d_
   std::vector<int32_t> hot_rank(nf, -1);
   // hot_min_count = -2: the hot class at its default threshold with FIXED-ORDER sums, where
   // the forward shapes this plan can take are built for them; otherwise as -1 (no hot class)
-  const bool fixed = hot_min_count == -2 && forward_fixed_order_ok(ctx, max_batch, n_factors) &&
-                     env_int("RFM_NO_FIXED_HOT", 0) == 0;
+  const bool fixed = hot_min_count == -2 && forward_fixed_order_ok(ctx, max_batch, n_factors);
   // Factor counts of more than one chunk per lane (k > 128, or odd k > 64) have NO on-chip
   // class: a column's LDS sums are k + 2 doubles (17 columns fit at k = 400) and every forward
   // workgroup -- four rows each at that width -- would leave a slab of them; measured at the
   // reference's published point (k = 400, B = 2 000; profiles/r3b): 76 us per step with the
   // class, 52 us without.  All sums then have a fixed order: such fits are bitwise
-  // reproducible whatever hot_min_count says.  (RFM_HOT_MULTI_CHUNK=1: the old behaviour.)
-  const bool chunked = shape_for(n_factors).nc > 1 && env_int("RFM_HOT_MULTI_CHUNK", 0) == 0;
+  // reproducible whatever hot_min_count says.
+  const bool chunked = shape_for(n_factors).nc > 1;
   if ((hot_min_count >= 0 || fixed) && !chunked) {
     const int64_t hot_min = hot_min_count > 0 ? hot_min_count : kDefaultHotMinCount;
     for (size_t c = 0; c < nf; ++c)
@@ -290,10 +274,9 @@ rfm_fm_plan* build_plan(rfm_ctx* ctx, const int64_t* d_indptr, const int32_t* d_
     std::stable_sort(hot_cols.begin(), hot_cols.end(),
                      [&](int32_t x, int32_t y) { return len(size_t(x)) > len(size_t(y)); });
     const size_t per_col = size_t(n_factors + 2) * 8;
-    // RFM_HOT_LDS_KB / RFM_MAX_HOT override the budget (tuning experiments only)
     // (the fixed-order form parks a trip's Q rows, row sets and cell sums in LDS as well)
-    const size_t budget = size_t(env_int("RFM_HOT_LDS_KB", int((fixed ? kHotLdsBudgetFixed : kHotLdsBudget) >> 10))) << 10;
-    const size_t cap = std::min<size_t>(size_t(env_int("RFM_MAX_HOT", kMaxHot)), budget / per_col);
+    const size_t budget = fixed ? kHotLdsBudgetFixed : kHotLdsBudget;
+    const size_t cap = std::min<size_t>(size_t(kMaxHot), budget / per_col);
     if (hot_cols.size() > cap) hot_cols.resize(cap);
     // (ranks descend by frequency: the forward deals the columns to its lane groups by rank)
     for (size_t h = 0; h < hot_cols.size(); ++h) hot_rank[size_t(hot_cols[h])] = int32_t(h);
@@ -312,8 +295,6 @@ rfm_fm_plan* build_plan(rfm_ctx* ctx, const int64_t* d_indptr, const int32_t* d_
   // 81 / 51 / 49 / 55 us per step at 2 / 4 / 8 / 16 words, profiles/r3c)
   const int task_marks = shp.nc > 1 ? 2 * kTaskMarks : kTaskMarks;
   while (W * 2 * 64 * density <= 1.5 * task_marks && W * 2 <= int64_t(kTaskTrips) * shp.lpr) W *= 2;
-  if (const int forced = env_int("RFM_TASK_WORDS", 0))  // tuning experiments only
-    W = std::max<int64_t>(1, std::min<int64_t>(forced, int64_t(kTaskTrips) * shp.lpr));
   const int64_t C = W * 64;     // slots of a task
   const int64_t BC = GPB * C;   // slots of a workgroup
   std::vector<int64_t> cptr(nf, 0);  // first slot of every sparse-class column
@@ -377,7 +358,6 @@ rfm_fm_plan* build_plan(rfm_ctx* ctx, const int64_t* d_indptr, const int32_t* d_
   for (const auto& pb : piece_blocks) tasks[size_t(pb.first * GPB)].part = pb.second;
   std::vector<SplitCol> split(split_short);
   split.insert(split.end(), split_long.begin(), split_long.end());
-  lap("classes, tasks, split columns (host)");
 
   // ---- entry and slot records ----------------------------------------------------------
   plan->n_slots = n_slots;
@@ -410,14 +390,7 @@ rfm_fm_plan* build_plan(rfm_ctx* ctx, const int64_t* d_indptr, const int32_t* d_
   const int64_t max_len = h_flags[3];
   plan->max_row_len = int32_t(max_len);
   plan->hot_rounds = int32_t(std::max<int64_t>(1, (max_len + shp.lpr - 1) / shp.lpr));
-  // ... and, with RFM_PREP=1 (an experiment that is measured and NOT the default: it removes a
-  // dependent level from each of the step's launches and changes nothing measurable --
-  // profiles/r3i), plans for small batches keep the row blocks as the source
-  // of PREPARED steps (rfm_fm_prep.hpp)
-  const bool many_rows = forward_many_rows(ctx, max_batch, n_factors);
-  const int prep_mode = many_rows ? 0 : env_int("RFM_PREP", 0);
-  const bool want_prep = prep_mode == 1;
-  if (nnz > 0 && max_len <= shp.lpr && (many_rows || want_prep) && env_int("RFM_NO_ELL", 0) == 0) {
+  if (nnz > 0 && max_len <= shp.lpr && forward_many_rows(ctx, max_batch, n_factors)) {
     plan->ell_stride = int64_t(shp.lpr) * int64_t(sizeof(Entry));
     plan->ell.alloc(nr * size_t(plan->ell_stride));
     plan->ell_yp.alloc(nr * 16);
@@ -428,23 +401,6 @@ rfm_fm_plan* build_plan(rfm_ctx* ctx, const int64_t* d_indptr, const int32_t* d_
     RFM_HIP_CHECK(hipStreamSynchronize(st));
     plan->ent.release();
     plan->rows.release();
-    if (want_prep) {
-      // iterations per chunk: what 384 MiB hold twice (two chunks are alive at a time)
-      plan->n_tasks = int32_t(n_blocks * GPB);
-      const size_t per_iter = size_t(max_batch) * (size_t(plan->ell_stride) + 16) +
-                              size_t(plan->n_tasks) * (size_t(kPrepCap) * 32 + 4);
-      const size_t fit = (size_t(env_int("RFM_PREP_MB", 384)) << 20) / std::max<size_t>(per_iter, 1);
-      plan->prep_iters = int32_t(std::min<size_t>(fit, 64));
-      plan->prep_ok = plan->prep_iters >= 8;
-    }
-  }
-  if (prep_mode == 2 && nnz > 0) {  // records only: nothing but the tasks' buckets per iteration
-    plan->n_tasks = int32_t(n_blocks * GPB);
-    const size_t per_iter = size_t(plan->n_tasks) * (size_t(kPrepCap) * 32 + 4);
-    const size_t fit = (size_t(env_int("RFM_PREP_MB", 384)) << 20) / std::max<size_t>(per_iter, 1);
-    plan->prep_iters = int32_t(std::min<size_t>(fit, 64));
-    plan->prep_ok = plan->prep_iters >= 8;
-    plan->prep_records_only = true;
   }
   // sliced loss forwards (rfm_fm_sliced.hpp): factor counts of several chunks per lane, even
   // (16-byte loads).  Slices: the power of two that covers k in 256-factor pieces (so that the
@@ -503,10 +459,8 @@ rfm_fm_plan* build_plan(rfm_ctx* ctx, const int64_t* d_indptr, const int32_t* d_
                        size_t(n_factors + 2) * 8);
   plan->err_partial.alloc(size_t(kMaxFwdGrid) * 8);
   plan->Q.alloc(size_t(max_batch) * size_t(n_factors) * 8);
-  plan->err.alloc(size_t(max_batch) * 8);
   // the host vectors and the transient device buffers die at scope exit: wait for the stream
   RFM_HIP_CHECK(hipStreamSynchronize(st));
-  lap("entry / slot records, uploads, scratch");
   return plan.release();
 }
 

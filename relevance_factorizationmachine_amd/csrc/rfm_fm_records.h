@@ -43,33 +43,13 @@ struct TaskRec {      // one task of fm_consume_kernel: task_words x 64 consecut
   int32_t part;       // >= 0: the task starts a workgroup that lies inside a column longer than a
                       // workgroup's tasks; the workgroup's sums go to this partial row
 };
-#ifndef RFM_TASK_TRIPS
-#define RFM_TASK_TRIPS 1
-#endif
-constexpr int kTaskTrips = RFM_TASK_TRIPS;  // bitmap words of its task a lane loads (task_words <= lanes of a group)
+constexpr int kTaskTrips = 1;  // bitmap words of its task a lane loads (task_words <= lanes of a group)
 struct SplitCol {      // a sparse-class column longer than a whole workgroup's tasks
   int32_t col;
   int32_t part_begin;  // its partial rows: parts[part_begin .. +part_count), in slot order
   int32_t part_count;
   int32_t pad;
 };
-
-// Prepared steps (rfm_fm_train): what a step needs that depends on the row ids alone is laid
-// out ahead of the loop, many iterations per launch -- the batch's row blocks in batch order
-// and, per task, the batch's entries of the task's slots in slot order (PrepRec), at a fixed
-// place: a task's records are then the gradient launch's FIRST load.
-constexpr int kPrepCap = 64;  // records of a task kept in place (more: the iteration is not prepared)
-struct PrepTmp {  // as gathered, unordered
-  int32_t slot;
-  int32_t t;
-  double x;
-};
-struct PrepRec {  // in slot order
-  int32_t t;      // batch position of the entry's row
-  int32_t col;    // feature column
-  double x;       // feature value
-};
-
 
 // Sliced loss forwards (rfm_fm_sliced.hpp): LDS of a workgroup (the cached columns' slices)
 constexpr int kSlicedLds = 160 << 10;

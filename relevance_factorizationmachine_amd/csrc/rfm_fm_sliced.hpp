@@ -41,10 +41,7 @@ constexpr int kSlWaves = kSlBlock / kWave;
 constexpr int kSlPairs = 2;    // pairs of factors per lane: a wavefront covers 256 factors of a row
 constexpr int kSlFill = 8;     // cached columns a wavefront requests together when it fills the LDS copy
 constexpr int kSlGlobals = 2;  // gathers of a row's uncached entries requested a row ahead
-#ifndef RFM_SL_BATCH
-#define RFM_SL_BATCH 4
-#endif
-constexpr int kSlBatch = RFM_SL_BATCH;  // cached entries whose LDS reads are in flight together
+constexpr int kSlBatch = 4;  // cached entries whose LDS reads are in flight together
 
 struct SlicedArgs {
   // log A: rows row_ids[t] (or t) for t < n_a; log B: rows t - n_a for n_a <= t < n_a + n_b;
@@ -72,7 +69,6 @@ struct SlicedArgs {
   int32_t ml_log2;             // records per translated row: 2^ml_log2 (16, 32 or 64)
   int32_t rows_per_wg;
   double* zpart;               // [ns][n_a + n_b]
-  long long* stamps;           // -DRFM_SLICED_STAMPS builds only: [workgroup][wave][8] clock readings
 };
 
 inline size_t sliced_lds_bytes(int n_cached, int sw) {
@@ -141,12 +137,6 @@ __global__ __launch_bounds__(kSlBlock) void fm_logit_slices_kernel(SlicedArgs a)
   }
   const double* Vs = a.V + f0;  // the slice of row 0
   const double w0 = slice == 0 ? a.w0[0] : 0.0;
-#ifdef RFM_SLICED_STAMPS
-#define RFM_STAMP(i) do { if (a.stamps && lane == 0) a.stamps[(int64_t(blockIdx.x) * kSlWaves + wave) * 8 + (i)] = __builtin_readcyclecounter(); } while (0)
-#else
-#define RFM_STAMP(i) do { } while (0)
-#endif
-  RFM_STAMP(0);
 
   // the rows of this wavefront: row_begin + wave + 16 j
   const int64_t rows_wg = row_end - row_begin;
@@ -219,9 +209,7 @@ __global__ __launch_bounds__(kSlBlock) void fm_logit_slices_kernel(SlicedArgs a)
       }
     }
   }
-  RFM_STAMP(1);
   __syncthreads();
-  RFM_STAMP(2);
 
   double q[2 * kSlPairs], s2[kSlPairs];  // (s2 per pair: an idle pair's sums are dropped whole)
   // Every load of the pipeline is UNCONDITIONAL and its value is always used: with a load under
@@ -317,10 +305,7 @@ __global__ __launch_bounds__(kSlBlock) void fm_logit_slices_kernel(SlicedArgs a)
     double x2;
     SlAhead g0, g1;
     request(o0, k0, x0, g0);
-    RFM_STAMP(3);
     for (int j = 0; j < nj; ++j) {
-      if (j == 1) RFM_STAMP(4);
-      if (j == 8) RFM_STAMP(5);
       records(j + 2, o2, k2, x2);
       request(o1, k1, x1, g1);
       const int64_t t = row_begin + wave + int64_t(kSlWaves) * (jb + j);
@@ -379,7 +364,6 @@ __global__ __launch_bounds__(kSlBlock) void fm_logit_slices_kernel(SlicedArgs a)
       o1 = o2; k1 = k2; x1 = x2;
       g0 = g1;
     }
-    RFM_STAMP(6);
     jb += kWave;
     if (jb < my_rows) {
       block();

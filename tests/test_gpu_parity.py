@@ -969,41 +969,6 @@ def test_deterministic_switch_gives_bitwise_reproducible_fits(rfm, shape, k, bat
     assert rel_err(fits[0][2], ref["train_loss"]) < TIGHT and rel_err(fits[0][3], ref["val_loss"]) < TIGHT
 
 
-@pytest.mark.parametrize("shape,k,batch,its", [("kuairec_small", 16, 2000, 150), ("kuairec_small", 400, 2000, 24),
-                                              ("coat", 8, 500, 150)])
-def test_prepared_steps_experiment_gives_the_same_fit(rfm, monkeypatch, shape, k, batch, its):
-    """RFM_PREP=1 (an opt-in experiment, off by default: profiles/r3i): the batches' row blocks and
-    the tasks' records of a chunk of iterations are laid out ahead of the loop and the gradient
-    launch takes its PREP form.  The sums and their order are those of the default form: in the
-    bitwise-reproducible mode the two fits are equal bit for bit -- more than one chunk here."""
-    pkg, _lib, runtime, rt = rfm
-    sh = synth.SHAPES[shape]
-    train, val = synth.make_log(sh, "FM", "IPS", seed=0)
-
-    def fit():
-        rt.clear_caches()  # (a remembered plan would keep the form it was built with)
-        m = pkg.FactorizationMachines(estimator="IPS", n_epochs=its, n_factors=k, lr=9e-6, batch_size=batch,
-                                      seed=12345, n_features=train["features"].shape[1])
-        m.deterministic = True
-        return m, m.fit(train, val)
-
-    # (48 MiB of chunk buffers: 10 iterations per chunk at k = 400, 64 at the small factor counts --
-    # several chunks in every case, and the hand-over between the two buffers)
-    monkeypatch.setenv("RFM_PREP_MB", "48")
-    base, (tr0, va0) = fit()
-    for mode in ("1", "2"):  # rows + records laid out ahead; records only
-        monkeypatch.setenv("RFM_PREP", mode)
-        prep, (tr1, va1) = fit()
-        monkeypatch.delenv("RFM_PREP")
-        rt.clear_caches()
-        np.testing.assert_array_equal(prep.V(), base.V())
-        np.testing.assert_array_equal(prep.w(), base.w())
-        assert prep.w0(0) == base.w0(0)
-        # (the loss curves: the same forwards, but the default form may score the batch and the
-        # validation rows in one launch -- another partition of the same sum)
-        assert rel_err(tr1, tr0) < 1e-13 and rel_err(va1, va0) < 1e-13
-
-
 @pytest.mark.parametrize("k", [129, 130, 191, 257, 258, 300, 383, 384, 385, 400, 511])
 def test_fm_fit_every_chunk_count(rfm, k):
     """Factor counts of several chunks per lane (2, 3, 4, 8 chunks of 64 lanes; one and two
