@@ -201,7 +201,7 @@ int32_t rfm_fm_plan_hot_columns(const rfm_fm_plan* plan, int32_t* h_out, int32_t
  * propensity arrays are the device copy of the log the plan was built from
  * (the step reads the plan's own records of it).
  * PRECONDITION of every call that takes the row ids of a step (rfm_fm_step,
- * rfm_fm_grad, rfm_fm_grad_rows, rfm_fm_train, rfm_fm_train_dp, rfm_fm_fit_dp): the ids of one
+ * rfm_fm_grad, rfm_fm_grad_rows, rfm_fm_train, rfm_fm_fit_dp): the ids of one
  * step lie in 0 .. n_rows-1 of the plan's log and are DISTINCT -- what
  * resample(replace=False) yields (src/fm.py:72-79).  A row's batch position is
  * recorded with a plain store, so a repeated id would silently lose one of its
@@ -461,18 +461,6 @@ int32_t rfm_comm_unique_id(uint8_t* h_out128);
 int32_t rfm_comm_init(rfm_ctx* ctx, int32_t n_ranks, int32_t rank, const uint8_t* h_id128);
 int32_t rfm_allreduce_sum(rfm_ctx* ctx, double* d_buf, int64_t count);
 int32_t rfm_comm_destroy(rfm_ctx* ctx);
-
-/* The data-parallel fit() loop of one rank, enqueued on the ctx stream without any
- * host synchronisation: for iteration it in [0, n_iters) the rank computes the
- * gradient of rows d_ids[it*global_batch + shard_lo .. + shard_hi) (its contiguous
- * shard of the global batch; an empty shard contributes zeros), all-reduces d_grad
- * over the ranks of rfm_comm_init (skipped when no communicator or one rank), and
- * applies theta -= lr * grad -- the same update on every rank.  d_grad is scratch
- * of n_features*(n_factors+1)+1 doubles. */
-int32_t rfm_fm_train_dp(rfm_ctx* ctx, rfm_fm_plan* plan, const int32_t* d_ids,
-                        int64_t global_batch, int64_t shard_lo, int64_t shard_hi,
-                        int64_t n_iters, double* d_w0, double* d_w, double* d_V, double lr,
-                        double* d_grad);
 
 /* HOGWILD-style variant of the same batch (NOT the reference's semantics): all
  * examples of the batch are updated concurrently without ordering, so examples

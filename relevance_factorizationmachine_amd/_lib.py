@@ -135,7 +135,6 @@ SIGNATURES = {
     "rfm_fm_train_eval": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _f64,
                      _vp, _vp, _vp, _vp, _vp, _i64, _f64, _vp, _vp,
                           _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _i64, _i64, _vp],
-    "rfm_fm_train_dp": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _f64, _vp],
     "rfm_fm_fit_dp": [_vp, _vp, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _f64, _vp, _vp, _vp, _vp, _vp,
                       _i64, _f64, _vp, _vp],
     "rfm_mf_predict": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _i32, _vp],

@@ -4,6 +4,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -205,3 +207,26 @@ struct rfm_ctx {
     prof_events.push_back(e);
   }
 };
+
+namespace rfm {
+
+// workgroups of a launch over `items` work items, `per_wg` to a workgroup: at most `per_cu` per CU
+// and at least `floor` (1 where a launch of no items still takes a workgroup)
+inline int capped_grid(const rfm_ctx* ctx, int64_t items, int64_t per_wg, int per_cu, int64_t floor) {
+  return int(std::max<int64_t>(floor, std::min<int64_t>((items + per_wg - 1) / per_wg,
+                                                         int64_t(ctx->n_cu) * per_cu)));
+}
+
+// Raises a kernel's dynamic-LDS limit to `bytes` where a launch needs more than the default 64 KiB.
+// The attribute belongs to the function ON a device: `allowed` (one per kernel) remembers it per
+// device, in atomics because contexts of different host threads share the kernel.
+constexpr int kMaxDevices = 64;  // devices of one process whose launch attributes are remembered
+using LdsLimits = std::atomic<size_t>[kMaxDevices];
+inline void allow_dynamic_lds(const rfm_ctx* ctx, const void* kernel, size_t bytes, LdsLimits& allowed) {
+  const int dev = ctx->device >= 0 && ctx->device < kMaxDevices ? ctx->device : -1;
+  if (bytes <= (64u << 10) || (dev >= 0 && bytes <= allowed[dev].load(std::memory_order_relaxed))) return;
+  RFM_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes)));
+  if (dev >= 0) allowed[dev].store(bytes, std::memory_order_relaxed);
+}
+
+}  // namespace rfm

@@ -100,11 +100,6 @@ SegList to_list(const rfm_csr_segment* h_segments, int32_t n_segments) {
   return l;
 }
 
-int grid_for(const rfm_ctx* ctx, int64_t items) {
-  return int(std::max<int64_t>(1, std::min<int64_t>((items + kCsrBlock - 1) / kCsrBlock,
-                                                    int64_t(ctx->n_cu) * 16)));
-}
-
 }  // namespace
 }  // namespace rfm
 
@@ -126,7 +121,7 @@ int32_t rfm_csr_assemble_count(rfm_ctx* ctx, const rfm_csr_segment* h_segments, 
     RFM_HIP_CHECK(hipMemsetAsync(flags.p, 0, 4, st));
     RFM_HIP_CHECK(hipMemsetAsync(len.as<int64_t>() + n_rows, 0, 8, st));
     if (n_rows > 0) {
-      hipLaunchKernelGGL(csr_count_kernel, dim3(grid_for(ctx, n_rows)), dim3(kCsrBlock), 0, st, segs,
+      hipLaunchKernelGGL(csr_count_kernel, dim3(capped_grid(ctx, n_rows, kCsrBlock, 16, 1)), dim3(kCsrBlock), 0, st, segs,
                          n_rows, len.as<int64_t>(), flags.as<int32_t>());
       RFM_HIP_CHECK(hipGetLastError());
     }
@@ -157,7 +152,7 @@ int32_t rfm_csr_assemble_fill(rfm_ctx* ctx, const rfm_csr_segment* h_segments, i
     if (n_rows == 0) return;
     RFM_REQUIRE(d_out_indices && d_out_values, "null output arrays");
     RFM_HIP_CHECK(hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(csr_fill_kernel, dim3(grid_for(ctx, n_rows)), dim3(kCsrBlock), 0, ctx->stream,
+    hipLaunchKernelGGL(csr_fill_kernel, dim3(capped_grid(ctx, n_rows, kCsrBlock, 16, 1)), dim3(kCsrBlock), 0, ctx->stream,
                        segs, n_rows, d_indptr, d_out_indices, d_out_values);
     RFM_HIP_CHECK(hipGetLastError());
   });

@@ -44,7 +44,6 @@ struct FwdGeom {
   int block, grid;
 };
 constexpr int kSmallBlock = 256;  // threads of the one-row-per-group shape
-constexpr int kMaxDevices = 64;  // devices of one process whose launch attributes are remembered
 
 inline FwdGeom forward_geom(const rfm_ctx* ctx, int64_t n_rows, const Shape& s, bool records) {
   constexpr int per_cu = kBigBlock >= 1024 ? 1 : 2;
@@ -57,12 +56,10 @@ inline FwdGeom forward_geom(const rfm_ctx* ctx, int64_t n_rows, const Shape& s, 
   // workgroups: 16 384 rows 26 vs 30 us, 8 192 rows 21 vs 20 us)
   if (blocks_big * 2 >= int64_t(ctx->n_cu) * per_cu) {
     g.block = kBigBlock;
-    g.grid = int(std::max<int64_t>(1, std::min<int64_t>(blocks_big, int64_t(ctx->n_cu) * per_cu)));
+    g.grid = capped_grid(ctx, n_rows, rows_big, per_cu, 1);
   } else {
     g.block = kSmallBlock;
-    const int gpb = kSmallBlock / s.lpr;
-    const int64_t want = (n_rows + gpb - 1) / gpb;
-    g.grid = int(std::max<int64_t>(1, std::min<int64_t>(want, int64_t(ctx->n_cu) * 8)));
+    g.grid = capped_grid(ctx, n_rows, kSmallBlock / s.lpr, 8, 1);
   }
   g.grid = std::min(g.grid, 2048);
   return g;
@@ -80,15 +77,8 @@ bool forward_many_rows(const rfm_ctx* ctx, int64_t rows, int n_factors) {
 template <int L, int Vv, int N, int BLOCK, int R, bool REC, bool ELL, bool DET, bool SEG = false, bool XTRA = false>
 void launch_forward_as(rfm_ctx* ctx, const FwdArgs& a, const FwdGeom& geom, size_t lds) {
   const auto kern = &fm_forward_kernel<L, Vv, N, BLOCK, R, REC, ELL, DET, SEG, XTRA>;
-  // (the attribute belongs to the function ON a device: kept per device; atomics because
-  // contexts of different host threads share the instantiation)
-  static std::atomic<size_t> lds_allowed[kMaxDevices];
-  const int dev = ctx->device >= 0 && ctx->device < kMaxDevices ? ctx->device : -1;
-  if (lds > (64u << 10) && (dev < 0 || lds > lds_allowed[dev].load(std::memory_order_relaxed))) {
-    RFM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-    if (dev >= 0) lds_allowed[dev].store(lds, std::memory_order_relaxed);
-  }
+  static LdsLimits allowed;
+  allow_dynamic_lds(ctx, reinterpret_cast<const void*>(kern), lds, allowed);
   hipLaunchKernelGGL(kern, dim3(geom.grid), dim3(BLOCK), lds, ctx->stream, a);
 }
 
@@ -230,7 +220,15 @@ SlicedGeom sliced_geom(const rfm_ctx* ctx, const rfm_fm_plan* plan, int64_t rows
   return g;
 }
 
-void launch_sliced(rfm_ctx* ctx, const rfm_fm_plan* plan, const SlicedGeom& g, SlicedArgs a) {
+// the arguments of a sliced forward that the plan and the parameters give (the caller adds its logs)
+SlicedArgs plan_sliced_args(const rfm_fm_plan* plan, const double* w0, const double* w, const double* V,
+                            double* zpart) {
+  SlicedArgs a{};
+  a.tr_a = plan->sl_train.as<SlEnt>();
+  a.pad = plan->sl_pad.as<SlEnt>();
+  a.w0 = w0;
+  a.w = w;
+  a.V = V;
   a.k = plan->k;
   a.ns = plan->sl_ns;
   a.sw = plan->sl_sw;
@@ -238,14 +236,14 @@ void launch_sliced(rfm_ctx* ctx, const rfm_fm_plan* plan, const SlicedGeom& g, S
   a.cached_cols = plan->sl_cols.as<int32_t>();
   a.cached_rank = plan->sl_rank.as<int32_t>();
   a.ml_log2 = plan->sl_ml_log2;
+  a.zpart = zpart;
+  return a;
+}
+
+void launch_sliced(rfm_ctx* ctx, const SlicedGeom& g, SlicedArgs a) {
   a.rows_per_wg = g.rows_per_wg;
-  static std::atomic<size_t> lds_allowed[kMaxDevices];
-  const int dev = ctx->device >= 0 && ctx->device < kMaxDevices ? ctx->device : -1;
-  if (g.lds > (64u << 10) && (dev < 0 || g.lds > lds_allowed[dev].load(std::memory_order_relaxed))) {
-    RFM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&fm_logit_slices_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, int(g.lds)));
-    if (dev >= 0) lds_allowed[dev].store(g.lds, std::memory_order_relaxed);
-  }
+  static LdsLimits allowed;
+  allow_dynamic_lds(ctx, reinterpret_cast<const void*>(&fm_logit_slices_kernel), g.lds, allowed);
   hipLaunchKernelGGL(fm_logit_slices_kernel, dim3(g.grid), dim3(kSlBlock), g.lds, ctx->stream, a);
   RFM_HIP_CHECK(hipGetLastError());
 }
@@ -280,7 +278,7 @@ void validate_ids(rfm_ctx* ctx, rfm_fm_plan* plan, const int32_t* d_ids, int64_t
   }
   RFM_HIP_CHECK(hipMemsetAsync(plan->ids_flags.p, 0, 8, ctx->stream));
   const int64_t total = batch * n_iters;
-  const int grid = int(std::min<int64_t>((total + kBlock - 1) / kBlock, int64_t(ctx->n_cu) * 8));
+  const int grid = capped_grid(ctx, total, kBlock, 8, 0);
   hipLaunchKernelGGL(ids_check_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, d_ids, batch,
                      n_iters, plan->n_rows, plan->ids_seen.as<int32_t>(), plan->ids_stamp + 1,
                      plan->ids_flags.as<int32_t>());
@@ -292,7 +290,6 @@ void validate_ids(rfm_ctx* ctx, rfm_fm_plan* plan, const int32_t* d_ids, int64_t
   RFM_REQUIRE(!flags[1], "a row id occurs twice in one batch: the ids of a step must be distinct");
 }
 
-// the three launches of one step; grad == nullptr -> update in place
 // rows of the plan's log that a step's forward launch scores on the side (fm_forward_kernel, XTRA)
 struct XtraRows {
   const int32_t* ids;  // rows ids[0 .. n) of the plan's log ...
@@ -303,53 +300,30 @@ struct XtraRows {
   int64_t n_y;
   double* out_pred_y;
 };
-// whether a step of `batch` rows can take them along: the one-row forward shape, arrival-order hot
-// sums, rows through the plan's records
-bool step_takes_extra_rows(const rfm_ctx* ctx, const rfm_fm_plan* plan, int64_t batch) {
-  return forward_geom(ctx, batch, shape_for(plan->k), true).block == kSmallBlock &&
-         !(plan->hot_fixed && plan->n_hot > 0);
-}
 
-void enqueue_step(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr,
-                  const int32_t* d_indices, const double* d_values, const double* d_y,
-                  const double* d_pscore, const int32_t* d_row_ids, int64_t batch, double* d_w0,
-                  double* d_w, double* d_V, double lr, double* d_grad, int32_t* d_touch = nullptr,
-                  int32_t touch_id = 0, const XtraRows* xtra = nullptr) {
-  const int k = plan->k;
-  const Shape s = shape_for(k);
-  (void)d_indptr;
-  (void)d_indices;
-  (void)d_values;
-  (void)d_y;
-  (void)d_pscore;
+// a forward of rows ids[0 .. n) of the plan's log, through the plan's records
+FwdArgs plan_fwd_args(const rfm_fm_plan* plan, const int32_t* ids, int64_t n, const double* w0,
+                      const double* w, const double* V) {
   FwdArgs f{};
   f.ent = plan->ent.as<Entry>();
   f.rows = plan->rows.as<RowRec>();
   f.ell = plan->ell.as<char>();
   f.ell_stride = plan->ell_stride;
   f.ell_yp = plan->ell_yp.as<double2>();
-  f.row_ids = d_row_ids;
-  f.n_rows = batch;
-  f.w0 = d_w0;
-  f.w = d_w;
-  f.V = d_V;
-  f.k = k;
-  f.out_Q = plan->Q.as<double>();
-  f.slot_mark = plan->slot_t.as<SlotMark>();
-  // more than one chunk per lane: the slot bitmap alternates between two buffers by step
-  // parity (see fm_consume_kernel, CH form)
-  const bool chunked = s.nc > 1;
-  const int64_t parity = chunked ? ((plan->step + 1) & 1) : 0;
-  unsigned long long* bits = plan->slot_bits.as<unsigned long long>() + parity * plan->bits_words;
-  unsigned long long* bits_other =
-      plan->slot_bits.as<unsigned long long>() + (1 - parity) * plan->bits_words;
-  f.slot_bits = bits;
-  f.n_hot = plan->n_hot;
-  f.hot_rounds = plan->hot_rounds;
-  f.hot_fixed = plan->hot_fixed ? 1 : 0;
-  f.hot_slab = plan->hot_slab.as<double>();
-  f.err_partial = plan->err_partial.as<double>();
-  const FwdGeom geom = forward_geom(ctx, batch, s, true);  // (the step's own workgroups: geom.grid slabs)
+  f.row_ids = ids;
+  f.n_rows = n;
+  f.w0 = w0;
+  f.w = w;
+  f.V = V;
+  f.k = plan->k;
+  return f;
+}
+
+// the step's forward launch: its own workgroups (returned: one hot-sum slab each), then those that
+// score the extra rows riding along
+int launch_step_forward(rfm_ctx* ctx, FwdArgs f, const XtraRows* xtra) {
+  const Shape s = shape_for(f.k);
+  const FwdGeom geom = forward_geom(ctx, f.n_rows, s, true);
   FwdGeom launch = geom;
   if (xtra && xtra->n > 0) {
     RFM_REQUIRE(geom.block == kSmallBlock && !(f.hot_fixed && f.n_hot > 0),
@@ -375,65 +349,115 @@ void enqueue_step(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr,
   ctx->prof_mark();
   launch_forward(ctx, f, launch);
   ctx->prof_mark();
+  return geom.grid;
+}
+
+// the step's consume launch (fm_consume_kernel): the slot-ordered sums and the updates
+void launch_consume(rfm_ctx* ctx, ConsArgs c, const Shape& s) {
+  const int grid = c.nb_tasks + c.n_hot + 1;  // tasks, then the hot columns, then w0
+  // LDS: the groups' lists + parked records + head rows, or the hot workgroups' scratch
+  const int gpb = kBlock / s.lpr;
+  const int win = s.lpr >= 32 ? 64 : 4 * s.lpr;  // WinShape<LPR>::WIN
+  const size_t lds = std::max<size_t>(size_t(gpb) * size_t(win) * (sizeof(WinRec) + 8) +
+                                          size_t(gpb) * size_t(c.k + 3) * 8,
+                                      size_t(kBlock + 1024 + 2) * 8);
+  if (s.nc > 1) {
+    // one workgroup per (four tasks, chunk of 64 lanes x vec factors)
+    const int n_chunks = ((c.k + s.vec - 1) / s.vec + 63) / 64;
+    c.n_chunks = n_chunks;
+    // chunks dealt to XCDs (see the kernel): every chunk gets at least 8 / n_chunks XCDs
+    c.xcd_chunks = n_chunks <= 8 ? 1 : 0;
+    const int per_chunk = 8 / n_chunks;  // (the fewest XCDs a chunk gets)
+    const dim3 g2 = c.xcd_chunks ? dim3(8 * ((grid + per_chunk - 1) / per_chunk)) : dim3(grid, n_chunks);
+    if (s.vec == 2)
+      hipLaunchKernelGGL((fm_consume_kernel<64, 2, 1, true>), g2, dim3(kBlock), lds, ctx->stream, c);
+    else
+      hipLaunchKernelGGL((fm_consume_kernel<64, 1, 1, true>), g2, dim3(kBlock), lds, ctx->stream, c);
+  } else {
+#define RFM_CALL_CONS(L, Vv, N) \
+  hipLaunchKernelGGL((fm_consume_kernel<L, Vv, N>), dim3(grid), dim3(kBlock), lds, ctx->stream, c)
+    RFM_FOR_SINGLE_CHUNK_SHAPE(s, RFM_CALL_CONS);
+#undef RFM_CALL_CONS
+  }
+  RFM_HIP_CHECK(hipGetLastError());
+}
+
+// the finalize launch of the columns cut into several tasks
+void launch_finalize(rfm_ctx* ctx, const FinArgs& fa, const Shape& s) {
+  const int gpb = kBlock / s.lpr;
+  const int nb_short = (fa.n_split_short + gpb - 1) / gpb;
+  const int grid = nb_short + fa.n_split_long;
+  if (s.nc > 1) {
+    const dim3 g2(grid, ((fa.k + s.vec - 1) / s.vec + 63) / 64);
+    if (s.vec == 2)
+      hipLaunchKernelGGL(fm_finalize_chunk_kernel<2>, g2, dim3(kBlock), 0, ctx->stream, fa, nb_short);
+    else
+      hipLaunchKernelGGL(fm_finalize_chunk_kernel<1>, g2, dim3(kBlock), 0, ctx->stream, fa, nb_short);
+  } else {
+#define RFM_CALL_FIN(L, Vv, N)                                                                 \
+  hipLaunchKernelGGL((fm_finalize_kernel<L, Vv, N>), dim3(grid), dim3(kBlock), 0, ctx->stream, \
+                     fa, nb_short)
+    RFM_FOR_SINGLE_CHUNK_SHAPE(s, RFM_CALL_FIN);
+#undef RFM_CALL_FIN
+  }
+  RFM_HIP_CHECK(hipGetLastError());
+}
+
+// the launches of one step; grad == nullptr -> update in place
+void enqueue_step(rfm_ctx* ctx, rfm_fm_plan* plan, const int32_t* d_row_ids, int64_t batch, double* d_w0,
+                  double* d_w, double* d_V, double lr, double* d_grad, int32_t* d_touch = nullptr,
+                  int32_t touch_id = 0, const XtraRows* xtra = nullptr) {
+  const int k = plan->k;
+  const Shape s = shape_for(k);
+  FwdArgs f = plan_fwd_args(plan, d_row_ids, batch, d_w0, d_w, d_V);
+  f.out_Q = plan->Q.as<double>();
+  f.slot_mark = plan->slot_t.as<SlotMark>();
+  // more than one chunk per lane: the slot bitmap alternates between two buffers by step
+  // parity (see fm_consume_kernel, CH form)
+  const bool chunked = s.nc > 1;
+  const int64_t parity = chunked ? ((plan->step + 1) & 1) : 0;
+  unsigned long long* bits = plan->slot_bits.as<unsigned long long>() + parity * plan->bits_words;
+  unsigned long long* bits_other =
+      plan->slot_bits.as<unsigned long long>() + (1 - parity) * plan->bits_words;
+  f.slot_bits = bits;
+  f.n_hot = plan->n_hot;
+  f.hot_rounds = plan->hot_rounds;
+  f.hot_fixed = plan->hot_fixed ? 1 : 0;
+  f.hot_slab = plan->hot_slab.as<double>();
+  f.err_partial = plan->err_partial.as<double>();
+  const int n_slabs = launch_step_forward(ctx, f, xtra);
 
   if (d_grad && !d_touch) {  // dense gradient: every element is written
     const size_t bytes = (size_t(plan->n_features) * (k + 1) + 1) * sizeof(double);
     RFM_HIP_CHECK(hipMemsetAsync(d_grad, 0, bytes, ctx->stream));
   }
   const double stamp = double(++plan->step);
-  {
-    ConsArgs c{};
-    c.tasks = plan->tasks.as<TaskRec>();
-    c.task_words = plan->task_words;
-    c.slot_bits = bits;
-    c.slot_bits_other = bits_other;
-    c.slot_mark = plan->slot_t.as<SlotMark>();
-    c.slots = plan->slots.as<SlotRec>();
-    c.Q = plan->Q.as<double>();
-    c.k = k;
-    c.n = plan->n_features;
-    c.w0 = d_w0;
-    c.V = d_V;
-    c.w = d_w;
-    c.lr = lr;
-    c.parts = plan->parts.as<double>();
-    c.stamp = stamp;
-    c.grad = d_grad;
-    c.touch = d_touch;
-    c.touch_id = touch_id;
-    c.nb_tasks = plan->n_task_blocks;  // one task per lane group
-    c.n_hot = plan->n_hot;
-    c.hot_cols = plan->hot_cols.as<int32_t>();
-    c.hot_slab = plan->hot_slab.as<double>();
-    c.n_slabs = geom.grid;
-    c.err_partial = plan->err_partial.as<double>();
-    const int grid = c.nb_tasks + c.n_hot + 1;  // tasks, then the hot columns, then w0
-    // LDS: the groups' lists + parked records + head rows, or the hot workgroups' scratch
-    const int gpb = kBlock / s.lpr;
-    const int win = s.lpr >= 32 ? 64 : 4 * s.lpr;  // WinShape<LPR>::WIN
-    const size_t lds = std::max<size_t>(size_t(gpb) * size_t(win) * (sizeof(WinRec) + 8) +
-                                            size_t(gpb) * size_t(k + 3) * 8,
-                                        size_t(kBlock + 1024 + 2) * 8);
-    if (chunked) {
-      // one workgroup per (four tasks, chunk of 64 lanes x vec factors)
-      const int n_chunks = ((k + s.vec - 1) / s.vec + 63) / 64;
-      c.n_chunks = n_chunks;
-      // chunks dealt to XCDs (see the kernel): every chunk gets at least 8 / n_chunks XCDs
-      c.xcd_chunks = n_chunks <= 8 ? 1 : 0;
-      const int per_chunk = 8 / n_chunks;  // (the fewest XCDs a chunk gets)
-      const dim3 g2 = c.xcd_chunks ? dim3(8 * ((grid + per_chunk - 1) / per_chunk)) : dim3(grid, n_chunks);
-      if (s.vec == 2)
-        hipLaunchKernelGGL((fm_consume_kernel<64, 2, 1, true>), g2, dim3(kBlock), lds, ctx->stream, c);
-      else
-        hipLaunchKernelGGL((fm_consume_kernel<64, 1, 1, true>), g2, dim3(kBlock), lds, ctx->stream, c);
-    } else {
-#define RFM_CALL_CONS(L, Vv, N) \
-  hipLaunchKernelGGL((fm_consume_kernel<L, Vv, N>), dim3(grid), dim3(kBlock), lds, ctx->stream, c)
-      RFM_FOR_SINGLE_CHUNK_SHAPE(s, RFM_CALL_CONS);
-#undef RFM_CALL_CONS
-    }
-    RFM_HIP_CHECK(hipGetLastError());
-  }
+  ConsArgs c{};
+  c.tasks = plan->tasks.as<TaskRec>();
+  c.task_words = plan->task_words;
+  c.slot_bits = bits;
+  c.slot_bits_other = bits_other;
+  c.slot_mark = plan->slot_t.as<SlotMark>();
+  c.slots = plan->slots.as<SlotRec>();
+  c.Q = plan->Q.as<double>();
+  c.k = k;
+  c.n = plan->n_features;
+  c.w0 = d_w0;
+  c.V = d_V;
+  c.w = d_w;
+  c.lr = lr;
+  c.parts = plan->parts.as<double>();
+  c.stamp = stamp;
+  c.grad = d_grad;
+  c.touch = d_touch;
+  c.touch_id = touch_id;
+  c.nb_tasks = plan->n_task_blocks;  // one task per lane group
+  c.n_hot = plan->n_hot;
+  c.hot_cols = plan->hot_cols.as<int32_t>();
+  c.hot_slab = plan->hot_slab.as<double>();
+  c.n_slabs = n_slabs;
+  c.err_partial = plan->err_partial.as<double>();
+  launch_consume(ctx, c, s);
   ctx->prof_mark();
   // columns cut into several tasks (none on most plans): their partial rows
   if (plan->n_split_short + plan->n_split_long > 0) {
@@ -451,23 +475,7 @@ void enqueue_step(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr,
     fa.grad = d_grad;
     fa.touch = d_touch;
     fa.touch_id = touch_id;
-    const int gpb = kBlock / s.lpr;
-    const int nb_short = (plan->n_split_short + gpb - 1) / gpb;
-    const int grid = nb_short + plan->n_split_long;
-    if (chunked) {
-      const dim3 g2(grid, ((k + s.vec - 1) / s.vec + 63) / 64);
-      if (s.vec == 2)
-        hipLaunchKernelGGL(fm_finalize_chunk_kernel<2>, g2, dim3(kBlock), 0, ctx->stream, fa, nb_short);
-      else
-        hipLaunchKernelGGL(fm_finalize_chunk_kernel<1>, g2, dim3(kBlock), 0, ctx->stream, fa, nb_short);
-    } else {
-#define RFM_CALL_FIN(L, Vv, N)                                                                 \
-  hipLaunchKernelGGL((fm_finalize_kernel<L, Vv, N>), dim3(grid), dim3(kBlock), 0, ctx->stream, \
-                     fa, nb_short)
-      RFM_FOR_SINGLE_CHUNK_SHAPE(s, RFM_CALL_FIN);
-#undef RFM_CALL_FIN
-    }
-    RFM_HIP_CHECK(hipGetLastError());
+    launch_finalize(ctx, fa, s);
   }
   ctx->prof_mark();
 }
@@ -487,6 +495,73 @@ FwdArgs forward_args(const int64_t* d_indptr, const int32_t* d_indices, const do
   f.k = k;
   return f;
 }
+
+// The loss partials of a run of iterations of a fit() loop (rfm_fm_train, rfm_fm_fit_dp): one row
+// of kMaxFwdGrid per-workgroup partials per iteration and loss in plan->loss_rows, finished by one
+// launch per run and loss (fixed order inside an iteration, as loss_finish_kernel does it).  A run
+// closed with `hold` is finished after the next step instead (finish_pending).
+constexpr int64_t kRun = 128;  // iterations of a run at most
+struct LossRun {
+  double* train_rows;
+  double* val_rows;
+  int train_parts = 0, val_parts = 0;  // partials per row
+  int64_t first = 0;                   // the open run's first iteration
+  int64_t pending_first = -1, pending_count = 0;
+
+  LossRun(rfm_fm_plan* plan, bool any) {
+    if (any) plan->loss_rows.ensure(size_t(2 * kRun) * size_t(kMaxFwdGrid) * sizeof(double));
+    train_rows = plan->loss_rows.as<double>();
+    val_rows = train_rows + kRun * kMaxFwdGrid;
+  }
+  int64_t slot(int64_t it) const { return it - first; }
+  double* train_row(int64_t it) const { return train_rows + slot(it) * kMaxFwdGrid; }
+  double* val_row(int64_t it) const { return val_rows + slot(it) * kMaxFwdGrid; }
+
+  // after iteration `it`: a run that has reached run_len iterations is finished (or held)
+  template <class Finish>
+  void close(int64_t it, int64_t run_len, bool hold, Finish&& finish) {
+    if (it - first + 1 != run_len) return;
+    if (hold) {
+      pending_first = first;
+      pending_count = run_len;
+    } else {
+      finish(first, run_len);
+    }
+    first = it + 1;
+  }
+  template <class Finish>
+  void finish_pending(Finish&& finish) {
+    if (pending_count <= 0) return;
+    finish(pending_first, pending_count);
+    pending_count = 0;
+  }
+  template <class Finish>
+  void finish_open(int64_t n_iters, Finish&& finish) {
+    if (n_iters > first) finish(first, n_iters - first);
+  }
+
+  // iterations first .. first + count into the means of n_* rows (rfm_fm_train) or into sums (a
+  // rank's part, rfm_fm_fit_dp); a null output: that loss is not asked for
+  void finish_means(rfm_ctx* ctx, int64_t first, int64_t count, int64_t n_train, double* out_train,
+                    int64_t n_val, double* out_val) const {
+    if (out_train)
+      hipLaunchKernelGGL(loss_finish_many_kernel, dim3(int(count)), dim3(kBlock), 0, ctx->stream,
+                         train_rows, int64_t(kMaxFwdGrid), train_parts, n_train, out_train + first);
+    if (out_val)
+      hipLaunchKernelGGL(loss_finish_many_kernel, dim3(int(count)), dim3(kBlock), 0, ctx->stream,
+                         val_rows, int64_t(kMaxFwdGrid), val_parts, n_val, out_val + first);
+    RFM_HIP_CHECK(hipGetLastError());
+  }
+  void finish_sums(rfm_ctx* ctx, int64_t first, int64_t count, double* sums_train, double* sums_val) const {
+    if (sums_train)
+      hipLaunchKernelGGL(loss_sum_many_kernel, dim3(int(count)), dim3(kBlock), 0, ctx->stream, train_rows,
+                         int64_t(kMaxFwdGrid), train_parts, sums_train + first);
+    if (sums_val)
+      hipLaunchKernelGGL(loss_sum_many_kernel, dim3(int(count)), dim3(kBlock), 0, ctx->stream, val_rows,
+                         int64_t(kMaxFwdGrid), val_parts, sums_val + first);
+    RFM_HIP_CHECK(hipGetLastError());
+  }
+};
 
 }  // namespace
 
@@ -517,8 +592,7 @@ int32_t rfm_ips_logloss(rfm_ctx* ctx, const double* d_y, const double* d_pred,
   return guarded([&] {
     RFM_REQUIRE(ctx && d_y && d_pred && d_pscore && d_out_loss, "null pointer");
     RFM_REQUIRE(n_rows >= 1, "loss of zero rows");
-    const int grid =
-        int(std::min<int64_t>((n_rows + kBlock - 1) / kBlock, int64_t(ctx->n_cu) * 8));
+    const int grid = capped_grid(ctx, n_rows, kBlock, 8, 0);
     ctx->loss_partials.ensure(size_t(std::max(kMaxFwdGrid, ctx->n_cu * 8)) * sizeof(double));
     hipLaunchKernelGGL(logloss_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, d_y, d_pred,
                        d_pscore, d_row_ids, n_rows, eps, ctx->loss_partials.as<double>());
@@ -557,8 +631,7 @@ int32_t rfm_fm_step(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr,
     RFM_REQUIRE(ctx && d_w0 && d_w && d_V, "null pointer");
     check_step_args(plan, d_indptr, d_indices, d_values, d_y, d_pscore, d_row_ids, batch);
     validate_ids(ctx, plan, d_row_ids, batch, 1);
-    enqueue_step(ctx, plan, d_indptr, d_indices, d_values, d_y, d_pscore, d_row_ids, batch,
-                 d_w0, d_w, d_V, lr, nullptr);
+    enqueue_step(ctx, plan, d_row_ids, batch, d_w0, d_w, d_V, lr, nullptr);
   });
 }
 
@@ -570,9 +643,8 @@ int32_t rfm_fm_grad(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr,
     RFM_REQUIRE(ctx && d_w0 && d_w && d_V && d_grad, "null pointer");
     check_step_args(plan, d_indptr, d_indices, d_values, d_y, d_pscore, d_row_ids, batch);
     validate_ids(ctx, plan, d_row_ids, batch, 1);
-    enqueue_step(ctx, plan, d_indptr, d_indices, d_values, d_y, d_pscore, d_row_ids, batch,
-                 const_cast<double*>(d_w0), const_cast<double*>(d_w), const_cast<double*>(d_V),
-                 0.0, d_grad);
+    enqueue_step(ctx, plan, d_row_ids, batch, const_cast<double*>(d_w0), const_cast<double*>(d_w),
+                 const_cast<double*>(d_V), 0.0, d_grad);
   });
 }
 
@@ -583,8 +655,7 @@ int32_t rfm_fm_apply(rfm_ctx* ctx, double* d_w0, double* d_w, double* d_V,
     RFM_REQUIRE(n_features >= 1 && n_factors >= 1, "bad shape");
     const int64_t nk = n_features * int64_t(n_factors);
     const int64_t total = nk + n_features + 1;
-    const int grid =
-        int(std::min<int64_t>((total + kBlock - 1) / kBlock, int64_t(ctx->n_cu) * 16));
+    const int grid = capped_grid(ctx, total, kBlock, 16, 0);
     hipLaunchKernelGGL(fm_apply_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, d_V, d_w, d_w0,
                        d_grad, nk, n_features, lr);
     RFM_HIP_CHECK(hipGetLastError());
@@ -620,9 +691,7 @@ int32_t rfm_fm_apply_rows(rfm_ctx* ctx, const double* d_rows, const int32_t* d_n
   return guarded([&] {
     RFM_REQUIRE(ctx && d_rows && d_n_rows && d_w0 && d_w && d_V, "null pointer");
     RFM_REQUIRE(n_features >= 1 && n_factors >= 1 && cap_rows >= 0, "bad shape");
-    const int wpb = kBlock / kWave;
-    const int grid = int(std::max<int64_t>(
-        1, std::min<int64_t>((cap_rows + wpb - 1) / wpb, int64_t(ctx->n_cu) * 8)));
+    const int grid = capped_grid(ctx, cap_rows, kBlock / kWave, 8, 1);
     hipLaunchKernelGGL(rows_apply_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, d_rows,
                        d_n_rows, cap_rows, d_gw0, d_w0, d_w, d_V, n_features, int(n_factors), lr);
     RFM_HIP_CHECK(hipGetLastError());
@@ -640,8 +709,7 @@ int32_t rfm_fm_reduce_rows(rfm_ctx* ctx, const double* d_rows, const int32_t* d_
     RFM_REQUIRE(n_features >= 1 && n_factors >= 1 && total_rows >= 0, "bad shape");
     if (total_rows == 0) return;
     RFM_REQUIRE(d_rows && d_out_rows, "null record lists");
-    const int wpb = kBlock / kWave;
-    const int grid = int(std::min<int64_t>((total_rows + wpb - 1) / wpb, int64_t(ctx->n_cu) * 8));
+    const int grid = capped_grid(ctx, total_rows, kBlock / kWave, 8, 0);
     hipLaunchKernelGGL(rows_reduce_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, d_rows,
                        d_seg_ptr, int(n_segments), d_w, d_V, n_features, int(n_factors), lr,
                        d_out_rows);
@@ -659,47 +727,11 @@ int32_t rfm_fm_set_rows(rfm_ctx* ctx, const double* d_rows, int64_t n_rows,
     RFM_REQUIRE(n_rows == 0 || d_rows, "null record list");
     RFM_REQUIRE(n_parts == 0 || d_gw0_parts, "null g_w0 partials");
     if (n_rows == 0 && n_parts == 0) return;
-    const int wpb = kBlock / kWave;
-    const int grid = int(std::max<int64_t>(
-        1, std::min<int64_t>((n_rows + wpb - 1) / wpb, int64_t(ctx->n_cu) * 8)));
+    const int grid = capped_grid(ctx, n_rows, kBlock / kWave, 8, 1);
     hipLaunchKernelGGL(rows_set_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, d_rows, n_rows,
                        n_parts ? d_gw0_parts : nullptr, int(n_parts), part_stride, d_w0, d_w, d_V,
                        n_features, int(n_factors), lr);
     RFM_HIP_CHECK(hipGetLastError());
-  });
-}
-
-int32_t rfm_fm_train_dp(rfm_ctx* ctx, rfm_fm_plan* plan, const int32_t* d_ids,
-                        int64_t global_batch, int64_t shard_lo, int64_t shard_hi,
-                        int64_t n_iters, double* d_w0, double* d_w, double* d_V, double lr,
-                        double* d_grad) {
-  return guarded([&] {
-    RFM_REQUIRE(ctx && plan && d_ids && d_w0 && d_w && d_V && d_grad, "null pointer");
-    RFM_REQUIRE(n_iters >= 0 && global_batch >= 1, "bad shape");
-    RFM_REQUIRE(0 <= shard_lo && shard_lo <= shard_hi && shard_hi <= global_batch, "bad shard");
-    RFM_REQUIRE(shard_hi - shard_lo <= plan->max_batch, "shard larger than the plan's max_batch");
-    for (int64_t it = 0; it < n_iters; ++it)
-      validate_ids(ctx, plan, d_ids + it * global_batch + shard_lo, shard_hi - shard_lo, 1);
-    const int64_t count = plan->n_features * int64_t(plan->k + 1) + 1;
-    const int64_t nk = plan->n_features * int64_t(plan->k);
-    const int apply_grid =
-        int(std::min<int64_t>((count + kBlock - 1) / kBlock, int64_t(ctx->n_cu) * 16));
-    for (int64_t it = 0; it < n_iters; ++it) {
-      if (shard_hi > shard_lo) {
-        enqueue_step(ctx, plan, nullptr, nullptr, nullptr, nullptr, nullptr,
-                     d_ids + it * global_batch + shard_lo, shard_hi - shard_lo, d_w0, d_w, d_V,
-                     0.0, d_grad);
-      } else {
-        RFM_HIP_CHECK(hipMemsetAsync(d_grad, 0, size_t(count) * sizeof(double), ctx->stream));
-      }
-      if (ctx->comm && ctx->comm_ranks > 1) {
-        const int32_t rc = rfm_allreduce_sum(ctx, d_grad, count);
-        if (rc != RFM_OK) throw Error(rc, "all-reduce of the gradient failed (see above)");
-      }
-      hipLaunchKernelGGL(fm_apply_kernel, dim3(apply_grid), dim3(kBlock), 0, ctx->stream, d_V,
-                         d_w, d_w0, d_grad, nk, plan->n_features, lr);
-      RFM_HIP_CHECK(hipGetLastError());
-    }
   });
 }
 
@@ -726,20 +758,14 @@ void plan_forward(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr, cons
     sliced_translate(ctx, plan, d_indptr, d_indices, d_values, n_rows, log.tr);
   }
   plan->sl_zf.ensure(size_t(plan->sl_ns) * size_t(n_rows) * 8);
-  SlicedArgs f{};
-  f.tr_a = plan->sl_train.as<SlEnt>();
+  SlicedArgs f = plan_sliced_args(plan, d_w0, d_w, d_V, plan->sl_zf.as<double>());
   f.tr_b = log.tr.as<SlEnt>();
-  f.pad = plan->sl_pad.as<SlEnt>();
   f.indptr_b = d_indptr;
   f.indices_b = d_indices;
   f.values_b = d_values;
   f.n_b = n_rows;
-  f.w0 = d_w0;
-  f.w = d_w;
-  f.V = d_V;
-  f.zpart = plan->sl_zf.as<double>();
-  launch_sliced(ctx, plan, sliced, f);
-  const int grid = int(std::min<int64_t>((n_rows + kBlock - 1) / kBlock, int64_t(ctx->n_cu) * 8));
+  launch_sliced(ctx, sliced, f);
+  const int grid = capped_grid(ctx, n_rows, kBlock, 8, 0);
   hipLaunchKernelGGL(scores_from_slices_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream,
                      plan->sl_zf.as<double>(), plan->sl_ns, n_rows, d_out_pred);
   RFM_HIP_CHECK(hipGetLastError());
@@ -765,12 +791,237 @@ struct EvalHook {
   double* dcg_out;       // [n_iters][2]
 };
 
-void train_loop(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr, const int32_t* d_indices,
-                const double* d_values, const double* d_y, const double* d_pscore, const int32_t* d_ids,
-                int64_t batch, int64_t n_iters, double* d_w0, double* d_w, double* d_V, double lr,
-                const int64_t* d_val_indptr, const int32_t* d_val_indices, const double* d_val_values,
-                const double* d_val_y, const double* d_val_pscore, int64_t n_val, double eps,
-                double* d_out_train_loss, double* d_out_val_loss, const EvalHook* hook);
+// the arguments of one rfm_fm_train / rfm_fm_train_eval call
+struct FitCall {
+  rfm_ctx* ctx;
+  rfm_fm_plan* plan;
+  const int64_t* indptr;  // the training log
+  const int32_t* indices;
+  const double *values, *y, *pscore;
+  const int32_t* ids;  // [n_iters][batch]
+  int64_t batch, n_iters;
+  double *w0, *w, *V;
+  double lr;
+  const int64_t* val_indptr;  // the validation log
+  const int32_t* val_indices;
+  const double *val_values, *val_y, *val_pscore;
+  int64_t n_val;
+  double eps;
+  double *out_train_loss, *out_val_loss;  // [n_iters] each, or null: not asked for
+  const EvalHook* hook;                   // or null
+};
+
+// How a call computes its loss forwards: one decision for the whole call (the partials of a run
+// are finished together).
+struct LossForms {
+  int64_t n_a = 0, n_b = 0;   // rows of an iteration's train / validation loss (0: not asked for)
+  SlicedGeom sliced;          // sliced by factors: partial logits, ONE launch per iteration
+  bool merge_call = false;    // both losses in ONE fm_forward_kernel launch (SEG form)
+  bool scores_only = false;   // plain forwards that leave scores; the run's logarithms come later
+  bool ride = false;          // the train rows ride in the next step's forward launch (XTRA form)
+  bool ride_val = false;      // ... and so do the validation rows
+  int zns = 0;                // partial logits per row in plan->sl_z (0: it holds scores)
+  int64_t z_per_iter = 0;     // doubles of plan->sl_z per iteration
+  int64_t run_len = kRun;     // iterations of a run
+  bool deferred() const { return sliced.ok || scores_only; }
+};
+
+LossForms loss_forms(const FitCall& c) {
+  rfm_ctx* ctx = c.ctx;
+  const rfm_fm_plan* plan = c.plan;
+  const Shape s = shape_for(plan->k);
+  LossForms f;
+  f.n_a = c.out_train_loss ? c.batch : 0;
+  f.n_b = c.out_val_loss ? c.n_val : 0;
+  // factor counts of several chunks per lane: the loss forwards sliced by factors, ONE launch
+  // per iteration that leaves partial logits; the scores and logarithms of a whole run of
+  // iterations are then computed together (rfm_fm_sliced.hpp)
+  f.sliced = sliced_geom(ctx, plan, f.n_a + f.n_b);
+  // Both losses asked for: ONE launch over the batch's rows of the training log and the
+  // validation log.  Only for factor counts of several chunks per lane: there it saves a launch
+  // (k = 400, B = 2 000: 0.098 -> 0.090 ms per iteration of fit()); at one chunk per lane the
+  // batch's rows are faster through the plan's padded row blocks than through the CSR arrays
+  // (config 3: 104.7 vs 111.6 us per iteration at B = 65 536).  RFM_MERGE_LOSS=0 / 2: never / always.
+  const int merge_mode = env_int("RFM_MERGE_LOSS", 1);
+  f.merge_call = !f.sliced.ok && merge_mode != 0 && (merge_mode == 2 || s.nc > 1) && c.out_train_loss &&
+                 c.out_val_loss && forward_geom(ctx, c.batch + c.n_val, s, false).block == kBigBlock;
+  // The plain loss forwards (neither sliced nor merged) leave their rows' SCORES and take no
+  // logarithms: the two logs of a row's term are ~200 dependent f64 instructions, and a whole
+  // run of iterations' terms are computed by one launch instead (RFM_DEFER_LOSS=0: in the
+  // forward, staged through LDS).
+  // (a call of a few iterations -- a fit() with a host evaluator trains one per call -- would only
+  // add the run's launches)
+  f.scores_only = !f.sliced.ok && !f.merge_call && f.n_a + f.n_b > 0 && c.n_iters >= 4 &&
+                  env_int("RFM_DEFER_LOSS", 1) != 0;
+  // Small batches: the train-loss forward of iteration it - 1 reads the parameters that step
+  // it's forward reads -- it RIDES in that launch (extra workgroups that only score the previous
+  // batch's rows; fm_forward_kernel's XTRA form), and only the last iteration's is a launch of
+  // its own.  A run's logarithms then wait for the next step's launch.  The step must take the
+  // one-row forward shape and arrival-order hot sums.  (RFM_RIDE_LOSS=0: never.)
+  f.ride = f.scores_only && c.out_train_loss && forward_geom(ctx, c.batch, s, true).block == kSmallBlock &&
+           !(plan->hot_fixed && plan->n_hot > 0) && env_int("RFM_RIDE_LOSS", 1) != 0;
+  // ... and so may the validation rows (the same parameters again), when the caller has registered
+  // the log (rfm_fm_plan_register_log keeps it as records), it takes the one-row shape too, and the
+  // plan holds plain records (RFM_RIDE_VAL=0: never)
+  const rfm_fm_plan::SlLog& vlog = plan->sl_log[0];
+  f.ride_val = f.ride && c.out_val_loss && vlog.records &&
+               vlog.holds(c.val_indptr, c.val_indices, c.val_values, c.n_val) && plan->ent.p && !plan->ell.p &&
+               forward_geom(ctx, c.n_val, s, true).block == kSmallBlock && env_int("RFM_RIDE_VAL", 1) != 0;
+  f.zns = f.sliced.ok ? plan->sl_ns : 0;
+  f.z_per_iter = int64_t(std::max(f.zns, 1)) * (f.n_a + f.n_b);
+  if (f.deferred()) {
+    f.run_len = std::max<int64_t>(1, std::min<int64_t>(kRun, (int64_t(256) << 20) / (f.z_per_iter * 8)));
+    f.run_len = std::min(f.run_len, c.n_iters);
+  }
+  return f;
+}
+
+// step `it`, with iteration it - 1's loss rows riding in its forward launch (LossForms::ride)
+void fit_step(const FitCall& c, const LossForms& f, const LossRun& run, int64_t it) {
+  const int32_t* ids = c.ids + it * c.batch;
+  XtraRows prev{};
+  if (f.ride && it > 0) {
+    const int64_t prev_slot = run.pending_count > 0 ? run.pending_count - 1 : run.slot(it) - 1;
+    double* zs = c.plan->sl_z.as<double>() + prev_slot * f.z_per_iter;
+    const rfm_fm_plan::SlLog& vlog = c.plan->sl_log[0];
+    prev = f.ride_val ? XtraRows{ids - c.batch, c.batch, zs, vlog.rows_rec.as<RowRec>(), vlog.ent_rec.as<Entry>(),
+                                 c.n_val, zs + f.n_a}
+                      : XtraRows{ids - c.batch, c.batch, zs, nullptr, nullptr, 0, nullptr};
+  }
+  enqueue_step(c.ctx, c.plan, ids, c.batch, c.w0, c.w, c.V, c.lr, nullptr, nullptr, 0,
+               prev.n > 0 ? &prev : nullptr);
+}
+
+// the loss forwards of iteration `it` after its step: into the run's slot of the iteration
+void fit_loss_forwards(const FitCall& c, const LossForms& f, LossRun& run, int64_t it) {
+  const int32_t* ids = c.ids + it * c.batch;
+  double* z = f.deferred() ? c.plan->sl_z.as<double>() + run.slot(it) * f.z_per_iter : nullptr;
+  if (f.sliced.ok) {
+    SlicedArgs a = plan_sliced_args(c.plan, c.w0, c.w, c.V, z);
+    a.tr_b = c.plan->sl_log[0].tr.as<SlEnt>();
+    a.indptr_a = c.indptr;
+    a.indices_a = c.indices;
+    a.values_a = c.values;
+    a.row_ids = ids;
+    a.n_a = f.n_a;
+    a.indptr_b = c.val_indptr;
+    a.indices_b = c.val_indices;
+    a.values_b = c.val_values;
+    a.n_b = f.n_b;
+    launch_sliced(c.ctx, f.sliced, a);
+    return;
+  }
+  if (f.merge_call) {
+    FwdArgs a = forward_args(c.indptr, c.indices, c.values, ids, c.batch + c.n_val, c.w0, c.w, c.V, c.plan->k);
+    a.n_rows_a = c.batch;
+    a.y = c.y;
+    a.pscore = c.pscore;
+    a.indptr2 = c.val_indptr;
+    a.indices2 = c.val_indices;
+    a.values2 = c.val_values;
+    a.y2 = c.val_y;
+    a.pscore2 = c.val_pscore;
+    a.eps = c.eps;
+    const int parts = forward_loss_pair_deferred(c.ctx, a, run.train_row(it), run.val_row(it));
+    RFM_REQUIRE(parts > 0, "merged loss forward: unexpected geometry");
+    run.train_parts = run.val_parts = parts;
+    return;
+  }
+  const bool last = it + 1 == c.n_iters;  // (riding rows of the last iteration have no next step)
+  if (c.out_train_loss && (!f.ride || last)) {
+    // same batch, new parameters (src/fm.py:90-96), through the plan's records
+    FwdArgs a = plan_fwd_args(c.plan, ids, c.batch, c.w0, c.w, c.V);
+    a.eps = c.eps;
+    if (f.scores_only) {
+      a.out_pred = z;
+      launch_forward(c.ctx, a);
+    } else {
+      run.train_parts = forward_loss_deferred(c.ctx, a, run.train_row(it));
+    }
+  }
+  if (c.out_val_loss && (!f.ride_val || last)) {
+    FwdArgs a = forward_args(c.val_indptr, c.val_indices, c.val_values, nullptr, c.n_val, c.w0, c.w, c.V,
+                             c.plan->k);
+    a.eps = c.eps;
+    if (f.scores_only) {
+      a.out_pred = z + f.n_a;
+      launch_forward(c.ctx, a);
+    } else {
+      a.y = c.val_y;
+      a.pscore = c.val_pscore;
+      run.val_parts = forward_loss_deferred(c.ctx, a, run.val_row(it));
+    }
+  }
+}
+
+// the evaluator's scores and their IPS-DCG@k, iteration `it`'s parameters
+void fit_eval(const FitCall& c, int64_t it) {
+  const EvalHook* h = c.hook;
+  double* sc = h->scores + (h->slot_first + it) * h->scores_stride;
+  plan_forward(c.ctx, c.plan, h->indptr, h->indices, h->values, h->n_rows, c.w0, c.w, c.V, sc);
+  const int32_t rc = rfm_val_dcg(c.ctx, sc, h->seg_ptr, h->rows, h->labels, h->pscores, h->n_segments, h->k,
+                                 h->user_scratch + (h->slot_first + it) * h->user_stride, h->dcg_out + 2 * it);
+  if (rc != RFM_OK) throw Error(rc, "the evaluator's DCG failed (see above)");
+}
+
+// iterations first .. first + count of a run -> the call's mean losses; deferred forms take the
+// logarithms of the run's scores / partial logits first
+void fit_finish(const FitCall& c, const LossForms& f, LossRun& run, int64_t first, int64_t count) {
+  if (f.deferred()) {
+    const auto shares = [](int64_t rows) { return int(std::min<int64_t>(64, (rows + kBlock - 1) / kBlock)); };
+    const double* z = c.plan->sl_z.as<double>();
+    if (f.n_a > 0) {
+      run.train_parts = shares(f.n_a);
+      hipLaunchKernelGGL(loss_from_slices_kernel, dim3(run.train_parts, int(count)), dim3(kBlock), 0,
+                         c.ctx->stream, z, f.z_per_iter, f.zns, f.n_a + f.n_b, int64_t(0), f.n_a,
+                         c.ids + first * c.batch, c.batch, c.y, c.pscore, c.eps, run.train_rows,
+                         int64_t(kMaxFwdGrid));
+    }
+    if (f.n_b > 0) {
+      run.val_parts = shares(f.n_b);
+      hipLaunchKernelGGL(loss_from_slices_kernel, dim3(run.val_parts, int(count)), dim3(kBlock), 0,
+                         c.ctx->stream, z, f.z_per_iter, f.zns, f.n_a + f.n_b, f.n_a, f.n_b,
+                         static_cast<const int32_t*>(nullptr), int64_t(0), c.val_y, c.val_pscore, c.eps,
+                         run.val_rows, int64_t(kMaxFwdGrid));
+    }
+  }
+  run.finish_means(c.ctx, first, count, c.batch, c.out_train_loss, c.n_val, c.out_val_loss);
+}
+
+// rfm_fm_train: per iteration the step (with riding loss rows), the loss forwards, the evaluator
+// hook; the losses of a run of iterations are finished together
+void train_loop(const FitCall& c) {
+  RFM_REQUIRE(c.ctx && c.w0 && c.w && c.V, "null pointer");
+  RFM_REQUIRE(c.n_iters >= 0, "negative n_iters");
+  if (c.n_iters == 0) return;
+  check_step_args(c.plan, c.indptr, c.indices, c.values, c.y, c.pscore, c.ids, c.batch);
+  validate_ids(c.ctx, c.plan, c.ids, c.batch, c.n_iters);
+  if (c.out_val_loss)
+    RFM_REQUIRE(c.val_indptr && c.val_indices && c.val_values && c.val_y && c.val_pscore && c.n_val >= 1,
+                "validation arrays missing");
+  LossRun run(c.plan, c.out_train_loss || c.out_val_loss);
+  const LossForms f = loss_forms(c);
+  if (f.deferred()) {
+    c.plan->sl_z.ensure(size_t(f.run_len) * size_t(f.z_per_iter) * 8);
+    // (the validation log is only known here: translated once per call)
+    // (... unless the caller has registered these arrays: rfm_fm_plan_register_log, slot 0)
+    rfm_fm_plan::SlLog& vlog = c.plan->sl_log[0];
+    if (f.sliced.ok && f.n_b > 0 && !vlog.holds(c.val_indptr, c.val_indices, c.val_values, f.n_b)) {
+      vlog.rows = -1;  // (the slot is about to hold another log)
+      sliced_translate(c.ctx, c.plan, c.val_indptr, c.val_indices, c.val_values, f.n_b, vlog.tr);
+    }
+  }
+  const auto finish = [&](int64_t first, int64_t count) { fit_finish(c, f, run, first, count); };
+  for (int64_t it = 0; it < c.n_iters; ++it) {
+    fit_step(c, f, run, it);
+    run.finish_pending(finish);  // (before this iteration's forwards reuse the run's first slots)
+    fit_loss_forwards(c, f, run, it);
+    if (c.hook) fit_eval(c, it);
+    // (riding train rows: a run's last scores arrive with the next step)
+    run.close(it, f.run_len, f.ride && it + 1 < c.n_iters, finish);
+  }
+  run.finish_open(c.n_iters, finish);
+}
 
 }  // namespace
 
@@ -796,9 +1047,9 @@ int32_t rfm_fm_train(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr,
                      const double* d_val_pscore, int64_t n_val, double eps,
                      double* d_out_train_loss, double* d_out_val_loss) {
   return guarded([&] {
-    train_loop(ctx, plan, d_indptr, d_indices, d_values, d_y, d_pscore, d_ids, batch, n_iters, d_w0, d_w,
-               d_V, lr, d_val_indptr, d_val_indices, d_val_values, d_val_y, d_val_pscore, n_val, eps,
-               d_out_train_loss, d_out_val_loss, nullptr);
+    train_loop(FitCall{ctx, plan, d_indptr, d_indices, d_values, d_y, d_pscore, d_ids, batch, n_iters, d_w0,
+                       d_w, d_V, lr, d_val_indptr, d_val_indices, d_val_values, d_val_y, d_val_pscore, n_val,
+                       eps, d_out_train_loss, d_out_val_loss, nullptr});
   });
 }
 
@@ -824,234 +1075,10 @@ int32_t rfm_fm_train_eval(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indp
     const EvalHook hook{d_ev_indptr, d_ev_indices, d_ev_values, n_ev, d_seg_ptr, d_rows, d_labels,
                         d_ev_pscores, n_segments, k, d_scores, scores_stride, d_user_scratch, user_stride,
                         slot_first, d_dcg_out};
-    train_loop(ctx, plan, d_indptr, d_indices, d_values, d_y, d_pscore, d_ids, batch, n_iters, d_w0, d_w,
-               d_V, lr, d_val_indptr, d_val_indices, d_val_values, d_val_y, d_val_pscore, n_val, eps,
-               d_out_train_loss, d_out_val_loss, &hook);
+    train_loop(FitCall{ctx, plan, d_indptr, d_indices, d_values, d_y, d_pscore, d_ids, batch, n_iters, d_w0,
+                       d_w, d_V, lr, d_val_indptr, d_val_indices, d_val_values, d_val_y, d_val_pscore, n_val,
+                       eps, d_out_train_loss, d_out_val_loss, &hook});
   });
 }
 
 }  // extern "C"
-
-namespace {
-
-void train_loop(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr, const int32_t* d_indices,
-                const double* d_values, const double* d_y, const double* d_pscore, const int32_t* d_ids,
-                int64_t batch, int64_t n_iters, double* d_w0, double* d_w, double* d_V, double lr,
-                const int64_t* d_val_indptr, const int32_t* d_val_indices, const double* d_val_values,
-                const double* d_val_y, const double* d_val_pscore, int64_t n_val, double eps,
-                double* d_out_train_loss, double* d_out_val_loss, const EvalHook* hook) {
-  {
-    RFM_REQUIRE(ctx && d_w0 && d_w && d_V, "null pointer");
-    RFM_REQUIRE(n_iters >= 0, "negative n_iters");
-    if (n_iters == 0) return;
-    check_step_args(plan, d_indptr, d_indices, d_values, d_y, d_pscore, d_ids, batch);
-    validate_ids(ctx, plan, d_ids, batch, n_iters);
-    if (d_out_val_loss)
-      RFM_REQUIRE(d_val_indptr && d_val_indices && d_val_values && d_val_y && d_val_pscore &&
-                      n_val >= 1,
-                  "validation arrays missing");
-    // the losses' per-workgroup partials of a run of iterations are finished by one launch
-    // per run (fixed order inside an iteration, as loss_finish_kernel does it)
-    constexpr int64_t kRun = 128;
-    if (d_out_train_loss || d_out_val_loss)
-      plan->loss_rows.ensure(size_t(2 * kRun) * size_t(kMaxFwdGrid) * sizeof(double));
-    double* train_rows = plan->loss_rows.as<double>();
-    double* val_rows = train_rows + kRun * kMaxFwdGrid;
-    int train_parts = 0, val_parts = 0;
-    // factor counts of several chunks per lane: the loss forwards sliced by factors, ONE launch
-    // per iteration that leaves partial logits; the scores and logarithms of a whole run of
-    // iterations are then computed together (rfm_fm_sliced.hpp)
-    const int64_t sl_a = d_out_train_loss ? batch : 0, sl_b = d_out_val_loss ? n_val : 0;
-    const SlicedGeom sliced = sliced_geom(ctx, plan, sl_a + sl_b);
-    // one decision for the whole call (the partials of a run are finished together).  Only for
-    // factor counts of several chunks per lane: there it saves a launch (k = 400, B = 2 000:
-    // 0.098 -> 0.090 ms per iteration of fit()); at one chunk per lane the batch's rows are
-    // faster through the plan's padded row blocks than through the CSR arrays (config 3:
-    // 104.7 vs 111.6 us per iteration at B = 65 536).  RFM_MERGE_LOSS=0 / 2: never / always.
-    const int merge_mode = env_int("RFM_MERGE_LOSS", 1);
-    const bool merge_call = !sliced.ok && merge_mode != 0 && (merge_mode == 2 || shape_for(plan->k).nc > 1) &&
-                            d_out_train_loss && d_out_val_loss &&
-                            forward_geom(ctx, batch + n_val, shape_for(plan->k), false).block == kBigBlock;
-    // The plain loss forwards (neither sliced nor merged) leave their rows' SCORES and take no
-    // logarithms: the two logs of a row's term are ~200 dependent f64 instructions, and a whole
-    // run of iterations' terms are computed by one launch instead (RFM_DEFER_LOSS=0: in the
-    // forward, staged through LDS).
-    // (a call of a few iterations -- a fit() with a host evaluator trains one per call -- would only
-    // add the run's launches)
-    const bool scores_only = !sliced.ok && !merge_call && sl_a + sl_b > 0 && n_iters >= 4 &&
-                             env_int("RFM_DEFER_LOSS", 1) != 0;
-    const bool deferred = sliced.ok || scores_only;
-    const int zns = sliced.ok ? plan->sl_ns : 0;  // (0: the buffer holds scores)
-    int64_t run_len = kRun;
-    const int64_t z_per_iter = int64_t(std::max(zns, 1)) * (sl_a + sl_b);
-    if (deferred) {
-      run_len = std::max<int64_t>(1, std::min<int64_t>(kRun, (int64_t(256) << 20) / (z_per_iter * 8)));
-      run_len = std::min(run_len, n_iters);
-      plan->sl_z.ensure(size_t(run_len) * size_t(z_per_iter) * 8);
-      // (the validation log is only known here: translated once per call)
-      // (... unless the caller has registered these arrays: rfm_fm_plan_register_log, slot 0)
-      if (sliced.ok && sl_b > 0 && !plan->sl_log[0].holds(d_val_indptr, d_val_indices, d_val_values, sl_b)) {
-        plan->sl_log[0].rows = -1;  // (the slot is about to hold another log)
-        sliced_translate(ctx, plan, d_val_indptr, d_val_indices, d_val_values, sl_b, plan->sl_log[0].tr);
-      }
-    }
-    const auto finish = [&](int64_t first, int64_t count) {
-      if (count <= 0) return;
-      if (deferred) {
-        const auto shares = [&](int64_t rows) { return int(std::min<int64_t>(64, (rows + kBlock - 1) / kBlock)); };
-        if (sl_a > 0) {
-          train_parts = shares(sl_a);
-          hipLaunchKernelGGL(loss_from_slices_kernel, dim3(train_parts, int(count)), dim3(kBlock), 0,
-                             ctx->stream, plan->sl_z.as<double>(), z_per_iter, zns,
-                             sl_a + sl_b, int64_t(0), sl_a, d_ids + first * batch, batch, d_y,
-                             d_pscore, eps, train_rows, int64_t(kMaxFwdGrid));
-        }
-        if (sl_b > 0) {
-          val_parts = shares(sl_b);
-          hipLaunchKernelGGL(loss_from_slices_kernel, dim3(val_parts, int(count)), dim3(kBlock), 0,
-                             ctx->stream, plan->sl_z.as<double>(), z_per_iter, zns,
-                             sl_a + sl_b, sl_a, sl_b, static_cast<const int32_t*>(nullptr),
-                             int64_t(0), d_val_y, d_val_pscore, eps, val_rows, int64_t(kMaxFwdGrid));
-        }
-      }
-      if (d_out_train_loss)
-        hipLaunchKernelGGL(loss_finish_many_kernel, dim3(int(count)), dim3(kBlock), 0, ctx->stream,
-                           train_rows, int64_t(kMaxFwdGrid), train_parts, batch,
-                           d_out_train_loss + first);
-      if (d_out_val_loss)
-        hipLaunchKernelGGL(loss_finish_many_kernel, dim3(int(count)), dim3(kBlock), 0, ctx->stream,
-                           val_rows, int64_t(kMaxFwdGrid), val_parts, n_val, d_out_val_loss + first);
-      RFM_HIP_CHECK(hipGetLastError());
-    };
-    // Small batches: the train-loss forward of iteration it - 1 reads the parameters that step
-    // it's forward reads -- it RIDES in that launch (extra workgroups that only score the previous
-    // batch's rows; fm_forward_kernel's XTRA form), and only the last iteration's is a launch of
-    // its own.  A run's logarithms then wait for the next step's launch.  (RFM_RIDE_LOSS=0: never.)
-    const bool ride = scores_only && d_out_train_loss && step_takes_extra_rows(ctx, plan, batch) &&
-                      env_int("RFM_RIDE_LOSS", 1) != 0;
-    // ... and so may the validation rows (the same parameters again), when the caller has registered
-    // the log (rfm_fm_plan_register_log keeps it as records), it takes the one-row shape too, and the
-    // plan holds plain records (RFM_RIDE_VAL=0: never)
-    const rfm_fm_plan::SlLog& vlog = plan->sl_log[0];
-    const bool ride_val = ride && d_out_val_loss && vlog.records &&
-                          vlog.holds(d_val_indptr, d_val_indices, d_val_values, n_val) && plan->ent.p &&
-                          !plan->ell.p && forward_geom(ctx, n_val, shape_for(plan->k), true).block == kSmallBlock &&
-                          env_int("RFM_RIDE_VAL", 1) != 0;
-    int64_t run_first = 0, pending_first = -1, pending_count = 0;
-    for (int64_t it = 0; it < n_iters; ++it) {
-      const int32_t* ids = d_ids + it * batch;
-      const int64_t slot = it - run_first;
-      XtraRows prev{};
-      if (ride && it > 0) {
-        const int64_t prev_slot = pending_count > 0 ? pending_count - 1 : slot - 1;
-        double* zs = plan->sl_z.as<double>() + prev_slot * z_per_iter;
-        prev = XtraRows{ids - batch, batch, zs, nullptr, nullptr, 0, nullptr};
-        if (ride_val)
-          prev = XtraRows{ids - batch, batch, zs, vlog.rows_rec.as<RowRec>(), vlog.ent_rec.as<Entry>(),
-                          n_val, zs + sl_a};
-      }
-      enqueue_step(ctx, plan, d_indptr, d_indices, d_values, d_y, d_pscore, ids, batch, d_w0,
-                   d_w, d_V, lr, nullptr, nullptr, 0, prev.n > 0 ? &prev : nullptr);
-      if (pending_count > 0) {  // (before this iteration's forwards reuse the run's first slots)
-        finish(pending_first, pending_count);
-        pending_count = 0;
-      }
-      // both losses asked for: ONE launch over the batch's rows of the training log and the
-      // validation log (RFM_MERGE_LOSS=0: two launches)
-      bool merged = false;
-      if (sliced.ok) {
-        SlicedArgs f{};
-        f.tr_a = plan->sl_train.as<SlEnt>();
-        f.tr_b = plan->sl_log[0].tr.as<SlEnt>();
-        f.pad = plan->sl_pad.as<SlEnt>();
-        f.indptr_a = d_indptr;
-        f.indices_a = d_indices;
-        f.values_a = d_values;
-        f.row_ids = ids;
-        f.n_a = sl_a;
-        f.indptr_b = d_val_indptr;
-        f.indices_b = d_val_indices;
-        f.values_b = d_val_values;
-        f.n_b = sl_b;
-        f.w0 = d_w0;
-        f.w = d_w;
-        f.V = d_V;
-        f.zpart = plan->sl_z.as<double>() + slot * z_per_iter;
-        launch_sliced(ctx, plan, sliced, f);
-        merged = true;
-      } else if (merge_call) {
-        FwdArgs f = forward_args(d_indptr, d_indices, d_values, ids, batch + n_val, d_w0, d_w, d_V, plan->k);
-        f.n_rows_a = batch;
-        f.y = d_y;
-        f.pscore = d_pscore;
-        f.indptr2 = d_val_indptr;
-        f.indices2 = d_val_indices;
-        f.values2 = d_val_values;
-        f.y2 = d_val_y;
-        f.pscore2 = d_val_pscore;
-        f.eps = eps;
-        const int parts = forward_loss_pair_deferred(ctx, f, train_rows + slot * kMaxFwdGrid,
-                                                     val_rows + slot * kMaxFwdGrid);
-        RFM_REQUIRE(parts > 0, "merged loss forward: unexpected geometry");
-        train_parts = val_parts = parts;
-        merged = true;
-      }
-      if (d_out_train_loss && !merged && !(ride && it + 1 < n_iters)) {
-        // same batch, new parameters (src/fm.py:90-96), through the plan's records
-        FwdArgs f{};
-        f.ent = plan->ent.as<Entry>();
-        f.rows = plan->rows.as<RowRec>();
-        f.ell = plan->ell.as<char>();
-        f.ell_stride = plan->ell_stride;
-        f.ell_yp = plan->ell_yp.as<double2>();
-        f.row_ids = ids;
-        f.n_rows = batch;
-        f.w0 = d_w0;
-        f.w = d_w;
-        f.V = d_V;
-        f.k = plan->k;
-        f.eps = eps;
-        if (scores_only) {
-          f.out_pred = plan->sl_z.as<double>() + slot * z_per_iter;
-          launch_forward(ctx, f);
-        } else {
-          train_parts = forward_loss_deferred(ctx, f, train_rows + slot * kMaxFwdGrid);
-        }
-      }
-      if (d_out_val_loss && !merged && !(ride_val && it + 1 < n_iters)) {
-        FwdArgs f = forward_args(d_val_indptr, d_val_indices, d_val_values, nullptr, n_val,
-                                 d_w0, d_w, d_V, plan->k);
-        f.eps = eps;
-        if (scores_only) {
-          f.out_pred = plan->sl_z.as<double>() + slot * z_per_iter + sl_a;
-          launch_forward(ctx, f);
-        } else {
-          f.y = d_val_y;
-          f.pscore = d_val_pscore;
-          val_parts = forward_loss_deferred(ctx, f, val_rows + slot * kMaxFwdGrid);
-        }
-      }
-      if (hook) {  // the evaluator's scores and their IPS-DCG@k, this iteration's parameters
-        double* sc = hook->scores + (hook->slot_first + it) * hook->scores_stride;
-        plan_forward(ctx, plan, hook->indptr, hook->indices, hook->values, hook->n_rows, d_w0, d_w, d_V, sc);
-        const int32_t rc = rfm_val_dcg(ctx, sc, hook->seg_ptr, hook->rows, hook->labels, hook->pscores,
-                                       hook->n_segments, hook->k,
-                                       hook->user_scratch + (hook->slot_first + it) * hook->user_stride,
-                                       hook->dcg_out + 2 * it);
-        if (rc != RFM_OK) throw Error(rc, "the evaluator's DCG failed (see above)");
-      }
-      if (slot + 1 == run_len) {
-        if (ride && it + 1 < n_iters) {  // (its last train scores arrive with the next step)
-          pending_first = run_first;
-          pending_count = run_len;
-        } else {
-          finish(run_first, run_len);
-        }
-        run_first = it + 1;
-      }
-    }
-    finish(run_first, n_iters - run_first);
-  }
-}
-
-}  // namespace

@@ -79,9 +79,8 @@ void enqueue_grad_rows(rfm_ctx* ctx, rfm_fm_plan* plan, int32_t id, const int32_
   double* table = plan->row_table.as<double>();
   int32_t* touch = plan->touch.as<int32_t>();
   if (batch > 0) {
-    enqueue_step(ctx, plan, nullptr, nullptr, nullptr, nullptr, nullptr, d_row_ids, batch,
-                 const_cast<double*>(d_w0), const_cast<double*>(d_w), const_cast<double*>(d_V), 0.0,
-                 table, touch, id);
+    enqueue_step(ctx, plan, d_row_ids, batch, const_cast<double*>(d_w0), const_cast<double*>(d_w),
+                 const_cast<double*>(d_V), 0.0, table, touch, id);
   } else {  // an empty shard touches nothing
     RFM_HIP_CHECK(hipMemsetAsync(table + n * (k + 1), 0, sizeof(double), ctx->stream));
   }
@@ -93,15 +92,36 @@ void enqueue_grad_rows(rfm_ctx* ctx, rfm_fm_plan* plan, int32_t id, const int32_
                      k, chunk, n_chunks, table, d_rows, cap_rows, d_n_rows, d_gw0,
                      n_ranges ? d_range_lo : nullptr, int(n_ranges), d_range_bounds);
   if (cap_rows > 0) {
-    const int wpb = kBlock / kWave;
-    const int64_t most = std::min<int64_t>(cap_rows, n);
-    const int grid = int(std::max<int64_t>(
-        1, std::min<int64_t>((most + wpb - 1) / wpb, int64_t(ctx->n_cu) * 8)));
+    const int grid = capped_grid(ctx, std::min<int64_t>(cap_rows, n), kBlock / kWave, 8, 1);
     hipLaunchKernelGGL(rows_fill_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, table, d_rows,
                        d_n_rows, cap_rows, n, k);
   }
   RFM_HIP_CHECK(hipGetLastError());
 }
+
+// small device scratch of rfm_fm_fit_dp (plan->dp_small): [0] record count | [1..2] error flag |
+// [8 .. 8+64) a step's real bounds | then the shard's g_w0
+struct DpSmall {
+  int32_t *n_rows, *flag, *chk;
+  double* gw0;
+  explicit DpSmall(rfm_fm_plan* plan) {
+    plan->dp_small.ensure(8 * 4 + 64 * 4 + 16);
+    n_rows = plan->dp_small.as<int32_t>();
+    flag = n_rows + 1;
+    chk = n_rows + 8;
+    gw0 = reinterpret_cast<double*>(plan->dp_small.as<char>() + 8 * 4 + 64 * 4);
+  }
+  // (synchronises) the flag bounds_check_kernel raises when the records do not match the plan
+  void check(hipStream_t st) const {
+    int32_t h[2] = {0, 0};
+    RFM_HIP_CHECK(hipMemcpyAsync(h, flag, 8, hipMemcpyDeviceToHost, st));
+    RFM_HIP_CHECK(hipStreamSynchronize(st));
+    if (h[0] != 0)
+      fail(RFM_ERR_INTERNAL,
+           "iteration %d: the gradient records do not match the transfer plan derived from the row ids",
+           h[0] - 1);
+  }
+};
 
 // Sizes of every transfer of a call of `n_iters` iterations, from the row ids alone.
 struct TransferPlan {
@@ -111,6 +131,7 @@ struct TransferPlan {
   std::vector<int32_t> seg;     // [n_iters][world + 1]: what this rank receives, by source
   std::vector<int64_t> out_off; // [n_iters][world + 1]: the updated rows, by owner
   int64_t cap_rows = 0, cap_recv = 0, cap_all = 0;
+  std::vector<int64_t> soff, sbytes, roff, rbytes;  // [world]: one all-to-all's offsets and sizes
   const int32_t* of(int s, int64_t it) const { return bounds.data() + (size_t(s) * n_iters + it) * (world + 1); }
 };
 
@@ -130,8 +151,7 @@ void plan_transfers(rfm_ctx* ctx, rfm_fm_plan* plan, DpExchange& ex, const int32
                                hipMemcpyHostToDevice, ctx->stream));
   plan->dp_bounds.ensure(size_t(n_iters) * nb * 4);
   plan->dp_all_bounds.ensure(size_t(W) * size_t(n_iters) * nb * 4);
-  plan->dp_small.ensure(8 * 4 + 64 * 4 + 16);
-  int32_t* d_n_rows = plan->dp_small.as<int32_t>();  // (layout: rfm_fm_fit_dp)
+  int32_t* d_n_rows = DpSmall(plan).n_rows;
   const int32_t id0 = next_touch_ids(ctx, plan, n_iters);
   const int n_chunks = int((n + kTouchChunk - 1) / kTouchChunk);
   const int64_t batch = hi - lo;
@@ -139,8 +159,7 @@ void plan_transfers(rfm_ctx* ctx, rfm_fm_plan* plan, DpExchange& ex, const int32
     const int32_t id = id0 + int32_t(it);
     if (batch > 0) {
       const int64_t items = plan->ell.p ? batch * shp.lpr : batch * kWave;
-      const int grid = int(std::max<int64_t>(1, std::min<int64_t>((items + kBlock - 1) / kBlock,
-                                                                  int64_t(ctx->n_cu) * 16)));
+      const int grid = capped_grid(ctx, items, kBlock, 16, 1);
       hipLaunchKernelGGL(rows_mark_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream,
                          plan->ent.as<Entry>(), plan->rows.as<RowRec>(), plan->ell.as<char>(),
                          plan->ell_stride, shp.lpr, d_ids + it * global_batch + lo, batch,
@@ -164,6 +183,7 @@ void plan_transfers(rfm_ctx* ctx, rfm_fm_plan* plan, DpExchange& ex, const int32
   // the record that carries a rank's g_w0 (column n) closes its list: owned by the last rank
   for (int s = 0; s < W; ++s)
     for (int64_t it = 0; it < n_iters; ++it) tp.bounds[(size_t(s) * n_iters + it) * nb + W] += 1;
+  for (auto* v : {&tp.soff, &tp.sbytes, &tp.roff, &tp.rbytes}) v->assign(size_t(W), 0);
   tp.seg.assign(size_t(n_iters) * nb, 0);
   tp.out_off.assign(size_t(n_iters) * nb, 0);
   for (int64_t it = 0; it < n_iters; ++it) {
@@ -198,6 +218,101 @@ void plan_transfers(rfm_ctx* ctx, rfm_fm_plan* plan, DpExchange& ex, const int32
   // consumed before the synchronisation)
 }
 
+// the collectives of a call: the caller's transport, else the ctx's communicator, else one rank
+DpExchange dp_exchange(rfm_ctx* ctx, const rfm_transport* transport) {
+  DpExchange ex{ctx, transport, 1, 0};
+  if (transport) {
+    RFM_REQUIRE(transport->all_gather && transport->all_reduce_sum && transport->all_to_all,
+                "transport lacks a function");
+    ex.world = transport->n_ranks;
+    ex.rank = transport->rank;
+  } else if (ctx->comm) {
+    ex.world = ctx->comm_ranks;
+    ex.rank = ctx->comm_rank;
+  }
+  RFM_REQUIRE(ex.world >= 1 && ex.world <= kMaxRanges - 1 && ex.rank >= 0 && ex.rank < ex.world,
+              "bad rank %d of %d", ex.rank, ex.world);
+  return ex;
+}
+
+// iteration `it` of the dense exchange: gradient of the shard -> all-reduce(sum) -> apply
+void exchange_dense(rfm_ctx* ctx, rfm_fm_plan* plan, DpExchange& ex, const int32_t* ids, int64_t batch,
+                    double* d_w0, double* d_w, double* d_V, double lr) {
+  const int64_t n = plan->n_features;
+  const int64_t count = n * int64_t(plan->k + 1) + 1;
+  double* grad = plan->dp_grad.as<double>();
+  if (batch > 0)
+    enqueue_step(ctx, plan, ids, batch, d_w0, d_w, d_V, 0.0, grad);
+  else
+    RFM_HIP_CHECK(hipMemsetAsync(grad, 0, size_t(count) * 8, ctx->stream));
+  ex.all_reduce_sum(grad, count);
+  hipLaunchKernelGGL(fm_apply_kernel, dim3(capped_grid(ctx, count, kBlock, 16, 0)), dim3(kBlock), 0, ctx->stream,
+                     d_V, d_w, d_w0, grad, n * int64_t(plan->k), n, lr);
+}
+
+// the ranks' loss sums [train (n_iters) | val (n_iters)] -> the mean losses, the same on every rank
+// (a null output: not asked for)
+void dp_losses(rfm_ctx* ctx, DpExchange& ex, bool exchange_on, double* sums, int64_t n_iters, int64_t n_train,
+               double* out_train, int64_t n_val, double* out_val) {
+  if (exchange_on && (out_train || out_val)) ex.all_reduce_sum(sums, 2 * n_iters);
+  const int sgrid = int((n_iters + kBlock - 1) / kBlock);
+  if (out_train)
+    hipLaunchKernelGGL(loss_scale_kernel, dim3(sgrid), dim3(kBlock), 0, ctx->stream, sums, n_iters,
+                       double(n_train), out_train);
+  if (out_val)
+    hipLaunchKernelGGL(loss_scale_kernel, dim3(sgrid), dim3(kBlock), 0, ctx->stream, sums + n_iters, n_iters,
+                       double(n_val), out_val);
+  RFM_HIP_CHECK(hipGetLastError());
+}
+
+// iteration `it` of the touched-rows exchange: the shard's gradient records to their owners, the
+// owners' ordered sums and updates, every owner's updated rows to everybody
+void exchange_rows(rfm_ctx* ctx, rfm_fm_plan* plan, DpExchange& ex, TransferPlan& tp, const DpSmall& small,
+                   int64_t it, int32_t id, const int32_t* ids, int64_t batch, double* d_w0, double* d_w,
+                   double* d_V, double lr) {
+  const int W = ex.world, nb = W + 1;
+  const int64_t n = plan->n_features;
+  const int k = plan->k;
+  const int64_t wb = int64_t(k + 2) * 8;
+  hipStream_t st = ctx->stream;
+  const int32_t* mine = tp.of(ex.rank, it);
+  const int32_t* seg = tp.seg.data() + it * nb;
+  const int64_t* off = tp.out_off.data() + it * nb;
+  double* rows = plan->dp_rows.as<double>();
+  enqueue_grad_rows(ctx, plan, id, ids, batch, d_w0, d_w, d_V, rows, tp.cap_rows, small.n_rows, small.gw0,
+                    plan->dp_range_lo.as<int32_t>(), W, small.chk);
+  hipLaunchKernelGGL(rows_append_w0_kernel, dim3(1), dim3(kWave), 0, st, rows, small.n_rows, tp.cap_rows,
+                     small.gw0, n, k);
+  hipLaunchKernelGGL(bounds_check_kernel, dim3(1), dim3(kWave * 2), 0, st, small.chk,
+                     plan->dp_bounds.as<int32_t>() + it * nb, W, tp.cap_rows, int32_t(it), small.flag);
+  // records to their owners
+  for (int p = 0; p < W; ++p) {
+    tp.soff[size_t(p)] = int64_t(mine[p]) * wb;
+    tp.sbytes[size_t(p)] = int64_t(mine[p + 1] - mine[p]) * wb;
+    tp.roff[size_t(p)] = int64_t(seg[p]) * wb;
+    tp.rbytes[size_t(p)] = int64_t(seg[p + 1] - seg[p]) * wb;
+  }
+  ex.all_to_all(rows, tp.soff.data(), tp.sbytes.data(), plan->dp_recv.p, tp.roff.data(), tp.rbytes.data());
+  // the owner's ordered sums and updated rows, written where they sit in the list of all
+  double* all = plan->dp_all.as<double>();
+  if (seg[W] > 0)
+    hipLaunchKernelGGL(rows_reduce_kernel, dim3(capped_grid(ctx, seg[W], kBlock / kWave, 8, 0)), dim3(kBlock),
+                       0, st, plan->dp_recv.as<double>(), plan->dp_seg.as<int32_t>() + it * nb, W, d_w, d_V, n,
+                       k, lr, all + off[ex.rank] * (k + 2), d_w0);
+  // every owner's updated rows to everybody
+  for (int p = 0; p < W; ++p) {
+    tp.soff[size_t(p)] = off[ex.rank] * wb;
+    tp.sbytes[size_t(p)] = (off[ex.rank + 1] - off[ex.rank]) * wb;
+    tp.roff[size_t(p)] = off[p] * wb;
+    tp.rbytes[size_t(p)] = (off[p + 1] - off[p]) * wb;
+  }
+  ex.all_to_all(all, tp.soff.data(), tp.sbytes.data(), all, tp.roff.data(), tp.rbytes.data());
+  if (off[W] > 0)
+    hipLaunchKernelGGL(rows_set_kernel, dim3(capped_grid(ctx, off[W], kBlock / kWave, 8, 1)), dim3(kBlock), 0,
+                       st, all, off[W], static_cast<const double*>(nullptr), 0, int64_t(1), d_w0, d_w, d_V, n,
+                       k, lr, true);
+}
+
 }  // namespace
 }  // namespace rfm
 
@@ -215,22 +330,10 @@ extern "C" int32_t rfm_fm_fit_dp(rfm_ctx* ctx, rfm_fm_plan* plan, const rfm_tran
     RFM_REQUIRE(n_iters >= 0 && global_batch >= 1 && n_val >= 0, "bad shape");
     if (n_iters == 0) return;
     RFM_REQUIRE(d_ids, "null row ids");
-    DpExchange ex{ctx, transport, 1, 0};
-    if (transport) {
-      RFM_REQUIRE(transport->all_gather && transport->all_reduce_sum && transport->all_to_all,
-                  "transport lacks a function");
-      ex.world = transport->n_ranks;
-      ex.rank = transport->rank;
-    } else if (ctx->comm) {
-      ex.world = ctx->comm_ranks;
-      ex.rank = ctx->comm_rank;
-    }
-    const int W = ex.world, nb = W + 1;
-    RFM_REQUIRE(W >= 1 && W <= kMaxRanges - 1 && ex.rank >= 0 && ex.rank < W, "bad rank %d of %d",
-                ex.rank, W);
+    DpExchange ex = dp_exchange(ctx, transport);
     int64_t lo, hi, vlo, vhi;
-    shard_of(global_batch, W, ex.rank, lo, hi);
-    shard_of(n_val, W, ex.rank, vlo, vhi);
+    shard_of(global_batch, ex.world, ex.rank, lo, hi);
+    shard_of(n_val, ex.world, ex.rank, vlo, vhi);
     const int64_t batch = hi - lo, n_my_val = vhi - vlo;
     RFM_REQUIRE(batch <= plan->max_batch, "shard of %lld rows exceeds the plan's max_batch %lld",
                 (long long)batch, (long long)plan->max_batch);
@@ -240,40 +343,25 @@ extern "C" int32_t rfm_fm_fit_dp(rfm_ctx* ctx, rfm_fm_plan* plan, const rfm_tran
                   "validation arrays missing");
     for (int64_t it = 0; it < n_iters && batch > 0; ++it)
       validate_ids(ctx, plan, d_ids + it * global_batch + lo, batch, 1);
-    const int64_t n = plan->n_features;
-    const int k = plan->k;
-    const int64_t count = n * int64_t(k + 1) + 1;
-    const int64_t nk = n * int64_t(k);
-    const size_t wb = size_t(k + 2) * 8;
+    const int64_t count = plan->n_features * int64_t(plan->k + 1) + 1;
     hipStream_t st = ctx->stream;
 
     // per-iteration loss SUMS of this rank: [train (n_iters) | val (n_iters)]
-    constexpr int64_t kRun = 128;
     plan->dp_sums.ensure(size_t(2 * n_iters) * 8);
     RFM_HIP_CHECK(hipMemsetAsync(plan->dp_sums.p, 0, size_t(2 * n_iters) * 8, st));
     double* sums_train = plan->dp_sums.as<double>();
     double* sums_val = sums_train + n_iters;
-    if (d_out_train_loss || want_val)
-      plan->loss_rows.ensure(size_t(2 * kRun) * size_t(kMaxFwdGrid) * sizeof(double));
-    double* train_rows = plan->loss_rows.as<double>();
-    double* val_rows = train_rows + kRun * kMaxFwdGrid;
-    int train_parts = 0, val_parts = 0;
+    LossRun run(plan, d_out_train_loss || want_val);
+    const bool train_here = d_out_train_loss && batch > 0, val_here = want_val && n_my_val > 0;
     const auto finish = [&](int64_t first, int64_t cnt) {
-      if (cnt <= 0) return;
-      if (d_out_train_loss && batch > 0)
-        hipLaunchKernelGGL(loss_sum_many_kernel, dim3(int(cnt)), dim3(kBlock), 0, st, train_rows,
-                           int64_t(kMaxFwdGrid), train_parts, sums_train + first);
-      if (want_val && n_my_val > 0)
-        hipLaunchKernelGGL(loss_sum_many_kernel, dim3(int(cnt)), dim3(kBlock), 0, st, val_rows,
-                           int64_t(kMaxFwdGrid), val_parts, sums_val + first);
-      RFM_HIP_CHECK(hipGetLastError());
+      run.finish_sums(ctx, first, cnt, train_here ? sums_train : nullptr, val_here ? sums_val : nullptr);
     };
 
     TransferPlan tp;
     // (RFM_DP_FORCE_EXCHANGE=1: a single rank goes through the exchange too -- every collective
     // with itself -- so that the whole multi-rank loop, RCCL calls included, can be run and
     // checked on one GPU)
-    const bool exchange_on = W > 1 || env_int("RFM_DP_FORCE_EXCHANGE", 0) != 0;
+    const bool exchange_on = ex.world > 1 || env_int("RFM_DP_FORCE_EXCHANGE", 0) != 0;
     const bool rows_mode = exchange == 1 && exchange_on;
     int32_t id0 = 0;
     if (rows_mode) {
@@ -282,130 +370,38 @@ extern "C" int32_t rfm_fm_fit_dp(rfm_ctx* ctx, rfm_fm_plan* plan, const rfm_tran
     } else if (exchange_on) {
       plan->dp_grad.ensure(size_t(count) * 8);
     }
-    // small device scratch: [0] record count | [1..2] error flag | [8 .. 8+64) a step's real
-    // bounds | then the shard's g_w0
-    plan->dp_small.ensure(8 * 4 + 64 * 4 + 16);
-    int32_t* d_n_rows = plan->dp_small.as<int32_t>();
-    int32_t* d_flag = d_n_rows + 1;
-    int32_t* d_chk = d_n_rows + 8;
-    double* d_gw0 = reinterpret_cast<double*>(plan->dp_small.as<char>() + 8 * 4 + 64 * 4);
-    RFM_HIP_CHECK(hipMemsetAsync(d_flag, 0, 8, st));
-    const int apply_grid = int(std::min<int64_t>((count + kBlock - 1) / kBlock, int64_t(ctx->n_cu) * 16));
-    std::vector<int64_t> soff(static_cast<size_t>(W)), sbytes(static_cast<size_t>(W)),
-        roff(static_cast<size_t>(W)), rbytes(static_cast<size_t>(W));
+    const DpSmall small(plan);
+    RFM_HIP_CHECK(hipMemsetAsync(small.flag, 0, 8, st));
 
-    int64_t run_first = 0;
     for (int64_t it = 0; it < n_iters; ++it) {
       const int32_t* ids = d_ids + it * global_batch + lo;
       if (!exchange_on) {
-        enqueue_step(ctx, plan, nullptr, nullptr, nullptr, nullptr, nullptr, ids, batch, d_w0, d_w,
-                     d_V, lr, nullptr);
+        enqueue_step(ctx, plan, ids, batch, d_w0, d_w, d_V, lr, nullptr);
       } else if (!rows_mode) {
-        double* grad = plan->dp_grad.as<double>();
-        if (batch > 0)
-          enqueue_step(ctx, plan, nullptr, nullptr, nullptr, nullptr, nullptr, ids, batch, d_w0, d_w,
-                       d_V, 0.0, grad);
-        else
-          RFM_HIP_CHECK(hipMemsetAsync(grad, 0, size_t(count) * 8, st));
-        ex.all_reduce_sum(grad, count);
-        hipLaunchKernelGGL(fm_apply_kernel, dim3(apply_grid), dim3(kBlock), 0, st, d_V, d_w, d_w0,
-                           grad, nk, n, lr);
+        exchange_dense(ctx, plan, ex, ids, batch, d_w0, d_w, d_V, lr);
       } else {
-        const int32_t* mine = tp.of(ex.rank, it);
-        const int32_t* seg = tp.seg.data() + it * nb;
-        const int64_t* off = tp.out_off.data() + it * nb;
-        double* rows = plan->dp_rows.as<double>();
-        enqueue_grad_rows(ctx, plan, id0 + int32_t(it), ids, batch, d_w0, d_w, d_V, rows, tp.cap_rows,
-                          d_n_rows, d_gw0, plan->dp_range_lo.as<int32_t>(), W, d_chk);
-        hipLaunchKernelGGL(rows_append_w0_kernel, dim3(1), dim3(kWave), 0, st, rows, d_n_rows,
-                           tp.cap_rows, d_gw0, n, k);
-        hipLaunchKernelGGL(bounds_check_kernel, dim3(1), dim3(kWave * 2), 0, st, d_chk,
-                           plan->dp_bounds.as<int32_t>() + it * nb, W, tp.cap_rows, int32_t(it), d_flag);
-        // records to their owners
-        for (int p = 0; p < W; ++p) {
-          soff[size_t(p)] = int64_t(mine[p]) * int64_t(wb);
-          sbytes[size_t(p)] = int64_t(mine[p + 1] - mine[p]) * int64_t(wb);
-          roff[size_t(p)] = int64_t(seg[p]) * int64_t(wb);
-          rbytes[size_t(p)] = int64_t(seg[p + 1] - seg[p]) * int64_t(wb);
-        }
-        ex.all_to_all(rows, soff.data(), sbytes.data(), plan->dp_recv.p, roff.data(), rbytes.data());
-        // the owner's ordered sums and updated rows, written where they sit in the list of all
-        double* all = plan->dp_all.as<double>();
-        double* out = all + off[ex.rank] * (k + 2);
-        const int64_t total = seg[W];
-        if (total > 0) {
-          const int wpb = kBlock / kWave;
-          const int grid = int(std::min<int64_t>((total + wpb - 1) / wpb, int64_t(ctx->n_cu) * 8));
-          hipLaunchKernelGGL(rows_reduce_kernel, dim3(grid), dim3(kBlock), 0, st,
-                             plan->dp_recv.as<double>(), plan->dp_seg.as<int32_t>() + it * nb, W, d_w,
-                             d_V, n, k, lr, out, d_w0);
-        }
-        // every owner's updated rows to everybody
-        for (int p = 0; p < W; ++p) {
-          soff[size_t(p)] = off[ex.rank] * int64_t(wb);
-          sbytes[size_t(p)] = (off[ex.rank + 1] - off[ex.rank]) * int64_t(wb);
-          roff[size_t(p)] = off[p] * int64_t(wb);
-          rbytes[size_t(p)] = (off[p + 1] - off[p]) * int64_t(wb);
-        }
-        ex.all_to_all(all, soff.data(), sbytes.data(), all, roff.data(), rbytes.data());
-        if (off[W] > 0) {
-          const int wpb = kBlock / kWave;
-          const int grid = int(std::max<int64_t>(
-              1, std::min<int64_t>((off[W] + wpb - 1) / wpb, int64_t(ctx->n_cu) * 8)));
-          hipLaunchKernelGGL(rows_set_kernel, dim3(grid), dim3(kBlock), 0, st, all, off[W],
-                             static_cast<const double*>(nullptr), 0, int64_t(1), d_w0, d_w, d_V, n, k,
-                             lr, true);
-        }
+        exchange_rows(ctx, plan, ex, tp, small, it, id0 + int32_t(it), ids, batch, d_w0, d_w, d_V, lr);
       }
       RFM_HIP_CHECK(hipGetLastError());
-      const int64_t slot = it - run_first;
-      if (d_out_train_loss && batch > 0) {
+      if (train_here) {
         // the shard's part of the train loss: same batch, new parameters (src/fm.py:90-96)
-        FwdArgs f{};
-        f.ent = plan->ent.as<Entry>();
-        f.rows = plan->rows.as<RowRec>();
-        f.ell = plan->ell.as<char>();
-        f.ell_stride = plan->ell_stride;
-        f.ell_yp = plan->ell_yp.as<double2>();
-        f.row_ids = ids;
-        f.n_rows = batch;
-        f.w0 = d_w0;
-        f.w = d_w;
-        f.V = d_V;
-        f.k = k;
+        FwdArgs f = plan_fwd_args(plan, ids, batch, d_w0, d_w, d_V);
         f.eps = eps;
-        train_parts = forward_loss_deferred(ctx, f, train_rows + slot * kMaxFwdGrid);
+        run.train_parts = forward_loss_deferred(ctx, f, run.train_row(it));
       }
-      if (want_val && n_my_val > 0) {
+      if (val_here) {
         FwdArgs f = forward_args(d_val_indptr + vlo, d_val_indices, d_val_values, nullptr, n_my_val,
-                                 d_w0, d_w, d_V, k);
+                                 d_w0, d_w, d_V, plan->k);
         f.y = d_val_y + vlo;
         f.pscore = d_val_pscore + vlo;
         f.eps = eps;
-        val_parts = forward_loss_deferred(ctx, f, val_rows + slot * kMaxFwdGrid);
+        run.val_parts = forward_loss_deferred(ctx, f, run.val_row(it));
       }
-      if (slot + 1 == kRun) {
-        finish(run_first, kRun);
-        run_first = it + 1;
-      }
+      run.close(it, kRun, false, finish);
     }
-    finish(run_first, n_iters - run_first);
-    // the ranks' sums -> the losses, the same on every rank
-    if (exchange_on && (d_out_train_loss || want_val)) ex.all_reduce_sum(plan->dp_sums.as<double>(), 2 * n_iters);
-    const int sgrid = int((n_iters + kBlock - 1) / kBlock);
-    if (d_out_train_loss)
-      hipLaunchKernelGGL(loss_scale_kernel, dim3(sgrid), dim3(kBlock), 0, st, sums_train, n_iters,
-                         double(global_batch), d_out_train_loss);
-    if (want_val)
-      hipLaunchKernelGGL(loss_scale_kernel, dim3(sgrid), dim3(kBlock), 0, st, sums_val, n_iters,
-                         double(n_val), d_out_val_loss);
-    RFM_HIP_CHECK(hipGetLastError());
-    int32_t flag[2] = {0, 0};
-    RFM_HIP_CHECK(hipMemcpyAsync(flag, d_flag, 8, hipMemcpyDeviceToHost, st));
-    RFM_HIP_CHECK(hipStreamSynchronize(st));
-    if (flag[0] != 0)
-      fail(RFM_ERR_INTERNAL,
-           "iteration %d: the gradient records do not match the transfer plan derived from the row ids",
-           flag[0] - 1);
+    run.finish_open(n_iters, finish);
+    dp_losses(ctx, ex, exchange_on, sums_train, n_iters, global_batch, d_out_train_loss, n_val,
+              want_val ? d_out_val_loss : nullptr);
+    small.check(st);
   });
 }

@@ -175,11 +175,6 @@ void upload(DevBuf& dst, const void* src, size_t bytes, hipStream_t stream) {
   if (bytes) RFM_HIP_CHECK(hipMemcpyAsync(dst.p, src, bytes, hipMemcpyHostToDevice, stream));
 }
 
-int grid_for(const rfm_ctx* ctx, int64_t items) {
-  return int(std::max<int64_t>(1, std::min<int64_t>((items + kBlock - 1) / kBlock,
-                                                    int64_t(ctx->n_cu) * 16)));
-}
-
 rfm_fm_plan* build_plan(rfm_ctx* ctx, const int64_t* d_indptr, const int32_t* d_indices,
                         const double* d_values, const double* d_y, const double* d_pscore,
                         int64_t n_rows, int64_t n_features, int32_t n_factors, int64_t max_batch,
@@ -216,7 +211,7 @@ rfm_fm_plan* build_plan(rfm_ctx* ctx, const int64_t* d_indptr, const int32_t* d_
   RFM_HIP_CHECK(hipMemsetAsync(flags.p, 0, 16, st));
   row_of.alloc(std::max<size_t>(nz, 1) * 4);
   plan->rows.alloc(nr * sizeof(RowRec));
-  hipLaunchKernelGGL(plan_rows_kernel, dim3(grid_for(ctx, n_rows)), dim3(kBlock), 0, st, d_indptr,
+  hipLaunchKernelGGL(plan_rows_kernel, dim3(capped_grid(ctx, n_rows, kBlock, 16, 1)), dim3(kBlock), 0, st, d_indptr,
                      d_indices, d_y, d_pscore, n_rows, nnz, n_features, plan->rows.as<RowRec>(),
                      row_of.as<int32_t>(), flags.as<int32_t>());
   RFM_HIP_CHECK(hipGetLastError());
@@ -242,7 +237,7 @@ rfm_fm_plan* build_plan(rfm_ctx* ctx, const int64_t* d_indptr, const int32_t* d_
                                             positions, pos.as<int32_t>(), nz, 0u, unsigned(bits),
                                             st));
   }
-  hipLaunchKernelGGL(plan_starts_kernel, dim3(grid_for(ctx, nnz + 1)), dim3(kBlock), 0, st,
+  hipLaunchKernelGGL(plan_starts_kernel, dim3(capped_grid(ctx, nnz + 1, kBlock, 16, 1)), dim3(kBlock), 0, st,
                      key.as<int32_t>(), pos.as<int32_t>(), row_of.as<int32_t>(), nnz, n_features,
                      cstart.as<int32_t>(), flags.as<int32_t>());
   RFM_HIP_CHECK(hipGetLastError());
@@ -378,7 +373,7 @@ rfm_fm_plan* build_plan(rfm_ctx* ctx, const int64_t* d_indptr, const int32_t* d_
   plan->slots.alloc((ns + 256) * sizeof(SlotRec));
   RFM_HIP_CHECK(hipMemsetAsync(plan->slots.p, 0, plan->slots.bytes, st));
   if (nnz > 0) {
-    hipLaunchKernelGGL(plan_scatter_kernel, dim3(grid_for(ctx, nnz)), dim3(kBlock), 0, st,
+    hipLaunchKernelGGL(plan_scatter_kernel, dim3(capped_grid(ctx, nnz, kBlock, 16, 1)), dim3(kBlock), 0, st,
                        key.as<int32_t>(), pos.as<int32_t>(), d_values, d_colinfo.as<int32_t>(),
                        nnz, plan->ent.as<Entry>(), plan->slots.as<SlotRec>());
     RFM_HIP_CHECK(hipGetLastError());
@@ -394,7 +389,7 @@ rfm_fm_plan* build_plan(rfm_ctx* ctx, const int64_t* d_indptr, const int32_t* d_
     plan->ell_stride = int64_t(shp.lpr) * int64_t(sizeof(Entry));
     plan->ell.alloc(nr * size_t(plan->ell_stride));
     plan->ell_yp.alloc(nr * 16);
-    hipLaunchKernelGGL(plan_ell_kernel, dim3(grid_for(ctx, n_rows * shp.lpr)), dim3(kBlock), 0, st,
+    hipLaunchKernelGGL(plan_ell_kernel, dim3(capped_grid(ctx, n_rows * shp.lpr, kBlock, 16, 1)), dim3(kBlock), 0, st,
                        plan->rows.as<RowRec>(), plan->ent.as<Entry>(), n_rows, shp.lpr,
                        plan->ell.as<char>(), plan->ell_stride, plan->ell_yp.as<double2>());
     RFM_HIP_CHECK(hipGetLastError());
@@ -436,7 +431,7 @@ rfm_fm_plan* build_plan(rfm_ctx* ctx, const int64_t* d_indptr, const int32_t* d_
       upload(plan->sl_pad, &pad_record, sizeof(SlEnt), st);
       // the training log in its translated form (rows of 2^mll records)
       plan->sl_train.alloc((nr << mll) * sizeof(SlEnt));
-      hipLaunchKernelGGL(sl_translate_kernel, dim3(grid_for(ctx, n_rows << mll)), dim3(kBlock), 0, st,
+      hipLaunchKernelGGL(sl_translate_kernel, dim3(capped_grid(ctx, n_rows << mll, kBlock, 16, 1)), dim3(kBlock), 0, st,
                          d_indptr, d_indices, d_values, n_rows, plan->sl_rank.as<int32_t>(), mll,
                          plan->sl_n_cached, sliced_row_bytes(sw), plan->sl_train.as<SlEnt>());
       RFM_HIP_CHECK(hipGetLastError());
@@ -471,7 +466,7 @@ void sliced_translate(rfm_ctx* ctx, const rfm_fm_plan* plan, const int64_t* d_in
   const int mll = plan->sl_ml_log2;
   out.ensure((size_t(std::max<int64_t>(n_rows, 1)) << mll) * sizeof(SlEnt));
   if (n_rows <= 0) return;
-  hipLaunchKernelGGL(sl_translate_kernel, dim3(grid_for(ctx, n_rows << mll)), dim3(kBlock), 0,
+  hipLaunchKernelGGL(sl_translate_kernel, dim3(capped_grid(ctx, n_rows << mll, kBlock, 16, 1)), dim3(kBlock), 0,
                      ctx->stream, d_indptr, d_indices, d_values, n_rows,
                      plan->sl_rank.as<int32_t>(), mll, plan->sl_n_cached,
                      sliced_row_bytes(plan->sl_sw), out.as<SlEnt>());
@@ -563,7 +558,7 @@ int32_t rfm_fm_plan_register_log(rfm_ctx* ctx, rfm_fm_plan* plan, int32_t slot, 
         log.rows_rec.ensure(size_t(n_rows) * sizeof(RowRec));
         log.ent_rec.ensure(size_t(nnz + 1) * sizeof(Entry));
         RFM_HIP_CHECK(hipMemsetAsync(log.ent_rec.as<Entry>() + nnz, 0, sizeof(Entry), ctx->stream));
-        hipLaunchKernelGGL(log_records_kernel, dim3(grid_for(ctx, n_rows)), dim3(kBlock), 0, ctx->stream,
+        hipLaunchKernelGGL(log_records_kernel, dim3(capped_grid(ctx, n_rows, kBlock, 16, 1)), dim3(kBlock), 0, ctx->stream,
                            d_indptr, d_indices, d_values, n_rows, log.rows_rec.as<RowRec>(),
                            log.ent_rec.as<Entry>());
         RFM_HIP_CHECK(hipGetLastError());

@@ -12,7 +12,6 @@
 // ONE workgroup that walks the levels with a barrier in between, so a batch
 // whose popular item forms a long chain costs one launch, not one per level.
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 
 #include "rfm_common.h"
@@ -486,17 +485,11 @@ __global__ __launch_bounds__(seq_block(NC)) void mf_sgd_seq_ex_kernel(MfExArgs a
 }
 
 // the sequential kernel with its dynamic-LDS limit raised where the item cache needs it
-// (remembered per device and instantiation)
 template <int L, int Vv, int N>
 static void launch_seq_ex(rfm_ctx* ctx, const MfExArgs& a, int threads, size_t lds) {
   const auto kern = &mf_sgd_seq_ex_kernel<L, Vv, N>;
-  static std::atomic<bool> raised[64];
-  const int dev = ctx->device >= 0 && ctx->device < 64 ? ctx->device : 0;
-  if (lds > (64u << 10) && !raised[dev].load(std::memory_order_relaxed)) {
-    RFM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10));
-    raised[dev].store(true, std::memory_order_relaxed);
-  }
+  static LdsLimits allowed;
+  allow_dynamic_lds(ctx, reinterpret_cast<const void*>(kern), lds, allowed);
   hipLaunchKernelGGL(kern, dim3(1), dim3(threads), lds, ctx->stream, a);
 }
 
@@ -504,8 +497,7 @@ static void mf_predict_launch(rfm_ctx* ctx, MfPredArgs a, double* d_out_loss) {
   if (a.n_rows <= 0) return;
   const Shape s = shape_for(a.k);
   const int gpb = kMfBlock / s.lpr;
-  const int grid = int(std::max<int64_t>(
-      1, std::min<int64_t>((a.n_rows + gpb - 1) / gpb, int64_t(ctx->n_cu) * 8)));
+  const int grid = capped_grid(ctx, a.n_rows, gpb, 8, 1);
   if (d_out_loss) {
     ctx->loss_partials.ensure(size_t(ctx->n_cu) * 8 * sizeof(double));
     a.loss_partial = ctx->loss_partials.as<double>();
@@ -639,7 +631,7 @@ int32_t rfm_mf_sgd_levels(rfm_ctx* ctx, const int32_t* d_users, const int32_t* d
         a.lo = h_level_ptr[lev];
         a.hi = h_level_ptr[lev + 1];
         const int gpb = kMfBlock / s.lpr;
-        const int grid = std::min((cnt + gpb - 1) / gpb, ctx->n_cu * 8);
+        const int grid = capped_grid(ctx, cnt, gpb, 8, 0);
 #define RFM_CALL_WIDE(L, Vv, N)                                                               \
   hipLaunchKernelGGL((mf_sgd_wide_kernel<L, Vv, N>), dim3(grid), dim3(kMfBlock), 0, ctx->stream, \
                      a)
@@ -707,7 +699,7 @@ int32_t rfm_mf_sgd_levels_ex(rfm_ctx* ctx, const void* d_ex, const int32_t* h_le
         a.lo = h_level_ptr[lev];
         a.hi = h_level_ptr[lev + 1];
         const int gpb = kMfBlock / s.lpr;
-        const int grid = std::min((cnt + gpb - 1) / gpb, ctx->n_cu * 8);
+        const int grid = capped_grid(ctx, cnt, gpb, 8, 0);
 #define RFM_CALL_WIDE_EX(L, Vv, N)                                                            \
   hipLaunchKernelGGL((mf_sgd_wide_ex_kernel<L, Vv, N>), dim3(grid), dim3(kMfBlock), 0,        \
                      ctx->stream, a)
@@ -769,7 +761,7 @@ int32_t rfm_mf_sgd_hogwild(rfm_ctx* ctx, const int32_t* d_users, const int32_t* 
     a.lr = lr;
     a.reg = reg;
     const int gpb = kMfBlock / s.lpr;
-    const int grid = int(std::min<int64_t>((batch + gpb - 1) / gpb, int64_t(ctx->n_cu) * 8));
+    const int grid = capped_grid(ctx, batch, gpb, 8, 0);
 #define RFM_CALL_HOG(L, Vv, N)                                                                \
   hipLaunchKernelGGL((mf_sgd_wide_kernel<L, Vv, N>), dim3(grid), dim3(kMfBlock), 0, ctx->stream, \
                      a)
@@ -785,7 +777,7 @@ int32_t rfm_mf_delta(rfm_ctx* ctx, const double* d_cur, const double* d_sync, do
     RFM_REQUIRE(ctx && count >= 0, "bad argument");
     if (count == 0) return;
     RFM_REQUIRE(d_cur && d_sync && d_out, "null pointer");
-    const int grid = int(std::min<int64_t>((count + 255) / 256, int64_t(ctx->n_cu) * 16));
+    const int grid = capped_grid(ctx, count, 256, 16, 0);
     hipLaunchKernelGGL(mf_delta_kernel, dim3(grid), dim3(256), 0, ctx->stream, d_cur, d_sync, d_out,
                        count);
     RFM_HIP_CHECK(hipGetLastError());
@@ -798,7 +790,7 @@ int32_t rfm_mf_merge(rfm_ctx* ctx, double* d_cur, double* d_sync, const double* 
     RFM_REQUIRE(ctx && count >= 0, "bad argument");
     if (count == 0) return;
     RFM_REQUIRE(d_cur && d_sync && d_total, "null pointer");
-    const int grid = int(std::min<int64_t>((count + 255) / 256, int64_t(ctx->n_cu) * 16));
+    const int grid = capped_grid(ctx, count, 256, 16, 0);
     hipLaunchKernelGGL(mf_merge_kernel, dim3(grid), dim3(256), 0, ctx->stream, d_cur, d_sync,
                        d_total, count);
     RFM_HIP_CHECK(hipGetLastError());

@@ -116,20 +116,6 @@ def init_direct_rccl(rt, world: int, rank: int) -> bool:
     return True
 
 
-def hip_fm_train_dp(rt, plan, d_ids, global_batch: int, first: int, count: int, model, grad,
-                    world: int, rank: int, lr: float) -> None:
-    """``count`` data-parallel iterations starting at ``first`` in one C call
-    (``rfm_fm_train_dp``): gradient of this rank's shard, RCCL all-reduce on the
-    compute stream, identical apply -- no host round trip between the three."""
-    from . import _lib
-
-    lo, hi = shard_bounds(global_batch, world, rank)
-    _lib.check(rt.lib.rfm_fm_train_dp(
-        rt.ctx, plan.handle, d_ids.data_ptr() + first * global_batch * 4, global_batch, lo, hi, count,
-        model.w0.dev.data_ptr(), model.w.dev.data_ptr(), model.V.dev.data_ptr(), float(lr),
-        grad.data_ptr()))
-
-
 # ---------------------------------------------------------------------------
 # touched-row exchange (SURVEY.md 8e, option 1: feature-range ownership)
 # ---------------------------------------------------------------------------

@@ -114,17 +114,26 @@ def test_rccl_binding_single_rank():
         _lib.check(rt.lib.rfm_comm_destroy(rt.ctx))
 
 
-def test_train_dp_single_rank_equals_step():
-    """rfm_fm_train_dp with the whole batch as this rank's shard (no exchange) is
-    grad + apply of every iteration, i.e. the fused step."""
-    import torch
+def test_fit_dp_dense_single_rank_equals_step(monkeypatch):
+    """rfm_fm_fit_dp's dense exchange (exchange=0) with the whole batch as this rank's shard, forced
+    through a one-rank RCCL communicator (RFM_DP_FORCE_EXCHANGE=1) and with no loss outputs, is
+    grad + all-reduce + apply of every iteration, i.e. the fused step."""
+    import ctypes as C
     from relevance_factorizationmachine_amd import _lib
-    from relevance_factorizationmachine_amd.dist import hip_fm_train_dp
 
+    monkeypatch.setenv("RFM_DP_FORCE_EXCHANGE", "1")
     rt, model, csr, y, p, plan, ids = _setup()
-    grad = rt.empty((model.n_features * (K + 1) + 1,), torch.float64)
-    hip_fm_train_dp(rt, plan, ids, BATCH, 0, N_STEPS, model, grad, 1, 0, LR)
-    rt.sync()
+    uid = (C.c_uint8 * 128)()
+    _lib.check(rt.lib.rfm_comm_unique_id(uid))
+    _lib.check(rt.lib.rfm_comm_init(rt.ctx, 1, 0, uid))
+    try:
+        _lib.check(rt.lib.rfm_fm_fit_dp(rt.ctx, plan.handle, None, 0, ids.data_ptr(), BATCH, N_STEPS,
+                                        model.w0.dev.data_ptr(), model.w.dev.data_ptr(), model.V.dev.data_ptr(),
+                                        LR, None, None, None, None, None, 0, 0.0, None, None))
+        rt.sync()
+    finally:
+        _lib.check(rt.lib.rfm_comm_destroy(rt.ctx))
+    monkeypatch.delenv("RFM_DP_FORCE_EXCHANGE")
     rt2, ref, csr2, y2, p2, plan2, ids2 = _setup()
     for it in range(N_STEPS):
         _lib.check(rt2.lib.rfm_fm_step(rt2.ctx, plan2.handle, csr2.indptr.data_ptr(), csr2.indices.data_ptr(),
