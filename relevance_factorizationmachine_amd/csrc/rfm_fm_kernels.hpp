@@ -147,6 +147,15 @@ struct FwdArgs {
   double* out_pred_y;
 };
 
+// what the arrival-order hot pass leaves in place of an entry record (16 B): the offset of the
+// entry's column in the hot sums (-1: no add) and err * x
+struct HotEnt {
+  int32_t off;
+  int32_t pad;
+  double coef;
+};
+static_assert(sizeof(HotEnt) == sizeof(Entry), "HotEnt replaces an Entry in place");
+
 // A row is handled by LPR consecutive lanes; lane l holds factors
 // (c*LPR + l)*VEC .. +VEC-1 for c < NC.  k=32 -> LPR=16, VEC=2: one 16-byte
 // load per lane covers a 256-byte row of V, four rows per wave.
@@ -423,6 +432,11 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? kBigWaves : 1)) void f
 #pragma unroll
       for (int i = 0; i < R; ++i) nxt[i] = parked[i * GPB + g];
     }
+    // the labels are in registers on every path from here: a path that leaves their loads
+    // pending makes the compiler drain ALL memory operations (the next trip's touches, the
+    // marks) with a vmcnt(0) in the hot pass, before it rewrites their registers
+#pragma unroll
+    for (int i = 0; i < R; ++i) asm volatile("" ::"v"(yy[i]), "v"(pp[i]));
 #pragma unroll
     for (int i = 0; i < R; ++i) {
       if (len[i] == 0) {  // an empty row scores sigmoid(w0) whatever its padding gathered
@@ -517,7 +531,7 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? kBigWaves : 1)) void f
           if (rounds_len > LPR) {  // (never in the padded form)
             em[i] = a.ent[len[i] > 0 ? p0[i] + min(pb + l, len[i] - 1) : 0];
             if (pb + l >= len[i]) em[i] = Entry{0, 0, 0.0};
-            ebuf[i * LPR + l] = em[i];
+            if (FIX) ebuf[i * LPR + l] = em[i];
           } else {
             em[i] = ebuf[i * LPR + l];
           }
@@ -665,40 +679,58 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? kBigWaves : 1)) void f
           }
           continue;
         }
+        // ---- arrival-order hot sums (LDS float atomics) ----
         const int cnt = (maxlen - pb) < LPR ? (maxlen - pb) : LPR;
+        // the entries of the round the wave walks: the largest count of its active groups
+        // (one ballot per bit: the lanes of groups that have left the rounds take no part),
+        // so that the walk below is a scalar loop
+        int wcnt = 0;
+#pragma unroll
+        for (int b = LPR; b > 0; b >>= 1)
+          if (__ballot(cnt >= (wcnt | b))) wcnt |= b;
         // the lane groups of a wave start at different entries: rows of one log
         // tend to hold the same hot column at the same position, and adds to one
         // LDS address from several groups in one instruction serialise
-        const int rot = ((g % (kWave / LPR)) * cnt) / (kWave / LPR);
-        for (int jj = 0; jj < cnt; ++jj) {
-          const int j = jj + rot < cnt ? jj + rot : jj + rot - cnt;
-          Entry eh[R];
-          bool on[R];
+        const int rot = ((g % (kWave / LPR)) * wcnt) / (kWave / LPR);
+        // each lane prepares its own entry once: the offset of its column's sums in `hot`
+        // (-1: not a hot entry, or past the row's end) and err * x, written over the round's
+        // records at position l - rot of the walk; and it adds the entry's [k] / [k+1] sums
+        // itself (the lanes of a row hold distinct columns)
+        HotEnt* const hbuf = reinterpret_cast<HotEnt*>(ebuf);
+        const int at = l - rot < 0 ? l - rot + wcnt : l - rot;
 #pragma unroll
-          for (int i = 0; i < R; ++i) {
-            eh[i] = ebuf[i * LPR + j];
-            on[i] = eh[i].slot < 0 && pb + j < len[i];
+        for (int i = 0; i < R; ++i) {
+          const bool on = pb + l < len[i] && em[i].slot < 0;
+          const int off = on ? (-1 - em[i].slot) * hot_w : -1;
+          const double coef = err[i] * em[i].x;
+          if (l < wcnt) hbuf[i * LPR + at] = HotEnt{off, 0, coef};
+          if (on) {  // (-slot * hot_w - 2 = off + k: no k in a scalar register here)
+            double* const hsum = hot + (-em[i].slot * hot_w - 2);
+            unsafeAtomicAdd(hsum, coef);
+            unsafeAtomicAdd(hsum + 1, coef * em[i].x);
           }
+        }
+        for (int j = 0; j < wcnt; ++j) {
+          HotEnt eh[R];
+#pragma unroll
+          for (int i = 0; i < R; ++i) eh[i] = hbuf[i * LPR + j];  // broadcast in the group
           // two rows of the group holding the same hot column: one add for both
-          const bool pair01 = R == 2 && on[0] && on[R - 1] && eh[0].slot == eh[R - 1].slot;
+          const bool pair01 = R == 2 && eh[0].off >= 0 && eh[0].off == eh[R - 1].off;
+          const double coef2 = pair01 ? eh[R - 1].coef : 0.0;
+          if (pair01) eh[R - 1].off = -1;
 #pragma unroll
           for (int i = 0; i < R; ++i) {
-            if (!on[i] || (pair01 && i == R - 1)) continue;
-            const double coef = err[i] * eh[i].x;
-            const double coef2 = pair01 ? err[R - 1] * eh[R - 1].x : 0.0;
-            double* hrow = hot + (-1 - eh[i].slot) * hot_w;
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
-              if (fok[c]) {
+              if (eh[i].off >= 0 && fok[c]) {
+                double* hrow = hot + eh[i].off + fo[c];
 #pragma unroll
                 for (int v = 0; v < VEC; ++v)
-                  unsafeAtomicAdd(hrow + fo[c] + v, coef * q[i][c][v] + coef2 * q[R - 1][c][v]);
+                  unsafeAtomicAdd(hrow + v, R == 2 && i == 0
+                                                ? eh[0].coef * q[0][c][v] + coef2 * q[R - 1][c][v]
+                                                : eh[i].coef * q[i][c][v]);
               }
             }
-            // sum coef (lane 0) and sum coef*x (lane 1) in one instruction
-            if (l < 2)
-              unsafeAtomicAdd(hrow + k + l, l == 0 ? coef + coef2
-                                                   : coef * eh[i].x + coef2 * eh[R - 1].x);
           }
         }
       }
