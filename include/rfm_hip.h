@@ -90,6 +90,21 @@ int32_t rfm_profile_end(rfm_ctx* ctx, double* h_ms, int64_t* h_count);
 int32_t rfm_sample_batches(int64_t n_rows, int64_t batch_size, int64_t epoch_begin,
                            int64_t n_epochs, int32_t* h_out_ids, int32_t n_threads);
 
+/* ---- mini-batch selection (device) -------------------------------------
+ * rfm_sample_batches on the GPU: d_out_ids[(e - epoch_begin) * batch_size + t], bit-identical
+ * to the host sampler, enqueued on hip_stream (NULL = the ctx's stream).  The swap partners of
+ * the shuffle are drawn by one wavefront per epoch; the first batch_size entries are then
+ * resolved in parallel from them (rfm_sample.hip).  Epochs run in groups that share
+ * d_workspace; the results do not depend on its size.  Argument checks and messages are those
+ * of rfm_sample_batches; RFM_ERR_BAD_ARG also when the workspace is short of one epoch's.
+ * rfm_sample_batches_device_workspace: the bytes `epochs_in_flight` epochs at once need
+ * (12 n_rows + 8 batch_size per epoch; host only). */
+int32_t rfm_sample_batches_device_workspace(int64_t n_rows, int64_t batch_size,
+                                            int64_t epochs_in_flight, int64_t* h_bytes);
+int32_t rfm_sample_batches_device(rfm_ctx* ctx, void* hip_stream, int64_t n_rows,
+                                  int64_t batch_size, int64_t epoch_begin, int64_t n_epochs,
+                                  int32_t* d_out_ids, void* d_workspace, int64_t workspace_bytes);
+
 /* ---- content fingerprint of a host buffer (host) -------------------------
  * Not on the reference's path: the reference reads its inputs on every fit()
  * (src/fm.py:72-79 gathers from train["features"] each iteration); this library keeps device

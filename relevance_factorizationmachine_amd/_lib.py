@@ -17,7 +17,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 # RFM_LIB_PATH: load another build of the same ABI (timing experiments under profiles/)
 LIB_PATH = os.environ.get("RFM_LIB_PATH") or os.path.join(PKG_DIR, "librfm_hip.so")
-SOURCES = ["rfm_capi.hip", "rfm_fm.hip", "rfm_fm_plan.hip", "rfm_mf.hip", "rfm_eval.hip", "rfm_csr.hip", "rfm_host.cpp", "rfm_comm.cpp"]
+SOURCES = ["rfm_capi.hip", "rfm_fm.hip", "rfm_fm_plan.hip", "rfm_mf.hip", "rfm_eval.hip", "rfm_csr.hip", "rfm_sample.hip", "rfm_host.cpp", "rfm_comm.cpp"]
 # every header under csrc/ (a change of any of them rebuilds every object) + the C ABI
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp"))) + [
     os.path.join(os.path.dirname(PKG_DIR), "include", "rfm_hip.h")]
@@ -109,6 +109,8 @@ SIGNATURES = {
     "rfm_profile_begin": [_vp],
     "rfm_profile_end": [_vp, _vp, _vp],
     "rfm_sample_batches": [_i64, _i64, _i64, _i64, _vp, _i32],
+    "rfm_sample_batches_device_workspace": [_i64, _i64, _i64, C.POINTER(_i64)],
+    "rfm_sample_batches_device": [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64],
     "rfm_hash_bytes": [_vp, _i64, _i32, _vp],
     "rfm_fm_forward": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp],
     "rfm_ips_logloss": [_vp, _vp, _vp, _vp, _vp, _i64, _f64, _vp],

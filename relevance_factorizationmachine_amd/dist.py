@@ -605,7 +605,8 @@ class HipDpEngine:
         if X.shape[1] != model.n_features:
             raise ValueError(f"train features have {X.shape[1]} columns, model has {model.n_features}")
         self.global_batch = model.batch_size
-        self.ids = BatchIdStream(rt, X.shape[0], self.global_batch, model.n_epochs, need_host=False)
+        self.ids = BatchIdStream(rt, X.shape[0], self.global_batch, model.n_epochs, need_host=False,
+                                 device_sampler=getattr(model, "device_sampler", False))
         try:
             self.tr = X if isinstance(X, DeviceCSR) else DeviceCSR(rt, X)
             self.y = rt.upload(np.asarray(train["labels"]), dtype=np.float64)

@@ -156,6 +156,11 @@ class FactorizationMachines(PointwiseBaseRecommender):
     # Not a constructor argument: a ValEvaluator-like ``evaluator`` (see evaluate.py) is
     # computed on the device; False keeps the host callback for every evaluator.
     device_evaluator = True
+    # Not a constructor argument: True samples the mini-batch ids on the device
+    # (runtime.sample_batches_device, bit-identical to the host sampler) instead of on the host
+    # cores; fit() and dist.fit_data_parallel honour it.  Off by default until it outruns the
+    # host threads on a cold fit.
+    device_sampler = False
 
     def __post_init__(self) -> None:
         # src/fm.py:31-53 -- the reference's NumPy calls, in its draw order
@@ -187,9 +192,11 @@ class FactorizationMachines(PointwiseBaseRecommender):
             raise ValueError(f"train features have {X.shape[1]} columns, model has {self.n_features}")
         if self.n_epochs <= 0:
             return [], []
-        # batch selection: resample(..., random_state=epoch) (src/fm.py:72-79), sampled on the
-        # host chunk by chunk while the GPU trains on the chunk before
-        id_stream = BatchIdStream(rt, n_rows, self.batch_size, self.n_epochs, need_host=False)
+        # batch selection: resample(..., random_state=epoch) (src/fm.py:72-79), sampled chunk by
+        # chunk on the host (or on the sampler stream: device_sampler) while the GPU trains on
+        # the chunk before
+        id_stream = BatchIdStream(rt, n_rows, self.batch_size, self.n_epochs, need_host=False,
+                                  device_sampler=self.device_sampler)
         try:
             return self._fit(train, val, id_stream)
         finally:

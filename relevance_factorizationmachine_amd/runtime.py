@@ -1,6 +1,6 @@
 """Device plumbing: a per-device context of librfm_hip.so, torch tensors as the
-device containers, and the host-side helpers (sampler, MF schedule) that need
-no GPU.  PyTorch is used for allocation, copies and streams only -- no torch
+device containers, the device sampler, and the host-side helpers (sampler, MF schedule) that
+need no GPU.  PyTorch is used for allocation, copies and streams only -- no torch
 operator runs on the training path."""
 from __future__ import annotations
 
@@ -93,6 +93,13 @@ class Runtime:
         if getattr(self, "_copy_stream", None) is None:
             self._copy_stream = _torch().cuda.Stream(device=self.torch_device)
         return self._copy_stream
+
+    def sampler_stream(self):
+        """A stream for the device sampler (``sample_batches_device``): its kernels run beside
+        the training kernels of the compute stream, which waits for each chunk's event."""
+        if getattr(self, "_sampler_stream", None) is None:
+            self._sampler_stream = _torch().cuda.Stream(device=self.torch_device)
+        return self._sampler_stream
 
     def copy_into_async(self, dst, pinned_src):
         """``dst.copy_(pinned_src)`` on the copy stream; returns the event that marks its end.
@@ -243,6 +250,47 @@ def sample_batches(n_rows: int, batch_size: int, epoch_begin: int, n_epochs: int
     return out
 
 
+# ---- the device sampler ------------------------------------------------------
+# the device sampler's workspace (12 N + 8 B bytes per epoch in flight) is capped at this
+SAMPLER_WORKSPACE_CAP = 1 << 30
+
+
+def sampler_workspace_bytes(n_rows: int, batch_size: int, epochs_in_flight: int = 1) -> int:
+    """Bytes of workspace ``rfm_sample_batches_device`` needs for ``epochs_in_flight`` epochs at
+    once (``rfm_sample_batches_device_workspace``); raises ValueError like ``sample_batches``."""
+    out = C.c_int64(0)
+    _lib.check(_lib.load().rfm_sample_batches_device_workspace(n_rows, batch_size, epochs_in_flight,
+                                                               C.byref(out)))
+    return int(out.value)
+
+
+def sample_batches_device(rt: "Runtime", n_rows: int, batch_size: int, epoch_begin: int, n_epochs: int,
+                          out=None, stream=None, workspace=None):
+    """``sample_batches`` on the GPU: the same ids, bit for bit, as an ``(n_epochs, B)`` int32
+    device tensor, enqueued on ``stream`` (a torch stream; None = the current stream).  The
+    workspace (``workspace``, a byte tensor, or one allocated here on that stream) holds as many
+    epochs at once as fit under ``SAMPLER_WORKSPACE_CAP``.  Raises ValueError if
+    ``batch_size > n_rows`` or the workspace is short of one epoch."""
+    torch = _torch()
+    n_epochs = max(int(n_epochs), 0)
+    per_epoch = sampler_workspace_bytes(n_rows, batch_size, 1)
+    if out is None:
+        out = rt.empty((n_epochs, batch_size), torch.int32)
+    assert (tuple(out.shape) == (n_epochs, batch_size) and out.dtype == torch.int32 and out.is_contiguous()
+            and out.device == rt.torch_device)
+    with torch.cuda.device(rt.device):
+        stream = torch.cuda.current_stream() if stream is None else stream
+        if workspace is None and n_epochs:
+            group = max(1, min(n_epochs, SAMPLER_WORKSPACE_CAP // per_epoch))
+            with torch.cuda.stream(stream):  # (freed into this stream's pool: reused in its order)
+                workspace = torch.empty((group * per_epoch,), dtype=torch.uint8, device=rt.torch_device)
+        ws_ptr, ws_bytes = (workspace.data_ptr(), workspace.numel()) if workspace is not None else (None, 0)
+        _lib.check(rt.lib.rfm_sample_batches_device(
+            rt.ctx, C.c_void_p(stream.cuda_stream), n_rows, batch_size, epoch_begin, n_epochs,
+            out.data_ptr() if n_epochs else None, ws_ptr, ws_bytes))
+    return out
+
+
 class _IdCache:
     """Row ids of iteration ``epoch`` of a log of ``n_rows`` rows depend on nothing else
     (``resample(..., random_state=epoch)``), and the drivers fit several models on the same
@@ -308,26 +356,35 @@ ID_CACHE = _IdCache()
 
 
 class BatchIdStream:
-    """The row-id lists of a whole ``fit()`` in chunks of iterations (the
-    Mersenne-Twister shuffle is inherently sequential per iteration, so it stays on the host
-    cores -- one iteration per thread -- and is overlapped rather than moved).  The first,
-    small chunk is sampled in the constructor (a batch larger than the log raises there,
-    before anything is uploaded); a background thread samples the rest, exact ``resample``
-    ids, while the caller uploads the log, builds the plan and the GPU trains.
+    """The row-id lists of a whole ``fit()`` in chunks of iterations, exact ``resample`` ids.
 
     ``need_host=False`` (FM: nothing on the host reads the ids): the fit's ids live in ONE
-    device buffer; every chunk is sampled straight into pinned memory and copied on the
-    runtime's copy stream by the sampler thread, and the consumer only makes the compute stream
-    wait for the copy's event -- no upload blocks the host or queues behind the kernels.  The
-    filled buffer is remembered (``ID_CACHE``): another fit on a log of the same length with
-    the same batch size samples and uploads nothing."""
+    device buffer, and with ``device_sampler=True`` the GPU samples them: every chunk
+    is enqueued in the constructor on the runtime's sampler stream (``sample_batches_device``:
+    the shuffle's swap partners are drawn by one wavefront per iteration, the batch is then
+    resolved from them in parallel), and the consumer only makes the compute stream wait for the
+    chunk's event -- the host samples nothing and the sampler kernels run beside the training
+    kernels.  Where one iteration's sampler workspace would exceed ``SAMPLER_WORKSPACE_CAP``, or
+    with ``device_sampler=False``, the host path below fills the buffer instead.  The filled
+    buffer is remembered (``ID_CACHE``): another fit on a log of the same length with the same
+    batch size samples nothing.  It is not the default: one wavefront draws an iteration's swap
+    partners in about 8 ms at N = 1 M and the workspace cap holds about 85 such iterations at
+    once, so at 150-180 us per iteration it does not yet outrun 16-32 host threads.
+
+    Host path (``need_host=True``, MF, whose schedule is built on the host; or as above): the
+    first, small chunk is sampled in the constructor (a batch larger than the log raises there,
+    before anything is uploaded); a background thread samples the rest on the host cores, one
+    iteration per thread, while the caller uploads the log, builds the plan and the GPU trains.
+    For a device buffer every chunk is sampled straight into pinned memory and copied on the
+    runtime's copy stream by the sampler thread; the compute stream waits for the copy's event."""
 
     CHUNK_IDS = 1 << 23   # most ids per chunk: 32 MiB of int32
     FIRST_ITERS = 16      # iterations of the first chunk: the GPU starts after one sampler round
     CHUNK_ITERS = 64      # iterations of the later chunks
     QUEUE_DEPTH = 4       # sampled chunks waiting for the consumer
 
-    def __init__(self, rt: Runtime, n_rows: int, batch_size: int, n_epochs: int, need_host: bool = True):
+    def __init__(self, rt: Runtime, n_rows: int, batch_size: int, n_epochs: int, need_host: bool = True,
+                 device_sampler: bool = False):
         import queue
         import threading
 
@@ -345,6 +402,8 @@ class BatchIdStream:
         self._dev_all = None     # the fit's ids in HBM (need_host=False)
         self._resident = False   # ... found there: nothing to sample
         self._staging = []       # [pinned buffer, event of the copy that last read it]
+        self._events = None      # device sampler: the event of each chunk's kernels
+        self._workspace = None   # ... and their workspace (allocated on the sampler stream)
         self._first = None
         if not cuts:
             return
@@ -358,6 +417,10 @@ class BatchIdStream:
                 return
             torch = _torch()
             self._dev_all = rt.empty((n_epochs, batch_size), torch.int32)
+            per_epoch = sampler_workspace_bytes(n_rows, batch_size)
+            if device_sampler and per_epoch <= SAMPLER_WORKSPACE_CAP:
+                self._sample_on_device(per_epoch)
+                return
             with torch.cuda.device(rt.device):  # (the block may have had a user on the compute stream)
                 rt.copy_stream().wait_stream(torch.cuda.current_stream())
             rows = max(size for _, size in cuts)
@@ -369,6 +432,33 @@ class BatchIdStream:
         if len(cuts) > 1:
             self._thread = threading.Thread(target=self._work, name="rfm-sampler", daemon=True)
             self._thread.start()
+
+    def _sample_on_device(self, per_epoch: int) -> None:
+        """Enqueue every chunk on the sampler stream.  Chunks are the sampler's groups (as many
+        iterations as fit in the workspace cap, evened out over the fit): the iterations of a
+        group are drawn at once, so a smaller chunk would not arrive sooner."""
+        torch = _torch()
+        rt, n_epochs = self.rt, self.n_epochs
+        group = max(1, min(n_epochs, SAMPLER_WORKSPACE_CAP // per_epoch))
+        n_groups = -(-n_epochs // group)
+        size = -(-n_epochs // n_groups)
+        self._cuts = [(at, min(size, n_epochs - at)) for at in range(0, n_epochs, size)]
+        stream = rt.sampler_stream()
+        with torch.cuda.device(rt.device):
+            stream.wait_stream(torch.cuda.current_stream())  # (the buffer's block may have had a user)
+            self._dev_all.record_stream(stream)
+            with torch.cuda.stream(stream):
+                # freed into the sampler stream's pool: no other stream reuses it before the
+                # kernels enqueued here are done
+                self._workspace = torch.empty((size * per_epoch,), dtype=torch.uint8, device=rt.torch_device)
+            self._events = []
+            for first, count in self._cuts:
+                sample_batches_device(rt, self.n_rows, self.batch_size, first, count,
+                                      out=self._dev_all[first:first + count], stream=stream,
+                                      workspace=self._workspace)
+                ev = torch.cuda.Event()
+                ev.record(stream)
+                self._events.append(ev)
 
     def _sample(self, first: int, count: int, out: Optional[np.ndarray] = None) -> np.ndarray:
         got = ID_CACHE.get(self.n_rows, self.batch_size, first, count)
@@ -414,7 +504,9 @@ class BatchIdStream:
         complete = False
         try:
             for i, (first, count) in enumerate(self._cuts):
-                if i == 0:
+                if self._events is not None:
+                    got = self._events[i]
+                elif i == 0:
                     got = self._first
                 else:
                     got_first, got = self._queue.get()
@@ -445,6 +537,7 @@ class BatchIdStream:
                     self._queue.get_nowait()
                 except Exception:  # noqa: BLE001 -- empty
                     thread.join(timeout=0.01)
+        self._workspace = None  # (its block goes back to the sampler stream's pool: see above)
         if self._dev_all is not None and not self._resident:
             for _, ev in self._staging:
                 if ev is not None:
