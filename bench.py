@@ -2,7 +2,7 @@
 """Headline benchmark: FM (k=32) training examples/s on the KuaiRec-big-shaped
 synthetic log (BASELINE.json config 3), one process per GPU.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A *step* is one mini-batch pass of the hot path over rows already resident in
 HBM: gather by row id -> forward -> IPS residual -> batch-sum gradients -> SGD
@@ -15,10 +15,14 @@ per GPU).  Rank 0 prints ONE JSON line.  ``--dump-outputs DIR`` also writes the 
 the last timed step left, W + reps x K steps from the seeded initial model (``DIR/w0.npy``,
 ``w.npy``, ``V.npy``), for build-to-build comparison.
 
-What the line carries besides the contract's fields:
- * the timed region (exactly K steps between barrier + synchronize) is repeated
-   --reps times; ``value`` / ``ms_per_step`` are the MEDIAN region, all regions
-   are listed in ``extra.rep_ms_per_step``;
+The timed region (exactly K steps between barrier + synchronize) is repeated --reps
+times; ``value`` / ``ms_per_step`` are the MEDIAN region, all regions are listed in
+``extra.rep_ms_per_step``.  A plain run does nothing else: it sets up, warms up, runs
+the timed regions, writes ``--dump-outputs`` and prints the line.
+
+``--full`` adds to the line, from runs and checks of its own outside the
+timed regions (``--no-pmc``, ``--no-extra``, ``--no-cpu-baseline`` drop parts of it):
+ * ``config.replicas_in_sync`` (N > 1): every rank holds the same parameters;
  * ``roofline``: the dominant kernel priced with SURVEY 8d's ALGORITHMIC bytes,
    the same model applied to the whole step (``whole_step_frac``; above 1 at
    this config because V is cache-resident -- then ``bound`` says
@@ -122,8 +126,8 @@ def _per_kernel_counter(dirpath: str, counter: str):
 def collect_traffic(args) -> dict:
     """rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes: the TCC slots do
     not hold both; --kernel-trace only, as MI355X_MICROARCH.md's rocprofv3 section says) of
-    this same bench command in child processes.  Called BEFORE this process initialises the
-    GPU.  FETCH_SIZE / WRITE_SIZE are KiB; on gfx950 FETCH_SIZE reports half the bytes of
+    this same bench command, run plain, in child processes.  Called BEFORE this process
+    initialises the GPU.  FETCH_SIZE / WRITE_SIZE are KiB; on gfx950 FETCH_SIZE reports half the bytes of
     wide coalesced reads, so the read side is doubled (same guide, HBM section)."""
     prof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     if not os.path.exists(prof):
@@ -137,7 +141,7 @@ def collect_traffic(args) -> dict:
     env = dict(os.environ, TMPDIR="/tmp")
     child = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(args.steps), "--warmup",
              str(args.warmup), "--batch-size", str(args.batch_size), "--workload", args.workload,
-             "--n-train", str(args.n_train), "--reps", "1", "--pmc-child"]
+             "--n-train", str(args.n_train), "--reps", "1"]
     per = {}
     t0 = time.perf_counter()
     for tag, counter in (("fetch", "FETCH_SIZE"), ("write", "WRITE_SIZE")):
@@ -163,7 +167,7 @@ def collect_traffic(args) -> dict:
     res = {"kernels": kernels, "seconds": time.perf_counter() - t0, "kernels_sha": kernels_sha(),
            "commit": git_head(), "batch": args.batch_size, "workload": args.workload,
            "how": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE --kernel-trace, one pass each, of "
-                  "`bench.py --pmc-child` with this run's steps/warmup/batch; average per launch; "
+                  "plain `bench.py --reps 1` with this run's steps/warmup/batch; average per launch; "
                   "hbm_bytes = 2 x FETCH_SIZE x 1024 + WRITE_SIZE x 1024 (gfx950 FETCH_SIZE correction)"}
     if keep:
         try:
@@ -629,11 +633,14 @@ def main() -> None:
                          "rows of a global batch are estimated at under a quarter of the dense buffer")
     ap.add_argument("--no-direct-rccl", action="store_true",
                     help="multi-GPU dense exchange through torch.distributed instead of the C ABI's RCCL binding")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 counter passes")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed regions, also measure and check everything beyond the headline: "
+                         "rocprofv3 counter passes, per-kernel times and roofline, extra.*, CPU baseline, "
+                         "replica agreement (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip extra.* beyond rep_ms_per_step")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the rocprofv3 counter passes")
     ap.add_argument("--pmc-timeout", type=int, default=240)
-    ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--mf-only", default=None, metavar="NAME|all",
                     help="run only extra.mf (c2_kuairec_small_k16, c5_1m_x_100k_k128 or all) and print it")
     ap.add_argument("--published-only", default=None, metavar="NAME|all",
@@ -643,8 +650,6 @@ def main() -> None:
                     help="after the timed steps, write the parameters the last timed step left (w0, w, V: "
                          "what a caller of the step receives) as DIR/<name>.npy, float64; see dump_outputs")
     args = ap.parse_args()
-    if args.pmc_child:
-        args.no_cpu_baseline = args.no_extra = args.no_pmc = True
     if args.steps < 1:
         raise SystemExit(f"--steps {args.steps}: at least one timed step is needed")
     if args.dump_outputs and (args.mf_only or args.published_only):
@@ -671,7 +676,7 @@ def main() -> None:
     # the counter passes run this command again under rocprofv3 in child processes; they
     # come first because a process that has initialised the GPU must not start them
     traffic_info = None
-    if world == 1 and not args.no_pmc:
+    if args.full and world == 1 and not args.no_pmc:
         traffic_info = collect_traffic(args)
 
     import torch
@@ -702,7 +707,9 @@ def main() -> None:
     if gB > n_train:
         raise SystemExit(f"global batch {gB} exceeds the log ({n_train} rows)")
 
-    want_fit = rank == 0 and world == 1 and not args.no_extra
+    # only the fit() walls of --full read the validation split; the training split does not
+    # depend on its size
+    want_fit = args.full and rank == 0 and world == 1 and not args.no_extra
     train, val = synth.make_log(shape, "FM", "IPS", seed=0, n_train=n_train,
                                 n_val=shape.n_val if want_fit else 16)
     X = train["features"]
@@ -812,7 +819,7 @@ def main() -> None:
     elapsed = float(np.median(region))
     value = K * gB / elapsed
     in_sync = None
-    if world > 1:
+    if args.full and world > 1:
         # outside the timed region: every replica must hold the same parameters
         chk = torch.stack([model.V.dev.sum(), model.w.dev.sum(), model.w0.dev.sum()]).to(
             "cuda" if args.backend == "nccl" else "cpu")
@@ -854,7 +861,7 @@ def main() -> None:
         "extra": {"rep_ms_per_step": [1e3 * e / K for e in region]},
     }
 
-    if rank == 0 and world == 1 and not args.pmc_child:
+    if args.full and rank == 0 and world == 1:
         # per-kernel durations with HIP events on the launch stream (same ids, one more region)
         ms = (C.c_double * 4)()
         cnt = (C.c_int64 * 4)()

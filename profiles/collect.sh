@@ -13,7 +13,7 @@ cd "$R"
 timeout -k 10 900 python -m pytest tests -m gpu -q > "$OUT/pytest_gpu.log" 2>&1
 echo "pytest exit=$?" | tee -a "$OUT/pytest_gpu.log"
 tail -3 "$OUT/pytest_gpu.log"
-timeout -k 10 900 python bench.py "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed"; tail -20 "$OUT/bench.err"; }
+timeout -k 10 900 python bench.py --full "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed"; tail -20 "$OUT/bench.err"; }
 cp gpurun_out/bench_pmc/pmc_summary.json "$OUT/pmc_summary.json" 2>/dev/null
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -- \
