@@ -381,6 +381,41 @@ int32_t rfm_fm_fit_dp(rfm_ctx* ctx, rfm_fm_plan* plan, const rfm_transport* tran
                       const double* d_val_values, const double* d_val_y,
                       const double* d_val_pscore, int64_t n_val, double eps,
                       double* d_out_train_loss, double* d_out_val_loss);
+/* rfm_fm_fit_dp with the evaluator of the reference's search loop inside (utils/search_params.py:
+ * 96-111: fit(..., evaluator=ValEvaluator), scored after every iteration, src/fm.py:104-110, as
+ * IPS-DCG@k, utils/evaluate.py:160-207) -- the data-parallel form of rfm_fm_train_eval.  The
+ * evaluation log's user groups (ascending user, as rfm_val_dcg) are cut into n_ranks contiguous
+ * ranges: rank r owns groups h_group_lo[r] .. h_group_lo[r + 1] - 1 (h_group_lo: n_ranks + 1 ints
+ * on the HOST, h_group_lo[n_ranks] = n_segments; a rank may own none) and holds only their rows,
+ * in grouped order, as the CSR d_ev_* of n_ev rows; d_seg_ptr / d_rows / d_labels / d_ev_pscores /
+ * n_local_segments / k describe them as rfm_val_dcg's arguments do.  After the update of
+ * iteration i the rank scores its rows (through rfm_fm_plan_forward, in the form -- sliced or
+ * plain -- that the whole log's n_ev_total rows take, so every score is bitwise the whole log's)
+ * into d_scores + (slot_first + i) * scores_stride and leaves its groups' per-user values in
+ * d_user_scratch + (slot_first + i) * user_stride as [vals | counted | order-dependent], each part
+ * max_local_segments apart (user_stride >= 3 * max_local_segments, the same on every rank, as is
+ * max_local_segments >= every rank's group count).  After the loop, next to the loss all-reduce,
+ * ONE all-gather moves the n_iters * user_stride doubles of every rank to every rank; they are
+ * merged into d_full_out[i][3 * n_segments] -- the table one rfm_val_dcg over the whole log
+ * would leave -- and its mean and order-dependent count go to d_dcg_out[2 i], [2 i + 1], bit for
+ * bit what rfm_val_dcg gives, the same on every rank.  Nothing inside the loop synchronises.
+ * With transport == NULL the all-gather is RCCL's (one process per GPU; not run on hardware with
+ * more than one rank). */
+int32_t rfm_fm_fit_dp_eval(rfm_ctx* ctx, rfm_fm_plan* plan, const rfm_transport* transport,
+                           int32_t exchange, const int32_t* d_ids, int64_t global_batch,
+                           int64_t n_iters, double* d_w0, double* d_w, double* d_V, double lr,
+                           const int64_t* d_val_indptr, const int32_t* d_val_indices,
+                           const double* d_val_values, const double* d_val_y,
+                           const double* d_val_pscore, int64_t n_val, double eps,
+                           double* d_out_train_loss, double* d_out_val_loss,
+                           const int64_t* d_ev_indptr, const int32_t* d_ev_indices,
+                           const double* d_ev_values, int64_t n_ev, int64_t n_ev_total,
+                           const int32_t* d_seg_ptr, const int32_t* d_rows, const double* d_labels,
+                           const double* d_ev_pscores, int32_t n_local_segments, int32_t k,
+                           double* d_scores, int64_t scores_stride, double* d_user_scratch,
+                           int64_t user_stride, int64_t slot_first, const int32_t* h_group_lo,
+                           int32_t max_local_segments, int32_t n_segments, double* d_full_out,
+                           double* d_dcg_out);
 
 /* ---- MF ------------------------------------------------------------------
  * Replaces LogisticMatrixFactorization.predict/_predict_pair

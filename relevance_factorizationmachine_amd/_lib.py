@@ -139,6 +139,10 @@ SIGNATURES = {
                           _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _i64, _i64, _vp],
     "rfm_fm_fit_dp": [_vp, _vp, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _f64, _vp, _vp, _vp, _vp, _vp,
                       _i64, _f64, _vp, _vp],
+    "rfm_fm_fit_dp_eval": [_vp, _vp, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _f64, _vp, _vp, _vp, _vp, _vp,
+                           _i64, _f64, _vp, _vp,
+                           _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _i64,
+                           _i64, _vp, _i32, _i32, _vp, _vp],
     "rfm_mf_predict": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _i32, _vp],
     "rfm_mf_predict_loss": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _i32,
                             _f64, _vp, _vp],

@@ -186,6 +186,17 @@ void comm_all_reduce_sum(rfm_ctx* ctx, double* d_buf, int64_t count);
 void comm_all_to_all(rfm_ctx* ctx, int rank, const void* d_send, const int64_t* send_off,
                      const int64_t* send_bytes, void* d_recv, const int64_t* recv_off,
                      const int64_t* recv_bytes);
+// launches of the validation metric (rfm_eval.hip) that the data-parallel fit shares: the
+// per-user values of rfm_val_dcg into three arrays; rank-padded per-user tables gathered from
+// the ranks into the whole log's layout; the means of many iterations' tables
+void enqueue_val_dcg_users(rfm_ctx* ctx, const double* d_scores, const int32_t* d_seg_ptr,
+                           const int32_t* d_rows, const double* d_labels, const double* d_pscores,
+                           int32_t n_segments, int32_t k, double* d_val, double* d_ok, double* d_amb);
+void enqueue_val_dcg_merge(rfm_ctx* ctx, const double* d_recv, int32_t n_ranks, int64_t n_iters,
+                           int64_t stride, int32_t pad, const int32_t* d_group_lo, int32_t n_segments,
+                           double* d_full);
+void enqueue_val_dcg_means(rfm_ctx* ctx, const double* d_full, int64_t n_iters, int32_t n_segments,
+                           double* d_out);
 }  // namespace rfm
 
 struct rfm_ctx {

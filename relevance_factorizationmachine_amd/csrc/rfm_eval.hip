@@ -105,12 +105,13 @@ __global__ __launch_bounds__(kEvalBlock) void val_dcg_users_kernel(
 }
 
 // mean over the users that count, summed in a fixed order; out[1] = number of users
-// whose value depends on how equal scores are ordered
-__global__ __launch_bounds__(1024) void val_dcg_mean_kernel(const double* __restrict__ user_val,
-                                                            const double* __restrict__ user_ok,
-                                                            const double* __restrict__ user_amb,
-                                                            int32_t n_seg,
-                                                            double* __restrict__ out) {
+// whose value depends on how equal scores are ordered.  One 1024-thread workgroup: thread t
+// adds users t, t + 1024, ... and the workgroup's tree takes the rest (the arithmetic every
+// caller shares, so that two launches over the same table agree bit for bit)
+__device__ __forceinline__ void val_dcg_mean_block(const double* __restrict__ user_val,
+                                                   const double* __restrict__ user_ok,
+                                                   const double* __restrict__ user_amb, int32_t n_seg,
+                                                   double* __restrict__ out) {
   __shared__ double sv[1024], sc[1024], sa[1024];
   double v = 0.0, c = 0.0, a = 0.0;
   for (int i = threadIdx.x; i < n_seg; i += 1024) {
@@ -135,6 +136,74 @@ __global__ __launch_bounds__(1024) void val_dcg_mean_kernel(const double* __rest
     out[0] = sv[0] / sc[0];  // no user counts -> nan, as np.mean([])
     out[1] = sa[0];
   }
+}
+
+__global__ __launch_bounds__(1024) void val_dcg_mean_kernel(const double* __restrict__ user_val,
+                                                            const double* __restrict__ user_ok,
+                                                            const double* __restrict__ user_amb,
+                                                            int32_t n_seg,
+                                                            double* __restrict__ out) {
+  val_dcg_mean_block(user_val, user_ok, user_amb, n_seg, out);
+}
+
+// the means of many iterations' tables [iteration][vals | counted | order-dependent] (n_seg each),
+// one workgroup per iteration -> out[2 i], out[2 i + 1]
+__global__ __launch_bounds__(1024) void val_dcg_means_kernel(const double* __restrict__ table,
+                                                             int32_t n_seg, double* __restrict__ out) {
+  const double* t = table + int64_t(blockIdx.x) * 3 * n_seg;
+  val_dcg_mean_block(t, t + n_seg, t + 2 * int64_t(n_seg), n_seg, out + 2 * int64_t(blockIdx.x));
+}
+
+// The per-user tables of the ranks of a data-parallel fit (rfm_fm_fit_dp_eval), gathered as
+// recv[rank][iteration][stride] with rank r's users group_lo[r] .. group_lo[r + 1] - 1 at
+// [u | pad + u | 2 pad + u], into the layout of one rfm_val_dcg over the whole log:
+// full[iteration][vals (n_seg) | counted (n_seg) | order-dependent (n_seg)].
+// Grid: (users / kEvalBlock, iterations).
+__global__ __launch_bounds__(kEvalBlock) void val_dcg_merge_kernel(
+    const double* __restrict__ recv, int32_t n_ranks, int64_t n_iters, int64_t stride, int32_t pad,
+    const int32_t* __restrict__ group_lo, int32_t n_seg, double* __restrict__ full) {
+  const int32_t g = int32_t(blockIdx.x) * kEvalBlock + int32_t(threadIdx.x);
+  const int64_t it = blockIdx.y;
+  if (g >= n_seg) return;
+  int r = 0;
+  while (r + 1 < n_ranks && group_lo[r + 1] <= g) ++r;  // the rank that owns user group g
+  const double* src = recv + (int64_t(r) * n_iters + it) * stride;
+  const int32_t u = g - group_lo[r];
+  double* dst = full + it * 3 * int64_t(n_seg);
+  dst[g] = src[u];
+  dst[n_seg + g] = src[pad + u];
+  dst[2 * int64_t(n_seg) + g] = src[2 * int64_t(pad) + u];
+}
+
+// launches shared with the data-parallel fit (rfm_fm_dp.hpp)
+void enqueue_val_dcg_users(rfm_ctx* ctx, const double* d_scores, const int32_t* d_seg_ptr,
+                           const int32_t* d_rows, const double* d_labels, const double* d_pscores,
+                           int32_t n_segments, int32_t k, double* d_val, double* d_ok, double* d_amb) {
+  if (n_segments <= 0) return;
+  const int per_block = kEvalBlock / kEvalWave;
+  const int grid = (n_segments + per_block - 1) / per_block;
+  hipLaunchKernelGGL(val_dcg_users_kernel, dim3(grid), dim3(kEvalBlock), 0, ctx->stream, d_scores,
+                     d_seg_ptr, d_rows, d_labels, d_pscores, n_segments, k, d_val, d_ok, d_amb);
+  RFM_HIP_CHECK(hipGetLastError());
+}
+
+void enqueue_val_dcg_merge(rfm_ctx* ctx, const double* d_recv, int32_t n_ranks, int64_t n_iters,
+                           int64_t stride, int32_t pad, const int32_t* d_group_lo, int32_t n_segments,
+                           double* d_full) {
+  if (n_segments <= 0 || n_iters <= 0) return;
+  RFM_REQUIRE(n_iters <= 65535, "%lld iterations in one merge", (long long)n_iters);
+  const int grid = (n_segments + kEvalBlock - 1) / kEvalBlock;
+  hipLaunchKernelGGL(val_dcg_merge_kernel, dim3(grid, unsigned(n_iters)), dim3(kEvalBlock), 0, ctx->stream,
+                     d_recv, n_ranks, n_iters, stride, pad, d_group_lo, n_segments, d_full);
+  RFM_HIP_CHECK(hipGetLastError());
+}
+
+void enqueue_val_dcg_means(rfm_ctx* ctx, const double* d_full, int64_t n_iters, int32_t n_segments,
+                           double* d_out) {
+  if (n_iters <= 0) return;
+  hipLaunchKernelGGL(val_dcg_means_kernel, dim3(unsigned(n_iters)), dim3(1024), 0, ctx->stream, d_full,
+                     n_segments, d_out);
+  RFM_HIP_CHECK(hipGetLastError());
 }
 
 // The k best rows of every user, for the metrics of the reference's TestEvaluator
@@ -221,14 +290,8 @@ int32_t rfm_val_dcg(rfm_ctx* ctx, const double* d_scores, const int32_t* d_seg_p
     double* val = d_user_scratch;
     double* ok = d_user_scratch + n_segments;
     double* amb = d_user_scratch + 2 * int64_t(n_segments);
-    if (n_segments > 0) {
-      const int per_block = kEvalBlock / kEvalWave;
-      const int grid = (n_segments + per_block - 1) / per_block;
-      hipLaunchKernelGGL(val_dcg_users_kernel, dim3(grid), dim3(kEvalBlock), 0, ctx->stream,
-                         d_scores, d_seg_ptr, d_rows, d_labels, d_pscores, n_segments, k, val,
-                         ok, amb);
-      RFM_HIP_CHECK(hipGetLastError());
-    }
+    enqueue_val_dcg_users(ctx, d_scores, d_seg_ptr, d_rows, d_labels, d_pscores, n_segments, k, val, ok,
+                          amb);
     hipLaunchKernelGGL(val_dcg_mean_kernel, dim3(1), dim3(1024), 0, ctx->stream, val, ok, amb,
                        n_segments, d_out);
     RFM_HIP_CHECK(hipGetLastError());

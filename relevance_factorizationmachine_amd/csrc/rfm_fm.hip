@@ -196,16 +196,17 @@ int forward_loss_deferred(rfm_ctx* ctx, FwdArgs a, double* partial_row) {
 // workgroup per CU, a multiple of the XCDs a slice is dealt to), rows per workgroup and per
 // staged chunk, LDS.  ok = false: the plan has no slices, or the rows are too few to pay for
 // every workgroup's copy of the cached columns (RFM_SLICED_MIN_ROWS, default 4 096;
-// RFM_SLICED_LOSS=0: never).
+// RFM_SLICED_LOSS=0: never).  `form_rows` (>= 0) takes that decision for another number of rows
+// than the launch's: a shard of a log then scores its rows in the form the whole log would.
 struct SlicedGeom {
   bool ok = false;
   int grid = 0, rows_per_wg = 0;
   size_t lds = 0;
 };
-SlicedGeom sliced_geom(const rfm_ctx* ctx, const rfm_fm_plan* plan, int64_t rows) {
+SlicedGeom sliced_geom(const rfm_ctx* ctx, const rfm_fm_plan* plan, int64_t rows, int64_t form_rows = -1) {
   SlicedGeom g;
   if (plan->sl_ns <= 0 || env_int("RFM_SLICED_LOSS", 1) == 0) return g;
-  if (rows < std::max(1, env_int("RFM_SLICED_MIN_ROWS", 4096))) return g;
+  if ((form_rows >= 0 ? form_rows : rows) < std::max(1, env_int("RFM_SLICED_MIN_ROWS", 4096))) return g;
   if (rows >= (int64_t(1) << 31) - 1) return g;  // (the kernel numbers a log's rows in 31 bits)
   const int xs = 8 / plan->sl_ns;
   int wps = std::max(xs, ctx->n_cu / plan->sl_ns / xs * xs);
@@ -563,6 +564,11 @@ struct LossRun {
   }
 };
 
+// scores of the rows of a CSR through the plan, in the form `form_rows` rows would take (-1: n_rows)
+void plan_forward(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr, const int32_t* d_indices,
+                  const double* d_values, int64_t n_rows, const double* d_w0, const double* d_w,
+                  const double* d_V, double* d_out_pred, int64_t form_rows = -1);
+
 }  // namespace
 
 #include "rfm_fm_dp.hpp"
@@ -740,12 +746,13 @@ int32_t rfm_fm_set_rows(rfm_ctx* ctx, const double* d_rows, int64_t n_rows,
 namespace {
 
 // scores of the rows of a CSR through the plan (rfm_fm_plan_forward): the sliced forward where
-// the plan has one and the rows are enough for it, else the plain one
+// the plan has one and the rows (form_rows, when given) are enough for it, else the plain one.  A
+// row's score does not depend on the other rows of the launch, only on the form.
 void plan_forward(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr, const int32_t* d_indices,
                   const double* d_values, int64_t n_rows, const double* d_w0, const double* d_w,
-                  const double* d_V, double* d_out_pred) {
+                  const double* d_V, double* d_out_pred, int64_t form_rows) {
   if (n_rows == 0) return;
-  const SlicedGeom sliced = sliced_geom(ctx, plan, n_rows);
+  const SlicedGeom sliced = sliced_geom(ctx, plan, n_rows, form_rows);
   if (!sliced.ok) {  // the plain forward (rfm_fm_forward)
     FwdArgs f = forward_args(d_indptr, d_indices, d_values, nullptr, n_rows, d_w0, d_w, d_V, plan->k);
     f.out_pred = d_out_pred;

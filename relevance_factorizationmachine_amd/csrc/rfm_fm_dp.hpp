@@ -313,6 +313,163 @@ void exchange_rows(rfm_ctx* ctx, rfm_fm_plan* plan, DpExchange& ex, TransferPlan
                        k, lr, true);
 }
 
+// the evaluator of rfm_fm_fit_dp_eval: this rank's shard of the evaluation log (the rows of its
+// user groups, in grouped order) and where its per-iteration results go
+struct DpEval {
+  const int64_t* indptr;
+  const int32_t* indices;
+  const double* values;
+  int64_t n_rows;        // rows of the shard
+  int64_t n_rows_total;  // rows of the whole log (they choose the forward's form)
+  const int32_t* seg_ptr;
+  const int32_t* rows;
+  const double* labels;
+  const double* pscores;
+  int32_t n_local, k;    // user groups of the shard, ranking depth
+  double* scores;        // [slots][scores_stride]: iteration i of the call -> slot slot_first + i
+  int64_t scores_stride;
+  double* user_scratch;  // [slots][user_stride]: [vals | counted | order-dependent], pad apart
+  int64_t user_stride;
+  int64_t slot_first;
+  const int32_t* h_group_lo;  // [n_ranks + 1]: first user group of every rank
+  int32_t pad;                // max_local_segments
+  int32_t n_segments;         // user groups of the whole log
+  double* full_out;           // [n_iters][3 n_segments]
+  double* dcg_out;            // [n_iters][2]
+};
+
+// iteration `it`: the shard's scores with the new parameters and its per-user values
+void dp_eval_iteration(rfm_ctx* ctx, rfm_fm_plan* plan, const DpEval& e, int64_t it, const double* d_w0,
+                       const double* d_w, const double* d_V) {
+  double* sc = e.scores + (e.slot_first + it) * e.scores_stride;
+  double* slot = e.user_scratch + (e.slot_first + it) * e.user_stride;
+  plan_forward(ctx, plan, e.indptr, e.indices, e.values, e.n_rows, d_w0, d_w, d_V, sc, e.n_rows_total);
+  enqueue_val_dcg_users(ctx, sc, e.seg_ptr, e.rows, e.labels, e.pscores, e.n_local, e.k, slot, slot + e.pad,
+                        slot + 2 * int64_t(e.pad));
+}
+
+// after the call's iterations: every rank's per-user tables to every rank (ONE all-gather of
+// n_iters x user_stride doubles per rank), merged into the whole log's table, and its means
+void dp_eval_finish(rfm_ctx* ctx, rfm_fm_plan* plan, DpExchange& ex, bool exchange_on, const DpEval& e,
+                    int64_t n_iters) {
+  const int64_t bytes = n_iters * e.user_stride * 8;
+  const double* mine = e.user_scratch + e.slot_first * e.user_stride;
+  const double* all = mine;
+  const int W = exchange_on ? ex.world : 1;
+  if (exchange_on) {
+    plan->dp_ev_all.ensure(size_t(ex.world) * size_t(bytes));
+    ex.all_gather(mine, plan->dp_ev_all.p, bytes);
+    all = plan->dp_ev_all.as<double>();
+  }
+  plan->dp_ev_lo.ensure(size_t(ex.world + 1) * 4);
+  RFM_HIP_CHECK(hipMemcpyAsync(plan->dp_ev_lo.p, e.h_group_lo, size_t(ex.world + 1) * 4, hipMemcpyHostToDevice,
+                               ctx->stream));
+  enqueue_val_dcg_merge(ctx, all, W, n_iters, e.user_stride, e.pad, plan->dp_ev_lo.as<int32_t>(), e.n_segments,
+                        e.full_out);
+  enqueue_val_dcg_means(ctx, e.full_out, n_iters, e.n_segments, e.dcg_out);
+}
+
+// rfm_fm_fit_dp, and with `ev` the evaluator of rfm_fm_fit_dp_eval after every update
+void fit_dp(rfm_ctx* ctx, rfm_fm_plan* plan, const rfm_transport* transport, int32_t exchange,
+            const int32_t* d_ids, int64_t global_batch, int64_t n_iters, double* d_w0, double* d_w, double* d_V,
+            double lr, const int64_t* d_val_indptr, const int32_t* d_val_indices, const double* d_val_values,
+            const double* d_val_y, const double* d_val_pscore, int64_t n_val, double eps,
+            double* d_out_train_loss, double* d_out_val_loss, const DpEval* ev) {
+  RFM_REQUIRE(ctx && plan && d_w0 && d_w && d_V, "null pointer");
+  RFM_REQUIRE(exchange == 0 || exchange == 1, "exchange=%d (0 dense, 1 touched rows)", exchange);
+  RFM_REQUIRE(n_iters >= 0 && global_batch >= 1 && n_val >= 0, "bad shape");
+  if (n_iters == 0) return;
+  RFM_REQUIRE(d_ids, "null row ids");
+  DpExchange ex = dp_exchange(ctx, transport);
+  if (ev) {
+    const int32_t* lo = ev->h_group_lo;
+    RFM_REQUIRE(lo, "null group bounds");
+    RFM_REQUIRE(lo[0] == 0 && lo[ex.world] == ev->n_segments, "group bounds do not cover the %d user groups",
+                ev->n_segments);
+    for (int r = 0; r < ex.world; ++r)
+      RFM_REQUIRE(lo[r + 1] >= lo[r] && lo[r + 1] - lo[r] <= ev->pad, "group bounds of rank %d", r);
+    RFM_REQUIRE(lo[ex.rank + 1] - lo[ex.rank] == ev->n_local, "rank %d holds %d user groups, bounds say %d",
+                ex.rank, ev->n_local, lo[ex.rank + 1] - lo[ex.rank]);
+  }
+  int64_t lo, hi, vlo, vhi;
+  shard_of(global_batch, ex.world, ex.rank, lo, hi);
+  shard_of(n_val, ex.world, ex.rank, vlo, vhi);
+  const int64_t batch = hi - lo, n_my_val = vhi - vlo;
+  RFM_REQUIRE(batch <= plan->max_batch, "shard of %lld rows exceeds the plan's max_batch %lld",
+              (long long)batch, (long long)plan->max_batch);
+  const bool want_val = d_out_val_loss && n_val > 0;
+  if (want_val)
+    RFM_REQUIRE(d_val_indptr && d_val_indices && d_val_values && d_val_y && d_val_pscore,
+                "validation arrays missing");
+  for (int64_t it = 0; it < n_iters && batch > 0; ++it)
+    validate_ids(ctx, plan, d_ids + it * global_batch + lo, batch, 1);
+  const int64_t count = plan->n_features * int64_t(plan->k + 1) + 1;
+  hipStream_t st = ctx->stream;
+
+  // per-iteration loss SUMS of this rank: [train (n_iters) | val (n_iters)]
+  plan->dp_sums.ensure(size_t(2 * n_iters) * 8);
+  RFM_HIP_CHECK(hipMemsetAsync(plan->dp_sums.p, 0, size_t(2 * n_iters) * 8, st));
+  double* sums_train = plan->dp_sums.as<double>();
+  double* sums_val = sums_train + n_iters;
+  LossRun run(plan, d_out_train_loss || want_val);
+  const bool train_here = d_out_train_loss && batch > 0, val_here = want_val && n_my_val > 0;
+  const auto finish = [&](int64_t first, int64_t cnt) {
+    run.finish_sums(ctx, first, cnt, train_here ? sums_train : nullptr, val_here ? sums_val : nullptr);
+  };
+  if (ev)  // (the padding of the per-user tables travels too: defined bytes)
+    RFM_HIP_CHECK(hipMemsetAsync(ev->user_scratch + ev->slot_first * ev->user_stride, 0,
+                                 size_t(n_iters * ev->user_stride) * 8, st));
+
+  TransferPlan tp;
+  // (RFM_DP_FORCE_EXCHANGE=1: a single rank goes through the exchange too -- every collective
+  // with itself -- so that the whole multi-rank loop, RCCL calls included, can be run and
+  // checked on one GPU)
+  const bool exchange_on = ex.world > 1 || env_int("RFM_DP_FORCE_EXCHANGE", 0) != 0;
+  const bool rows_mode = exchange == 1 && exchange_on;
+  int32_t id0 = 0;
+  if (rows_mode) {
+    plan_transfers(ctx, plan, ex, d_ids, global_batch, lo, hi, n_iters, tp);
+    id0 = next_touch_ids(ctx, plan, n_iters);
+  } else if (exchange_on) {
+    plan->dp_grad.ensure(size_t(count) * 8);
+  }
+  const DpSmall small(plan);
+  RFM_HIP_CHECK(hipMemsetAsync(small.flag, 0, 8, st));
+
+  for (int64_t it = 0; it < n_iters; ++it) {
+    const int32_t* ids = d_ids + it * global_batch + lo;
+    if (!exchange_on) {
+      enqueue_step(ctx, plan, ids, batch, d_w0, d_w, d_V, lr, nullptr);
+    } else if (!rows_mode) {
+      exchange_dense(ctx, plan, ex, ids, batch, d_w0, d_w, d_V, lr);
+    } else {
+      exchange_rows(ctx, plan, ex, tp, small, it, id0 + int32_t(it), ids, batch, d_w0, d_w, d_V, lr);
+    }
+    RFM_HIP_CHECK(hipGetLastError());
+    if (train_here) {
+      // the shard's part of the train loss: same batch, new parameters (src/fm.py:90-96)
+      FwdArgs f = plan_fwd_args(plan, ids, batch, d_w0, d_w, d_V);
+      f.eps = eps;
+      run.train_parts = forward_loss_deferred(ctx, f, run.train_row(it));
+    }
+    if (val_here) {
+      FwdArgs f = forward_args(d_val_indptr + vlo, d_val_indices, d_val_values, nullptr, n_my_val,
+                               d_w0, d_w, d_V, plan->k);
+      f.y = d_val_y + vlo;
+      f.pscore = d_val_pscore + vlo;
+      f.eps = eps;
+      run.val_parts = forward_loss_deferred(ctx, f, run.val_row(it));
+    }
+    if (ev) dp_eval_iteration(ctx, plan, *ev, it, d_w0, d_w, d_V);
+    run.close(it, kRun, false, finish);
+  }
+  run.finish_open(n_iters, finish);
+  dp_losses(ctx, ex, exchange_on, sums_train, n_iters, global_batch, d_out_train_loss, n_val,
+            want_val ? d_out_val_loss : nullptr);
+  if (ev) dp_eval_finish(ctx, plan, ex, exchange_on, *ev, n_iters);
+  small.check(st);
+}
+
 }  // namespace
 }  // namespace rfm
 
@@ -323,85 +480,39 @@ extern "C" int32_t rfm_fm_fit_dp(rfm_ctx* ctx, rfm_fm_plan* plan, const rfm_tran
                                  const int32_t* d_val_indices, const double* d_val_values,
                                  const double* d_val_y, const double* d_val_pscore, int64_t n_val,
                                  double eps, double* d_out_train_loss, double* d_out_val_loss) {
+  return rfm::guarded([&] {
+    rfm::fit_dp(ctx, plan, transport, exchange, d_ids, global_batch, n_iters, d_w0, d_w, d_V, lr, d_val_indptr,
+                d_val_indices, d_val_values, d_val_y, d_val_pscore, n_val, eps, d_out_train_loss, d_out_val_loss,
+                nullptr);
+  });
+}
+
+extern "C" int32_t rfm_fm_fit_dp_eval(
+    rfm_ctx* ctx, rfm_fm_plan* plan, const rfm_transport* transport, int32_t exchange, const int32_t* d_ids,
+    int64_t global_batch, int64_t n_iters, double* d_w0, double* d_w, double* d_V, double lr,
+    const int64_t* d_val_indptr, const int32_t* d_val_indices, const double* d_val_values, const double* d_val_y,
+    const double* d_val_pscore, int64_t n_val, double eps, double* d_out_train_loss, double* d_out_val_loss,
+    const int64_t* d_ev_indptr, const int32_t* d_ev_indices, const double* d_ev_values, int64_t n_ev,
+    int64_t n_ev_total, const int32_t* d_seg_ptr, const int32_t* d_rows, const double* d_labels,
+    const double* d_ev_pscores, int32_t n_local_segments, int32_t k, double* d_scores, int64_t scores_stride,
+    double* d_user_scratch, int64_t user_stride, int64_t slot_first, const int32_t* h_group_lo,
+    int32_t max_local_segments, int32_t n_segments, double* d_full_out, double* d_dcg_out) {
   using namespace rfm;
   return guarded([&] {
-    RFM_REQUIRE(ctx && plan && d_w0 && d_w && d_V, "null pointer");
-    RFM_REQUIRE(exchange == 0 || exchange == 1, "exchange=%d (0 dense, 1 touched rows)", exchange);
-    RFM_REQUIRE(n_iters >= 0 && global_batch >= 1 && n_val >= 0, "bad shape");
-    if (n_iters == 0) return;
-    RFM_REQUIRE(d_ids, "null row ids");
-    DpExchange ex = dp_exchange(ctx, transport);
-    int64_t lo, hi, vlo, vhi;
-    shard_of(global_batch, ex.world, ex.rank, lo, hi);
-    shard_of(n_val, ex.world, ex.rank, vlo, vhi);
-    const int64_t batch = hi - lo, n_my_val = vhi - vlo;
-    RFM_REQUIRE(batch <= plan->max_batch, "shard of %lld rows exceeds the plan's max_batch %lld",
-                (long long)batch, (long long)plan->max_batch);
-    const bool want_val = d_out_val_loss && n_val > 0;
-    if (want_val)
-      RFM_REQUIRE(d_val_indptr && d_val_indices && d_val_values && d_val_y && d_val_pscore,
-                  "validation arrays missing");
-    for (int64_t it = 0; it < n_iters && batch > 0; ++it)
-      validate_ids(ctx, plan, d_ids + it * global_batch + lo, batch, 1);
-    const int64_t count = plan->n_features * int64_t(plan->k + 1) + 1;
-    hipStream_t st = ctx->stream;
-
-    // per-iteration loss SUMS of this rank: [train (n_iters) | val (n_iters)]
-    plan->dp_sums.ensure(size_t(2 * n_iters) * 8);
-    RFM_HIP_CHECK(hipMemsetAsync(plan->dp_sums.p, 0, size_t(2 * n_iters) * 8, st));
-    double* sums_train = plan->dp_sums.as<double>();
-    double* sums_val = sums_train + n_iters;
-    LossRun run(plan, d_out_train_loss || want_val);
-    const bool train_here = d_out_train_loss && batch > 0, val_here = want_val && n_my_val > 0;
-    const auto finish = [&](int64_t first, int64_t cnt) {
-      run.finish_sums(ctx, first, cnt, train_here ? sums_train : nullptr, val_here ? sums_val : nullptr);
-    };
-
-    TransferPlan tp;
-    // (RFM_DP_FORCE_EXCHANGE=1: a single rank goes through the exchange too -- every collective
-    // with itself -- so that the whole multi-rank loop, RCCL calls included, can be run and
-    // checked on one GPU)
-    const bool exchange_on = ex.world > 1 || env_int("RFM_DP_FORCE_EXCHANGE", 0) != 0;
-    const bool rows_mode = exchange == 1 && exchange_on;
-    int32_t id0 = 0;
-    if (rows_mode) {
-      plan_transfers(ctx, plan, ex, d_ids, global_batch, lo, hi, n_iters, tp);
-      id0 = next_touch_ids(ctx, plan, n_iters);
-    } else if (exchange_on) {
-      plan->dp_grad.ensure(size_t(count) * 8);
-    }
-    const DpSmall small(plan);
-    RFM_HIP_CHECK(hipMemsetAsync(small.flag, 0, 8, st));
-
-    for (int64_t it = 0; it < n_iters; ++it) {
-      const int32_t* ids = d_ids + it * global_batch + lo;
-      if (!exchange_on) {
-        enqueue_step(ctx, plan, ids, batch, d_w0, d_w, d_V, lr, nullptr);
-      } else if (!rows_mode) {
-        exchange_dense(ctx, plan, ex, ids, batch, d_w0, d_w, d_V, lr);
-      } else {
-        exchange_rows(ctx, plan, ex, tp, small, it, id0 + int32_t(it), ids, batch, d_w0, d_w, d_V, lr);
-      }
-      RFM_HIP_CHECK(hipGetLastError());
-      if (train_here) {
-        // the shard's part of the train loss: same batch, new parameters (src/fm.py:90-96)
-        FwdArgs f = plan_fwd_args(plan, ids, batch, d_w0, d_w, d_V);
-        f.eps = eps;
-        run.train_parts = forward_loss_deferred(ctx, f, run.train_row(it));
-      }
-      if (val_here) {
-        FwdArgs f = forward_args(d_val_indptr + vlo, d_val_indices, d_val_values, nullptr, n_my_val,
-                                 d_w0, d_w, d_V, plan->k);
-        f.y = d_val_y + vlo;
-        f.pscore = d_val_pscore + vlo;
-        f.eps = eps;
-        run.val_parts = forward_loss_deferred(ctx, f, run.val_row(it));
-      }
-      run.close(it, kRun, false, finish);
-    }
-    run.finish_open(n_iters, finish);
-    dp_losses(ctx, ex, exchange_on, sums_train, n_iters, global_batch, d_out_train_loss, n_val,
-              want_val ? d_out_val_loss : nullptr);
-    small.check(st);
+    RFM_REQUIRE(k >= 1, "k=%d (ranking positions) must be >= 1", k);
+    RFM_REQUIRE(n_segments >= 0 && n_local_segments >= 0 && max_local_segments >= n_local_segments &&
+                    n_local_segments <= n_segments,
+                "bad user groups: %d of %d, padded to %d", n_local_segments, n_segments, max_local_segments);
+    RFM_REQUIRE(n_ev >= 0 && n_ev_total >= n_ev && slot_first >= 0 && scores_stride >= n_ev &&
+                    user_stride >= std::max<int64_t>(1, 3 * int64_t(max_local_segments)),
+                "bad evaluation shape");
+    RFM_REQUIRE(d_user_scratch && d_full_out && d_dcg_out, "null pointer (evaluation)");
+    if (n_ev > 0) RFM_REQUIRE(d_ev_indptr && d_scores, "null pointer (evaluation log)");
+    if (n_local_segments > 0) RFM_REQUIRE(n_ev > 0 && d_seg_ptr && d_labels, "null pointer (user groups)");
+    const DpEval ev{d_ev_indptr, d_ev_indices, d_ev_values, n_ev, n_ev_total, d_seg_ptr, d_rows, d_labels,
+                    d_ev_pscores, n_local_segments, k, d_scores, scores_stride, d_user_scratch, user_stride,
+                    slot_first, h_group_lo, max_local_segments, n_segments, d_full_out, d_dcg_out};
+    fit_dp(ctx, plan, transport, exchange, d_ids, global_batch, n_iters, d_w0, d_w, d_V, lr, d_val_indptr,
+           d_val_indices, d_val_values, d_val_y, d_val_pscore, n_val, eps, d_out_train_loss, d_out_val_loss, &ev);
   });
 }

@@ -61,6 +61,8 @@ struct rfm_fm_plan {
   // lists (mine / received / everybody's updated rows), transfer-plan arrays, small scratch
   rfm::DevBuf dp_grad, dp_sums, dp_rows, dp_recv, dp_all, dp_bounds, dp_all_bounds, dp_seg,
       dp_range_lo, dp_small;
+  // rfm_fm_fit_dp_eval: every rank's per-user tables of a call, the ranks' first user groups
+  rfm::DevBuf dp_ev_all, dp_ev_lo;
   rfm::DevBuf ids_seen, ids_flags;  // RFM_CHECK_IDS=1: validation of the steps' row ids
   int32_t ids_stamp = 0;
   size_t device_bytes() const {

@@ -27,6 +27,24 @@ def shard_bounds(batch: int, world: int, rank: int) -> Tuple[int, int]:
     return lo, lo + base + (1 if rank < extra else 0)
 
 
+def group_shard_bounds(seg_ptr, world: int):
+    """First user group of every rank (``world + 1`` entries, the last = the number of groups):
+    the groups of an evaluation log (``seg_ptr``: their row bounds, ascending user) cut into
+    ``world`` contiguous ranges balanced by rows.  Rank r starts at the first group that starts
+    at or after row ``total * r / world``, so without its last group no rank holds more than the
+    ideal share; a rank may hold no group (more ranks than groups, or one long group)."""
+    import numpy as np
+
+    seg = np.asarray(seg_ptr, dtype=np.int64)
+    if world < 1 or seg.ndim != 1 or seg.shape[0] < 1:
+        raise ValueError(f"bad group bounds for {world} ranks")
+    n_groups, total = seg.shape[0] - 1, int(seg[-1])
+    lo = np.searchsorted(seg * world, total * np.arange(world + 1, dtype=np.int64), side="left")
+    lo = np.minimum(lo, n_groups)
+    lo[0], lo[-1] = 0, n_groups
+    return lo.astype(np.int64)
+
+
 class DataParallelStep:
     """One exchange step per mini-batch.
 
@@ -587,6 +605,132 @@ def choose_exchange(n_features: int, n_factors: int, global_batch: int) -> str:
     return "rows" if 4 * touched * (n_factors + 2) * 2 < n_features * (n_factors + 1) else "dense"
 
 
+class DpEvalLoop:
+    """The evaluator of a data-parallel fit on the device (``rfm_fm_fit_dp_eval``): ``EvalLoop``
+    with the evaluation log cut by user groups.
+
+    Rank r keeps only the rows of its groups (``group_shard_bounds``), gathered once into a device
+    CSR in grouped order and registered with the plan, and scores and ranks them after every
+    update; one all-gather per run of iterations hands every rank the whole table of per-user
+    values, so every rank holds the same metric list.  Iterations with tie-order dependent users
+    are finished on the host when a chunk of score slots is full: the rank that owns such a user
+    recomputes it from its own shard's scores (``ValFrame.host_user_values``), the ranks swap those
+    few values (``all_gather_object``), and every rank forms the mean ``ValFrame.resolve`` would."""
+
+    def __init__(self, rt, plan, frame, ev, evaluator, world: int, rank: int, n_epochs: int, group=None):
+        import numpy as np
+        import torch
+
+        from . import _lib
+        from .evaluate import EvalLoop
+        from .features import take_rows
+
+        self.rt, self.frame, self.evaluator, self.world, self.rank, self.group = rt, frame, evaluator, world, rank, group
+        self.ev = ev  # the whole log on the device (the scores left behind at the end)
+        seg = frame.h_seg_ptr
+        self.group_lo = np.ascontiguousarray(group_shard_bounds(seg, world), dtype=np.int32)
+        self.g0, self.g1 = int(self.group_lo[rank]), int(self.group_lo[rank + 1])
+        self.local = frame.take_groups(self.g0, self.g1)
+        self.n_rows = self.local.n_rows
+        self.pad = max(int(np.diff(self.group_lo).max()), 1)  # groups of the largest shard
+        self.user_stride = 3 * self.pad
+        max_rows = int((seg[self.group_lo[1:]] - seg[self.group_lo[:-1]]).max())
+        r0 = int(seg[self.g0])
+        self.csr = take_rows(rt, ev, frame.h_order[r0: r0 + self.n_rows]) if self.n_rows else None
+        if self.csr is not None:  # (the plan translates the shard once, not once per iteration)
+            _lib.check(rt.lib.rfm_fm_plan_register_log(
+                rt.ctx, plan.handle, 1, self.csr.indptr.data_ptr(), self.csr.indices.data_ptr(),
+                self.csr.values.data_ptr(), self.n_rows))
+        loc = self.local
+        self.seg_ptr = rt.upload(loc.h_seg_ptr)
+        self.labels = rt.upload(loc.h_labels if self.n_rows else np.zeros(1))
+        ones = loc.h_pscores is None or bool(np.all(loc.h_pscores == 1.0))  # (Naive: ones_pscore)
+        self.pscores = None if ones else rt.upload(loc.h_pscores)
+        # every rank cuts its runs at the same iterations (the collectives pair up): the chunk is
+        # sized by the largest shard, not by this one
+        n = frame.n_segments
+        per_iter = 8 * (max_rows + self.user_stride + 3 * n) + 16
+        self.chunk = int(max(1, min(max(n_epochs, 1), EvalLoop.CHUNK_BYTES // per_iter)))
+        f64 = torch.float64
+        self.scores = rt.empty((self.chunk, max(self.n_rows, 1)), f64)
+        self.slots = rt.empty((self.chunk, self.user_stride), f64)
+        self.full = rt.empty((self.chunk, max(3 * n, 1)), f64)
+        self.out = rt.empty((max(n_epochs, 1), 2), f64)
+        self.values: list = []
+        self.host_calls = 0
+        self.host_users = 0
+        self._flushed = 0
+
+    def room(self, epoch: int) -> int:
+        """Iterations from ``epoch`` on that fit the current chunk of score slots."""
+        return self.chunk - epoch % self.chunk
+
+    def call_args(self, first: int) -> tuple:
+        """The evaluation arguments of ``rfm_fm_fit_dp_eval`` for a run that starts at ``first``."""
+        slot = first % self.chunk
+        c, n = self.csr, self.frame.n_segments
+        return (c.indptr.data_ptr() if c else None, c.indices.data_ptr() if c else None,
+                c.values.data_ptr() if c else None, self.n_rows, self.frame.n_rows,
+                self.seg_ptr.data_ptr(), None, self.labels.data_ptr(),
+                None if self.pscores is None else self.pscores.data_ptr(), self.local.n_segments, self.frame.k,
+                self.scores.data_ptr(), self.scores.shape[1], self.slots.data_ptr(), self.user_stride, slot,
+                self.group_lo.ctypes.data, self.pad, n, self.full.data_ptr() + slot * self.full.shape[1] * 8,
+                self.out.data_ptr() + first * 16)
+
+    def ran(self, first: int, count: int) -> None:
+        """Iterations ``first .. first + count`` (inside one chunk) were scored and measured."""
+        if (first + count) % self.chunk == 0:
+            self._flush(first + count)
+
+    def _flush(self, upto: int) -> None:
+        import numpy as np
+
+        if upto <= self._flushed:
+            return
+        self.rt.sync()
+        n = self.frame.n_segments
+        o = self.out[self._flushed:upto].cpu().numpy()
+        # (the table and its means are the same on every rank, bit for bit: so is this list, and
+        # every rank takes part in the exchange below or none does)
+        flagged = [e for i, e in enumerate(range(self._flushed, upto)) if o[i, 1] != 0.0]
+        tables, mine = {}, []
+        for e in flagged:
+            t = self.full[e % self.chunk][: 3 * n].cpu().numpy()
+            tables[e] = t
+            redo = np.flatnonzero(t[2 * n:] != 0.0)
+            own = redo[(redo >= self.g0) & (redo < self.g1)]
+            if own.size:
+                sc = self.scores[e % self.chunk][: self.n_rows].cpu().numpy()
+                mine.append((e, own, self.local.host_user_values(sc, own - self.g0)))
+        parts = [mine]
+        if flagged and self.world > 1:
+            import torch.distributed as dist
+
+            parts = [None] * self.world
+            dist.all_gather_object(parts, mine, group=self.group)
+        fixed = {}
+        for part in parts:
+            for e, groups, vals in part:
+                fixed.setdefault(e, []).append((groups, vals))
+        for i, e in enumerate(range(self._flushed, upto)):
+            if o[i, 1] == 0.0:
+                self.values.append(float(o[i, 0]))
+                continue
+            t = tables[e]
+            vals = t[:n].copy()
+            counted = t[n: 2 * n] != 0.0
+            for groups, v in fixed.get(e, []):
+                vals[groups] = v
+            self.values.append(float(np.mean(vals[counted])))
+            self.host_calls += 1
+            self.host_users += int(o[i, 1])
+        self._flushed = upto
+
+    def finish(self, n_done: int) -> list:
+        self._flush(n_done)
+        return self.values
+
+
 class HipDpEngine:
     """One rank's side of ``fit_data_parallel`` on the HIP kernels: the log replicated in HBM,
     a training plan for this rank's shard size, and runs of iterations handed to
@@ -653,6 +797,63 @@ class HipDpEngine:
             raise self.transport.error
         self._lib.check(rc)
 
+    def eval_loop(self, evaluator):
+        """The device form of ``evaluator`` for ``run_eval`` (``DpEvalLoop``), or ``None`` when it is
+        not recognised -- the rule of the single-GPU ``fit()`` (``evaluate.device_frame``)."""
+        from .evaluate import host_frame
+
+        m = self.model
+        ev_X = evaluator.features[m.model_name]
+        frame = host_frame(evaluator, m.estimator, ev_X.shape[0])
+        if frame is None:
+            return None
+        if ev_X.shape[1] != m.n_features:
+            raise ValueError(f"X has {ev_X.shape[1]} columns, model has {m.n_features}")
+        ev = m._csr_cache.get(ev_X)
+        self._loop = DpEvalLoop(self.rt, self.plan, frame, ev, evaluator, self.world, self.rank, m.n_epochs,
+                                getattr(self.transport, "group", None))
+        return self._loop
+
+    def run_eval(self, first: int, count: int, chunk_first: int, dev_ids, loop) -> None:
+        """``run`` with the evaluator of ``loop`` after every update (``rfm_fm_fit_dp_eval``);
+        ``count <= loop.room(first)``."""
+        import ctypes as C
+
+        from .base import LOSS_EPS
+
+        m, rt, B = self.model, self.rt, self.global_batch
+        ids_ptr = dev_ids.data_ptr() + (first - chunk_first) * B * 4
+        tp = C.byref(self._c_transport) if self._c_transport is not None else None
+        rc = rt.lib.rfm_fm_fit_dp_eval(
+            rt.ctx, self.plan.handle, tp, self.exchange, ids_ptr, B, count,
+            m.w0.dev.data_ptr(), m.w.dev.data_ptr(), m.V.dev.data_ptr(), float(m.lr),
+            self.va.indptr.data_ptr(), self.va.indices.data_ptr(), self.va.values.data_ptr(),
+            self.vy.data_ptr(), self.vp.data_ptr(), self.va.shape[0], LOSS_EPS,
+            self.tl.data_ptr() + first * 8, self.vl.data_ptr() + first * 8 if self.has_val else None,
+            *loop.call_args(first))
+        if rc != 0 and self.transport is not None and self.transport.error is not None:
+            raise self.transport.error
+        self._lib.check(rc)
+
+    def leave_scores(self, loop) -> None:
+        """The reference's ``evaluate`` leaves the scores it was given in its frame
+        (``interaction_df["y_score"]``, utils/evaluate.py:224): the whole log's scores with the
+        final parameters, one ``rfm_fm_plan_forward`` (the same on every rank)."""
+        import torch
+
+        m, rt, ev = self.model, self.rt, loop.ev
+        n = ev.shape[0]
+        out = rt.empty((max(n, 1),), torch.float64)
+        if n:
+            self._lib.check(rt.lib.rfm_fm_plan_forward(
+                rt.ctx, self.plan.handle, ev.indptr.data_ptr(), ev.indices.data_ptr(), ev.values.data_ptr(), n,
+                m.w0.dev.data_ptr(), m.w.dev.data_ptr(), m.V.dev.data_ptr(), out.data_ptr()))
+        rt.sync()
+        try:
+            loop.evaluator.interaction_df["y_score"] = out[:n].cpu().numpy()
+        except Exception:  # noqa: BLE001 -- a read-only or exotic frame: nothing to leave
+            pass
+
     def predict(self, X):
         return self.model.predict(X=X)
 
@@ -663,6 +864,9 @@ class HipDpEngine:
     def close(self) -> None:
         self.ids.close()
         self.rt.sync()
+        if getattr(self, "_loop", None) is not None:  # (the shard's registration ends with the fit)
+            self.rt.lib.rfm_fm_plan_register_log(self.rt.ctx, self.plan.handle, 1, None, None, None, 0)
+            self._loop = None
         self.plan.close()
 
 
@@ -683,9 +887,13 @@ def fit_data_parallel(model, train: dict, val: dict, exchange: str = "auto", tra
     differ from the single-GPU fit in summation order only.
 
     ``transport``: None = RCCL inside the library (backend nccl: one process per GPU);
-    ``HostStagedTransport`` otherwise.  ``model.evaluator`` is called after every iteration on
-    every rank (the replicas are identical, so are the metrics), as ``src/fm.py:104-110``.
-    ``engine_factory`` replaces the arithmetic (tests)."""
+    ``HostStagedTransport`` otherwise.  ``model.evaluator``, as ``src/fm.py:104-110``: a
+    ValEvaluator that the single-GPU ``fit()`` computes on the device (``evaluate.device_frame``,
+    ``model.device_evaluator``) is computed on the device here too, inside the library's loop,
+    each rank scoring the rows of its share of the user groups (``DpEvalLoop``); any other
+    evaluator -- or an engine without ``run_eval`` -- is called after every iteration on every rank
+    (the replicas are identical, so are the metrics).  ``engine_factory`` replaces the arithmetic
+    (tests)."""
     import torch.distributed as dist
 
     world, rank = dist.get_world_size(), dist.get_rank()
@@ -707,14 +915,30 @@ def fit_data_parallel(model, train: dict, val: dict, exchange: str = "auto", tra
     engine = engine_factory(model, train, val, world, rank, exchange, transport)
     try:
         evaluator = getattr(model, "evaluator", None)
+        loop = None
+        if evaluator is not None and getattr(model, "device_evaluator", False) and hasattr(engine, "run_eval"):
+            loop = engine.eval_loop(evaluator)
         for chunk_first, count, ids in engine.chunks():
             if evaluator is None:
                 engine.run(chunk_first, count, chunk_first, ids)
-                continue
-            for epoch in range(chunk_first, chunk_first + count):
-                engine.run(epoch, 1, chunk_first, ids)
-                scores = engine.predict(evaluator.features[model.model_name])
-                model.val_metrics.append(evaluator.evaluate(y_scores=scores, estimator=model.estimator))
+            elif loop is not None:
+                # one library call per run of iterations that fits the chunk of score slots
+                at = chunk_first
+                while at < chunk_first + count:
+                    n = min(chunk_first + count - at, loop.room(at), 1 << 15)
+                    engine.run_eval(at, n, chunk_first, ids, loop)
+                    loop.ran(at, n)
+                    at += n
+            else:
+                for epoch in range(chunk_first, chunk_first + count):
+                    engine.run(epoch, 1, chunk_first, ids)
+                    scores = engine.predict(evaluator.features[model.model_name])
+                    model.val_metrics.append(evaluator.evaluate(y_scores=scores, estimator=model.estimator))
+        if loop is not None:
+            model.val_metrics.extend(loop.finish(model.n_epochs))
+            model.evaluator_host_calls = loop.host_calls
+            model.evaluator_host_users = loop.host_users
+            engine.leave_scores(loop)
         return engine.losses()
     finally:
         engine.close()

@@ -71,6 +71,20 @@ class ValFrame:
                 raise ValueError("pscores must match the frame's rows")
             self.h_pscores = pscores[self.h_order] if n else np.zeros(0)
 
+    def take_groups(self, lo: int, hi: int) -> "ValFrame":
+        """User groups ``lo .. hi - 1`` as a frame of their own whose rows are theirs in grouped
+        order: its row ``j`` is row ``h_order[h_seg_ptr[lo] + j]`` of this frame, its group ``g``
+        is group ``lo + g`` here (a rank's shard of the log in ``dist.fit_data_parallel``)."""
+        r0, r1 = int(self.h_seg_ptr[lo]), int(self.h_seg_ptr[hi])
+        out = ValFrame.__new__(ValFrame)
+        out.k, out.n_rows = self.k, r1 - r0
+        out.h_order = np.arange(r1 - r0, dtype=np.int32)
+        out.h_seg_ptr = (self.h_seg_ptr[lo: hi + 1] - r0).astype(np.int32)
+        out.n_segments = int(hi - lo)
+        out.h_labels = self.h_labels[r0:r1].copy()
+        out.h_pscores = None if self.h_pscores is None else self.h_pscores[r0:r1].copy()
+        return out
+
     def host_user_value(self, scores: np.ndarray, g: int) -> float:
         """IPS-DCG@k of user group ``g`` exactly as the reference computes it
         (utils/evaluate.py:194-204 with utils/metrics.py:53-80), including whatever order
@@ -285,6 +299,16 @@ def recognise(evaluator, estimator: str, any_implementation: bool = False):
     # evaluate.py:222: pscore for IPS, ones_pscore for every other estimator
     p = cols["pscore"] if estimator == "IPS" else cols["ones_pscore"]
     return cols["user"], cols["label"], p, int(k)
+
+
+def host_frame(evaluator, estimator: str, n_scores: int) -> Optional[ValFrame]:
+    """The grouped host frame of ``evaluator`` under the rule of ``device_frame`` (recognised, and
+    ``n_scores`` rows); else ``None``."""
+    got = recognise(evaluator, estimator)
+    if got is None or got[0].shape[0] != n_scores:
+        return None
+    users, labels, pscores, k = got
+    return ValFrame(users, labels, pscores, k)
 
 
 def device_frame(rt: Runtime, evaluator, estimator: str, n_scores: int) -> Optional[DeviceValFrame]:
