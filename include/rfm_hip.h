@@ -596,6 +596,53 @@ int32_t rfm_csr_assemble_fill(rfm_ctx* ctx, const rfm_csr_segment* h_segments, i
                               int64_t n_rows, const int64_t* d_indptr, int32_t* d_out_indices,
                               double* d_out_values);
 
+/* ---- catalogue scoring and top-K -----------------------------
+ * Every (user, item) pair of a trained model without the design matrix of the pairs.  The FM
+ * rows the reference's loaders build are "the user's entries + the item's entries" on disjoint
+ * columns, x(u,i) = xu(u) + xi(i); with a_u = sum_j xu_j V[j,:], b_i = sum_j xi_j V[j,:] and, per
+ * side, L(x) = w.x + 0.5 sum_f((sum_j x_j V[j,f])^2 - sum_j x_j^2 V[j,f]^2), the logit of
+ * FactorizationMachines.predict (src/fm.py:114-133) is exactly
+ *     logit(u,i) = w0 + L(xu) + L(xi) + a_u . b_i,
+ * and LogisticMatrixFactorization._predict_pair (src/mf.py:136-170) has the same shape with
+ * a = P, b = Q, L = b_u, b_i and the constant b.
+ *
+ * rfm_fm_side_sums: A[n_rows][kpad] and L[n_rows] of a CSR side matrix (one row per user, or
+ * per item; dtypes as everywhere), kpad = n_factors rounded up to a multiple of 4, the padding
+ * zero-filled.  Entries are summed in stored order and the factors in a fixed order: bitwise
+ * reproducible.  A column index outside 0..n_features-1 is never read; with RFM_CHECK_IDS=1 it
+ * is RFM_ERR_BAD_ARG (this synchronises), otherwise the entry is skipped. */
+int32_t rfm_fm_side_sums(rfm_ctx* ctx, const int64_t* d_indptr, const int32_t* d_indices,
+                         const double* d_values, int64_t n_rows, const double* d_w, const double* d_V,
+                         int64_t n_features, int32_t n_factors, double* d_A, double* d_L);
+/* d_out[s][i] = sigmoid(clip(*d_c + LU[u] + LI[i] + A[u,:].B[i,:], +-700)) (src/base.py:63-66; a
+ * NaN logit stays NaN) for every item i and selected user s, u = d_user_ids ? d_user_ids[s] : s
+ * (any order, repeats allowed; NULL needs n_sel_users == n_users).  A is [n_users][kpad], B is
+ * [n_items][kpad] with kpad as above (MF: P and Q themselves when n_factors % 4 == 0); the
+ * product runs on the f64 matrix core in 64 x 64 tiles.  *d_c is FM's w0 / MF's b, read on the
+ * device.  A user id outside 0..n_users-1 scores NaN (RFM_CHECK_IDS=1: RFM_ERR_BAD_ARG). */
+int32_t rfm_pair_scores(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t n_users,
+                        const int32_t* d_user_ids, int64_t n_sel_users, const double* d_B,
+                        const double* d_LI, int64_t n_items, int32_t n_factors, const double* d_c,
+                        double* d_out);
+/* The k best items of every selected user, 1 <= k <= 64 (else RFM_ERR_BAD_ARG), under the TOTAL
+ * order (logit descending, then item index descending): np.argsort(logit, kind="stable")[::-1][:k],
+ * the tie rule of rfm_val_dcg / rfm_topk_users.  Ranking is by the logit, never by the
+ * probability (which saturates to exactly 0.0 / 1.0).  A NaN logit is never ranked.
+ * d_out_items[s][r] = item of rank r, d_out_scores[s][r] = its sigmoid(logit); fewer than k
+ * rankable items pads with item -1 / score NaN.  Optional exclusion lists, CSR by USER ID
+ * (d_excl_indptr[n_users + 1], strictly ascending item ids; NULL = none): a listed item is never
+ * returned to that user.  The items are split over workgroups that keep partial lists in
+ * d_workspace (rfm_pair_topk_workspace bytes; host only, a function of the three sizes), merged by
+ * a second launch; because the order is total the result does not depend on the split, and no
+ * float atomic is used: the same inputs give the same bits.  RFM_CHECK_IDS=1 validates the user
+ * ids and the exclusion lists first (RFM_ERR_BAD_ARG; this synchronises). */
+int32_t rfm_pair_topk_workspace(int64_t n_sel_users, int64_t n_items, int32_t k, int64_t* h_bytes);
+int32_t rfm_pair_topk(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t n_users,
+                      const int32_t* d_user_ids, int64_t n_sel_users, const double* d_B,
+                      const double* d_LI, int64_t n_items, int32_t n_factors, const double* d_c,
+                      const int64_t* d_excl_indptr, const int32_t* d_excl_items, int32_t k,
+                      void* d_workspace, int32_t* d_out_items, double* d_out_scores);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,7 +17,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 # RFM_LIB_PATH: load another build of the same ABI (timing experiments under profiles/)
 LIB_PATH = os.environ.get("RFM_LIB_PATH") or os.path.join(PKG_DIR, "librfm_hip.so")
-SOURCES = ["rfm_capi.hip", "rfm_fm.hip", "rfm_fm_plan.hip", "rfm_mf.hip", "rfm_eval.hip", "rfm_csr.hip", "rfm_sample.hip", "rfm_host.cpp", "rfm_comm.cpp"]
+SOURCES = ["rfm_capi.hip", "rfm_fm.hip", "rfm_fm_plan.hip", "rfm_mf.hip", "rfm_eval.hip", "rfm_csr.hip", "rfm_sample.hip", "rfm_pairs.hip", "rfm_host.cpp", "rfm_comm.cpp"]
 # every header under csrc/ (a change of any of them rebuilds every object) + the C ABI
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp"))) + [
     os.path.join(os.path.dirname(PKG_DIR), "include", "rfm_hip.h")]
@@ -166,6 +166,11 @@ SIGNATURES = {
     "rfm_csr_assemble_count": [_vp, _vp, _i32, _i64, _vp, _vp],
     "rfm_csr_assemble_fill": [_vp, _vp, _i32, _i64, _vp, _vp, _vp],
     "rfm_topk_users": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
+    "rfm_fm_side_sums": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp],
+    "rfm_pair_scores": [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp],
+    "rfm_pair_topk_workspace": [_i64, _i64, _i32, C.POINTER(_i64)],
+    "rfm_pair_topk": [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _vp,
+                      _vp],
 }
 
 

@@ -1,0 +1,549 @@
+// Catalogue scoring and top-K: every (user, item) pair of a trained model
+// without the design matrix of the pairs.
+//
+// A pair's FM row is the user's entries + the item's entries on disjoint columns,
+// x(u,i) = xu(u) + xi(i).  With a_u = sum_j xu_j V[j,:], b_i = sum_j xi_j V[j,:] and, per side,
+// L(x) = w.x + 0.5 sum_f((sum_j x_j V[j,f])^2 - sum_j x_j^2 V[j,f]^2), the reference's logit
+// (src/fm.py:124-132) is exactly
+//     logit(u,i) = w0 + L(xu) + L(xi) + a_u . b_i
+// and MF's (src/mf.py:154-170) has the same shape with a = P, b = Q, L = b_u, b_i and the
+// constant b.  Two kernels: the side sums (one wavefront per sparse row) and the pair tile, a
+// dense [users x k].[k x items] product on the f64 matrix core (v_mfma_f64_16x16x4_f64) with
+// two epilogues: sigmoid scores, or the K best items per user under the total order
+// (logit descending, item index descending).  Every sum has a fixed order and no float
+// atomic is used: the same inputs give the same bits.
+#include <cmath>
+#include <cstdlib>
+
+#include "rfm_common.h"
+#include "rfm_device_utils.hpp"
+
+namespace rfm {
+namespace {
+
+constexpr int kPairBlock = 256;  // 4 wavefronts, 2 x 2 over the tile
+constexpr int kTile = 64;        // users and items of a workgroup tile
+constexpr int kChunk = 32;       // factors staged in LDS at a time
+// LDS row stride (doubles) of one factor's 64 tile rows.  A k-step's ds_read_b64 takes lanes
+// 0-31 (MFMA k-slots 0 and 1) in one LDS cycle; slot s reads factor s * 8 + step, so the two
+// slots are 8 * 66 = 16 (mod 32) doubles apart and the 32 lanes fall on 32 distinct 8-byte
+// bank pairs.  The staging writes (factor fastest) are 2-way conflicted: 1 write per 2+ reads.
+constexpr int kLd = 66;
+constexpr int kOperandDoubles = 2 * kChunk * kLd;  // A and B chunk
+constexpr int kLogitLd = kTile + 1;                // top-K epilogue: the tile's logits [user][item]
+constexpr int kMaxTopK = 64;
+constexpr int kTargetWorkgroups = 1024;  // top-K: item splits are chosen to reach about this many
+
+using f64x4 = __attribute__((__vector_size__(4 * sizeof(double)))) double;
+
+inline int64_t pad4(int64_t k) { return (k + 3) / 4 * 4; }
+
+inline bool check_ids_enabled() {
+  const char* v = std::getenv("RFM_CHECK_IDS");
+  return v && std::atoi(v) != 0;
+}
+
+// ---------------------------------------------------------------------------
+// side sums: A[r, 0:kpad] = sum_j S[r,j] V[j,:] (zero beyond k), L[r] as above.
+// One wavefront per row, lanes over factors (64 at a time: coalesced V row reads), entries in
+// stored order, the factors' partial sums reduced by a fixed xor tree.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kPairBlock) void side_sums_kernel(
+    const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
+    const double* __restrict__ values, int64_t n_rows, const double* __restrict__ w,
+    const double* __restrict__ V, int64_t n_features, int k, int kpad, double* __restrict__ A,
+    double* __restrict__ L, int32_t* flags) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = int64_t(blockIdx.x) * (kPairBlock / 64) + (threadIdx.x >> 6);
+  if (r >= n_rows) return;
+  const int64_t lo = indptr[r], hi = indptr[r + 1];
+  double lin = 0.0, cross = 0.0;
+  for (int f0 = 0; f0 < kpad; f0 += 64) {
+    const int f = f0 + lane;
+    double s = 0.0, q = 0.0;
+    for (int64_t e = lo; e < hi; ++e) {
+      const int64_t col = indices[e];
+      if (col < 0 || col >= n_features) {  // never read outside V; reported under RFM_CHECK_IDS
+        if (flags && lane == 0) atomicOr(flags, 1);
+        continue;
+      }
+      const double x = values[e];
+      if (f0 == 0) lin += x * w[col];
+      if (f < k) {
+        const double v = V[col * int64_t(k) + f];
+        s += x * v;
+        q += (x * x) * (v * v);
+      }
+    }
+    if (f < kpad) A[r * int64_t(kpad) + f] = s;
+    cross += s * s - q;
+  }
+  for (int m = 32; m >= 1; m >>= 1) cross += __shfl_xor(cross, m, 64);
+  if (lane == 0) L[r] = lin + 0.5 * cross;
+}
+
+// ---------------------------------------------------------------------------
+// top-K lists.  Entry = (logit, item); an empty slot is (-inf, -1), which every real
+// candidate beats.  Lane j of a wavefront holds entry j of a list sorted best first.
+// ---------------------------------------------------------------------------
+__device__ inline bool better(double la, int ia, double lb, int ib) {
+  return la > lb || (la == lb && ia > ib);
+}
+
+// Value of lane `src` (wave-uniform) for every lane: v_readlane, no LDS round trip.
+__device__ inline int lane_get(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
+__device__ inline double lane_get(double v, int src) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src),
+                          __builtin_amdgcn_readlane(__double2loint(v), src));
+}
+// Value of the lane below (lane 0 keeps its own): DPP wave_shr:1.
+__device__ inline int lane_below(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xF, 0xF, false); }
+__device__ inline double lane_below(double v) {
+  return __hiloint2double(lane_below(__double2hiint(v)), lane_below(__double2loint(v)));
+}
+
+// Insert the candidates of the lanes named by `mask` (one per lane; wave-uniform) into the list
+// held by lanes 0 .. K-1.  The order is total, so the result does not depend on the order of
+// insertion.  Must be called with all 64 lanes active.
+__device__ inline void list_insert(unsigned long long mask, double cl, int ci, int K, int lane,
+                                   double& ml, int& mi) {
+  while (mask) {
+    const int b = __builtin_amdgcn_readfirstlane(__ffsll((long long)mask) - 1);
+    mask &= mask - 1;
+    const double l = lane_get(cl, b);
+    const int i = lane_get(ci, b);
+    if (!better(l, i, lane_get(ml, K - 1), lane_get(mi, K - 1))) continue;
+    // the entries that stay in front of the candidate are a prefix of the list
+    const int p = __popcll(__ballot(lane < K && better(ml, mi, l, i)));
+    const double ul = lane_below(ml);
+    const int ui = lane_below(mi);
+    if (lane == p) {
+      ml = l;
+      mi = i;
+    } else if (lane > p) {
+      ml = ul;
+      mi = ui;
+    }
+  }
+}
+
+// true if `item` is in the ascending list excl[lo, hi)
+__device__ inline bool excluded(const int32_t* __restrict__ excl, int64_t lo, int64_t hi, int item) {
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    const int v = excl[mid];
+    if (v == item) return true;
+    if (v < item) lo = mid + 1; else hi = mid;
+  }
+  return false;
+}
+
+struct PairArgs {
+  const double* A;         // [n_users][kpad]
+  const double* LU;        // [n_users]
+  const int32_t* user_ids; // [n_sel] or null (selected user s = user s)
+  int64_t n_users, n_sel;
+  const double* B;         // [n_items][kpad]
+  const double* LI;        // [n_items]
+  int64_t n_items;
+  int kpad;
+  const double* c;         // device scalar
+  // scores epilogue
+  double* out;             // [n_sel][n_items]
+  // top-K epilogue
+  const int64_t* excl_indptr;  // [n_users + 1] or null
+  const int32_t* excl_items;
+  int K, n_splits, tiles_per_split;
+  double* ws_logit;        // [n_splits][n_sel][K]
+  int32_t* ws_item;
+  int32_t* flags;          // RFM_CHECK_IDS: bit 1 = a user id outside the table
+};
+
+// logit[u,i] = c + LU[u] + LI[i] + A[u,:].B[i,:] over a 64 x 64 tile: wavefront (wm, wn) owns
+// the 32 x 32 quarter at (32 wm, 32 wn) as 2 x 2 MFMA blocks of 16 x 16; the factors go
+// through LDS in chunks of 32 so that each operand element is read from memory once per tile.
+// TOPK: blockIdx.x is an item split; the workgroup walks the split's tiles and keeps the K best
+// items of each of its 64 users in LDS lists, written to the workspace at the end.
+template <bool TOPK>
+__global__ __launch_bounds__(kPairBlock) void pair_tile_kernel(PairArgs a) {
+  extern __shared__ double lds[];
+  double* As = lds;                    // [kChunk][kLd]
+  double* Bs = lds + kChunk * kLd;     // [kChunk][kLd]
+  double* T = lds;                     // TOPK epilogue, after the product: [kTile][kLogitLd]
+  constexpr int kUnion = kOperandDoubles > kTile * kLogitLd ? kOperandDoubles : kTile * kLogitLd;
+  double* list_l = lds + kUnion;                                        // [kTile][K]
+  int32_t* list_i = reinterpret_cast<int32_t*>(list_l + kTile * (TOPK ? a.K : 0));
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int64_t u0 = int64_t(blockIdx.y) * kTile;
+  const int kpad = a.kpad;
+
+  // staging: thread -> factor tid & 31 of rows (tid >> 5) + 8 j: 256-byte runs of a row
+  const int sk = tid & (kChunk - 1), sr = tid >> 5;
+  const double* a_row[8];
+  bool user_ok[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int64_t s = u0 + sr + 8 * j;
+    int64_t u = -1;
+    if (s < a.n_sel) {
+      u = a.user_ids ? int64_t(a.user_ids[s]) : s;
+      if (u < 0 || u >= a.n_users) {
+        if (a.flags && sk == 0) atomicOr(a.flags, 2);
+        u = -1;
+      }
+    }
+    user_ok[j] = u >= 0;
+    a_row[j] = a.A + (u >= 0 ? u : 0) * int64_t(kpad);
+  }
+
+  if (TOPK) {
+    for (int e = tid; e < kTile * a.K; e += kPairBlock) {
+      list_l[e] = -INFINITY;
+      list_i[e] = -1;
+    }
+  }
+
+  const int n_item_tiles = int((a.n_items + kTile - 1) / kTile);
+  const int t_first = TOPK ? blockIdx.x * a.tiles_per_split : blockIdx.x;
+  const int t_last = TOPK ? min(t_first + a.tiles_per_split, n_item_tiles) : t_first + 1;
+  const double c = a.c[0];
+
+  for (int t = t_first; t < t_last; ++t) {
+    const int64_t i0 = int64_t(t) * kTile;
+    f64x4 acc[2][2];
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+      for (int y = 0; y < 2; ++y) acc[x][y] = f64x4{0.0, 0.0, 0.0, 0.0};
+
+    double ra[8], rb[8];  // the next chunk on its way from memory while this one is multiplied
+    auto fetch = [&](int k0) {
+      const int kk = k0 + sk;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int64_t item = i0 + sr + 8 * j;
+        ra[j] = (kk < kpad && user_ok[j]) ? a_row[j][kk] : 0.0;
+        rb[j] = (kk < kpad && item < a.n_items) ? a.B[item * int64_t(kpad) + kk] : 0.0;
+      }
+    };
+    fetch(0);
+    for (int k0 = 0; k0 < kpad; k0 += kChunk) {
+      __syncthreads();  // the chunk before (or the epilogue's T, or the lists' init) is done with
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        As[sk * kLd + sr + 8 * j] = ra[j];
+        Bs[sk * kLd + sr + 8 * j] = rb[j];
+      }
+      __syncthreads();
+      if (k0 + kChunk < kpad) fetch(k0 + kChunk);
+      // factors of this chunk (a multiple of 4): MFMA k-slot s takes the quarter [s q, s q + q)
+      const int q = min(kChunk, kpad - k0) >> 2;
+      const double* ap = As + ((lane >> 4) * q) * kLd + wm * 32 + (lane & 15);
+      const double* bp = Bs + ((lane >> 4) * q) * kLd + wn * 32 + (lane & 15);
+      for (int s = 0; s < q; ++s) {
+        const double a0 = ap[s * kLd], a1 = ap[s * kLd + 16];
+        const double b0 = bp[s * kLd], b1 = bp[s * kLd + 16];
+        acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+      }
+    }
+
+    // C/D layout of the f64 MFMA: column (item) = lane & 15, row (user) = (lane >> 4) + 4 reg
+    if (TOPK) __syncthreads();  // every wavefront has read its operands: T may overwrite them
+#pragma unroll
+    for (int x = 0; x < 2; ++x) {
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int ul = wm * 32 + x * 16 + (lane >> 4) + 4 * reg;
+        const int64_t s = u0 + ul;
+        int64_t u = -1;
+        if (s < a.n_sel) {
+          u = a.user_ids ? int64_t(a.user_ids[s]) : s;
+          if (u < 0 || u >= a.n_users) u = -1;
+        }
+        const double lu = u >= 0 ? a.LU[u] : NAN;  // a user id outside the table scores NaN
+#pragma unroll
+        for (int y = 0; y < 2; ++y) {
+          const int il = wn * 32 + y * 16 + (lane & 15);
+          const int64_t item = i0 + il;
+          const bool in = s < a.n_sel && item < a.n_items;
+          const double logit = in ? ((c + lu) + a.LI[item]) + acc[x][y][reg] : NAN;
+          if (TOPK) {
+            T[ul * kLogitLd + il] = logit;
+          } else if (in) {
+            a.out[s * a.n_items + item] = sigmoid_clipped(logit);
+          }
+        }
+      }
+    }
+    if (!TOPK) continue;
+    __syncthreads();
+    // wavefront w ranks users 16 w .. 16 w + 15, lane = item of the tile.  A candidate is
+    // looked at further only if it beats the list's current K-th entry; after the first tiles
+    // almost none does.  NaN logits (and the tile's padding) are never ranked.
+    for (int j = 0; j < 16; ++j) {
+      const int ul = wave * 16 + j;
+      const int64_t s = u0 + ul;
+      if (s >= a.n_sel) break;
+      const double cl = T[ul * kLogitLd + lane];
+      const int ci = int(i0) + lane;
+      double* ll = list_l + ul * a.K;
+      int32_t* li = list_i + ul * a.K;
+      bool pass = cl == cl && better(cl, ci, ll[a.K - 1], li[a.K - 1]);
+      if (__ballot(pass) == 0) continue;
+      if (pass && a.excl_indptr) {
+        const int64_t u = a.user_ids ? int64_t(a.user_ids[s]) : s;  // (in range: its logits are not NaN)
+        pass = !excluded(a.excl_items, a.excl_indptr[u], a.excl_indptr[u + 1], ci);
+      }
+      unsigned long long mask = __ballot(pass);
+      if (mask == 0) continue;
+      if (__popcll(mask) > a.K) {
+        // (a split's first tiles) only the K best of the tile's own candidates can enter the
+        // list: every lane counts the candidates that beat its own, in parallel, which is much
+        // cheaper than letting the serial insertion below turn the others away one by one
+        int rank = 0;
+        for (unsigned long long m = mask; m; m &= m - 1) {
+          const int b = __builtin_amdgcn_readfirstlane(__ffsll((long long)m) - 1);
+          rank += better(lane_get(cl, b), lane_get(ci, b), cl, ci) ? 1 : 0;
+        }
+        pass = pass && rank < a.K;
+        mask = __ballot(pass);
+      }
+      double ml = lane < a.K ? ll[lane] : -INFINITY;
+      int mi = lane < a.K ? li[lane] : -1;
+      list_insert(mask, cl, ci, a.K, lane, ml, mi);
+      if (lane < a.K) {
+        ll[lane] = ml;
+        li[lane] = mi;
+      }
+    }
+    // (the next tile's first barrier orders these reads of T before its staging writes)
+  }
+
+  if (TOPK) {
+    // a wavefront wrote the lists it now copies out: no barrier needed
+    for (int j = 0; j < 16; ++j) {
+      const int ul = wave * 16 + j;
+      const int64_t s = u0 + ul;
+      if (s >= a.n_sel) break;
+      if (lane < a.K) {
+        const int64_t at = (int64_t(blockIdx.x) * a.n_sel + s) * a.K + lane;
+        a.ws_logit[at] = list_l[ul * a.K + lane];
+        a.ws_item[at] = list_i[ul * a.K + lane];
+      }
+    }
+  }
+}
+
+// One wavefront per selected user: the splits' partial lists (each sorted) into the final one;
+// scores = sigmoid(logit), an empty slot = item -1 / score NaN.
+__global__ __launch_bounds__(kPairBlock) void topk_merge_kernel(
+    const double* __restrict__ ws_logit, const int32_t* __restrict__ ws_item, int n_splits,
+    int64_t n_sel, int K, int32_t* __restrict__ out_items, double* __restrict__ out_scores) {
+  const int lane = threadIdx.x & 63;
+  const int64_t s = int64_t(blockIdx.x) * (kPairBlock / 64) + (threadIdx.x >> 6);
+  if (s >= n_sel) return;
+  double ml = -INFINITY;
+  int mi = -1;
+  for (int p = 0; p < n_splits; ++p) {
+    const int64_t at = (int64_t(p) * n_sel + s) * K + lane;
+    const double cl = lane < K ? ws_logit[at] : -INFINITY;
+    const int ci = lane < K ? ws_item[at] : -1;
+    const double tl = lane_get(ml, K - 1);
+    const int ti = lane_get(mi, K - 1);
+    const bool pass = ci >= 0 && better(cl, ci, tl, ti);
+    const unsigned long long mask = __ballot(pass);
+    if (mask) list_insert(mask, cl, ci, K, lane, ml, mi);
+  }
+  if (lane < K) {
+    out_items[s * K + lane] = mi;
+    out_scores[s * K + lane] = mi >= 0 ? sigmoid_clipped(ml) : NAN;
+  }
+}
+
+// RFM_CHECK_IDS=1: indptr monotone from 0, every list strictly ascending inside 0 .. n_items-1
+__global__ __launch_bounds__(kPairBlock) void excl_check_kernel(const int64_t* indptr,
+                                                               const int32_t* items, int64_t n_users,
+                                                               int64_t n_items, int32_t* flags) {
+  for (int64_t u = int64_t(blockIdx.x) * kPairBlock + threadIdx.x; u < n_users;
+       u += int64_t(gridDim.x) * kPairBlock) {
+    const int64_t lo = indptr[u], hi = indptr[u + 1];
+    if ((u == 0 && lo != 0) || hi < lo) {
+      atomicOr(flags, 4);
+      continue;
+    }
+    for (int64_t e = lo; e < hi; ++e)
+      if (items[e] < 0 || items[e] >= n_items || (e > lo && items[e] <= items[e - 1])) {
+        atomicOr(flags, 8);
+        break;
+      }
+  }
+}
+
+struct Split {
+  int n_splits, tiles_per_split;
+};
+
+// item splits of the top-K launch: a function of the sizes only (the workspace is sized by it)
+Split topk_split(int64_t n_sel, int64_t n_items) {
+  const int64_t user_tiles = std::max<int64_t>(1, (n_sel + kTile - 1) / kTile);
+  const int64_t item_tiles = std::max<int64_t>(1, (n_items + kTile - 1) / kTile);
+  const int64_t want = std::max<int64_t>(1, std::min(item_tiles, (kTargetWorkgroups + user_tiles - 1) / user_tiles));
+  Split s;
+  s.tiles_per_split = int((item_tiles + want - 1) / want);
+  s.n_splits = int((item_tiles + s.tiles_per_split - 1) / s.tiles_per_split);
+  return s;
+}
+
+size_t topk_lds_bytes(int K) {
+  const int kUnion = std::max(kOperandDoubles, kTile * kLogitLd);
+  return size_t(kUnion) * 8 + size_t(kTile) * K * 12;
+}
+
+void require_pair_args(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t n_users,
+                       int64_t n_sel, const double* d_B, const double* d_LI, int64_t n_items,
+                       int32_t n_factors, const double* d_c) {
+  RFM_REQUIRE(ctx && d_A && d_LU && d_B && d_LI && d_c, "null pointer");
+  RFM_REQUIRE(n_factors >= 1 && n_factors <= RFM_MAX_FACTORS, "n_factors=%d unsupported (1..%d)",
+              n_factors, RFM_MAX_FACTORS);
+  RFM_REQUIRE(n_users >= 1 && n_items >= 1, "empty user or item table");
+  RFM_REQUIRE(n_sel >= 0 && n_sel <= (int64_t(65535) * kTile), "n_sel_users=%lld outside 0..%lld",
+              (long long)n_sel, (long long)(int64_t(65535) * kTile));
+  RFM_REQUIRE(n_items < (int64_t(1) << 31) - kTile, "n_items=%lld does not fit int32 item ids",
+              (long long)n_items);
+}
+
+// flags of a checked call (RFM_CHECK_IDS=1): read back after a synchronisation
+struct IdCheck {
+  DevBuf buf;
+  rfm_ctx* ctx;
+  explicit IdCheck(rfm_ctx* c) : ctx(c) {
+    if (!check_ids_enabled()) return;
+    buf.alloc(4);
+    RFM_HIP_CHECK(hipMemsetAsync(buf.p, 0, 4, ctx->stream));
+  }
+  int32_t* flags() const { return buf.as<int32_t>(); }
+  void finish() {
+    if (!buf.p) return;
+    int32_t h = 0;
+    RFM_HIP_CHECK(hipMemcpyAsync(&h, buf.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    RFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    RFM_REQUIRE(!(h & 1), "a column index lies outside 0..n_features-1");
+    RFM_REQUIRE(!(h & 2), "a user id lies outside 0..n_users-1");
+    RFM_REQUIRE(!(h & 4), "the exclusion indptr is not monotone from 0");
+    RFM_REQUIRE(!(h & 8), "an exclusion list is not strictly ascending inside 0..n_items-1");
+  }
+};
+
+LdsLimits g_topk_lds;
+
+}  // namespace
+}  // namespace rfm
+
+using namespace rfm;
+
+extern "C" {
+
+int32_t rfm_fm_side_sums(rfm_ctx* ctx, const int64_t* d_indptr, const int32_t* d_indices,
+                         const double* d_values, int64_t n_rows, const double* d_w, const double* d_V,
+                         int64_t n_features, int32_t n_factors, double* d_A, double* d_L) {
+  return guarded([&] {
+    RFM_REQUIRE(ctx && d_indptr && d_indices && d_values && d_w && d_V && d_A && d_L, "null pointer");
+    RFM_REQUIRE(n_factors >= 1 && n_factors <= RFM_MAX_FACTORS, "n_factors=%d unsupported (1..%d)",
+                n_factors, RFM_MAX_FACTORS);
+    RFM_REQUIRE(n_rows >= 0 && n_features >= 1, "negative n_rows or no features");
+    if (n_rows == 0) return;
+    RFM_HIP_CHECK(hipSetDevice(ctx->device));
+    IdCheck chk(ctx);
+    const int64_t grid = (n_rows + kPairBlock / 64 - 1) / (kPairBlock / 64);
+    RFM_REQUIRE(grid < (int64_t(1) << 31), "n_rows=%lld too large", (long long)n_rows);
+    hipLaunchKernelGGL(side_sums_kernel, dim3((unsigned)grid), dim3(kPairBlock), 0, ctx->stream, d_indptr,
+                       d_indices, d_values, n_rows, d_w, d_V, n_features, n_factors, int(pad4(n_factors)),
+                       d_A, d_L, chk.flags());
+    RFM_HIP_CHECK(hipGetLastError());
+    chk.finish();
+  });
+}
+
+int32_t rfm_pair_scores(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t n_users,
+                        const int32_t* d_user_ids, int64_t n_sel_users, const double* d_B,
+                        const double* d_LI, int64_t n_items, int32_t n_factors, const double* d_c,
+                        double* d_out) {
+  return guarded([&] {
+    require_pair_args(ctx, d_A, d_LU, n_users, n_sel_users, d_B, d_LI, n_items, n_factors, d_c);
+    RFM_REQUIRE(d_user_ids || n_sel_users == n_users, "without user ids every user is selected");
+    if (n_sel_users == 0) return;
+    RFM_REQUIRE(d_out, "null output");
+    RFM_HIP_CHECK(hipSetDevice(ctx->device));
+    IdCheck chk(ctx);
+    PairArgs a{};
+    a.A = d_A, a.LU = d_LU, a.user_ids = d_user_ids, a.n_users = n_users, a.n_sel = n_sel_users;
+    a.B = d_B, a.LI = d_LI, a.n_items = n_items, a.kpad = int(pad4(n_factors)), a.c = d_c;
+    a.out = d_out, a.flags = chk.flags();
+    const dim3 grid((unsigned)((n_items + kTile - 1) / kTile), (unsigned)((n_sel_users + kTile - 1) / kTile));
+    hipLaunchKernelGGL(pair_tile_kernel<false>, grid, dim3(kPairBlock), size_t(kOperandDoubles) * 8,
+                       ctx->stream, a);
+    RFM_HIP_CHECK(hipGetLastError());
+    chk.finish();
+  });
+}
+
+int32_t rfm_pair_topk_workspace(int64_t n_sel_users, int64_t n_items, int32_t k, int64_t* h_bytes) {
+  return guarded([&] {
+    RFM_REQUIRE(h_bytes, "null pointer");
+    RFM_REQUIRE(k >= 1 && k <= kMaxTopK, "k=%d outside 1..%d", k, kMaxTopK);
+    RFM_REQUIRE(n_sel_users >= 0 && n_items >= 1, "negative n_sel_users or no items");
+    const Split sp = topk_split(n_sel_users, n_items);
+    *h_bytes = std::max<int64_t>(16, int64_t(sp.n_splits) * n_sel_users * k * 12);
+  });
+}
+
+int32_t rfm_pair_topk(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t n_users,
+                      const int32_t* d_user_ids, int64_t n_sel_users, const double* d_B,
+                      const double* d_LI, int64_t n_items, int32_t n_factors, const double* d_c,
+                      const int64_t* d_excl_indptr, const int32_t* d_excl_items, int32_t k,
+                      void* d_workspace, int32_t* d_out_items, double* d_out_scores) {
+  return guarded([&] {
+    RFM_REQUIRE(k >= 1 && k <= kMaxTopK, "k=%d outside 1..%d", k, kMaxTopK);
+    require_pair_args(ctx, d_A, d_LU, n_users, n_sel_users, d_B, d_LI, n_items, n_factors, d_c);
+    RFM_REQUIRE(d_user_ids || n_sel_users == n_users, "without user ids every user is selected");
+    RFM_REQUIRE(!d_excl_indptr || d_excl_items, "exclusion lists without items");
+    if (n_sel_users == 0) return;
+    RFM_REQUIRE(d_workspace && d_out_items && d_out_scores, "null workspace or output");
+    RFM_HIP_CHECK(hipSetDevice(ctx->device));
+    IdCheck chk(ctx);
+    if (chk.flags() && d_excl_indptr) {
+      hipLaunchKernelGGL(excl_check_kernel, dim3(capped_grid(ctx, n_users, kPairBlock, 16, 1)),
+                         dim3(kPairBlock), 0, ctx->stream, d_excl_indptr, d_excl_items, n_users, n_items,
+                         chk.flags());
+      RFM_HIP_CHECK(hipGetLastError());
+      chk.finish();  // (before any list is searched)
+      RFM_HIP_CHECK(hipMemsetAsync(chk.buf.p, 0, 4, ctx->stream));
+    }
+    const Split sp = topk_split(n_sel_users, n_items);
+    PairArgs a{};
+    a.A = d_A, a.LU = d_LU, a.user_ids = d_user_ids, a.n_users = n_users, a.n_sel = n_sel_users;
+    a.B = d_B, a.LI = d_LI, a.n_items = n_items, a.kpad = int(pad4(n_factors)), a.c = d_c;
+    a.excl_indptr = d_excl_indptr, a.excl_items = d_excl_items;
+    a.K = k, a.n_splits = sp.n_splits, a.tiles_per_split = sp.tiles_per_split;
+    a.ws_logit = static_cast<double*>(d_workspace);
+    a.ws_item = reinterpret_cast<int32_t*>(a.ws_logit + int64_t(sp.n_splits) * n_sel_users * k);
+    a.flags = chk.flags();
+    const size_t lds = topk_lds_bytes(k);
+    allow_dynamic_lds(ctx, reinterpret_cast<const void*>(&pair_tile_kernel<true>), lds, g_topk_lds);
+    const dim3 grid((unsigned)sp.n_splits, (unsigned)((n_sel_users + kTile - 1) / kTile));
+    hipLaunchKernelGGL(pair_tile_kernel<true>, grid, dim3(kPairBlock), lds, ctx->stream, a);
+    RFM_HIP_CHECK(hipGetLastError());
+    const int64_t mgrid = (n_sel_users + kPairBlock / 64 - 1) / (kPairBlock / 64);
+    hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)mgrid), dim3(kPairBlock), 0, ctx->stream,
+                       a.ws_logit, a.ws_item, sp.n_splits, n_sel_users, int(k), d_out_items, d_out_scores);
+    RFM_HIP_CHECK(hipGetLastError());
+    chk.finish();
+  });
+}
+
+}  // extern "C"

@@ -113,6 +113,14 @@ class Rows:
         self.width = int(block.shape[1])
 
 
+class Empty:
+    """Segment: ``width`` columns with no stored entry (a gathered block without entries) -- the
+    other side's columns in the side matrices of :func:`sides_kuairec` / :func:`sides_coat`."""
+
+    def __init__(self, width: int):
+        self.width = int(width)
+
+
 def assemble(rt: Runtime, n_rows: int, segments: Sequence) -> DeviceCSR:
     """The design matrix whose row ``r`` is the concatenation of ``segments`` (each shifted
     behind the one before it), built on the device; returns a ``DeviceCSR`` (``.to_scipy()``
@@ -124,6 +132,10 @@ def assemble(rt: Runtime, n_rows: int, segments: Sequence) -> DeviceCSR:
     keep = []
     col = 0
     for d, seg in zip(descs, segments):
+        if isinstance(seg, Empty):
+            from scipy.sparse import csr_matrix
+
+            seg = Rows(csr_matrix((n_rows, seg.width), dtype=np.float64))
         if isinstance(seg, OneHot):
             if seg.ids.shape[0] != n_rows:
                 raise ValueError("a one-hot segment needs one id per row")
@@ -172,6 +184,36 @@ def fm_features_coat(rt: Runtime, users, items, user_table, item_table) -> Devic
     the tables are long (:51-55)."""
     return assemble(rt, len(users), [OneHot(users, user_table.shape[0]), Rows(user_table, users),
                                      OneHot(items, item_table.shape[0]), Rows(item_table, items)])
+
+
+def sides_kuairec(rt: Runtime, n_users: int, n_items: int, context_rows, user_table, item_table):
+    """The user side and the item side of :func:`fm_features_kuairec` as a ``recommend.Sides``:
+    ``XU[u] + XI[i]`` is the row that function builds for the pair (u, i).  The per-interaction
+    columns (KuaiRec: the timestamp, ``conf/setting/kuairec.yaml:17-20``) are not a property of an
+    unseen pair: the caller supplies one row per user (``context_rows``, ``[n_users, width]``),
+    which rides on the user side."""
+    from .recommend import Sides
+
+    if context_rows.shape[0] != n_users or user_table.shape[0] != n_users or item_table.shape[0] != n_items:
+        raise ValueError("context_rows / user_table need one row per user, item_table one per item")
+    cw, uw, iw = int(context_rows.shape[1]), int(user_table.shape[1]), int(item_table.shape[1])
+    XU = assemble(rt, n_users, [OneHot(np.arange(n_users), n_users), Empty(n_items), Rows(context_rows),
+                                Rows(user_table), Empty(iw)])
+    XI = assemble(rt, n_items, [Empty(n_users), OneHot(np.arange(n_items), n_items), Empty(cw), Empty(uw),
+                                Rows(item_table)])
+    return Sides(user_rows=XU, item_rows=XI)
+
+
+def sides_coat(rt: Runtime, user_table, item_table):
+    """The two sides of :func:`fm_features_coat` ([one-hot user | user table | one-hot item | item
+    table]) as a ``recommend.Sides``."""
+    from .recommend import Sides
+
+    nu, ni = int(user_table.shape[0]), int(item_table.shape[0])
+    uw, iw = int(user_table.shape[1]), int(item_table.shape[1])
+    XU = assemble(rt, nu, [OneHot(np.arange(nu), nu), Rows(user_table), Empty(ni), Empty(iw)])
+    XI = assemble(rt, ni, [Empty(nu), Empty(uw), OneHot(np.arange(ni), ni), Rows(item_table)])
+    return Sides(user_rows=XU, item_rows=XI)
 
 
 def take_rows(rt: Runtime, X, indices) -> DeviceCSR:

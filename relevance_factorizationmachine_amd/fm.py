@@ -324,3 +324,22 @@ class FactorizationMachines(PointwiseBaseRecommender):
             self.n_features, self.n_factors, out.data_ptr()))
         rt.sync()
         return out.cpu().numpy()
+
+    # ------------------------------------------------------------ catalogue
+    def score_pairs(self, sides, users=None) -> np.ndarray:
+        """``predict()`` of every (user, item) pair of ``sides`` (``recommend.Sides``) as a
+        ``[n_users (or len(users)), n_items]`` matrix, without the pairs' design matrix: side
+        sums + one dense product (recommend.py; src/fm.py:114-133 restated)."""
+        from . import recommend as rec
+
+        A, LU, B, LI, c = rec.fm_operands(self, sides)
+        return rec.score_pairs(self._rt, A, LU, B, LI, c, self.n_factors, users)
+
+    def recommend(self, sides, k: int, users=None, exclude=None):
+        """The ``k`` (1..64) best items of the catalogue per user: ``(items int32 [n, k], scores
+        float64 [n, k])``, ranked by logit (ties: higher item index first), scores as
+        ``predict()`` gives them; ``exclude``: items never to return, CSR by user id."""
+        from . import recommend as rec
+
+        A, LU, B, LI, c = rec.fm_operands(self, sides)
+        return rec.topk(self._rt, A, LU, B, LI, c, self.n_factors, k, users, exclude)

@@ -305,3 +305,20 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
             self.b_i.dev.data_ptr(), float(self.b), self.n_factors, out.data_ptr()))
         rt.sync()
         return out.cpu().numpy()
+
+    # ------------------------------------------------------------ catalogue
+    def score_pairs(self, users=None) -> np.ndarray:
+        """``predict()`` of every (user, item) pair as a ``[n_users (or len(users)), n_items]``
+        matrix: one dense product (recommend.py; src/mf.py:136-170 restated)."""
+        from . import recommend as rec
+
+        P, bu, Q, bi, c = rec.mf_operands(self)
+        return rec.score_pairs(self._rt, P, bu, Q, bi, c, self.n_factors, users)
+
+    def recommend(self, k: int, users=None, exclude=None):
+        """The ``k`` (1..64) best items per user: ``(items int32 [n, k], scores float64 [n, k])``,
+        ranked by logit (ties: higher item index first); ``exclude``: CSR by user id."""
+        from . import recommend as rec
+
+        P, bu, Q, bi, c = rec.mf_operands(self)
+        return rec.topk(self._rt, P, bu, Q, bi, c, self.n_factors, k, users, exclude)

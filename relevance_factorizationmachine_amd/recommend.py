@@ -1,0 +1,206 @@
+"""Catalogue scoring and top-K recommendation: every (user, item) pair of a
+trained model without the design matrix of the pairs.
+
+The FM rows the reference's loaders build are "the user's entries + the item's entries" on
+disjoint columns (``features.fm_features_kuairec`` / ``fm_features_coat``: every segment is keyed
+by the user id or by the item id), ``x(u,i) = xu(u) + xi(i)``.  With
+``a_u = sum_j xu_j V[j,:]``, ``b_i = sum_j xi_j V[j,:]`` and, per side,
+``L(x) = w.x + 0.5 sum_f((sum_j x_j V[j,f])^2 - sum_j x_j^2 V[j,f]^2)`` the reference's logit
+(``src/fm.py:124-132``) is exactly ``w0 + L(xu) + L(xi) + a_u . b_i``; MF's
+(``src/mf.py:154-170``) has the same shape with ``a = P``, ``b = Q``, ``L = b_u``, ``b_i`` and the
+constant ``b``.  :class:`Sides` holds the two side matrices in HBM; ``FactorizationMachines.
+recommend`` / ``score_pairs`` and their MF counterparts call the functions below.
+
+Ranking is by the LOGIT under the total order (logit descending, then item index descending) --
+``np.argsort(logit, kind="stable")[::-1][:k]``; the probabilities saturate to exactly 0.0 / 1.0 and
+would tie.  The returned scores are probabilities, ``sigmoid(logit)``, as ``predict()`` gives.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Tuple
+
+import numpy as np
+
+from . import _lib
+from .runtime import DeviceCSR, Runtime
+
+MAX_K = 64
+
+
+def pad4(n_factors: int) -> int:
+    """Row stride of the dense operands: the factor count rounded up to a multiple of 4."""
+    return (int(n_factors) + 3) // 4 * 4
+
+
+def topk_workspace_bytes(n_sel_users: int, n_items: int, k: int) -> int:
+    """Bytes of workspace ``rfm_pair_topk`` needs (host only); ``ValueError`` unless 1 <= k <= 64."""
+    out = C.c_int64(0)
+    _lib.check(_lib.load().rfm_pair_topk_workspace(int(n_sel_users), int(n_items), int(k), C.byref(out)))
+    return int(out.value)
+
+
+def _stored_columns(X) -> np.ndarray:
+    if isinstance(X, DeviceCSR):
+        idx = X.h_indices if X.h_indices is not None else X.indices.cpu().numpy()[: X.nnz]
+    else:
+        idx = X.indices
+    return np.unique(np.asarray(idx))
+
+
+class Sides:
+    """The user side and the item side of a design matrix whose pair rows are
+    ``user_rows[u] + item_rows[i]``: two CSR matrices (scipy or ``DeviceCSR``), both ``n_features``
+    wide, with DISJOINT column support -- a column stored on both sides makes the identity false
+    and is a ``ValueError``.  Uploaded once (on first use), reusable across models and calls."""
+
+    def __init__(self, user_rows, item_rows):
+        if len(user_rows.shape) != 2 or len(item_rows.shape) != 2 or user_rows.shape[1] != item_rows.shape[1]:
+            raise ValueError(f"the two sides must be matrices of the same width, got {tuple(user_rows.shape)} "
+                             f"and {tuple(item_rows.shape)}")
+        if not isinstance(user_rows, DeviceCSR):
+            user_rows = user_rows.tocsr()
+        if not isinstance(item_rows, DeviceCSR):
+            item_rows = item_rows.tocsr()
+        both = np.intersect1d(_stored_columns(user_rows), _stored_columns(item_rows))
+        if both.size:
+            raise ValueError(f"column {int(both[0])} is stored on the user side and on the item side "
+                             f"({both.size} such columns): pair rows are not user_rows[u] + item_rows[i]")
+        self.n_users, self.n_items = int(user_rows.shape[0]), int(item_rows.shape[0])
+        self.n_features = int(user_rows.shape[1])
+        if self.n_users < 1 or self.n_items < 1:
+            raise ValueError("a side without rows")
+        self._host = (user_rows, item_rows)
+        self._dev = None
+
+    def device(self, rt: Runtime) -> Tuple[DeviceCSR, DeviceCSR]:
+        if self._dev is None:
+            self._dev = tuple(X if isinstance(X, DeviceCSR) else DeviceCSR(rt, X) for X in self._host)
+        return self._dev
+
+
+def side_sums(rt: Runtime, X: DeviceCSR, w, V, n_features: int, n_factors: int):
+    """``(A [n, kpad], L [n])`` of a side matrix for the parameters ``w``, ``V`` (device tensors)."""
+    torch = __import__("torch")
+    n = X.shape[0]
+    A = rt.empty((n, pad4(n_factors)), torch.float64)
+    L = rt.empty((n,), torch.float64)
+    _lib.check(rt.lib.rfm_fm_side_sums(rt.ctx, X.indptr.data_ptr(), X.indices.data_ptr(), X.values.data_ptr(), n,
+                                       w.data_ptr(), V.data_ptr(), n_features, n_factors, A.data_ptr(),
+                                       L.data_ptr()))
+    return A, L
+
+
+def padded(rt: Runtime, M, n_factors: int):
+    """A dense ``[n, k]`` device matrix as ``[n, kpad]`` (itself when ``k % 4 == 0``)."""
+    torch = __import__("torch")
+    kp = pad4(n_factors)
+    if kp == n_factors:
+        return M
+    out = torch.zeros((M.shape[0], kp), dtype=torch.float64, device=rt.torch_device)
+    out[:, :n_factors] = M
+    return out
+
+
+def _users(rt: Runtime, users, n_users: int):
+    if users is None:
+        return None, n_users
+    ids = np.asarray(users)
+    if ids.ndim != 1 or (ids.size and not np.issubdtype(ids.dtype, np.integer)):
+        raise ValueError("users must be a 1-d array of user ids")
+    if ids.size and (ids.min() < 0 or ids.max() >= n_users):
+        raise ValueError(f"a user id lies outside 0..{n_users - 1}")
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    return rt.upload(ids if ids.size else np.zeros(1, np.int32)), int(ids.shape[0])
+
+
+def _exclusions(rt: Runtime, exclude, n_users: int, n_items: int):
+    """``exclude``: scipy sparse matrix (row = user id, stored columns = items) or
+    ``(indptr, indices)``; device ``(indptr int64, items int32)`` with ascending items per user."""
+    if exclude is None:
+        return None
+    if isinstance(exclude, (tuple, list)):
+        indptr, items = (np.asarray(a) for a in exclude)
+    else:
+        E = exclude.tocsr()
+        if E.shape != (n_users, n_items):
+            raise ValueError(f"exclude has shape {E.shape}, expected {(n_users, n_items)}")
+        if not E.has_canonical_format:
+            E = E.copy()
+            E.sum_duplicates()
+        indptr, items = E.indptr, E.indices
+    indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+    items = np.ascontiguousarray(items, dtype=np.int32)
+    if (indptr.shape != (n_users + 1,) or indptr[0] != 0 or indptr[-1] != items.shape[0]
+            or np.any(np.diff(indptr) < 0)):
+        raise ValueError(f"exclude: indptr must have {n_users + 1} monotone entries spanning the items")
+    if items.size:
+        if items.min() < 0 or items.max() >= n_items:
+            raise ValueError(f"exclude: an item id lies outside 0..{n_items - 1}")
+        rising = np.diff(items) > 0
+        rising[indptr[1:-1][(indptr[1:-1] > 0) & (indptr[1:-1] < items.shape[0])] - 1] = True
+        if not rising.all():
+            raise ValueError("exclude: the item ids of a user must be strictly ascending")
+    return rt.upload(indptr), rt.upload(items if items.size else np.zeros(1, np.int32))
+
+
+def score_pairs(rt: Runtime, A, LU, B, LI, c, n_factors: int, users=None) -> np.ndarray:
+    """Probabilities of every (selected user, item) pair, ``float64 [n_sel, n_items]``."""
+    torch = __import__("torch")
+    n_users, n_items = int(A.shape[0]), int(B.shape[0])
+    ids, n_sel = _users(rt, users, n_users)
+    out = rt.empty((n_sel, n_items), torch.float64)
+    _lib.check(rt.lib.rfm_pair_scores(rt.ctx, A.data_ptr(), LU.data_ptr(), n_users,
+                                      None if ids is None else ids.data_ptr(), n_sel, B.data_ptr(),
+                                      LI.data_ptr(), n_items, n_factors, c.data_ptr(), out.data_ptr()))
+    rt.sync()
+    return out.cpu().numpy()
+
+
+def topk(rt: Runtime, A, LU, B, LI, c, n_factors: int, k: int, users=None, exclude=None):
+    """``(items int32 [n_sel, k], scores float64 [n_sel, k])``: the k best items per selected user by
+    logit (ties: higher item index first), scores = sigmoid(logit); fewer than k rankable items
+    pads with item -1 / score NaN."""
+    torch = __import__("torch")
+    n_users, n_items = int(A.shape[0]), int(B.shape[0])
+    k = int(k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f"k={k} outside 1..{MAX_K}")
+    ids, n_sel = _users(rt, users, n_users)
+    excl = _exclusions(rt, exclude, n_users, n_items)
+    ws = rt.empty((topk_workspace_bytes(n_sel, n_items, k),), torch.uint8)
+    items = rt.empty((n_sel, k), torch.int32)
+    scores = rt.empty((n_sel, k), torch.float64)
+    _lib.check(rt.lib.rfm_pair_topk(rt.ctx, A.data_ptr(), LU.data_ptr(), n_users,
+                                    None if ids is None else ids.data_ptr(), n_sel, B.data_ptr(),
+                                    LI.data_ptr(), n_items, n_factors, c.data_ptr(),
+                                    None if excl is None else excl[0].data_ptr(),
+                                    None if excl is None else excl[1].data_ptr(), k, ws.data_ptr(),
+                                    items.data_ptr(), scores.data_ptr()))
+    rt.sync()
+    return items.cpu().numpy(), scores.cpu().numpy()
+
+
+def fm_operands(model, sides: Sides):
+    """``(A, LU, B, LI, c)`` of an FM model for ``sides``: two side-sum launches per call (they
+    depend on the parameters)."""
+    rt = model._rt
+    if not isinstance(sides, Sides):
+        raise TypeError("sides must be a recommend.Sides")
+    if sides.n_features != model.n_features:
+        raise ValueError(f"sides have {sides.n_features} columns, model has {model.n_features}")
+    XU, XI = sides.device(rt)
+    A, LU = side_sums(rt, XU, model.w.dev, model.V.dev, model.n_features, model.n_factors)
+    B, LI = side_sums(rt, XI, model.w.dev, model.V.dev, model.n_features, model.n_factors)
+    return A, LU, B, LI, model.w0.dev
+
+
+def mf_operands(model):
+    """``(P, b_u, Q, b_i, b)`` of an MF model (padded copies of P, Q when ``n_factors % 4``)."""
+    rt = model._rt
+    if not hasattr(model, "b"):
+        # the reference's global bias exists only after fit() (src/mf.py:84)
+        raise AttributeError("'LogisticMatrixFactorization' object has no attribute 'b'")
+    c = rt.upload(np.array([float(model.b)], dtype=np.float64))
+    return (padded(rt, model.P.dev, model.n_factors), model.b_u.dev, padded(rt, model.Q.dev, model.n_factors),
+            model.b_i.dev, c)
