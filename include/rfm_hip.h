@@ -642,6 +642,36 @@ int32_t rfm_pair_topk(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64
                       const double* d_LI, int64_t n_items, int32_t n_factors, const double* d_c,
                       const int64_t* d_excl_indptr, const int32_t* d_excl_items, int32_t k,
                       void* d_workspace, int32_t* d_out_items, double* d_out_scores);
+/* Ranks against the whole catalogue: where given (user, item) pairs land in the
+ * order rfm_pair_topk ranks by.  The first eleven arguments, the user ids, the exclusion lists and
+ * RFM_CHECK_IDS are rfm_pair_topk's.  The CANDIDATES of selected user s are the items whose logit
+ * is not NaN and that the user's exclusion list does not name; j is BETTER than i when
+ * logit(j) > logit(i), or they are equal and j > i.  The TARGETS of selected user s are
+ * d_tgt_items[d_tgt_indptr[s] .. d_tgt_indptr[s + 1]) (CSR by SELECTED user, not by user id;
+ * d_tgt_indptr[0] = 0, item ids ascending, repeats allowed; n_targets = d_tgt_indptr[n_sel_users] is
+ * read back from the device, which synchronises).  Per target t = (s, i):
+ *     d_out_ranks[t]  = number of candidates j != i of s that are better than i (0-based), i.e. the
+ *                       position of i in np.argsort(logit[s], kind="stable")[::-1] once the NaNs and
+ *                       the excluded items are taken out; -1 if the target's own logit is NaN (NaN
+ *                       item row, user id or item id outside its table);
+ *     d_out_scores[t] = sigmoid(clip(logit, +-700)), NaN where the rank is -1;
+ * and d_out_candidates[s] = the number of candidates of s.  A target that the exclusion list names
+ * is still ranked, against the candidates (it is not one of them).  The logit is the pair tile's,
+ * bit for bit: the rank of rfm_pair_topk's r-th item is r, and its score has the same bytes.  Two
+ * passes over the product: the first stores the targets' logits in d_workspace
+ * (rfm_pair_ranks_workspace bytes; host only), the second counts, per tile, the logits better
+ * than each target.  Counts are integers added with integer atomics and no float atomic is used:
+ * the result does not depend on the split of the items over workgroups, and the same inputs give
+ * the same bits.  n_targets == 0 is legal (d_tgt_items, d_workspace, d_out_ranks, d_out_scores may
+ * be NULL) and still fills d_out_candidates.  RFM_CHECK_IDS=1 validates user ids, exclusion lists
+ * and target lists (ids inside 0..n_items-1, ascending) first: RFM_ERR_BAD_ARG. */
+int32_t rfm_pair_ranks_workspace(int64_t n_sel_users, int64_t n_items, int64_t n_targets, int64_t* h_bytes);
+int32_t rfm_pair_ranks(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t n_users,
+                       const int32_t* d_user_ids, int64_t n_sel_users, const double* d_B,
+                       const double* d_LI, int64_t n_items, int32_t n_factors, const double* d_c,
+                       const int64_t* d_excl_indptr, const int32_t* d_excl_items,
+                       const int64_t* d_tgt_indptr, const int32_t* d_tgt_items, void* d_workspace,
+                       int32_t* d_out_ranks, double* d_out_scores, int32_t* d_out_candidates);
 
 #ifdef __cplusplus
 }

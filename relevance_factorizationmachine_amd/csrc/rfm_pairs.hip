@@ -12,6 +12,11 @@
 // two epilogues: sigmoid scores, or the K best items per user under the total order
 // (logit descending, item index descending).  Every sum has a fixed order and no float
 // atomic is used: the same inputs give the same bits.
+//
+// Ranks against the catalogue are two more epilogues of the same tile: one
+// stores the logit of every target pair that falls into the tile, one counts, per target, the
+// tile's candidates that are better than it.  The counts are integers, summed with integer
+// atomics: they do not depend on the split or on timing.
 #include <cmath>
 #include <cstdlib>
 
@@ -33,6 +38,12 @@ constexpr int kOperandDoubles = 2 * kChunk * kLd;  // A and B chunk
 constexpr int kLogitLd = kTile + 1;                // top-K epilogue: the tile's logits [user][item]
 constexpr int kMaxTopK = 64;
 constexpr int kTargetWorkgroups = 1024;  // top-K: item splits are chosen to reach about this many
+// rank counting: a workgroup sums the counts of the first kRankAccum targets of its 64 users in
+// LDS over its tiles (one atomic per target and workgroup); later targets go to memory per tile
+constexpr int kRankAccum = 4096;
+
+// epilogue of the pair tile
+enum PairMode { kScores = 0, kTopK = 1, kTargetLogits = 2, kRankCount = 3 };
 
 using f64x4 = __attribute__((__vector_size__(4 * sizeof(double)))) double;
 
@@ -157,15 +168,27 @@ struct PairArgs {
   double* ws_logit;        // [n_splits][n_sel][K]
   int32_t* ws_item;
   int32_t* flags;          // RFM_CHECK_IDS: bit 1 = a user id outside the table
+  // rank epilogues: the targets of selected user s are tgt_items[tgt_indptr[s] .. tgt_indptr[s+1])
+  const int64_t* tgt_indptr;   // [n_sel + 1]
+  const int32_t* tgt_items;    // [n_targets], ascending per user
+  int64_t n_targets;
+  double* tgt_logit;           // [n_targets]: written by kTargetLogits, read by kRankCount
+  int32_t* out_ranks;          // [n_targets], zeroed before kRankCount
+  int32_t* out_candidates;     // [n_sel], zeroed before kRankCount
 };
 
 // logit[u,i] = c + LU[u] + LI[i] + A[u,:].B[i,:] over a 64 x 64 tile: wavefront (wm, wn) owns
 // the 32 x 32 quarter at (32 wm, 32 wn) as 2 x 2 MFMA blocks of 16 x 16; the factors go
 // through LDS in chunks of 32 so that each operand element is read from memory once per tile.
-// TOPK: blockIdx.x is an item split; the workgroup walks the split's tiles and keeps the K best
-// items of each of its 64 users in LDS lists, written to the workspace at the end.
-template <bool TOPK>
+// Every mode but kScores: blockIdx.x is an item split; the workgroup walks the split's tiles and
+// hands each tile's logits over in LDS (T[user][item]).  kTopK keeps the K best items of each of
+// its 64 users in LDS lists, written to the workspace at the end.  kTargetLogits stores the logit
+// of every target of its users that lies in the tile.  kRankCount turns excluded items into NaN
+// and adds, per target of a user, the number of the tile's logits that are better than it.
+template <int MODE>
 __global__ __launch_bounds__(kPairBlock) void pair_tile_kernel(PairArgs a) {
+  constexpr bool TOPK = MODE == kTopK;
+  constexpr bool WALK = MODE != kScores;  // item splits, logits through T
   extern __shared__ double lds[];
   double* As = lds;                    // [kChunk][kLd]
   double* Bs = lds + kChunk * kLd;     // [kChunk][kLd]
@@ -173,6 +196,8 @@ __global__ __launch_bounds__(kPairBlock) void pair_tile_kernel(PairArgs a) {
   constexpr int kUnion = kOperandDoubles > kTile * kLogitLd ? kOperandDoubles : kTile * kLogitLd;
   double* list_l = lds + kUnion;                                        // [kTile][K]
   int32_t* list_i = reinterpret_cast<int32_t*>(list_l + kTile * (TOPK ? a.K : 0));
+  int32_t* rank_acc = reinterpret_cast<int32_t*>(lds + kUnion);  // kRankCount: [kRankAccum]
+  int32_t* cand_acc = rank_acc + kRankAccum;                     // kRankCount: [kTile]
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
@@ -204,10 +229,13 @@ __global__ __launch_bounds__(kPairBlock) void pair_tile_kernel(PairArgs a) {
       list_i[e] = -1;
     }
   }
+  if (MODE == kRankCount) {
+    for (int e = tid; e < kRankAccum + kTile; e += kPairBlock) rank_acc[e] = 0;
+  }
 
   const int n_item_tiles = int((a.n_items + kTile - 1) / kTile);
-  const int t_first = TOPK ? blockIdx.x * a.tiles_per_split : blockIdx.x;
-  const int t_last = TOPK ? min(t_first + a.tiles_per_split, n_item_tiles) : t_first + 1;
+  const int t_first = WALK ? blockIdx.x * a.tiles_per_split : blockIdx.x;
+  const int t_last = WALK ? min(t_first + a.tiles_per_split, n_item_tiles) : t_first + 1;
   const double c = a.c[0];
 
   for (int t = t_first; t < t_last; ++t) {
@@ -253,7 +281,7 @@ __global__ __launch_bounds__(kPairBlock) void pair_tile_kernel(PairArgs a) {
     }
 
     // C/D layout of the f64 MFMA: column (item) = lane & 15, row (user) = (lane >> 4) + 4 reg
-    if (TOPK) __syncthreads();  // every wavefront has read its operands: T may overwrite them
+    if (WALK) __syncthreads();  // every wavefront has read its operands: T may overwrite them
 #pragma unroll
     for (int x = 0; x < 2; ++x) {
 #pragma unroll
@@ -272,7 +300,7 @@ __global__ __launch_bounds__(kPairBlock) void pair_tile_kernel(PairArgs a) {
           const int64_t item = i0 + il;
           const bool in = s < a.n_sel && item < a.n_items;
           const double logit = in ? ((c + lu) + a.LI[item]) + acc[x][y][reg] : NAN;
-          if (TOPK) {
+          if (WALK) {
             T[ul * kLogitLd + il] = logit;
           } else if (in) {
             a.out[s * a.n_items + item] = sigmoid_clipped(logit);
@@ -280,8 +308,71 @@ __global__ __launch_bounds__(kPairBlock) void pair_tile_kernel(PairArgs a) {
         }
       }
     }
-    if (!TOPK) continue;
+    if (!WALK) continue;
     __syncthreads();
+    if (MODE == kTargetLogits) {
+      // wavefront w serves users 16 w .. 16 w + 15: the user's targets are ascending, the ones
+      // of this tile start at the first id >= i0 (the same search in every lane) and the lanes
+      // take them 64 at a time.  A target id outside the catalogue is in no tile: its logit
+      // keeps the NaN the workspace was filled with.
+      for (int j = 0; j < 16; ++j) {
+        const int ul = wave * 16 + j;
+        const int64_t s = u0 + ul;
+        if (s >= a.n_sel) break;
+        int64_t lo = max(a.tgt_indptr[s], int64_t(0));
+        const int64_t thi = min(a.tgt_indptr[s + 1], a.n_targets);
+        for (int64_t hi = thi; lo < hi;) {
+          const int64_t mid = lo + ((hi - lo) >> 1);
+          if (int64_t(a.tgt_items[mid]) < i0) lo = mid + 1; else hi = mid;
+        }
+        for (int64_t p = lo + lane;; p += 64) {
+          const int64_t it = p < thi ? int64_t(a.tgt_items[p]) : -1;
+          const bool in = it >= i0 && it < i0 + kTile;
+          if (in) a.tgt_logit[p] = T[ul * kLogitLd + int(it - i0)];
+          if (__ballot(in) != ~0ull) break;
+        }
+      }
+      continue;  // (the next tile's first barrier orders these reads of T before its staging writes)
+    }
+    if (MODE == kRankCount) {
+      const int64_t tbase = max(a.tgt_indptr[u0], int64_t(0));  // (u0 < n_sel: the grid has no empty user tile)
+      for (int j = 0; j < 16; ++j) {
+        const int ul = wave * 16 + j;
+        const int64_t s = u0 + ul;
+        if (s >= a.n_sel) break;
+        double* row = T + ul * kLogitLd;
+        double cl = row[lane];
+        if (a.excl_indptr) {
+          if (cl == cl) {
+            const int64_t u = a.user_ids ? int64_t(a.user_ids[s]) : s;  // (in range: its logits are not NaN)
+            if (excluded(a.excl_items, a.excl_indptr[u], a.excl_indptr[u + 1], int(i0) + lane)) cl = NAN;
+          }
+          row[lane] = cl;  // the wavefront's own row: its LDS accesses are executed in order
+        }
+        const int n_cand = __popcll(__ballot(cl == cl));
+        if (n_cand == 0) continue;  // NaN beats nothing
+        if (lane == 0) cand_acc[ul] += n_cand;
+        // lane = one target of the user, 64 at a time; the tile's logits come as broadcast reads
+        const int64_t tlo = max(a.tgt_indptr[s], int64_t(0)), thi = min(a.tgt_indptr[s + 1], a.n_targets);
+        for (int64_t p0 = tlo; p0 < thi; p0 += 64) {
+          const int64_t p = p0 + lane;
+          const double tl = p < thi ? a.tgt_logit[p] : NAN;  // NaN is beaten by nothing
+          const int ti = p < thi ? a.tgt_items[p] : 0;
+          int cnt = 0;
+#pragma unroll 8
+          for (int e = 0; e < kTile; ++e) {  // better(row[e], i0 + e, tl, ti) without its branches
+            const double l = row[e];
+            cnt += int(l > tl) + int((l == tl) & (int(i0) + e > ti));
+          }
+          if (cnt) {
+            const int64_t at = p - tbase;
+            if (at >= 0 && at < kRankAccum) rank_acc[at] += cnt;  // target p belongs to this lane alone
+            else atomicAdd(a.out_ranks + p, cnt);
+          }
+        }
+      }
+      continue;
+    }
     // wavefront w ranks users 16 w .. 16 w + 15, lane = item of the tile.  A candidate is
     // looked at further only if it beats the list's current K-th entry; after the first tiles
     // almost none does.  NaN logits (and the tile's padding) are never ranked.
@@ -324,6 +415,13 @@ __global__ __launch_bounds__(kPairBlock) void pair_tile_kernel(PairArgs a) {
     // (the next tile's first barrier orders these reads of T before its staging writes)
   }
 
+  if (MODE == kRankCount) {
+    __syncthreads();
+    const int64_t tbase = max(a.tgt_indptr[u0], int64_t(0));
+    for (int e = tid; e < kRankAccum; e += kPairBlock)
+      if (rank_acc[e] && tbase + e < a.n_targets) atomicAdd(a.out_ranks + tbase + e, rank_acc[e]);
+    if (tid < kTile && u0 + tid < a.n_sel && cand_acc[tid]) atomicAdd(a.out_candidates + u0 + tid, cand_acc[tid]);
+  }
   if (TOPK) {
     // a wavefront wrote the lists it now copies out: no barrier needed
     for (int j = 0; j < 16; ++j) {
@@ -384,6 +482,41 @@ __global__ __launch_bounds__(kPairBlock) void excl_check_kernel(const int64_t* i
   }
 }
 
+// RFM_CHECK_IDS=1: target indptr monotone from 0 up to n_targets, every list ascending (repeats
+// allowed) inside 0 .. n_items-1
+__global__ __launch_bounds__(kPairBlock) void target_check_kernel(const int64_t* indptr,
+                                                                 const int32_t* items, int64_t n_sel,
+                                                                 int64_t n_items, int64_t n_targets,
+                                                                 int32_t* flags) {
+  for (int64_t s = int64_t(blockIdx.x) * kPairBlock + threadIdx.x; s < n_sel;
+       s += int64_t(gridDim.x) * kPairBlock) {
+    const int64_t lo = indptr[s], hi = indptr[s + 1];
+    if ((s == 0 && lo != 0) || hi < lo || hi > n_targets || (s == n_sel - 1 && hi != n_targets)) {
+      atomicOr(flags, 16);
+      continue;
+    }
+    for (int64_t e = lo; e < hi; ++e)
+      if (items[e] < 0 || items[e] >= n_items || (e > lo && items[e] < items[e - 1])) {
+        atomicOr(flags, 32);
+        break;
+      }
+  }
+}
+
+// Per target: a NaN logit (NaN item row, user or item id outside its table) has rank -1 and
+// score NaN; every other target keeps its count and gets sigmoid(logit).
+__global__ __launch_bounds__(kPairBlock) void rank_finish_kernel(const double* __restrict__ tgt_logit,
+                                                                int64_t n_targets,
+                                                                int32_t* __restrict__ out_ranks,
+                                                                double* __restrict__ out_scores) {
+  for (int64_t t = int64_t(blockIdx.x) * kPairBlock + threadIdx.x; t < n_targets;
+       t += int64_t(gridDim.x) * kPairBlock) {
+    const double z = tgt_logit[t];
+    if (z != z) out_ranks[t] = -1;
+    out_scores[t] = z == z ? sigmoid_clipped(z) : NAN;
+  }
+}
+
 struct Split {
   int n_splits, tiles_per_split;
 };
@@ -397,6 +530,11 @@ Split topk_split(int64_t n_sel, int64_t n_items) {
   s.tiles_per_split = int((item_tiles + want - 1) / want);
   s.n_splits = int((item_tiles + s.tiles_per_split - 1) / s.tiles_per_split);
   return s;
+}
+
+size_t rank_lds_bytes(bool count) {
+  const int kUnion = std::max(kOperandDoubles, kTile * kLogitLd);
+  return size_t(kUnion) * 8 + (count ? size_t(kRankAccum + kTile) * 4 : 0);
 }
 
 size_t topk_lds_bytes(int K) {
@@ -436,6 +574,8 @@ struct IdCheck {
     RFM_REQUIRE(!(h & 2), "a user id lies outside 0..n_users-1");
     RFM_REQUIRE(!(h & 4), "the exclusion indptr is not monotone from 0");
     RFM_REQUIRE(!(h & 8), "an exclusion list is not strictly ascending inside 0..n_items-1");
+    RFM_REQUIRE(!(h & 16), "the target indptr is not monotone from 0 to n_targets");
+    RFM_REQUIRE(!(h & 32), "a target list is not ascending inside 0..n_items-1");
   }
 };
 
@@ -485,7 +625,7 @@ int32_t rfm_pair_scores(rfm_ctx* ctx, const double* d_A, const double* d_LU, int
     a.B = d_B, a.LI = d_LI, a.n_items = n_items, a.kpad = int(pad4(n_factors)), a.c = d_c;
     a.out = d_out, a.flags = chk.flags();
     const dim3 grid((unsigned)((n_items + kTile - 1) / kTile), (unsigned)((n_sel_users + kTile - 1) / kTile));
-    hipLaunchKernelGGL(pair_tile_kernel<false>, grid, dim3(kPairBlock), size_t(kOperandDoubles) * 8,
+    hipLaunchKernelGGL(pair_tile_kernel<kScores>, grid, dim3(kPairBlock), size_t(kOperandDoubles) * 8,
                        ctx->stream, a);
     RFM_HIP_CHECK(hipGetLastError());
     chk.finish();
@@ -534,14 +674,89 @@ int32_t rfm_pair_topk(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64
     a.ws_item = reinterpret_cast<int32_t*>(a.ws_logit + int64_t(sp.n_splits) * n_sel_users * k);
     a.flags = chk.flags();
     const size_t lds = topk_lds_bytes(k);
-    allow_dynamic_lds(ctx, reinterpret_cast<const void*>(&pair_tile_kernel<true>), lds, g_topk_lds);
+    allow_dynamic_lds(ctx, reinterpret_cast<const void*>(&pair_tile_kernel<kTopK>), lds, g_topk_lds);
     const dim3 grid((unsigned)sp.n_splits, (unsigned)((n_sel_users + kTile - 1) / kTile));
-    hipLaunchKernelGGL(pair_tile_kernel<true>, grid, dim3(kPairBlock), lds, ctx->stream, a);
+    hipLaunchKernelGGL(pair_tile_kernel<kTopK>, grid, dim3(kPairBlock), lds, ctx->stream, a);
     RFM_HIP_CHECK(hipGetLastError());
     const int64_t mgrid = (n_sel_users + kPairBlock / 64 - 1) / (kPairBlock / 64);
     hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)mgrid), dim3(kPairBlock), 0, ctx->stream,
                        a.ws_logit, a.ws_item, sp.n_splits, n_sel_users, int(k), d_out_items, d_out_scores);
     RFM_HIP_CHECK(hipGetLastError());
+    chk.finish();
+  });
+}
+
+int32_t rfm_pair_ranks_workspace(int64_t n_sel_users, int64_t n_items, int64_t n_targets, int64_t* h_bytes) {
+  return guarded([&] {
+    RFM_REQUIRE(h_bytes, "null pointer");
+    RFM_REQUIRE(n_sel_users >= 0 && n_items >= 1 && n_targets >= 0, "negative n_sel_users or n_targets, or no items");
+    *h_bytes = std::max<int64_t>(16, n_targets * 8);  // the targets' logits
+  });
+}
+
+int32_t rfm_pair_ranks(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t n_users,
+                       const int32_t* d_user_ids, int64_t n_sel_users, const double* d_B,
+                       const double* d_LI, int64_t n_items, int32_t n_factors, const double* d_c,
+                       const int64_t* d_excl_indptr, const int32_t* d_excl_items,
+                       const int64_t* d_tgt_indptr, const int32_t* d_tgt_items, void* d_workspace,
+                       int32_t* d_out_ranks, double* d_out_scores, int32_t* d_out_candidates) {
+  return guarded([&] {
+    require_pair_args(ctx, d_A, d_LU, n_users, n_sel_users, d_B, d_LI, n_items, n_factors, d_c);
+    RFM_REQUIRE(d_user_ids || n_sel_users == n_users, "without user ids every user is selected");
+    RFM_REQUIRE(!d_excl_indptr || d_excl_items, "exclusion lists without items");
+    if (n_sel_users == 0) return;
+    RFM_REQUIRE(d_tgt_indptr && d_out_candidates, "null target indptr or candidates output");
+    RFM_HIP_CHECK(hipSetDevice(ctx->device));
+    // the number of targets is the last entry of the indptr: the launches are sized by it
+    int64_t n_targets = 0;
+    RFM_HIP_CHECK(hipMemcpyAsync(&n_targets, d_tgt_indptr + n_sel_users, 8, hipMemcpyDeviceToHost, ctx->stream));
+    RFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    RFM_REQUIRE(n_targets >= 0 && n_targets < (int64_t(1) << 40), "d_tgt_indptr ends at %lld targets", (long long)n_targets);
+    RFM_REQUIRE(n_targets == 0 || (d_tgt_items && d_workspace && d_out_ranks && d_out_scores),
+                "null target items, workspace or output");
+    IdCheck chk(ctx);
+    if (chk.flags()) {
+      if (d_excl_indptr) {
+        hipLaunchKernelGGL(excl_check_kernel, dim3(capped_grid(ctx, n_users, kPairBlock, 16, 1)),
+                           dim3(kPairBlock), 0, ctx->stream, d_excl_indptr, d_excl_items, n_users, n_items,
+                           chk.flags());
+        RFM_HIP_CHECK(hipGetLastError());
+      }
+      hipLaunchKernelGGL(target_check_kernel, dim3(capped_grid(ctx, n_sel_users, kPairBlock, 16, 1)),
+                         dim3(kPairBlock), 0, ctx->stream, d_tgt_indptr, d_tgt_items, n_sel_users, n_items,
+                         n_targets, chk.flags());
+      RFM_HIP_CHECK(hipGetLastError());
+      chk.finish();  // (before any list is searched)
+      RFM_HIP_CHECK(hipMemsetAsync(chk.buf.p, 0, 4, ctx->stream));
+    }
+    const Split sp = topk_split(n_sel_users, n_items);
+    PairArgs a{};
+    a.A = d_A, a.LU = d_LU, a.user_ids = d_user_ids, a.n_users = n_users, a.n_sel = n_sel_users;
+    a.B = d_B, a.LI = d_LI, a.n_items = n_items, a.kpad = int(pad4(n_factors)), a.c = d_c;
+    a.excl_indptr = d_excl_indptr, a.excl_items = d_excl_items;
+    a.n_splits = sp.n_splits, a.tiles_per_split = sp.tiles_per_split;
+    a.tgt_indptr = d_tgt_indptr, a.tgt_items = d_tgt_items, a.n_targets = n_targets;
+    a.tgt_logit = static_cast<double*>(d_workspace);
+    a.out_ranks = d_out_ranks, a.out_candidates = d_out_candidates;
+    a.flags = chk.flags();
+    const dim3 grid((unsigned)sp.n_splits, (unsigned)((n_sel_users + kTile - 1) / kTile));
+    RFM_HIP_CHECK(hipMemsetAsync(d_out_candidates, 0, size_t(n_sel_users) * 4, ctx->stream));
+    if (n_targets > 0) {
+      // every byte 0xFF is a NaN: the logit of a target that no tile holds
+      RFM_HIP_CHECK(hipMemsetAsync(d_workspace, 0xFF, size_t(n_targets) * 8, ctx->stream));
+      RFM_HIP_CHECK(hipMemsetAsync(d_out_ranks, 0, size_t(n_targets) * 4, ctx->stream));
+      const size_t lds1 = rank_lds_bytes(false);  // (both passes stay under the 64 KiB a launch may ask for as it is)
+      hipLaunchKernelGGL(pair_tile_kernel<kTargetLogits>, grid, dim3(kPairBlock), lds1, ctx->stream, a);
+      RFM_HIP_CHECK(hipGetLastError());
+    }
+    const size_t lds2 = rank_lds_bytes(true);
+    hipLaunchKernelGGL(pair_tile_kernel<kRankCount>, grid, dim3(kPairBlock), lds2, ctx->stream, a);
+    RFM_HIP_CHECK(hipGetLastError());
+    if (n_targets > 0) {
+      hipLaunchKernelGGL(rank_finish_kernel, dim3(capped_grid(ctx, n_targets, kPairBlock, 16, 1)),
+                         dim3(kPairBlock), 0, ctx->stream, a.tgt_logit, n_targets, d_out_ranks, d_out_scores);
+      RFM_HIP_CHECK(hipGetLastError());
+    }
     chk.finish();
   });
 }

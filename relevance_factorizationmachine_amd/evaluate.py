@@ -478,3 +478,85 @@ class DeviceTestEvaluator:
         for name, vals in self.frame.metrics(pos, flags, host_scores).items():
             results[name] = list(vals)
         return results
+
+
+class CatalogueEvaluator:
+    """Held-out interactions ranked against the WHOLE catalogue, where
+    ``TestEvaluator`` ranks only the rows of the test log: every positive's position among all
+    items its user could be shown, from ``model.rank_items`` (one call), and from the ranks on
+    the host the reference's ``calc_dcg_at_k`` / ``calc_recall_at_k`` /
+    ``calc_average_precision_at_k`` (``utils/metrics.py:9-107``) as they come out for the 0/1
+    vector of the user's candidates in catalogue order, plus MRR and AUC.
+
+    ``positives``: ``(users, items)`` of the held-out interactions (repeats are dropped);
+    ``K``: ranking depths, any positive integers; ``used_metrics``: a subset of ``METRICS``;
+    ``exclude``: items never shown to a user (the train pairs), as ``recommend()`` takes them --
+    a positive that it lists is a ``ValueError`` of ``evaluate``.  ``evaluate`` returns
+    ``{metric: [value per K]}`` (MRR, AUC: one value): the nan-mean over the users that have a
+    ranked positive.  A positive of rank -1 (NaN logit) is left out and counted in ``unranked``."""
+
+    METRICS = ("DCG", "Recall", "MAP", "MRR", "AUC")
+
+    def __init__(self, positives, n_items: int, K, used_metrics, exclude=None):
+        users, items = (np.asarray(a) for a in positives)
+        if users.ndim != 1 or users.shape != items.shape:
+            raise ValueError("positives must be two 1-d arrays of equal length: users, items")
+        for a in (users, items):
+            if a.size and not np.issubdtype(a.dtype, np.integer):
+                raise ValueError("positives must be integer ids")
+        self.n_items = int(n_items)
+        if items.size and (items.min() < 0 or items.max() >= self.n_items):
+            raise ValueError(f"an item id lies outside 0..{self.n_items - 1}")
+        self.K = [int(k) for k in K]
+        if any(k < 1 for k in self.K):
+            raise ValueError("K must be positive integers")
+        unknown = [m for m in used_metrics if m not in self.METRICS]
+        if unknown:
+            raise ValueError(f"unknown metric {unknown[0]!r} (known: {', '.join(self.METRICS)})")
+        self.used_metrics = list(used_metrics)
+        keys = np.unique(users.astype(np.int64) * self.n_items + items.astype(np.int64))
+        self.users, self.items = keys // self.n_items, keys % self.n_items
+        self.exclude = exclude
+        self.unranked = 0  # positives without a rank in the last evaluate() / metrics()
+
+    def metrics(self, users, ranks, candidates) -> dict:
+        """The metrics from ``(user, rank, candidate count of the user)`` per positive: host only."""
+        users, ranks, candidates = np.asarray(users), np.asarray(ranks).astype(np.int64), np.asarray(candidates)
+        ranked = ranks >= 0
+        self.unranked = int(np.count_nonzero(~ranked))
+        users, ranks, candidates = users[ranked], ranks[ranked], candidates[ranked]
+        order = np.lexsort((ranks, users))
+        _, seg_ptr = group_by_user(users[order])
+        per_user = {m: [] for m in self.used_metrics}
+        for g in range(seg_ptr.shape[0] - 1):
+            rows = order[seg_ptr[g]:seg_ptr[g + 1]]
+            if rows.size == 0:
+                continue
+            r = ranks[rows].astype(np.float64)      # ascending: r_1 < ... < r_P
+            P, C = r.shape[0], float(candidates[rows[0]])
+            j = np.arange(1, P + 1, dtype=np.float64)
+            gain = np.where(r == 0, 1.0, 1.0 / np.log2(np.maximum(r, 1.0) + 1.0))
+            for m in self.used_metrics:
+                if m == "DCG":
+                    per_user[m].append([float(np.sum(gain[r < k])) for k in self.K])
+                elif m == "Recall":
+                    per_user[m].append([np.count_nonzero(r < k) / P for k in self.K])
+                elif m == "MAP":
+                    per_user[m].append([float(np.sum((j / (r + 1.0))[r < k])) for k in self.K])
+                elif m == "MRR":
+                    per_user[m].append([1.0 / (r[0] + 1.0)])
+                elif m == "AUC":
+                    per_user[m].append([1.0 - float(np.sum(r - (j - 1.0))) / (P * (C - P)) if C > P else np.nan])
+        out = {}
+        for m in self.used_metrics:
+            width = 1 if m in ("MRR", "AUC") else len(self.K)
+            vals = np.asarray(per_user[m], dtype=np.float64).reshape(-1, width)
+            out[m] = [_nanmean(vals[:, c]) for c in range(width)]
+        return out
+
+    def evaluate(self, model, sides=None) -> dict:
+        """``model``: a ``FactorizationMachines`` (with its ``recommend.Sides``) or a fitted
+        ``LogisticMatrixFactorization``."""
+        args = (self.users, self.items, self.exclude)
+        ranks, _, candidates = model.rank_items(*args) if sides is None else model.rank_items(sides, *args)
+        return self.metrics(self.users, ranks, candidates)

@@ -343,3 +343,13 @@ class FactorizationMachines(PointwiseBaseRecommender):
 
         A, LU, B, LI, c = rec.fm_operands(self, sides)
         return rec.topk(self._rt, A, LU, B, LI, c, self.n_factors, k, users, exclude)
+
+    def rank_items(self, sides, users, items, exclude=None):
+        """Where the pairs ``(users[n], items[n])`` land in their users' ranking of the whole
+        catalogue of ``sides``: ``(ranks int32 [n], scores float64 [n], candidates int32 [n])`` in
+        input order -- ``ranks`` 0-based under ``recommend()``'s order among the user's
+        ``candidates`` (logit not NaN, not in ``exclude``), at any depth (recommend.py)."""
+        from . import recommend as rec
+
+        A, LU, B, LI, c = rec.fm_operands(self, sides)
+        return rec.rank_items(self._rt, A, LU, B, LI, c, self.n_factors, users, items, exclude)

@@ -322,3 +322,12 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
 
         P, bu, Q, bi, c = rec.mf_operands(self)
         return rec.topk(self._rt, P, bu, Q, bi, c, self.n_factors, k, users, exclude)
+
+    def rank_items(self, users, items, exclude=None):
+        """Where the pairs ``(users[n], items[n])`` land in their users' ranking of all items:
+        ``(ranks int32 [n], scores float64 [n], candidates int32 [n])`` in input order, ranks
+        0-based under ``recommend()``'s order, at any depth (recommend.py)."""
+        from . import recommend as rec
+
+        P, bu, Q, bi, c = rec.mf_operands(self)
+        return rec.rank_items(self._rt, P, bu, Q, bi, c, self.n_factors, users, items, exclude)

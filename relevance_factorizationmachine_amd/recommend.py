@@ -14,6 +14,8 @@ recommend`` / ``score_pairs`` and their MF counterparts call the functions below
 Ranking is by the LOGIT under the total order (logit descending, then item index descending) --
 ``np.argsort(logit, kind="stable")[::-1][:k]``; the probabilities saturate to exactly 0.0 / 1.0 and
 would tie.  The returned scores are probabilities, ``sigmoid(logit)``, as ``predict()`` gives.
+``rank_items`` is the opposite question under the same order: the position of
+given (user, item) pairs in the user's ranking of the whole catalogue, at any depth.
 """
 from __future__ import annotations
 
@@ -119,6 +121,12 @@ def _exclusions(rt: Runtime, exclude, n_users: int, n_items: int):
     ``(indptr, indices)``; device ``(indptr int64, items int32)`` with ascending items per user."""
     if exclude is None:
         return None
+    indptr, items = _host_exclusions(exclude, n_users, n_items)
+    return rt.upload(indptr), rt.upload(items if items.size else np.zeros(1, np.int32))
+
+
+def _host_exclusions(exclude, n_users: int, n_items: int):
+    """The checked host arrays ``(indptr int64, items int32)`` of ``exclude``."""
     if isinstance(exclude, (tuple, list)):
         indptr, items = (np.asarray(a) for a in exclude)
     else:
@@ -141,7 +149,7 @@ def _exclusions(rt: Runtime, exclude, n_users: int, n_items: int):
         rising[indptr[1:-1][(indptr[1:-1] > 0) & (indptr[1:-1] < items.shape[0])] - 1] = True
         if not rising.all():
             raise ValueError("exclude: the item ids of a user must be strictly ascending")
-    return rt.upload(indptr), rt.upload(items if items.size else np.zeros(1, np.int32))
+    return indptr, items
 
 
 def score_pairs(rt: Runtime, A, LU, B, LI, c, n_factors: int, users=None) -> np.ndarray:
@@ -179,6 +187,93 @@ def topk(rt: Runtime, A, LU, B, LI, c, n_factors: int, k: int, users=None, exclu
                                     items.data_ptr(), scores.data_ptr()))
     rt.sync()
     return items.cpu().numpy(), scores.cpu().numpy()
+
+
+def ranks_workspace_bytes(n_sel_users: int, n_items: int, n_targets: int) -> int:
+    """Bytes of workspace ``rfm_pair_ranks`` needs (host only)."""
+    out = C.c_int64(0)
+    _lib.check(_lib.load().rfm_pair_ranks_workspace(int(n_sel_users), int(n_items), int(n_targets), C.byref(out)))
+    return int(out.value)
+
+
+def _id_array(a, what: str) -> np.ndarray:
+    a = np.asarray(a)
+    if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+        raise ValueError(f"{what} must be a 1-d array of integer ids")
+    return a.astype(np.int64)
+
+
+def group_pairs(users, items, n_users: int, n_items: int):
+    """(user, item) pairs in any order, repeats allowed, as ``rfm_pair_ranks`` takes them:
+    ``(sel_users int32, tgt_indptr int64, tgt_items int32, order)`` -- the unique users ascending,
+    the items of selected user s ascending in ``tgt_items[tgt_indptr[s]:tgt_indptr[s + 1]]``, and
+    ``order`` with grouped target t = input pair ``order[t]``.  ``ValueError`` for anything but two
+    equal-length 1-d integer arrays of ids inside their tables."""
+    users, items = _id_array(users, "users"), _id_array(items, "items")
+    if users.shape != items.shape:
+        raise ValueError(f"{users.shape[0]} users for {items.shape[0]} items: the pairs need one of each")
+    if users.size and (users.min() < 0 or users.max() >= n_users):
+        raise ValueError(f"a user id lies outside 0..{n_users - 1}")
+    if items.size and (items.min() < 0 or items.max() >= n_items):
+        raise ValueError(f"an item id lies outside 0..{n_items - 1}")
+    order = np.lexsort((items, users))
+    sel, counts = np.unique(users, return_counts=True)
+    indptr = np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
+    return sel.astype(np.int32), indptr, items[order].astype(np.int32), order
+
+
+def _first_excluded_pair(users, items, excl, n_items: int):
+    """Index of the first input pair that the host exclusion lists ``excl`` name, or None."""
+    indptr, listed = excl
+    keys = np.repeat(np.arange(indptr.shape[0] - 1, dtype=np.int64), np.diff(indptr)) * n_items + listed
+    hit = np.flatnonzero(np.isin(np.asarray(users, dtype=np.int64) * n_items + np.asarray(items, dtype=np.int64), keys))
+    return int(hit[0]) if hit.size else None
+
+
+def _rank_grouped(rt: Runtime, A, LU, B, LI, c, n_factors: int, sel, tgt_indptr, tgt_items, excl):
+    """One ``rfm_pair_ranks`` call for grouped targets (``group_pairs``); ``excl``: host lists or
+    None.  ``(ranks [n_targets], scores [n_targets], candidates [n_sel])``."""
+    torch = __import__("torch")
+    n_users, n_items = int(A.shape[0]), int(B.shape[0])
+    n_sel, n_tgt = int(sel.shape[0]), int(tgt_items.shape[0])
+    if n_sel == 0:
+        return np.zeros(0, np.int32), np.zeros(0, np.float64), np.zeros(0, np.int32)
+    d_excl = None if excl is None else (rt.upload(excl[0]), rt.upload(excl[1] if excl[1].size else np.zeros(1, np.int32)))
+    d_sel, d_indptr, d_items = rt.upload(sel), rt.upload(tgt_indptr), rt.upload(tgt_items)
+    ws = rt.empty((ranks_workspace_bytes(n_sel, n_items, n_tgt),), torch.uint8)
+    ranks, scores = rt.empty((n_tgt,), torch.int32), rt.empty((n_tgt,), torch.float64)
+    cand = rt.empty((n_sel,), torch.int32)
+    _lib.check(rt.lib.rfm_pair_ranks(rt.ctx, A.data_ptr(), LU.data_ptr(), n_users, d_sel.data_ptr(), n_sel,
+                                     B.data_ptr(), LI.data_ptr(), n_items, n_factors, c.data_ptr(),
+                                     None if d_excl is None else d_excl[0].data_ptr(),
+                                     None if d_excl is None else d_excl[1].data_ptr(), d_indptr.data_ptr(),
+                                     d_items.data_ptr(), ws.data_ptr(), ranks.data_ptr(), scores.data_ptr(),
+                                     cand.data_ptr()))
+    rt.sync()
+    return ranks.cpu().numpy(), scores.cpu().numpy(), cand.cpu().numpy()
+
+
+def rank_items(rt: Runtime, A, LU, B, LI, c, n_factors: int, users, items, exclude=None):
+    """Where the pairs ``(users[n], items[n])`` land in their users' ranking of the whole catalogue
+    (DESIGN.md 8 N6): ``(ranks int32 [n], scores float64 [n], candidates int32 [n])`` in input
+    order.  ``ranks[p]`` = number of items the user could be shown (logit not NaN, not in the
+    user's ``exclude`` list) that are better than ``items[p]`` under ``topk``'s order, so that
+    ``rank_items`` of ``topk``'s r-th item is r; ``candidates[p]`` = how many such items the user
+    has; scores = sigmoid(logit).  A pair that ``exclude`` lists is a ``ValueError``."""
+    n_users, n_items = int(A.shape[0]), int(B.shape[0])
+    sel, tgt_indptr, tgt_items, order = group_pairs(users, items, n_users, n_items)
+    excl = None if exclude is None else _host_exclusions(exclude, n_users, n_items)
+    if excl is not None:
+        p = _first_excluded_pair(users, items, excl, n_items)
+        if p is not None:
+            raise ValueError(f"pair {p} (user {int(np.asarray(users)[p])}, item {int(np.asarray(items)[p])}) "
+                             f"is in the user's exclusion list: it has no rank")
+    g_ranks, g_scores, g_cand = _rank_grouped(rt, A, LU, B, LI, c, n_factors, sel, tgt_indptr, tgt_items, excl)
+    n = order.shape[0]
+    ranks, scores, cand = np.empty(n, np.int32), np.empty(n, np.float64), np.empty(n, np.int32)
+    ranks[order], scores[order] = g_ranks, g_scores
+    cand[order] = np.repeat(g_cand, np.diff(tgt_indptr))
+    return ranks, scores, cand
 
 
 def fm_operands(model, sides: Sides):
