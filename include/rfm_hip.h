@@ -672,6 +672,36 @@ int32_t rfm_pair_ranks(rfm_ctx* ctx, const double* d_A, const double* d_LU, int6
                        const int64_t* d_excl_indptr, const int32_t* d_excl_items,
                        const int64_t* d_tgt_indptr, const int32_t* d_tgt_items, void* d_workspace,
                        int32_t* d_out_ranks, double* d_out_scores, int32_t* d_out_candidates);
+/* A user's ranking of the catalogue to any depth: the items at positions
+ * 0 .. depth-1 of the order rfm_pair_topk and rfm_pair_ranks use, depth >= 1 and not bounded by 64 --
+ * a candidate list for a re-ranker, a user's full ordering (depth >= n_items), and the lists the
+ * reference's mean exposure, catalogue coverage and Gini are taken from (utils/metrics.py:110-166,
+ * utils/evaluate.py:93-125) when the catalogue is what is ranked.  The first eleven arguments, the
+ * user ids, the exclusion lists and RFM_CHECK_IDS are rfm_pair_topk's; candidates and BETTER are
+ * rfm_pair_ranks'.  Per selected user s:
+ *     d_out_items[s][r]  = the candidate at position r, -1 past the user's last candidate;
+ *     d_out_scores[s][r] = sigmoid(clip(logit, +-700)) of that item, NaN where the item is -1;
+ *     d_out_n_ranked[s]  = the number of candidates of s (rfm_pair_ranks' d_out_candidates).
+ * +-inf logits are ordinary candidates; a user id outside the table gives an all-NaN row (items -1,
+ * n_ranked 0).  The logit is the pair tile's, bit for bit, so the first min(depth, 64) columns are
+ * rfm_pair_topk's bytes and rfm_pair_ranks of the r-th returned item is r.  Two stages per block of
+ * users: the tile stores the block's raw logits [users][n_items] in d_workspace, then one workgroup
+ * per user keeps the best min(depth, 4096) (rounded up to a power of two) in LDS while it streams
+ * the row, sorting and merging a staging area of the same size (bitonic); deeper lists go in pages
+ * of 4096 ranks, each page ranking what comes strictly after the last entry of the page before.
+ * The caller chooses workspace_bytes: the users are worked through in blocks of as many rows as fit
+ * (a multiple of 64).  rfm_pair_order_workspace (host only) gives the least size -- one block of 64
+ * users, less is RFM_ERR_BAD_ARG -- and the size that takes every selected user in one block.  The
+ * order is total and no float atomic is used: the result does not depend on the block cut, the
+ * pages or timing, and the same inputs give the same bits. */
+int32_t rfm_pair_order_workspace(int64_t n_sel_users, int64_t n_items, int64_t depth, int64_t* h_min_bytes,
+                                 int64_t* h_preferred_bytes);
+int32_t rfm_pair_order(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t n_users,
+                       const int32_t* d_user_ids, int64_t n_sel_users, const double* d_B,
+                       const double* d_LI, int64_t n_items, int32_t n_factors, const double* d_c,
+                       const int64_t* d_excl_indptr, const int32_t* d_excl_items, int64_t depth,
+                       void* d_workspace, int64_t workspace_bytes, int32_t* d_out_items,
+                       double* d_out_scores, int32_t* d_out_n_ranked);
 
 #ifdef __cplusplus
 }

@@ -174,6 +174,9 @@ SIGNATURES = {
     "rfm_pair_ranks_workspace": [_i64, _i64, _i64, C.POINTER(_i64)],
     "rfm_pair_ranks": [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                        _vp, _vp],
+    "rfm_pair_order_workspace": [_i64, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64)],
+    "rfm_pair_order": [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
+                       _vp, _vp],
 }
 
 

@@ -17,6 +17,10 @@
 // stores the logit of every target pair that falls into the tile, one counts, per target, the
 // tile's candidates that are better than it.  The counts are integers, summed with integer
 // atomics: they do not depend on the split or on timing.
+//
+// A user's ranking of the catalogue to any depth is a fifth epilogue, the raw
+// logits of a block of users to a workspace, and a ranking kernel of its own: one workgroup per
+// row, a streaming selection under the same total order with bitonic sorts and merges in LDS.
 #include <cmath>
 #include <cstdlib>
 
@@ -43,7 +47,7 @@ constexpr int kTargetWorkgroups = 1024;  // top-K: item splits are chosen to rea
 constexpr int kRankAccum = 4096;
 
 // epilogue of the pair tile
-enum PairMode { kScores = 0, kTopK = 1, kTargetLogits = 2, kRankCount = 3 };
+enum PairMode { kScores = 0, kTopK = 1, kTargetLogits = 2, kRankCount = 3, kLogits = 4 };
 
 using f64x4 = __attribute__((__vector_size__(4 * sizeof(double)))) double;
 
@@ -175,12 +179,17 @@ struct PairArgs {
   double* tgt_logit;           // [n_targets]: written by kTargetLogits, read by kRankCount
   int32_t* out_ranks;          // [n_targets], zeroed before kRankCount
   int32_t* out_candidates;     // [n_sel], zeroed before kRankCount
+  // kLogits: the launch covers the selected users sel_first .. sel_first + n_sel - 1 (user_ids,
+  // if given, already points at the first of them) and `out` takes their raw logits
+  int64_t sel_first;
 };
 
 // logit[u,i] = c + LU[u] + LI[i] + A[u,:].B[i,:] over a 64 x 64 tile: wavefront (wm, wn) owns
 // the 32 x 32 quarter at (32 wm, 32 wn) as 2 x 2 MFMA blocks of 16 x 16; the factors go
 // through LDS in chunks of 32 so that each operand element is read from memory once per tile.
-// Every mode but kScores: blockIdx.x is an item split; the workgroup walks the split's tiles and
+// kLogits is kScores without the sigmoid: one tile per workgroup, the raw logit
+// stored to out[user of the launch][item], NaN for a user id outside the table.
+// Every other mode: blockIdx.x is an item split; the workgroup walks the split's tiles and
 // hands each tile's logits over in LDS (T[user][item]).  kTopK keeps the K best items of each of
 // its 64 users in LDS lists, written to the workspace at the end.  kTargetLogits stores the logit
 // of every target of its users that lies in the tile.  kRankCount turns excluded items into NaN
@@ -188,7 +197,7 @@ struct PairArgs {
 template <int MODE>
 __global__ __launch_bounds__(kPairBlock) void pair_tile_kernel(PairArgs a) {
   constexpr bool TOPK = MODE == kTopK;
-  constexpr bool WALK = MODE != kScores;  // item splits, logits through T
+  constexpr bool WALK = MODE != kScores && MODE != kLogits;  // item splits, logits through T
   extern __shared__ double lds[];
   double* As = lds;                    // [kChunk][kLd]
   double* Bs = lds + kChunk * kLd;     // [kChunk][kLd]
@@ -213,7 +222,7 @@ __global__ __launch_bounds__(kPairBlock) void pair_tile_kernel(PairArgs a) {
     const int64_t s = u0 + sr + 8 * j;
     int64_t u = -1;
     if (s < a.n_sel) {
-      u = a.user_ids ? int64_t(a.user_ids[s]) : s;
+      u = a.user_ids ? int64_t(a.user_ids[s]) : s + (MODE == kLogits ? a.sel_first : 0);
       if (u < 0 || u >= a.n_users) {
         if (a.flags && sk == 0) atomicOr(a.flags, 2);
         u = -1;
@@ -290,7 +299,7 @@ __global__ __launch_bounds__(kPairBlock) void pair_tile_kernel(PairArgs a) {
         const int64_t s = u0 + ul;
         int64_t u = -1;
         if (s < a.n_sel) {
-          u = a.user_ids ? int64_t(a.user_ids[s]) : s;
+          u = a.user_ids ? int64_t(a.user_ids[s]) : s + (MODE == kLogits ? a.sel_first : 0);
           if (u < 0 || u >= a.n_users) u = -1;
         }
         const double lu = u >= 0 ? a.LU[u] : NAN;  // a user id outside the table scores NaN
@@ -303,7 +312,7 @@ __global__ __launch_bounds__(kPairBlock) void pair_tile_kernel(PairArgs a) {
           if (WALK) {
             T[ul * kLogitLd + il] = logit;
           } else if (in) {
-            a.out[s * a.n_items + item] = sigmoid_clipped(logit);
+            a.out[s * a.n_items + item] = MODE == kLogits ? logit : sigmoid_clipped(logit);
           }
         }
       }
@@ -517,6 +526,181 @@ __global__ __launch_bounds__(kPairBlock) void rank_finish_kernel(const double* _
   }
 }
 
+// ---------------------------------------------------------------------------
+// A user's ranking of the catalogue to any depth: one workgroup per row of raw
+// logits (kLogits), a streaming selection under better().  LDS holds the P best entries seen so
+// far, sorted best first, and a staging area of P; logits and items in separate arrays (8- and
+// 4-byte strides: the compare-exchanges of a wavefront fall on distinct banks).  The threads walk
+// the row kOrderPass(P) items at a time and append, through an integer LDS counter, the
+// candidates that beat the current P-th entry; a staging area that could not take another pass
+// is sorted (bitonic) and merged (half-cleaner + bitonic merge) into the best.  The order is
+// total, so neither the order of appending nor the places of the flushes change the result.
+// Depths above kOrderMaxP go in pages: a page ranks only what comes strictly after the row's
+// cutoff, the last entry of the page before.
+// ---------------------------------------------------------------------------
+constexpr int kOrderMaxP = 4096;        // entries of the list = ranks of a page
+constexpr int kOrderMinP = kPairBlock;  // (a pass appends up to one item per thread)
+
+inline int order_list_len(int64_t n_ranks) {  // power of two >= min(n_ranks, kOrderMaxP)
+  int p = kOrderMinP;
+  while (p < kOrderMaxP && p < n_ranks) p <<= 1;
+  return p;
+}
+__host__ __device__ inline int order_pass(int P) { return P < 4 * kPairBlock ? P : 4 * kPairBlock; }
+
+struct OrderArgs {
+  const double* logits;        // [rows of the launch][n_items]
+  int64_t n_items;
+  const int32_t* user_ids;     // of the launch's first row, or null (row r = user sel_first + r)
+  int64_t sel_first, n_users;
+  const int64_t* excl_indptr;  // [n_users + 1] or null
+  const int32_t* excl_items;
+  int P;                       // list length: a power of two, kOrderMinP .. kOrderMaxP
+  int first_page;              // no cutoff; counts the candidates
+  int64_t depth;               // columns of the outputs
+  int64_t col0, n_cols;        // the page ranks columns col0 .. col0 + n_cols - 1, n_cols <= P
+  int64_t fill_to;             // columns up to fill_to - 1 get the padding (the last page: depth)
+  double* cut_l;               // [rows]: the page's last entry, the cutoff of the next page
+  int32_t* cut_i;              //         (item -1: the row has no further candidate)
+  int32_t* out_items;          // [rows][depth]
+  double* out_scores;
+  int32_t* out_n_ranked;       // [rows]
+};
+
+// entries i < j of a list: the better one goes to i (better_first) or to j
+__device__ inline void order_cmpx(double* l, int32_t* it, int i, int j, bool better_first) {
+  const double li = l[i], lj = l[j];
+  const int ii = it[i], ij = it[j];
+  if (better_first ? better(lj, ij, li, ii) : better(li, ii, lj, ij)) {
+    l[i] = lj, l[j] = li;
+    it[i] = ij, it[j] = ii;
+  }
+}
+
+// The n staged entries into the best P.  Called by the whole workgroup after a barrier that
+// follows the last append; ends with a barrier, the counter back at 0.
+__device__ inline void order_flush(double* bl, int32_t* bi, double* sl, int32_t* si, int P, int n, int* count) {
+  const int tid = threadIdx.x;
+  int m = 1;
+  while (m < n) m <<= 1;
+  for (int e = n + tid; e < m; e += kPairBlock) {  // empty slots: beaten by every candidate
+    sl[e] = -INFINITY;
+    si[e] = -1;
+  }
+  __syncthreads();
+  if (tid == 0) *count = 0;
+  for (int k = 2; k <= m; k <<= 1) {  // bitonic sort of the m staged entries, best first
+    for (int j = k >> 1; j >= 1; j >>= 1) {
+      for (int t = tid; t < (m >> 1); t += kPairBlock) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+        order_cmpx(sl, si, i, i | j, (i & k) == 0);
+      }
+      __syncthreads();
+    }
+  }
+  // best[P - 1 - t] against staged[t]: the P best of both, as a bitonic sequence
+  for (int t = tid; t < m; t += kPairBlock) {
+    const int b = P - 1 - t;
+    if (better(sl[t], si[t], bl[b], bi[b])) {
+      bl[b] = sl[t];
+      bi[b] = si[t];
+    }
+  }
+  __syncthreads();
+  for (int j = P >> 1; j >= 1; j >>= 1) {
+    for (int t = tid; t < (P >> 1); t += kPairBlock) {
+      const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+      order_cmpx(bl, bi, i, i | j, true);
+    }
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(kPairBlock) void order_rows_kernel(OrderArgs a) {
+  extern __shared__ double lds[];
+  __shared__ int s_count, s_cand;
+  const int P = a.P, pass = order_pass(P);
+  double* bl = lds;       // [P] the best, sorted best first
+  double* sl = lds + P;   // [P] staging
+  int32_t* bi = reinterpret_cast<int32_t*>(lds + 2 * P);
+  int32_t* si = bi + P;
+  const int tid = threadIdx.x;
+  const int64_t row = blockIdx.x;
+  const double* z = a.logits + row * a.n_items;
+  int32_t* oi = a.out_items + row * a.depth;
+  double* os = a.out_scores + row * a.depth;
+
+  double cl = 0.0;
+  int ci = 0;
+  if (!a.first_page) {
+    cl = a.cut_l[row];
+    ci = a.cut_i[row];
+    if (ci < 0) {  // (the whole workgroup) the row ended on an earlier page
+      for (int64_t col = a.col0 + tid; col < a.fill_to; col += kPairBlock) {
+        oi[col] = -1;
+        os[col] = NAN;
+      }
+      return;
+    }
+  }
+  int64_t elo = 0, ehi = 0;
+  if (a.excl_indptr) {
+    const int64_t u = a.user_ids ? int64_t(a.user_ids[row]) : a.sel_first + row;
+    if (u >= 0 && u < a.n_users) elo = a.excl_indptr[u], ehi = a.excl_indptr[u + 1];  // (else every logit is NaN)
+  }
+  for (int e = tid; e < P; e += kPairBlock) {
+    bl[e] = -INFINITY;
+    bi[e] = -1;
+  }
+  if (tid == 0) s_count = 0, s_cand = 0;
+  __syncthreads();
+
+  int n_cand = 0;
+  for (int64_t i0 = 0; i0 < a.n_items; i0 += pass) {
+    const int staged = s_count;
+    __syncthreads();  // everybody has read the counter before anybody appends
+    if (staged > P - pass) order_flush(bl, bi, sl, si, P, staged, &s_count);
+    const double tl = bl[P - 1];
+    const int ti = bi[P - 1];
+    for (int64_t i = i0 + tid; i < min(i0 + pass, a.n_items); i += kPairBlock) {
+      const double l = z[i];
+      bool ok = l == l;
+      if (a.first_page) {
+        if (ok && elo < ehi) ok = !excluded(a.excl_items, elo, ehi, int(i));
+        n_cand += ok ? 1 : 0;
+        ok = ok && better(l, int(i), tl, ti);
+      } else {
+        ok = ok && better(cl, ci, l, int(i)) && better(l, int(i), tl, ti);
+        if (ok && elo < ehi) ok = !excluded(a.excl_items, elo, ehi, int(i));
+      }
+      if (ok) {
+        const int at = atomicAdd(&s_count, 1);  // < P: at most `pass` appends since staged <= P - pass
+        sl[at] = l;
+        si[at] = int(i);
+      }
+    }
+    __syncthreads();
+  }
+  const int staged = s_count;
+  if (a.first_page && n_cand) atomicAdd(&s_cand, n_cand);
+  __syncthreads();
+  if (staged > 0) order_flush(bl, bi, sl, si, P, staged, &s_count);
+
+  for (int64_t e = tid; a.col0 + e < a.fill_to; e += kPairBlock) {
+    const int it = e < a.n_cols ? bi[e] : -1;
+    oi[a.col0 + e] = it;
+    os[a.col0 + e] = it >= 0 ? sigmoid_clipped(bl[e]) : NAN;
+  }
+  if (tid == 0) {
+    a.cut_l[row] = bl[a.n_cols - 1];
+    a.cut_i[row] = bi[a.n_cols - 1];
+    if (a.first_page) a.out_n_ranked[row] = s_cand;
+  }
+}
+
+// rfm_pair_order's workspace: per user of a block a row of logits and a cutoff
+inline int64_t order_row_bytes(int64_t n_items) { return n_items * 8 + 12; }
+
 struct Split {
   int n_splits, tiles_per_split;
 };
@@ -580,6 +764,7 @@ struct IdCheck {
 };
 
 LdsLimits g_topk_lds;
+LdsLimits g_order_lds;
 
 }  // namespace
 }  // namespace rfm
@@ -756,6 +941,80 @@ int32_t rfm_pair_ranks(rfm_ctx* ctx, const double* d_A, const double* d_LU, int6
       hipLaunchKernelGGL(rank_finish_kernel, dim3(capped_grid(ctx, n_targets, kPairBlock, 16, 1)),
                          dim3(kPairBlock), 0, ctx->stream, a.tgt_logit, n_targets, d_out_ranks, d_out_scores);
       RFM_HIP_CHECK(hipGetLastError());
+    }
+    chk.finish();
+  });
+}
+
+int32_t rfm_pair_order_workspace(int64_t n_sel_users, int64_t n_items, int64_t depth, int64_t* h_min_bytes,
+                                 int64_t* h_preferred_bytes) {
+  return guarded([&] {
+    RFM_REQUIRE(h_min_bytes && h_preferred_bytes, "null pointer");
+    RFM_REQUIRE(depth >= 1, "depth=%lld: the ranking depth must be at least 1", (long long)depth);
+    RFM_REQUIRE(n_sel_users >= 0 && n_items >= 1, "negative n_sel_users or no items");
+    RFM_REQUIRE(n_items < (int64_t(1) << 31) - kTile, "n_items=%lld does not fit int32 item ids", (long long)n_items);
+    *h_min_bytes = kTile * order_row_bytes(n_items);
+    *h_preferred_bytes = std::max<int64_t>(1, (n_sel_users + kTile - 1) / kTile) * kTile * order_row_bytes(n_items);
+  });
+}
+
+int32_t rfm_pair_order(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t n_users,
+                       const int32_t* d_user_ids, int64_t n_sel_users, const double* d_B,
+                       const double* d_LI, int64_t n_items, int32_t n_factors, const double* d_c,
+                       const int64_t* d_excl_indptr, const int32_t* d_excl_items, int64_t depth,
+                       void* d_workspace, int64_t workspace_bytes, int32_t* d_out_items,
+                       double* d_out_scores, int32_t* d_out_n_ranked) {
+  return guarded([&] {
+    RFM_REQUIRE(depth >= 1, "depth=%lld: the ranking depth must be at least 1", (long long)depth);
+    require_pair_args(ctx, d_A, d_LU, n_users, n_sel_users, d_B, d_LI, n_items, n_factors, d_c);
+    RFM_REQUIRE(d_user_ids || n_sel_users == n_users, "without user ids every user is selected");
+    RFM_REQUIRE(!d_excl_indptr || d_excl_items, "exclusion lists without items");
+    if (n_sel_users == 0) return;
+    RFM_REQUIRE(d_workspace && d_out_items && d_out_scores && d_out_n_ranked, "null workspace or output");
+    const int64_t block_rows = workspace_bytes / order_row_bytes(n_items) / kTile * kTile;
+    RFM_REQUIRE(block_rows >= kTile, "workspace_bytes=%lld is less than one block of %d users (%lld bytes)",
+                (long long)workspace_bytes, kTile, (long long)(kTile * order_row_bytes(n_items)));
+    RFM_HIP_CHECK(hipSetDevice(ctx->device));
+    IdCheck chk(ctx);
+    if (chk.flags() && d_excl_indptr) {
+      hipLaunchKernelGGL(excl_check_kernel, dim3(capped_grid(ctx, n_users, kPairBlock, 16, 1)),
+                         dim3(kPairBlock), 0, ctx->stream, d_excl_indptr, d_excl_items, n_users, n_items,
+                         chk.flags());
+      RFM_HIP_CHECK(hipGetLastError());
+      chk.finish();  // (before any list is searched)
+      RFM_HIP_CHECK(hipMemsetAsync(chk.buf.p, 0, 4, ctx->stream));
+    }
+    // ranks beyond the catalogue are padding whatever the logits: they take no page of their own
+    const int64_t n_ranks = std::min(depth, n_items);
+    const int P = order_list_len(n_ranks);
+    const size_t lds = size_t(P) * 2 * 12;
+    allow_dynamic_lds(ctx, reinterpret_cast<const void*>(&order_rows_kernel), lds, g_order_lds);
+    double* ws_logits = static_cast<double*>(d_workspace);
+    double* ws_cut_l = ws_logits + block_rows * n_items;
+    int32_t* ws_cut_i = reinterpret_cast<int32_t*>(ws_cut_l + block_rows);
+    for (int64_t first = 0; first < n_sel_users; first += block_rows) {
+      const int64_t rows = std::min(block_rows, n_sel_users - first);
+      PairArgs a{};
+      a.A = d_A, a.LU = d_LU, a.user_ids = d_user_ids ? d_user_ids + first : nullptr, a.n_users = n_users;
+      a.n_sel = rows, a.sel_first = first;
+      a.B = d_B, a.LI = d_LI, a.n_items = n_items, a.kpad = int(pad4(n_factors)), a.c = d_c;
+      a.out = ws_logits, a.flags = chk.flags();
+      const dim3 grid((unsigned)((n_items + kTile - 1) / kTile), (unsigned)((rows + kTile - 1) / kTile));
+      hipLaunchKernelGGL(pair_tile_kernel<kLogits>, grid, dim3(kPairBlock), size_t(kOperandDoubles) * 8,
+                         ctx->stream, a);
+      RFM_HIP_CHECK(hipGetLastError());
+      OrderArgs o{};
+      o.logits = ws_logits, o.n_items = n_items, o.user_ids = a.user_ids, o.sel_first = first, o.n_users = n_users;
+      o.excl_indptr = d_excl_indptr, o.excl_items = d_excl_items, o.P = P, o.depth = depth;
+      o.cut_l = ws_cut_l, o.cut_i = ws_cut_i;
+      o.out_items = d_out_items + first * depth, o.out_scores = d_out_scores + first * depth;
+      o.out_n_ranked = d_out_n_ranked + first;
+      for (int64_t col0 = 0; col0 < n_ranks; col0 += P) {  // (more than one page only with P = kOrderMaxP)
+        o.first_page = col0 == 0, o.col0 = col0, o.n_cols = std::min<int64_t>(P, n_ranks - col0);
+        o.fill_to = col0 + o.n_cols < n_ranks ? col0 + o.n_cols : depth;
+        hipLaunchKernelGGL(order_rows_kernel, dim3((unsigned)rows), dim3(kPairBlock), lds, ctx->stream, o);
+        RFM_HIP_CHECK(hipGetLastError());
+      }
     }
     chk.finish();
   });

@@ -560,3 +560,75 @@ class CatalogueEvaluator:
         args = (self.users, self.items, self.exclude)
         ranks, _, candidates = model.rank_items(*args) if sides is None else model.rank_items(sides, *args)
         return self.metrics(self.users, ranks, candidates)
+
+
+class CatalogueExposure:
+    """The reference's three qualitative metrics -- mean exposure, catalogue coverage and Gini
+    (``utils/metrics.py:110-166``, as ``TestEvaluator`` sums them, ``utils/evaluate.py:93-125``) --
+    of every selected user's ranking of the WHOLE catalogue, from one
+    ``model.rank_catalogue(depth=max(K))`` call.
+
+    ``K``: ranking depths, any positive integers; ``used_metrics``: a subset of ``METRICS``;
+    ``item_pscores [n_items]``: the propensity of an item, required by ``"ME"`` (in the reference
+    the KuaiRec propensity is a function of the item, ``utils/dataloader/kuairec/_click.py:170-204``);
+    ``exclude``: items never shown to a user, as ``recommend()`` takes them; ``users``: the users
+    that count (default: all) -- there are no labels here, so ``TestEvaluator``'s "users with a
+    positive" is the caller's choice.  ``evaluate`` returns ``{metric: [value per K]}``:
+    ``CatalogCoverage@k`` = distinct items in the lists' first k columns / ``n_items``, ``Gini@k``
+    = ``calc_gini_at_k`` over the same items, ``ME@k`` = nan-mean over the users of the propensity
+    of the item at position k - 1 (NaN for a user with fewer than k ranked items)."""
+
+    METRICS = ("ME", "CatalogCoverage", "Gini")
+
+    def __init__(self, n_items: int, K, used_metrics, item_pscores=None, exclude=None, users=None):
+        self.n_items = int(n_items)
+        self.K = [int(k) for k in K]
+        if not self.K or any(k < 1 for k in self.K):
+            raise ValueError("K must be positive integers")
+        unknown = [m for m in used_metrics if m not in self.METRICS]
+        if unknown:
+            raise ValueError(f"unknown metric {unknown[0]!r} (known: {', '.join(self.METRICS)})")
+        self.used_metrics = list(used_metrics)
+        self.item_pscores = None if item_pscores is None else np.asarray(item_pscores, dtype=np.float64)
+        if "ME" in self.used_metrics and self.item_pscores is None:
+            raise ValueError("'ME' needs item_pscores: the propensity of every item")
+        if self.item_pscores is not None and self.item_pscores.shape != (self.n_items,):
+            raise ValueError(f"item_pscores has shape {self.item_pscores.shape}, expected {(self.n_items,)}")
+        self.exclude, self.users = exclude, users
+
+    def metrics(self, items) -> dict:
+        """The metrics from the lists ``items [n_users, depth]`` (-1 = no item): host only.  Columns
+        past ``depth`` count as padding."""
+        items = np.asarray(items).astype(np.int64)
+        if items.ndim != 2:
+            raise ValueError("items must be [n_users, depth]")
+        kmax = max(self.K)
+        if items.shape[1] < kmax:
+            items = np.hstack([items, np.full((items.shape[0], kmax - items.shape[1]), -1, dtype=np.int64)])
+        valid = items >= 0
+        idx = np.arange(1, self.n_items + 1)
+        out = {}
+        for name in self.used_metrics:
+            vals = []
+            for k in self.K:
+                if name == "ME":  # utils/metrics.py:110-126
+                    col = items[:, k - 1]
+                    vals.append(_nanmean(np.where(col >= 0, self.item_pscores[np.maximum(col, 0)], np.nan)))
+                    continue
+                rec = items[:, :k][valid[:, :k]]
+                rec = rec[rec < self.n_items]
+                if name == "CatalogCoverage":  # utils/metrics.py:151-166
+                    vals.append(len(np.unique(rec)) / self.n_items)
+                else:  # Gini, utils/metrics.py:129-148
+                    freqs = np.sort(np.bincount(rec, minlength=self.n_items), kind="merge")
+                    with np.errstate(invalid="ignore", divide="ignore"):
+                        vals.append(float(np.sum((2 * idx - self.n_items - 1) * freqs) / (self.n_items * np.sum(freqs))))
+            out[name] = vals
+        return out
+
+    def evaluate(self, model, sides=None) -> dict:
+        """``model``: a ``FactorizationMachines`` (with its ``recommend.Sides``) or a fitted
+        ``LogisticMatrixFactorization``."""
+        args = (max(self.K), self.users, self.exclude)
+        items, _, _ = model.rank_catalogue(*args) if sides is None else model.rank_catalogue(sides, *args)
+        return self.metrics(items)

@@ -353,3 +353,13 @@ class FactorizationMachines(PointwiseBaseRecommender):
 
         A, LU, B, LI, c = rec.fm_operands(self, sides)
         return rec.rank_items(self._rt, A, LU, B, LI, c, self.n_factors, users, items, exclude)
+
+    def rank_catalogue(self, sides, depth: int, users=None, exclude=None):
+        """Every user's ranking of the catalogue of ``sides`` down to ``depth`` (any integer >= 1;
+        ``depth >= n_items``: the full ordering): ``(items int32 [n, depth], scores float64
+        [n, depth], n_ranked int32 [n])`` under ``recommend()``'s order, short rows padded with
+        item -1 / score NaN; the first 64 columns are ``recommend(k=64)``'s (recommend.py)."""
+        from . import recommend as rec
+
+        A, LU, B, LI, c = rec.fm_operands(self, sides)
+        return rec.rank_catalogue(self._rt, A, LU, B, LI, c, self.n_factors, depth, users, exclude)

@@ -331,3 +331,12 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
 
         P, bu, Q, bi, c = rec.mf_operands(self)
         return rec.rank_items(self._rt, P, bu, Q, bi, c, self.n_factors, users, items, exclude)
+
+    def rank_catalogue(self, depth: int, users=None, exclude=None):
+        """Every user's ranking of all items down to ``depth`` (any integer >= 1): ``(items int32
+        [n, depth], scores float64 [n, depth], n_ranked int32 [n])`` under ``recommend()``'s
+        order, short rows padded with item -1 / score NaN (recommend.py)."""
+        from . import recommend as rec
+
+        P, bu, Q, bi, c = rec.mf_operands(self)
+        return rec.rank_catalogue(self._rt, P, bu, Q, bi, c, self.n_factors, depth, users, exclude)

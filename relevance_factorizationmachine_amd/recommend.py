@@ -16,6 +16,8 @@ Ranking is by the LOGIT under the total order (logit descending, then item index
 would tie.  The returned scores are probabilities, ``sigmoid(logit)``, as ``predict()`` gives.
 ``rank_items`` is the opposite question under the same order: the position of
 given (user, item) pairs in the user's ranking of the whole catalogue, at any depth.
+``rank_catalogue`` is ``topk`` without the limit of 64: the items at positions
+0 .. depth-1, up to the user's full ordering of the catalogue.
 """
 from __future__ import annotations
 
@@ -28,6 +30,11 @@ from . import _lib
 from .runtime import DeviceCSR, Runtime
 
 MAX_K = 64
+# rank_catalogue(workspace_bytes=None): the most workspace it takes by itself.  One row of logits per
+# user of a block, so 1 GiB is a single block up to 12 500 users x 10 728 items (the reference's
+# KuaiRec catalogue: 7 176 users) and about 1 300 users a block at 100 000 items -- hundreds of
+# workgroups per launch either way, on a device with 288 GB.  Never below the ABI's minimum.
+ORDER_WORKSPACE_BYTES = 1 << 30
 
 
 def pad4(n_factors: int) -> int:
@@ -274,6 +281,62 @@ def rank_items(rt: Runtime, A, LU, B, LI, c, n_factors: int, users, items, exclu
     ranks[order], scores[order] = g_ranks, g_scores
     cand[order] = np.repeat(g_cand, np.diff(tgt_indptr))
     return ranks, scores, cand
+
+
+def order_workspace_bytes(n_sel_users: int, n_items: int, depth: int) -> Tuple[int, int]:
+    """``(min, preferred)`` bytes of workspace for ``rfm_pair_order`` (host only): one block of 64
+    users / every selected user in one block; ``ValueError`` unless ``depth >= 1``."""
+    lo, hi = C.c_int64(0), C.c_int64(0)
+    _lib.check(_lib.load().rfm_pair_order_workspace(int(n_sel_users), int(n_items), _depth(depth), C.byref(lo),
+                                                    C.byref(hi)))
+    return int(lo.value), int(hi.value)
+
+
+def _depth(depth) -> int:
+    if isinstance(depth, (bool, np.bool_)) or not isinstance(depth, (int, np.integer)):
+        raise ValueError(f"depth must be an integer, got {depth!r}")
+    if depth < 1:
+        raise ValueError(f"depth={int(depth)}: the ranking depth must be at least 1")
+    return int(depth)
+
+
+def rank_catalogue(rt: Runtime, A, LU, B, LI, c, n_factors: int, depth: int, users=None, exclude=None,
+                   workspace_bytes: Optional[int] = None):
+    """Every selected user's ranking of the catalogue down to ``depth``:
+    ``(items int32 [n_sel, depth], scores float64 [n_sel, depth], n_ranked int32 [n_sel])``.
+    Column r holds the candidate (logit not NaN, not in the user's ``exclude`` list) at position r
+    of ``topk``'s order -- logit descending, ties: higher item index first -- and its
+    sigmoid(logit); a row with fewer than ``depth`` candidates pads with item -1 / score NaN, and
+    ``n_ranked`` is the user's candidate count (``rank_items``' ``candidates``).  ``depth`` is any
+    integer >= 1; ``depth >= n_items`` gives the full ordering.  The first ``min(depth, 64)``
+    columns are ``topk``'s bytes, and ``rank_items`` of the r-th returned item is r.
+    ``workspace_bytes``: device memory for the logits of a block of users (``order_workspace_bytes``;
+    default: the preferred size, at most ``ORDER_WORKSPACE_BYTES``); the result does not depend on it."""
+    torch = __import__("torch")
+    n_users, n_items = int(A.shape[0]), int(B.shape[0])
+    depth = _depth(depth)
+    ids, n_sel = _users(rt, users, n_users)
+    excl = _exclusions(rt, exclude, n_users, n_items)
+    if n_sel == 0:
+        return np.zeros((0, depth), np.int32), np.zeros((0, depth), np.float64), np.zeros(0, np.int32)
+    least, preferred = order_workspace_bytes(n_sel, n_items, depth)
+    if workspace_bytes is None:
+        workspace_bytes = max(least, min(preferred, ORDER_WORKSPACE_BYTES))
+    workspace_bytes = int(workspace_bytes)
+    if workspace_bytes < least:
+        raise ValueError(f"workspace_bytes={workspace_bytes} is less than one block of 64 users ({least} bytes)")
+    ws = rt.empty((workspace_bytes,), torch.uint8)
+    items = rt.empty((n_sel, depth), torch.int32)
+    scores = rt.empty((n_sel, depth), torch.float64)
+    n_ranked = rt.empty((n_sel,), torch.int32)
+    _lib.check(rt.lib.rfm_pair_order(rt.ctx, A.data_ptr(), LU.data_ptr(), n_users,
+                                     None if ids is None else ids.data_ptr(), n_sel, B.data_ptr(),
+                                     LI.data_ptr(), n_items, n_factors, c.data_ptr(),
+                                     None if excl is None else excl[0].data_ptr(),
+                                     None if excl is None else excl[1].data_ptr(), depth, ws.data_ptr(),
+                                     workspace_bytes, items.data_ptr(), scores.data_ptr(), n_ranked.data_ptr()))
+    rt.sync()
+    return items.cpu().numpy(), scores.cpu().numpy(), n_ranked.cpu().numpy()
 
 
 def fm_operands(model, sides: Sides):
