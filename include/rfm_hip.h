@@ -309,6 +309,22 @@ int32_t rfm_fm_train(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr,
                      const double* d_val_values, const double* d_val_y,
                      const double* d_val_pscore, int64_t n_val, double eps,
                      double* d_out_train_loss, double* d_out_val_loss);
+/* rfm_fm_train for a piece of a longer call (src/fm.py:71-102, cut where the caller has something
+ * to enqueue between two iterations -- the catalogue metrics of DESIGN.md 8 N8): n_iters
+ * iterations of a call that would have had call_iters >= n_iters of them.  rfm_fm_train chooses
+ * the form of its loss forwards by the length of the call (a call of fewer than 4 iterations takes
+ * the logarithms inside the forward), and the forms differ in the order of their sums; here the
+ * form is the one a call of call_iters iterations takes, so the pieces of a call leave the losses
+ * that call leaves, bit for bit where the fit is reproducible at all.  Everything else is
+ * rfm_fm_train's. */
+int32_t rfm_fm_train_part(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr,
+                          const int32_t* d_indices, const double* d_values, const double* d_y,
+                          const double* d_pscore, const int32_t* d_ids, int64_t batch,
+                          int64_t n_iters, double* d_w0, double* d_w, double* d_V, double lr,
+                          const int64_t* d_val_indptr, const int32_t* d_val_indices,
+                          const double* d_val_values, const double* d_val_y,
+                          const double* d_val_pscore, int64_t n_val, double eps,
+                          double* d_out_train_loss, double* d_out_val_loss, int64_t call_iters);
 /* rfm_fm_train with the evaluator hook of the reference's search loop inside
  * (utils/search_params.py:96-111: fit(..., evaluator=ValEvaluator) -- after every iteration the
  * scores of the evaluation log, src/fm.py:104-110, and their IPS-DCG@k, utils/evaluate.py:160-207):
@@ -672,6 +688,46 @@ int32_t rfm_pair_ranks(rfm_ctx* ctx, const double* d_A, const double* d_LU, int6
                        const int64_t* d_excl_indptr, const int32_t* d_excl_items,
                        const int64_t* d_tgt_indptr, const int32_t* d_tgt_items, void* d_workspace,
                        int32_t* d_out_ranks, double* d_out_scores, int32_t* d_out_candidates);
+/* rfm_pair_ranks with the number of targets given by the host: n_targets must be
+ * d_tgt_indptr[n_sel_users].  Nothing is read back and nothing synchronises (unless RFM_CHECK_IDS=1),
+ * so the call can be enqueued between the iterations of a fit; every other argument, the launches
+ * and the results, byte for byte, are rfm_pair_ranks' (the ranks utils/metrics.py:9-107 are taken
+ * from when the whole catalogue is ranked). */
+int32_t rfm_pair_ranks_n(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t n_users,
+                         const int32_t* d_user_ids, int64_t n_sel_users, const double* d_B,
+                         const double* d_LI, int64_t n_items, int32_t n_factors, const double* d_c,
+                         const int64_t* d_excl_indptr, const int32_t* d_excl_items,
+                         const int64_t* d_tgt_indptr, const int32_t* d_tgt_items, int64_t n_targets,
+                         void* d_workspace, int32_t* d_out_ranks, double* d_out_scores,
+                         int32_t* d_out_candidates);
+/* Catalogue metrics from ranks, on the device: the reference's calc_dcg_at_k,
+ * calc_recall_at_k and calc_average_precision_at_k (utils/metrics.py:9-107; the IPS form of the
+ * DCG: calc_ips_of_dcg_at_k, utils/metrics.py:53-80) as they come out for the 0/1 vector of a
+ * user's candidates in ranked order, plus MRR and AUC, from the ranks of the user's positives.
+ * The targets are grouped as rfm_pair_ranks takes them (d_tgt_indptr[n_sel_users + 1], n_targets =
+ * its last entry, given by the host); d_ranks[n_targets] is rfm_pair_ranks' output (-1 = unranked:
+ * left out), d_candidates[n_sel_users] its candidate counts, d_weights[n_targets] an optional weight
+ * per target (NULL = ones; 1 / propensity for the IPS estimate).  The targets of a user must be
+ * distinct items, so that the ranks are.  h_K[n_K]: depths >= 1 on the host, 1 <= n_K <= 16.  Per
+ * selected user with ranked positives r_1 < ... < r_P, weights v_j and C candidates:
+ *     DCG@K    = sum_{r_j < K} v_j g(r_j),  g(0) = 1, g(r) = 1 / log2(r + 1)
+ *     Recall@K = #{r_j < K} / P
+ *     MAP@K    = sum_{r_j < K} j / (r_j + 1)
+ *     MRR      = 1 / (r_1 + 1)
+ *     AUC      = 1 - sum_j (r_j - (j - 1)) / (P (C - P)),  NaN when C <= P.
+ * d_out[3 n_K + 2] = DCG@K[0..] | Recall@K[0..] | MAP@K[0..] | MRR | AUC: the mean of each column
+ * over the users with at least one ranked positive, the AUC over those of them with C > P; NaN for a
+ * column without a user.  d_out_counts[3] = users counted, users counted for the AUC, unranked
+ * positives.  One wavefront per user orders the ranks by counting and adds a user's terms in
+ * ascending rank order; the means are a second launch with a fixed order; no float atomic: the same
+ * inputs give the same bits.  Nothing synchronises.  d_workspace: rfm_rank_metrics_workspace bytes
+ * (host only).  An indptr that leaves 0..n_targets is clamped, never followed outside the arrays;
+ * RFM_CHECK_IDS=1 makes it RFM_ERR_BAD_ARG (this synchronises). */
+int32_t rfm_rank_metrics_workspace(int64_t n_sel_users, int64_t n_targets, int32_t n_K, int64_t* h_bytes);
+int32_t rfm_rank_metrics(rfm_ctx* ctx, const int64_t* d_tgt_indptr, int64_t n_sel_users, int64_t n_targets,
+                         const int32_t* d_ranks, const int32_t* d_candidates, const double* d_weights,
+                         const int64_t* h_K, int32_t n_K, void* d_workspace, double* d_out,
+                         int64_t* d_out_counts);
 /* A user's ranking of the catalogue to any depth: the items at positions
  * 0 .. depth-1 of the order rfm_pair_topk and rfm_pair_ranks use, depth >= 1 and not bounded by 64 --
  * a candidate list for a re-ranker, a user's full ordering (depth >= n_items), and the lists the

@@ -134,6 +134,8 @@ SIGNATURES = {
     "rfm_fm_set_rows": [_vp, _vp, _i64, _vp, _i32, _i64, _vp, _vp, _vp, _i64, _i32, _f64],
     "rfm_fm_train": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _f64,
                      _vp, _vp, _vp, _vp, _vp, _i64, _f64, _vp, _vp],
+    "rfm_fm_train_part": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _f64,
+                          _vp, _vp, _vp, _vp, _vp, _i64, _f64, _vp, _vp, _i64],
     "rfm_fm_train_eval": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _f64,
                      _vp, _vp, _vp, _vp, _vp, _i64, _f64, _vp, _vp,
                           _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _i64, _i64, _vp],
@@ -174,6 +176,10 @@ SIGNATURES = {
     "rfm_pair_ranks_workspace": [_i64, _i64, _i64, C.POINTER(_i64)],
     "rfm_pair_ranks": [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                        _vp, _vp],
+    "rfm_pair_ranks_n": [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp,
+                         _vp, _vp, _vp],
+    "rfm_rank_metrics_workspace": [_i64, _i64, _i32, C.POINTER(_i64)],
+    "rfm_rank_metrics": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
     "rfm_pair_order_workspace": [_i64, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64)],
     "rfm_pair_order": [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
                        _vp, _vp],

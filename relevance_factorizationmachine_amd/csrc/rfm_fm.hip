@@ -816,6 +816,9 @@ struct FitCall {
   double eps;
   double *out_train_loss, *out_val_loss;  // [n_iters] each, or null: not asked for
   const EvalHook* hook;                   // or null
+  // rfm_fm_train_part: the iterations of the longer call this one is a piece of (0: n_iters).
+  // The loss forms are chosen for that length, so a fit's losses do not depend on the cut.
+  int64_t form_iters = 0;
 };
 
 // How a call computes its loss forwards: one decision for the whole call (the partials of a run
@@ -858,7 +861,8 @@ LossForms loss_forms(const FitCall& c) {
   // forward, staged through LDS).
   // (a call of a few iterations -- a fit() with a host evaluator trains one per call -- would only
   // add the run's launches)
-  f.scores_only = !f.sliced.ok && !f.merge_call && f.n_a + f.n_b > 0 && c.n_iters >= 4 &&
+  f.scores_only = !f.sliced.ok && !f.merge_call && f.n_a + f.n_b > 0 &&
+                  (c.form_iters > 0 ? c.form_iters : c.n_iters) >= 4 &&
                   env_int("RFM_DEFER_LOSS", 1) != 0;
   // Small batches: the train-loss forward of iteration it - 1 reads the parameters that step
   // it's forward reads -- it RIDES in that launch (extra workgroups that only score the previous
@@ -1057,6 +1061,23 @@ int32_t rfm_fm_train(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr,
     train_loop(FitCall{ctx, plan, d_indptr, d_indices, d_values, d_y, d_pscore, d_ids, batch, n_iters, d_w0,
                        d_w, d_V, lr, d_val_indptr, d_val_indices, d_val_values, d_val_y, d_val_pscore, n_val,
                        eps, d_out_train_loss, d_out_val_loss, nullptr});
+  });
+}
+
+int32_t rfm_fm_train_part(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr,
+                          const int32_t* d_indices, const double* d_values, const double* d_y,
+                          const double* d_pscore, const int32_t* d_ids, int64_t batch,
+                          int64_t n_iters, double* d_w0, double* d_w, double* d_V, double lr,
+                          const int64_t* d_val_indptr, const int32_t* d_val_indices,
+                          const double* d_val_values, const double* d_val_y,
+                          const double* d_val_pscore, int64_t n_val, double eps,
+                          double* d_out_train_loss, double* d_out_val_loss, int64_t call_iters) {
+  return guarded([&] {
+    RFM_REQUIRE(call_iters >= n_iters, "call_iters=%lld is less than n_iters=%lld", (long long)call_iters,
+                (long long)n_iters);
+    train_loop(FitCall{ctx, plan, d_indptr, d_indices, d_values, d_y, d_pscore, d_ids, batch, n_iters, d_w0,
+                       d_w, d_V, lr, d_val_indptr, d_val_indices, d_val_values, d_val_y, d_val_pscore, n_val,
+                       eps, d_out_train_loss, d_out_val_loss, nullptr, call_iters});
   });
 }
 

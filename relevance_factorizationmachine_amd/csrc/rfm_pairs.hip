@@ -766,6 +766,233 @@ struct IdCheck {
 LdsLimits g_topk_lds;
 LdsLimits g_order_lds;
 
+// rfm_pair_ranks / rfm_pair_ranks_n: `h_n_targets` null = the number of targets is read back from
+// the end of the device indptr (which synchronises); everything after that is the same code
+void pair_ranks_run(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t n_users,
+                    const int32_t* d_user_ids, int64_t n_sel_users, const double* d_B, const double* d_LI,
+                    int64_t n_items, int32_t n_factors, const double* d_c, const int64_t* d_excl_indptr,
+                    const int32_t* d_excl_items, const int64_t* d_tgt_indptr, const int32_t* d_tgt_items,
+                    const int64_t* h_n_targets, void* d_workspace, int32_t* d_out_ranks, double* d_out_scores,
+                    int32_t* d_out_candidates) {
+  require_pair_args(ctx, d_A, d_LU, n_users, n_sel_users, d_B, d_LI, n_items, n_factors, d_c);
+  RFM_REQUIRE(d_user_ids || n_sel_users == n_users, "without user ids every user is selected");
+  RFM_REQUIRE(!d_excl_indptr || d_excl_items, "exclusion lists without items");
+  if (n_sel_users == 0) return;
+  RFM_REQUIRE(d_tgt_indptr && d_out_candidates, "null target indptr or candidates output");
+  RFM_HIP_CHECK(hipSetDevice(ctx->device));
+  int64_t n_targets = 0;
+  if (h_n_targets) {
+    n_targets = *h_n_targets;
+    RFM_REQUIRE(n_targets >= 0 && n_targets < (int64_t(1) << 40), "n_targets=%lld", (long long)n_targets);
+  } else {
+    // the number of targets is the last entry of the indptr: the launches are sized by it
+    RFM_HIP_CHECK(hipMemcpyAsync(&n_targets, d_tgt_indptr + n_sel_users, 8, hipMemcpyDeviceToHost, ctx->stream));
+    RFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    RFM_REQUIRE(n_targets >= 0 && n_targets < (int64_t(1) << 40), "d_tgt_indptr ends at %lld targets", (long long)n_targets);
+  }
+  RFM_REQUIRE(n_targets == 0 || (d_tgt_items && d_workspace && d_out_ranks && d_out_scores),
+              "null target items, workspace or output");
+  IdCheck chk(ctx);
+  if (chk.flags()) {
+    if (d_excl_indptr) {
+      hipLaunchKernelGGL(excl_check_kernel, dim3(capped_grid(ctx, n_users, kPairBlock, 16, 1)),
+                         dim3(kPairBlock), 0, ctx->stream, d_excl_indptr, d_excl_items, n_users, n_items,
+                         chk.flags());
+      RFM_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(target_check_kernel, dim3(capped_grid(ctx, n_sel_users, kPairBlock, 16, 1)),
+                       dim3(kPairBlock), 0, ctx->stream, d_tgt_indptr, d_tgt_items, n_sel_users, n_items,
+                       n_targets, chk.flags());
+    RFM_HIP_CHECK(hipGetLastError());
+    chk.finish();  // (before any list is searched)
+    RFM_HIP_CHECK(hipMemsetAsync(chk.buf.p, 0, 4, ctx->stream));
+  }
+  const Split sp = topk_split(n_sel_users, n_items);
+  PairArgs a{};
+  a.A = d_A, a.LU = d_LU, a.user_ids = d_user_ids, a.n_users = n_users, a.n_sel = n_sel_users;
+  a.B = d_B, a.LI = d_LI, a.n_items = n_items, a.kpad = int(pad4(n_factors)), a.c = d_c;
+  a.excl_indptr = d_excl_indptr, a.excl_items = d_excl_items;
+  a.n_splits = sp.n_splits, a.tiles_per_split = sp.tiles_per_split;
+  a.tgt_indptr = d_tgt_indptr, a.tgt_items = d_tgt_items, a.n_targets = n_targets;
+  a.tgt_logit = static_cast<double*>(d_workspace);
+  a.out_ranks = d_out_ranks, a.out_candidates = d_out_candidates;
+  a.flags = chk.flags();
+  const dim3 grid((unsigned)sp.n_splits, (unsigned)((n_sel_users + kTile - 1) / kTile));
+  RFM_HIP_CHECK(hipMemsetAsync(d_out_candidates, 0, size_t(n_sel_users) * 4, ctx->stream));
+  if (n_targets > 0) {
+    // every byte 0xFF is a NaN: the logit of a target that no tile holds
+    RFM_HIP_CHECK(hipMemsetAsync(d_workspace, 0xFF, size_t(n_targets) * 8, ctx->stream));
+    RFM_HIP_CHECK(hipMemsetAsync(d_out_ranks, 0, size_t(n_targets) * 4, ctx->stream));
+    const size_t lds1 = rank_lds_bytes(false);  // (both passes stay under the 64 KiB a launch may ask for as it is)
+    hipLaunchKernelGGL(pair_tile_kernel<kTargetLogits>, grid, dim3(kPairBlock), lds1, ctx->stream, a);
+    RFM_HIP_CHECK(hipGetLastError());
+  }
+  const size_t lds2 = rank_lds_bytes(true);
+  hipLaunchKernelGGL(pair_tile_kernel<kRankCount>, grid, dim3(kPairBlock), lds2, ctx->stream, a);
+  RFM_HIP_CHECK(hipGetLastError());
+  if (n_targets > 0) {
+    hipLaunchKernelGGL(rank_finish_kernel, dim3(capped_grid(ctx, n_targets, kPairBlock, 16, 1)),
+                       dim3(kPairBlock), 0, ctx->stream, a.tgt_logit, n_targets, d_out_ranks, d_out_scores);
+    RFM_HIP_CHECK(hipGetLastError());
+  }
+  chk.finish();
+}
+
+// ---------------------------------------------------------------------------
+// Catalogue metrics from ranks: DCG@K, Recall@K, MAP@K, MRR and AUC of the
+// reference's calc_dcg_at_k / calc_recall_at_k / calc_average_precision_at_k
+// (utils/metrics.py:9-107) as they come out for the 0/1 vector of a user's candidates, from the
+// ranks of the user's positives alone (evaluate.CatalogueEvaluator.metrics states the sums).
+// One wavefront per selected user, two steps.  Step 1 puts the user's ranked positives in
+// ascending rank order by counting: the place of a positive is the number of the user's ranked
+// positives below it (equal ranks, which distinct targets never have, go by position), 64
+// positives against 64 at a time through v_readlane.  Step 2 walks the ordered ranks 64 at a
+// time; lane c owns output column c (DCG@K_c, Recall@K_c, MAP@K_c) and adds the terms one by one
+// in ascending rank order.  The sum of the ranks (AUC) is an integer.  A second launch takes the
+// mean of every column over the users in a fixed order: no float atomic anywhere.
+// ---------------------------------------------------------------------------
+constexpr int kMaxMetricK = 16;
+
+struct MetricArgs {
+  const int64_t* tgt_indptr;   // [n_sel + 1]
+  const int32_t* ranks;        // [n_targets], -1 = unranked
+  const int32_t* candidates;   // [n_sel]
+  const double* weights;       // [n_targets] or null (all ones): DCG only
+  int64_t n_sel, n_targets;
+  int n_K;
+  int64_t K[kMaxMetricK], max_K;
+  double* user_vals;           // [n_sel][3 n_K + 2]: DCG | Recall | MAP | MRR | AUC, NaN = not counted
+  int32_t* sorted_rank;        // [n_targets]: per user, the ranked positives' ranks ascending
+  int32_t* sorted_src;         // [n_targets]: ... and which of the user's targets each one is
+  int32_t* user_unranked;      // [n_sel]
+};
+
+inline int64_t metric_workspace_bytes(int64_t n_sel, int64_t n_targets, int n_K) {
+  return n_sel * (3 * n_K + 2) * 8 + n_targets * 8 + n_sel * 4;
+}
+
+__global__ __launch_bounds__(kPairBlock) void rank_metrics_users_kernel(MetricArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int64_t s = int64_t(blockIdx.x) * (kPairBlock / 64) + (threadIdx.x >> 6);
+  if (s >= a.n_sel) return;  // (the whole wavefront)
+  const int nK = a.n_K, cols = 3 * nK + 2;
+  double* out = a.user_vals + s * cols;
+  // never outside the arrays, whatever the indptr holds (RFM_CHECK_IDS reports a bad one)
+  const int64_t lo = min(max(a.tgt_indptr[s], int64_t(0)), a.n_targets);
+  const int64_t hi = min(max(a.tgt_indptr[s + 1], lo), a.n_targets);
+
+  int n_unranked = 0;
+  long long rank_sum = 0;
+  for (int64_t p0 = lo; p0 < hi; p0 += 64) {
+    const int64_t p = p0 + lane;
+    const int rp = p < hi ? a.ranks[p] : -1;
+    int below = 0;
+    for (int64_t q0 = lo; q0 < hi; q0 += 64) {
+      const int rq = q0 + lane < hi ? a.ranks[q0 + lane] : -1;
+      const int n = int(min(int64_t(64), hi - q0));
+      for (int b = 0; b < n; ++b) {
+        const int rb = lane_get(rq, b);
+        below += int(rb >= 0 && (rb < rp || (rb == rp && q0 + b < p)));
+      }
+    }
+    if (p < hi) {
+      if (rp >= 0) {  // below < the number of ranked positives <= hi - lo
+        a.sorted_rank[lo + below] = rp;
+        a.sorted_src[lo + below] = int(p - lo);
+        rank_sum += rp;
+      } else {
+        ++n_unranked;
+      }
+    }
+  }
+  for (int m = 32; m >= 1; m >>= 1) {
+    n_unranked += __shfl_xor(n_unranked, m, 64);
+    rank_sum += __shfl_xor(rank_sum, m, 64);
+  }
+  if (lane == 0) a.user_unranked[s] = n_unranked;
+  const int64_t P = (hi - lo) - n_unranked;
+  if (P == 0) {  // no ranked positive: the user is in no mean
+    if (lane < cols) out[lane] = NAN;
+    return;
+  }
+  __threadfence_block();  // the ordered ranks were written by other lanes of this wavefront
+
+  const int kind = lane / nK;  // 0 DCG, 1 Recall, 2 MAP; the lanes beyond add nothing
+  const int64_t my_K = kind < 3 ? a.K[lane - kind * nK] : 0;
+  double acc = 0.0;
+  int r_first = 0;
+  for (int64_t e0 = 0; e0 < P; e0 += 64) {
+    const int64_t e = e0 + lane;
+    const int re = e < P ? a.sorted_rank[lo + e] : 0x7fffffff;
+    if (e0 == 0) r_first = lane_get(re, 0);
+    if (int64_t(lane_get(re, 0)) >= a.max_K) break;  // ascending: no depth reaches the rest
+    double t_dcg = 0.0, t_map = 0.0;
+    if (e < P) {
+      const double v = a.weights ? a.weights[lo + a.sorted_src[lo + e]] : 1.0;
+      const double g = re == 0 ? 1.0 : 1.0 / log2(double(re) + 1.0);
+      t_dcg = v * g;
+      t_map = double(e + 1) / (double(re) + 1.0);
+    }
+    const int n = int(min(int64_t(64), P - e0));
+    for (int b = 0; b < n; ++b) {
+      const int r = lane_get(re, b);
+      const double d = lane_get(t_dcg, b), m = lane_get(t_map, b);
+      if (r < my_K) acc += kind == 0 ? d : kind == 1 ? 1.0 : m;
+    }
+  }
+  if (lane < 3 * nK) out[lane] = kind == 1 ? acc / double(P) : acc;
+  if (lane == 3 * nK) out[lane] = 1.0 / (double(r_first) + 1.0);
+  if (lane == 3 * nK + 1) {
+    const int64_t C = a.candidates[s];
+    out[lane] = C > P ? 1.0 - double(rank_sum - P * (P - 1) / 2) / (double(P) * (double(C) - double(P))) : NAN;
+  }
+}
+
+// Column blockIdx.x of the per-user table: the mean over the users whose value is not NaN (the
+// host's nan-mean; a user that is not counted has NaN everywhere, a user with C <= P in the AUC
+// column only), thread t adding users t, t + 256, ... and a fixed tree over the threads.
+// counts[0] = users counted (the MRR column's), counts[1] = the AUC column's, counts[2] = unranked
+// positives.
+__global__ __launch_bounds__(kPairBlock) void rank_metrics_mean_kernel(
+    const double* __restrict__ user_vals, const int32_t* __restrict__ user_unranked, int64_t n_sel,
+    int n_K, double* __restrict__ out, int64_t* __restrict__ counts) {
+  __shared__ double sv[kPairBlock];
+  __shared__ long long sn[kPairBlock], su[kPairBlock];
+  const int cols = 3 * n_K + 2, c = blockIdx.x, tid = threadIdx.x;
+  double v = 0.0;
+  long long n = 0, un = 0;
+  for (int64_t s = tid; s < n_sel; s += kPairBlock) {
+    const double x = user_vals[s * cols + c];
+    if (x == x) {
+      v += x;
+      ++n;
+    }
+    if (c == 3 * n_K) un += user_unranked[s];
+  }
+  sv[tid] = v, sn[tid] = n, su[tid] = un;
+  __syncthreads();
+  for (int w = kPairBlock / 2; w >= 1; w >>= 1) {
+    if (tid < w) sv[tid] += sv[tid + w], sn[tid] += sn[tid + w], su[tid] += su[tid + w];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    out[c] = sv[0] / double(sn[0]);  // no user -> NaN
+    if (c == 3 * n_K) counts[0] = sn[0], counts[2] = su[0];
+    if (c == 3 * n_K + 1) counts[1] = sn[0];
+  }
+}
+
+// RFM_CHECK_IDS=1: target indptr monotone from 0 up to n_targets
+__global__ __launch_bounds__(kPairBlock) void indptr_check_kernel(const int64_t* indptr, int64_t n_sel,
+                                                                 int64_t n_targets, int32_t* flags) {
+  for (int64_t s = int64_t(blockIdx.x) * kPairBlock + threadIdx.x; s < n_sel;
+       s += int64_t(gridDim.x) * kPairBlock) {
+    const int64_t lo = indptr[s], hi = indptr[s + 1];
+    if ((s == 0 && lo != 0) || hi < lo || hi > n_targets || (s == n_sel - 1 && hi != n_targets))
+      atomicOr(flags, 16);
+  }
+}
+
 }  // namespace
 }  // namespace rfm
 
@@ -886,63 +1113,77 @@ int32_t rfm_pair_ranks(rfm_ctx* ctx, const double* d_A, const double* d_LU, int6
                        const int64_t* d_tgt_indptr, const int32_t* d_tgt_items, void* d_workspace,
                        int32_t* d_out_ranks, double* d_out_scores, int32_t* d_out_candidates) {
   return guarded([&] {
-    require_pair_args(ctx, d_A, d_LU, n_users, n_sel_users, d_B, d_LI, n_items, n_factors, d_c);
-    RFM_REQUIRE(d_user_ids || n_sel_users == n_users, "without user ids every user is selected");
-    RFM_REQUIRE(!d_excl_indptr || d_excl_items, "exclusion lists without items");
-    if (n_sel_users == 0) return;
-    RFM_REQUIRE(d_tgt_indptr && d_out_candidates, "null target indptr or candidates output");
+    pair_ranks_run(ctx, d_A, d_LU, n_users, d_user_ids, n_sel_users, d_B, d_LI, n_items, n_factors, d_c,
+                   d_excl_indptr, d_excl_items, d_tgt_indptr, d_tgt_items, nullptr, d_workspace, d_out_ranks,
+                   d_out_scores, d_out_candidates);
+  });
+}
+
+int32_t rfm_pair_ranks_n(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t n_users,
+                         const int32_t* d_user_ids, int64_t n_sel_users, const double* d_B,
+                         const double* d_LI, int64_t n_items, int32_t n_factors, const double* d_c,
+                         const int64_t* d_excl_indptr, const int32_t* d_excl_items,
+                         const int64_t* d_tgt_indptr, const int32_t* d_tgt_items, int64_t n_targets,
+                         void* d_workspace, int32_t* d_out_ranks, double* d_out_scores,
+                         int32_t* d_out_candidates) {
+  return guarded([&] {
+    pair_ranks_run(ctx, d_A, d_LU, n_users, d_user_ids, n_sel_users, d_B, d_LI, n_items, n_factors, d_c,
+                   d_excl_indptr, d_excl_items, d_tgt_indptr, d_tgt_items, &n_targets, d_workspace, d_out_ranks,
+                   d_out_scores, d_out_candidates);
+  });
+}
+
+int32_t rfm_rank_metrics_workspace(int64_t n_sel_users, int64_t n_targets, int32_t n_K, int64_t* h_bytes) {
+  return guarded([&] {
+    RFM_REQUIRE(h_bytes, "null pointer");
+    RFM_REQUIRE(n_K >= 1 && n_K <= kMaxMetricK, "n_K=%d outside 1..%d", n_K, kMaxMetricK);
+    RFM_REQUIRE(n_sel_users >= 0 && n_targets >= 0, "negative n_sel_users or n_targets");
+    *h_bytes = std::max<int64_t>(16, metric_workspace_bytes(n_sel_users, n_targets, n_K));
+  });
+}
+
+int32_t rfm_rank_metrics(rfm_ctx* ctx, const int64_t* d_tgt_indptr, int64_t n_sel_users, int64_t n_targets,
+                         const int32_t* d_ranks, const int32_t* d_candidates, const double* d_weights,
+                         const int64_t* h_K, int32_t n_K, void* d_workspace, double* d_out,
+                         int64_t* d_out_counts) {
+  return guarded([&] {
+    RFM_REQUIRE(ctx && h_K && d_workspace && d_out && d_out_counts, "null pointer");
+    RFM_REQUIRE(n_K >= 1 && n_K <= kMaxMetricK, "n_K=%d outside 1..%d", n_K, kMaxMetricK);
+    RFM_REQUIRE(n_sel_users >= 0 && n_sel_users <= (int64_t(65535) * kTile), "n_sel_users=%lld outside 0..%lld",
+                (long long)n_sel_users, (long long)(int64_t(65535) * kTile));
+    RFM_REQUIRE(n_targets >= 0 && n_targets < (int64_t(1) << 40), "n_targets=%lld", (long long)n_targets);
+    RFM_REQUIRE(n_sel_users == 0 || (d_tgt_indptr && d_candidates), "null target indptr or candidates");
+    RFM_REQUIRE(n_targets == 0 || d_ranks, "null ranks");
+    MetricArgs a{};
+    a.n_K = n_K;
+    for (int c = 0; c < n_K; ++c) {
+      RFM_REQUIRE(h_K[c] >= 1, "K[%d]=%lld: a ranking depth must be at least 1", c, (long long)h_K[c]);
+      a.K[c] = h_K[c];
+      a.max_K = std::max(a.max_K, h_K[c]);
+    }
     RFM_HIP_CHECK(hipSetDevice(ctx->device));
-    // the number of targets is the last entry of the indptr: the launches are sized by it
-    int64_t n_targets = 0;
-    RFM_HIP_CHECK(hipMemcpyAsync(&n_targets, d_tgt_indptr + n_sel_users, 8, hipMemcpyDeviceToHost, ctx->stream));
-    RFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    RFM_REQUIRE(n_targets >= 0 && n_targets < (int64_t(1) << 40), "d_tgt_indptr ends at %lld targets", (long long)n_targets);
-    RFM_REQUIRE(n_targets == 0 || (d_tgt_items && d_workspace && d_out_ranks && d_out_scores),
-                "null target items, workspace or output");
     IdCheck chk(ctx);
-    if (chk.flags()) {
-      if (d_excl_indptr) {
-        hipLaunchKernelGGL(excl_check_kernel, dim3(capped_grid(ctx, n_users, kPairBlock, 16, 1)),
-                           dim3(kPairBlock), 0, ctx->stream, d_excl_indptr, d_excl_items, n_users, n_items,
-                           chk.flags());
-        RFM_HIP_CHECK(hipGetLastError());
-      }
-      hipLaunchKernelGGL(target_check_kernel, dim3(capped_grid(ctx, n_sel_users, kPairBlock, 16, 1)),
-                         dim3(kPairBlock), 0, ctx->stream, d_tgt_indptr, d_tgt_items, n_sel_users, n_items,
-                         n_targets, chk.flags());
+    if (chk.flags() && n_sel_users > 0) {
+      hipLaunchKernelGGL(indptr_check_kernel, dim3(capped_grid(ctx, n_sel_users, kPairBlock, 16, 1)),
+                         dim3(kPairBlock), 0, ctx->stream, d_tgt_indptr, n_sel_users, n_targets, chk.flags());
       RFM_HIP_CHECK(hipGetLastError());
-      chk.finish();  // (before any list is searched)
-      RFM_HIP_CHECK(hipMemsetAsync(chk.buf.p, 0, 4, ctx->stream));
+      chk.finish();
     }
-    const Split sp = topk_split(n_sel_users, n_items);
-    PairArgs a{};
-    a.A = d_A, a.LU = d_LU, a.user_ids = d_user_ids, a.n_users = n_users, a.n_sel = n_sel_users;
-    a.B = d_B, a.LI = d_LI, a.n_items = n_items, a.kpad = int(pad4(n_factors)), a.c = d_c;
-    a.excl_indptr = d_excl_indptr, a.excl_items = d_excl_items;
-    a.n_splits = sp.n_splits, a.tiles_per_split = sp.tiles_per_split;
-    a.tgt_indptr = d_tgt_indptr, a.tgt_items = d_tgt_items, a.n_targets = n_targets;
-    a.tgt_logit = static_cast<double*>(d_workspace);
-    a.out_ranks = d_out_ranks, a.out_candidates = d_out_candidates;
-    a.flags = chk.flags();
-    const dim3 grid((unsigned)sp.n_splits, (unsigned)((n_sel_users + kTile - 1) / kTile));
-    RFM_HIP_CHECK(hipMemsetAsync(d_out_candidates, 0, size_t(n_sel_users) * 4, ctx->stream));
-    if (n_targets > 0) {
-      // every byte 0xFF is a NaN: the logit of a target that no tile holds
-      RFM_HIP_CHECK(hipMemsetAsync(d_workspace, 0xFF, size_t(n_targets) * 8, ctx->stream));
-      RFM_HIP_CHECK(hipMemsetAsync(d_out_ranks, 0, size_t(n_targets) * 4, ctx->stream));
-      const size_t lds1 = rank_lds_bytes(false);  // (both passes stay under the 64 KiB a launch may ask for as it is)
-      hipLaunchKernelGGL(pair_tile_kernel<kTargetLogits>, grid, dim3(kPairBlock), lds1, ctx->stream, a);
+    a.tgt_indptr = d_tgt_indptr, a.ranks = d_ranks, a.candidates = d_candidates, a.weights = d_weights;
+    a.n_sel = n_sel_users, a.n_targets = n_targets;
+    const int cols = 3 * n_K + 2;
+    a.user_vals = static_cast<double*>(d_workspace);
+    a.sorted_rank = reinterpret_cast<int32_t*>(a.user_vals + n_sel_users * cols);
+    a.sorted_src = a.sorted_rank + n_targets;
+    a.user_unranked = a.sorted_src + n_targets;
+    if (n_sel_users > 0) {
+      const int64_t grid = (n_sel_users + kPairBlock / 64 - 1) / (kPairBlock / 64);
+      hipLaunchKernelGGL(rank_metrics_users_kernel, dim3((unsigned)grid), dim3(kPairBlock), 0, ctx->stream, a);
       RFM_HIP_CHECK(hipGetLastError());
     }
-    const size_t lds2 = rank_lds_bytes(true);
-    hipLaunchKernelGGL(pair_tile_kernel<kRankCount>, grid, dim3(kPairBlock), lds2, ctx->stream, a);
+    hipLaunchKernelGGL(rank_metrics_mean_kernel, dim3((unsigned)cols), dim3(kPairBlock), 0, ctx->stream,
+                       a.user_vals, a.user_unranked, n_sel_users, n_K, d_out, d_out_counts);
     RFM_HIP_CHECK(hipGetLastError());
-    if (n_targets > 0) {
-      hipLaunchKernelGGL(rank_finish_kernel, dim3(capped_grid(ctx, n_targets, kPairBlock, 16, 1)),
-                         dim3(kPairBlock), 0, ctx->stream, a.tgt_logit, n_targets, d_out_ranks, d_out_scores);
-      RFM_HIP_CHECK(hipGetLastError());
-    }
-    chk.finish();
   });
 }
 

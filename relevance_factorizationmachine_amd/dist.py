@@ -894,6 +894,12 @@ def fit_data_parallel(model, train: dict, val: dict, exchange: str = "auto", tra
     evaluator -- or an engine without ``run_eval`` -- is called after every iteration on every rank
     (the replicas are identical, so are the metrics).  ``engine_factory`` replaces the arithmetic
     (tests)."""
+    from .evaluate import CatalogueValEvaluator
+
+    if isinstance(getattr(model, "evaluator", None), CatalogueValEvaluator):
+        # (its users would have to be shared out over the ranks: DESIGN.md 8 N8, not built)
+        raise NotImplementedError("fit_data_parallel does not take a CatalogueValEvaluator: the catalogue "
+                                  "metrics per iteration are computed by the single-GPU fit() only")
     import torch.distributed as dist
 
     world, rank = dist.get_world_size(), dist.get_rank()

@@ -24,6 +24,7 @@ the device (``EvalLoop``).
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import Optional
 
 import numpy as np
@@ -632,3 +633,235 @@ class CatalogueExposure:
         args = (max(self.K), self.users, self.exclude)
         items, _, _ = model.rank_catalogue(*args) if sides is None else model.rank_catalogue(sides, *args)
         return self.metrics(items)
+
+
+class CatalogueValEvaluator:
+    """``CatalogueEvaluator``'s metrics per iteration of a ``fit()``: given as
+    ``evaluator=`` to ``FactorizationMachines`` / ``LogisticMatrixFactorization``, it fills
+    ``model.val_metrics`` with one column of the catalogue metrics -- the curve the reference's
+    hyper-parameter search takes ``argmax`` of -- computed on the device from the model's
+    parameters (side sums, ``rfm_pair_ranks_n``, ``rfm_rank_metrics``) with nothing coming back to
+    the host before the fit ends.  ``evaluate(model)`` is the same evaluation, one-shot.
+
+    ``positives``, ``n_items``, ``K`` (1 to 16 depths), ``used_metrics``, ``exclude``: as
+    ``CatalogueEvaluator`` takes them, a positive that ``exclude`` names is a ``ValueError`` here.
+    ``monitor``: ``(metric, k)``, the column that goes to ``val_metrics`` (``("MRR", None)``,
+    ``("AUC", None)`` for the two without a depth).  ``sides``: the model's ``recommend.Sides`` for
+    FM, None for MF.  ``pscores``: one propensity per positive, in input order; under the estimator
+    ``"IPS"`` DCG@K becomes the reference's ``calc_ips_of_dcg_at_k`` (``utils/metrics.py:53-80``:
+    every positive's gain divided by its propensity), every other estimator uses ones
+    (``utils/evaluate.py:223``) and every other metric has no propensity-weighted form in the
+    reference.  ``every``: evaluate after iteration e (0-based) when ``(e + 1) % every == 0``, and
+    after the last one.
+
+    After a fit: ``history = {metric: ndarray [n_epochs, width]}`` and ``unranked_history int64
+    [n_epochs]``, NaN / -1 in the rows of iterations that were not evaluated."""
+
+    METRICS = CatalogueEvaluator.METRICS
+    MAX_DEPTHS = 16
+
+    def __init__(self, positives, n_items: int, K, used_metrics, monitor, sides=None, exclude=None,
+                 pscores=None, every: int = 1):
+        from . import recommend as rec
+
+        base = CatalogueEvaluator(positives, n_items, K, used_metrics, exclude)  # (its checks)
+        self.n_items, self.K, self.used_metrics, self.exclude = base.n_items, base.K, base.used_metrics, exclude
+        if not 1 <= len(self.K) <= self.MAX_DEPTHS:
+            raise ValueError(f"K must hold 1 to {self.MAX_DEPTHS} depths, got {len(self.K)}")
+        users, items = (np.asarray(a).astype(np.int64) for a in positives)
+        if users.size and users.min() < 0:
+            raise ValueError("a user id is negative")
+        keys, first, inverse = np.unique(users * self.n_items + items, return_index=True, return_inverse=True)
+        self.users, self.items = keys // self.n_items, keys % self.n_items
+        self.pscores = None
+        if pscores is not None:
+            ps = np.asarray(pscores, dtype=np.float64)
+            if ps.shape != users.shape:
+                raise ValueError(f"{ps.shape[0] if ps.ndim == 1 else ps.shape} pscores for {users.shape[0]} positives")
+            if ps.size and not (np.isfinite(ps).all() and ps.min() > 0.0):
+                raise ValueError("pscores must be positive and finite")
+            self.pscores = ps[first]
+            if np.any(ps != self.pscores[inverse.reshape(-1)]):
+                raise ValueError("a repeated positive carries two different pscores")
+        try:
+            metric, depth = monitor
+        except (TypeError, ValueError):
+            raise ValueError("monitor must be (metric, k)") from None
+        if metric not in self.used_metrics:
+            raise ValueError(f"monitor: {metric!r} is not among used_metrics {self.used_metrics}")
+        if metric in ("MRR", "AUC"):
+            if depth is not None:
+                raise ValueError(f"monitor: {metric} has no depth, use ({metric!r}, None)")
+            self._monitor = (metric, 0)
+        else:
+            if isinstance(depth, (bool, np.bool_)) or not isinstance(depth, (int, np.integer)) or int(depth) not in self.K:
+                raise ValueError(f"monitor: depth {depth!r} is not among K {self.K}")
+            self._monitor = (metric, self.K.index(int(depth)))
+        self.monitor = (metric, depth)
+        if isinstance(every, (bool, np.bool_)) or not isinstance(every, (int, np.integer)) or every < 1:
+            raise ValueError(f"every must be an integer >= 1, got {every!r}")
+        self.every = int(every)
+        if sides is not None and not isinstance(sides, rec.Sides):
+            raise ValueError("sides must be a recommend.Sides (FM) or None (MF)")
+        self.sides = sides
+        self._excl = None
+        if exclude is not None:
+            n_rows = (len(exclude[0]) - 1) if isinstance(exclude, (tuple, list)) else exclude.shape[0]
+            self._excl = rec._host_exclusions(exclude, int(n_rows), self.n_items)
+            p = rec._first_excluded_pair(self.users, self.items, self._excl, self.n_items)
+            if p is not None:
+                raise ValueError(f"positive (user {int(self.users[p])}, item {int(self.items[p])}) is in the "
+                                 f"user's exclusion list: it has no rank")
+        # the targets as rfm_pair_ranks takes them: the keys are sorted by (user, item)
+        sel, counts = np.unique(self.users, return_counts=True)
+        self._sel = sel.astype(np.int32)
+        self._indptr = np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
+        self._h_K = np.ascontiguousarray(self.K, dtype=np.int64)
+        self.unranked = 0  # positives without a rank in the last evaluate()
+        self.history: dict = {}
+        self.unranked_history = np.zeros(0, dtype=np.int64)
+        self._dev = self._fit = None
+
+    # ------------------------------------------------------------------ layout of a result row
+    @property
+    def n_columns(self) -> int:
+        return 3 * len(self.K) + 2
+
+    def _split(self, table: np.ndarray) -> dict:
+        """``{metric: [rows, width]}`` of result rows ``[rows, 3 n_K + 2]`` (DCG | Recall | MAP | MRR | AUC)."""
+        n = len(self.K)
+        at = {"DCG": (0, n), "Recall": (n, 2 * n), "MAP": (2 * n, 3 * n), "MRR": (3 * n, 3 * n + 1),
+              "AUC": (3 * n + 1, 3 * n + 2)}
+        return {m: table[:, at[m][0]:at[m][1]].copy() for m in self.used_metrics}
+
+    # ------------------------------------------------------------------ device state
+    def _bind(self, model):
+        """The device-resident state for ``model`` (uploaded once, reused while the model's kind,
+        runtime and shapes stay the same)."""
+        from . import recommend as rec
+
+        torch = __import__("torch")
+        is_fm = hasattr(model, "n_features")
+        if is_fm:
+            if self.sides is None:
+                raise ValueError("a FactorizationMachines needs sides=: its recommend.Sides")
+            if self.sides.n_features != model.n_features:
+                raise ValueError(f"sides have {self.sides.n_features} columns, model has {model.n_features}")
+            n_users, n_items = self.sides.n_users, self.sides.n_items
+        else:
+            if self.sides is not None:
+                raise ValueError("a LogisticMatrixFactorization takes no sides: give sides=None")
+            if not hasattr(model, "b"):
+                raise AttributeError("'LogisticMatrixFactorization' object has no attribute 'b'")
+            n_users, n_items = int(model.n_users), int(model.n_items)
+        if n_items != self.n_items:
+            raise ValueError(f"the model ranks {n_items} items, the evaluator was given n_items={self.n_items}")
+        if self.users.size and self.users.max() >= n_users:
+            raise ValueError(f"a user id lies outside 0..{n_users - 1}")
+        if self._excl is not None and self._excl[0].shape[0] != n_users + 1:
+            raise ValueError(f"exclude lists {self._excl[0].shape[0] - 1} users, the model has {n_users}")
+        rt = model._rt
+        kf = int(model.n_factors)
+        key = (id(rt), is_fm, n_users, kf)
+        d = self._dev
+        if d is None or d["key"] != key:
+            n_sel, n_tgt = int(self._sel.shape[0]), int(self.items.shape[0])
+            i32 = lambda a: rt.upload(np.ascontiguousarray(a, dtype=np.int32) if len(a) else np.zeros(1, np.int32))  # noqa: E731
+            ws_m = C.c_int64(0)
+            _lib.check(rt.lib.rfm_rank_metrics_workspace(n_sel, n_tgt, len(self.K), C.byref(ws_m)))
+            d = {"key": key, "rt": rt, "n_users": n_users, "n_sel": n_sel, "n_tgt": n_tgt,
+                 "sel": i32(self._sel), "indptr": rt.upload(self._indptr), "items": i32(self.items),
+                 "weights": None if self.pscores is None else rt.upload(1.0 / self.pscores if n_tgt else np.ones(1)),
+                 "excl": None if self._excl is None else (rt.upload(self._excl[0]), i32(self._excl[1])),
+                 "ranks": rt.empty((max(n_tgt, 1),), torch.int32), "scores": rt.empty((max(n_tgt, 1),), torch.float64),
+                 "cand": rt.empty((max(n_sel, 1),), torch.int32),
+                 "ws_ranks": rt.empty((rec.ranks_workspace_bytes(n_sel, n_items, n_tgt),), torch.uint8),
+                 "ws_metrics": rt.empty((int(ws_m.value),), torch.uint8),
+                 "out": rt.empty((self.n_columns,), torch.float64), "counts": rt.empty((3,), torch.int64)}
+            kp = rec.pad4(kf)
+            if is_fm:
+                d["A"], d["LU"] = rt.empty((n_users, kp), torch.float64), rt.empty((n_users,), torch.float64)
+                d["B"], d["LI"] = rt.empty((n_items, kp), torch.float64), rt.empty((n_items,), torch.float64)
+            elif kp != kf:  # the tile's operands have a row stride of kpad: zero-padded copies of P, Q
+                d["A"] = torch.zeros((n_users, kp), dtype=torch.float64, device=rt.torch_device)
+                d["B"] = torch.zeros((n_items, kp), dtype=torch.float64, device=rt.torch_device)
+            self._dev = d
+        if not is_fm:
+            d["c"] = rt.upload(np.array([float(model.b)], dtype=np.float64))
+        return d
+
+    def _enqueue(self, model, d, weighted: bool, out_ptr: int, counts_ptr: int) -> None:
+        """One evaluation of the model's current parameters, enqueued: side sums (FM), the two rank
+        passes, the metrics; the result row goes to ``out_ptr``, the three counts to ``counts_ptr``."""
+        rt, kf = d["rt"], int(model.n_factors)
+        if hasattr(model, "n_features"):
+            for X, A, L in zip(self.sides.device(rt), (d["A"], d["B"]), (d["LU"], d["LI"])):
+                _lib.check(rt.lib.rfm_fm_side_sums(
+                    rt.ctx, X.indptr.data_ptr(), X.indices.data_ptr(), X.values.data_ptr(), X.shape[0],
+                    model.w.dev.data_ptr(), model.V.dev.data_ptr(), model.n_features, kf, A.data_ptr(), L.data_ptr()))
+            A, LU, B, LI, c = d["A"], d["LU"], d["B"], d["LI"], model.w0.dev
+        else:
+            A, B = model.P.dev, model.Q.dev
+            if "A" in d:  # (device-to-device, on the same stream)
+                d["A"][:, :kf].copy_(A)
+                d["B"][:, :kf].copy_(B)
+                A, B = d["A"], d["B"]
+            LU, LI, c = model.b_u.dev, model.b_i.dev, d["c"]
+        excl = d["excl"]
+        _lib.check(rt.lib.rfm_pair_ranks_n(
+            rt.ctx, A.data_ptr(), LU.data_ptr(), d["n_users"], d["sel"].data_ptr(), d["n_sel"], B.data_ptr(),
+            LI.data_ptr(), self.n_items, kf, c.data_ptr(), None if excl is None else excl[0].data_ptr(),
+            None if excl is None else excl[1].data_ptr(), d["indptr"].data_ptr(), d["items"].data_ptr(), d["n_tgt"],
+            d["ws_ranks"].data_ptr(), d["ranks"].data_ptr(), d["scores"].data_ptr(), d["cand"].data_ptr()))
+        _lib.check(rt.lib.rfm_rank_metrics(
+            rt.ctx, d["indptr"].data_ptr(), d["n_sel"], d["n_tgt"], d["ranks"].data_ptr(), d["cand"].data_ptr(),
+            d["weights"].data_ptr() if weighted and d["weights"] is not None else None, self._h_K.ctypes.data,
+            len(self.K), d["ws_metrics"].data_ptr(), out_ptr, counts_ptr))
+
+    # ------------------------------------------------------------------ one-shot
+    def evaluate(self, model, estimator: str = "Naive") -> dict:
+        """``{metric: [value per K]}`` (MRR, AUC: one value) of the model as it stands; only the
+        result row comes back from the device.  Sets ``unranked``."""
+        d = self._bind(model)
+        self._enqueue(model, d, estimator == "IPS", d["out"].data_ptr(), d["counts"].data_ptr())
+        d["rt"].sync()
+        self.unranked = int(d["counts"].cpu().numpy()[2])
+        return {m: v[0].tolist() for m, v in self._split(d["out"].cpu().numpy()[None, :]).items()}
+
+    # ------------------------------------------------------------------ inside fit()
+    def fit_begin(self, model, n_epochs: int) -> None:
+        """Called by ``fit()`` before its first iteration: the device table of ``n_epochs`` result
+        rows (NaN) and counts (-1)."""
+        torch = __import__("torch")
+        d = self._bind(model)
+        rt = d["rt"]
+        self._fit = {
+            "model": model, "d": d, "n_epochs": int(n_epochs), "weighted": model.estimator == "IPS",
+            "table": torch.full((int(n_epochs), self.n_columns), float("nan"), dtype=torch.float64, device=rt.torch_device),
+            "counts": torch.full((int(n_epochs), 3), -1, dtype=torch.int64, device=rt.torch_device)}
+
+    def fit_due(self, epoch: int) -> bool:
+        return (epoch + 1) % self.every == 0 or epoch == self._fit["n_epochs"] - 1
+
+    def fit_run_length(self, epoch: int) -> int:
+        """Iterations from ``epoch`` up to and including the next one that is evaluated."""
+        return min(self.every - epoch % self.every, self._fit["n_epochs"] - epoch)
+
+    def fit_enqueue(self, epoch: int) -> None:
+        """The evaluation after iteration ``epoch``, into that iteration's row of the device table."""
+        f = self._fit
+        self._enqueue(f["model"], f["d"], f["weighted"], f["table"].data_ptr() + epoch * self.n_columns * 8,
+                      f["counts"].data_ptr() + epoch * 24)
+
+    def fit_end(self) -> list:
+        """Called by ``fit()`` after its synchronisation: the one download; fills ``history`` /
+        ``unranked_history`` and returns the monitored column, one float per iteration."""
+        f, self._fit = self._fit, None
+        table, counts = f["table"].cpu().numpy(), f["counts"].cpu().numpy()
+        self.history = self._split(table)
+        self.unranked_history = counts[:, 2].astype(np.int64)
+        done = np.flatnonzero(self.unranked_history >= 0)
+        if done.size:
+            self.unranked = int(self.unranked_history[done[-1]])
+        metric, col = self._monitor
+        return [float(v) for v in self.history[metric][:, col]]

@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _lib
 from .base import LOSS_EPS, PointwiseBaseRecommender
-from .evaluate import EvalLoop, device_frame
+from .evaluate import CatalogueValEvaluator, EvalLoop, device_frame
 from .optimizer import DeviceSGD
 from .runtime import BatchIdStream, CsrCache, DeviceCSR, Runtime
 
@@ -234,7 +234,7 @@ class FactorizationMachines(PointwiseBaseRecommender):
 
         chunk = {"first": 0, "ids": None}
 
-        def run(first: int, count: int, loop=None) -> None:
+        def run(first: int, count: int, loop=None, part_of: int = 0) -> None:
             ids_ptr = chunk["ids"].data_ptr() + (first - chunk["first"]) * self.batch_size * 4
             args = (rt.ctx, plan.handle, tr.indptr.data_ptr(), tr.indices.data_ptr(), tr.values.data_ptr(),
                     y.data_ptr(), p.data_ptr(), ids_ptr, self.batch_size, count,
@@ -242,6 +242,11 @@ class FactorizationMachines(PointwiseBaseRecommender):
                     va.indptr.data_ptr(), va.indices.data_ptr(), va.values.data_ptr(),
                     vy.data_ptr(), vp.data_ptr(), va.shape[0], LOSS_EPS,
                     tl.data_ptr() + first * 8, vl.data_ptr() + first * 8 if has_val else None)
+            if part_of:
+                # a piece of the call of `part_of` iterations that a fit without an evaluator makes:
+                # the same loss forms, hence the same losses bit for bit
+                _lib.check(rt.lib.rfm_fm_train_part(*args, part_of))
+                return
             if loop is None:
                 _lib.check(rt.lib.rfm_fm_train(*args))
                 return
@@ -255,7 +260,12 @@ class FactorizationMachines(PointwiseBaseRecommender):
 
         try:
             frame = loop = ev = ev_X = None
-            if self.evaluator is not None:
+            # catalogue metrics per iteration: the evaluator is given the model,
+            # not scores of a feature matrix
+            cat = self.evaluator if isinstance(self.evaluator, CatalogueValEvaluator) else None
+            if cat is not None:
+                cat.fit_begin(self, self.n_epochs)
+            elif self.evaluator is not None:
                 ev_X = self.evaluator.features[self.model_name]
                 frame = (device_frame(rt, self.evaluator, self.estimator, ev_X.shape[0])
                          if self.device_evaluator else None)
@@ -275,6 +285,16 @@ class FactorizationMachines(PointwiseBaseRecommender):
                 count = dev_ids.shape[0]
                 if self.evaluator is None:
                     run(first, count)
+                elif cat is not None:
+                    # runs of iterations that end at the next evaluation point, the evaluation
+                    # enqueued behind each on the same stream
+                    at = first
+                    while at < first + count:
+                        n = min(first + count - at, cat.fit_run_length(at))
+                        run(at, n, part_of=count)
+                        at += n
+                        if cat.fit_due(at - 1):
+                            cat.fit_enqueue(at - 1)
                 elif frame is None:
                     # an evaluator of unknown kind is a host callback: one iteration per enqueue
                     for epoch in range(first, first + count):
@@ -298,6 +318,8 @@ class FactorizationMachines(PointwiseBaseRecommender):
                 self.evaluator_host_users = loop.host_users
                 loop.leave_scores(self.n_epochs - 1)
             rt.sync()
+            if cat is not None:
+                self.val_metrics.extend(cat.fit_end())
         finally:
             rt.sync()
             # (the registration ends with the fit: the plan may outlive this split's device copy)

@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _lib
 from .base import LOSS_EPS, PointwiseBaseRecommender
-from .evaluate import EvalLoop, device_frame
+from .evaluate import CatalogueValEvaluator, EvalLoop, device_frame
 from .optimizer import DeviceSGD
 from .runtime import BatchIdStream, Runtime, mf_cache_capacity, mf_schedule_ex
 
@@ -207,7 +207,12 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
         cache_cap = mf_cache_capacity(self.n_factors)
 
         ev_frame = ev_pairs = ev_loop = None
-        if self.evaluator is not None:
+        # catalogue metrics per iteration: the evaluator is given the model, not
+        # scores of a list of pairs
+        cat = self.evaluator if isinstance(self.evaluator, CatalogueValEvaluator) else None
+        if cat is not None:
+            cat.fit_begin(self, self.n_epochs)
+        elif self.evaluator is not None:
             ev_X = self.evaluator.features[self.model_name]
             if self.device_evaluator:
                 ev_frame = device_frame(rt, self.evaluator, self.estimator, int(np.asarray(ev_X).shape[0]))
@@ -232,6 +237,9 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
                     rt.ctx, ev_pairs.users.data_ptr(), ev_pairs.items.data_ptr(), None, ev_pairs.n,
                     *params, b, self.n_factors, ev_loop.slot(epoch).data_ptr()))
                 ev_loop.done(epoch)
+            elif cat is not None:
+                if cat.fit_due(epoch):
+                    cat.fit_enqueue(epoch)  # (behind the iteration, on the same stream)
             elif self.evaluator is not None:
                 y_scores = self.predict(self.evaluator.features[self.model_name])
                 self.val_metrics.append(
@@ -275,6 +283,8 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
                 worker.join(timeout=5.0)
         rt.sync()
         self._keep_ids = []
+        if cat is not None:
+            self.val_metrics.extend(cat.fit_end())
         if ev_frame is not None:
             self.val_metrics.extend(ev_loop.finish(self.n_epochs))
             self.evaluator_host_calls = ev_loop.host_calls
