@@ -40,6 +40,9 @@ constexpr int kChunk = 32;       // factors staged in LDS at a time
 constexpr int kLd = 66;
 constexpr int kOperandDoubles = 2 * kChunk * kLd;  // A and B chunk
 constexpr int kLogitLd = kTile + 1;                // top-K epilogue: the tile's logits [user][item]
+// LDS doubles shared by the operand chunks and, after the product, the tile's logits
+constexpr int kUnion = kOperandDoubles > kTile * kLogitLd ? kOperandDoubles : kTile * kLogitLd;
+constexpr int64_t kMaxSel = int64_t(65535) * kTile;  // selected users of a launch: grid y
 constexpr int kMaxTopK = 64;
 constexpr int kTargetWorkgroups = 1024;  // top-K: item splits are chosen to reach about this many
 // rank counting: a workgroup sums the counts of the first kRankAccum targets of its 64 users in
@@ -153,6 +156,22 @@ __device__ inline bool excluded(const int32_t* __restrict__ excl, int64_t lo, in
   return false;
 }
 
+// Selected user s of a launch whose first is selected user `first` -> the user's id (user_of; for a
+// user known to be in the table: its row) and -> row of the user table, or -1 for an id outside it,
+// which `report` raises in `flags` if given (RFM_CHECK_IDS: bit 1).
+__device__ inline int64_t user_of(const int32_t* user_ids, int64_t s, int64_t first) {
+  return user_ids ? int64_t(user_ids[s]) : s + first;
+}
+__device__ inline int64_t user_row(const int32_t* user_ids, int64_t s, int64_t first, int64_t n_users,
+                                   int32_t* flags = nullptr, bool report = false) {
+  int64_t u = user_of(user_ids, s, first);
+  if (u < 0 || u >= n_users) {
+    if (flags && report) atomicOr(flags, 2);
+    u = -1;
+  }
+  return u;
+}
+
 struct PairArgs {
   const double* A;         // [n_users][kpad]
   const double* LU;        // [n_users]
@@ -202,7 +221,6 @@ __global__ __launch_bounds__(kPairBlock) void pair_tile_kernel(PairArgs a) {
   double* As = lds;                    // [kChunk][kLd]
   double* Bs = lds + kChunk * kLd;     // [kChunk][kLd]
   double* T = lds;                     // TOPK epilogue, after the product: [kTile][kLogitLd]
-  constexpr int kUnion = kOperandDoubles > kTile * kLogitLd ? kOperandDoubles : kTile * kLogitLd;
   double* list_l = lds + kUnion;                                        // [kTile][K]
   int32_t* list_i = reinterpret_cast<int32_t*>(list_l + kTile * (TOPK ? a.K : 0));
   int32_t* rank_acc = reinterpret_cast<int32_t*>(lds + kUnion);  // kRankCount: [kRankAccum]
@@ -212,6 +230,7 @@ __global__ __launch_bounds__(kPairBlock) void pair_tile_kernel(PairArgs a) {
   const int wm = wave >> 1, wn = wave & 1;
   const int64_t u0 = int64_t(blockIdx.y) * kTile;
   const int kpad = a.kpad;
+  const int64_t first = MODE == kLogits ? a.sel_first : 0;  // (compile time: the others take no add)
 
   // staging: thread -> factor tid & 31 of rows (tid >> 5) + 8 j: 256-byte runs of a row
   const int sk = tid & (kChunk - 1), sr = tid >> 5;
@@ -221,13 +240,7 @@ __global__ __launch_bounds__(kPairBlock) void pair_tile_kernel(PairArgs a) {
   for (int j = 0; j < 8; ++j) {
     const int64_t s = u0 + sr + 8 * j;
     int64_t u = -1;
-    if (s < a.n_sel) {
-      u = a.user_ids ? int64_t(a.user_ids[s]) : s + (MODE == kLogits ? a.sel_first : 0);
-      if (u < 0 || u >= a.n_users) {
-        if (a.flags && sk == 0) atomicOr(a.flags, 2);
-        u = -1;
-      }
-    }
+    if (s < a.n_sel) u = user_row(a.user_ids, s, first, a.n_users, a.flags, sk == 0);
     user_ok[j] = u >= 0;
     a_row[j] = a.A + (u >= 0 ? u : 0) * int64_t(kpad);
   }
@@ -298,10 +311,7 @@ __global__ __launch_bounds__(kPairBlock) void pair_tile_kernel(PairArgs a) {
         const int ul = wm * 32 + x * 16 + (lane >> 4) + 4 * reg;
         const int64_t s = u0 + ul;
         int64_t u = -1;
-        if (s < a.n_sel) {
-          u = a.user_ids ? int64_t(a.user_ids[s]) : s + (MODE == kLogits ? a.sel_first : 0);
-          if (u < 0 || u >= a.n_users) u = -1;
-        }
+        if (s < a.n_sel) u = user_row(a.user_ids, s, first, a.n_users);
         const double lu = u >= 0 ? a.LU[u] : NAN;  // a user id outside the table scores NaN
 #pragma unroll
         for (int y = 0; y < 2; ++y) {
@@ -353,7 +363,7 @@ __global__ __launch_bounds__(kPairBlock) void pair_tile_kernel(PairArgs a) {
         double cl = row[lane];
         if (a.excl_indptr) {
           if (cl == cl) {
-            const int64_t u = a.user_ids ? int64_t(a.user_ids[s]) : s;  // (in range: its logits are not NaN)
+            const int64_t u = user_of(a.user_ids, s, first);  // (in range: its logits are not NaN)
             if (excluded(a.excl_items, a.excl_indptr[u], a.excl_indptr[u + 1], int(i0) + lane)) cl = NAN;
           }
           row[lane] = cl;  // the wavefront's own row: its LDS accesses are executed in order
@@ -396,7 +406,7 @@ __global__ __launch_bounds__(kPairBlock) void pair_tile_kernel(PairArgs a) {
       bool pass = cl == cl && better(cl, ci, ll[a.K - 1], li[a.K - 1]);
       if (__ballot(pass) == 0) continue;
       if (pass && a.excl_indptr) {
-        const int64_t u = a.user_ids ? int64_t(a.user_ids[s]) : s;  // (in range: its logits are not NaN)
+        const int64_t u = user_of(a.user_ids, s, first);  // (in range: its logits are not NaN)
         pass = !excluded(a.excl_items, a.excl_indptr[u], a.excl_indptr[u + 1], ci);
       }
       unsigned long long mask = __ballot(pass);
@@ -492,7 +502,7 @@ __global__ __launch_bounds__(kPairBlock) void excl_check_kernel(const int64_t* i
 }
 
 // RFM_CHECK_IDS=1: target indptr monotone from 0 up to n_targets, every list ascending (repeats
-// allowed) inside 0 .. n_items-1
+// allowed) inside 0 .. n_items-1; null items = the indptr only
 __global__ __launch_bounds__(kPairBlock) void target_check_kernel(const int64_t* indptr,
                                                                  const int32_t* items, int64_t n_sel,
                                                                  int64_t n_items, int64_t n_targets,
@@ -504,7 +514,7 @@ __global__ __launch_bounds__(kPairBlock) void target_check_kernel(const int64_t*
       atomicOr(flags, 16);
       continue;
     }
-    for (int64_t e = lo; e < hi; ++e)
+    for (int64_t e = lo; items && e < hi; ++e)
       if (items[e] < 0 || items[e] >= n_items || (e > lo && items[e] < items[e - 1])) {
         atomicOr(flags, 32);
         break;
@@ -645,8 +655,8 @@ __global__ __launch_bounds__(kPairBlock) void order_rows_kernel(OrderArgs a) {
   }
   int64_t elo = 0, ehi = 0;
   if (a.excl_indptr) {
-    const int64_t u = a.user_ids ? int64_t(a.user_ids[row]) : a.sel_first + row;
-    if (u >= 0 && u < a.n_users) elo = a.excl_indptr[u], ehi = a.excl_indptr[u + 1];  // (else every logit is NaN)
+    const int64_t u = user_row(a.user_ids, row, a.sel_first, a.n_users);
+    if (u >= 0) elo = a.excl_indptr[u], ehi = a.excl_indptr[u + 1];  // (else every logit is NaN)
   }
   for (int e = tid; e < P; e += kPairBlock) {
     bl[e] = -INFINITY;
@@ -717,26 +727,33 @@ Split topk_split(int64_t n_sel, int64_t n_items) {
 }
 
 size_t rank_lds_bytes(bool count) {
-  const int kUnion = std::max(kOperandDoubles, kTile * kLogitLd);
   return size_t(kUnion) * 8 + (count ? size_t(kRankAccum + kTile) * 4 : 0);
 }
 
 size_t topk_lds_bytes(int K) {
-  const int kUnion = std::max(kOperandDoubles, kTile * kLogitLd);
   return size_t(kUnion) * 8 + size_t(kTile) * K * 12;
 }
 
-void require_pair_args(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t n_users,
-                       int64_t n_sel, const double* d_B, const double* d_LI, int64_t n_items,
-                       int32_t n_factors, const double* d_c) {
+// The checks and the fields that every rfm_pair_* entry shares; the entry adds its own fields.
+PairArgs pair_args(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t n_users,
+                   const int32_t* d_user_ids, int64_t n_sel, const double* d_B, const double* d_LI,
+                   int64_t n_items, int32_t n_factors, const double* d_c, const int64_t* d_excl_indptr,
+                   const int32_t* d_excl_items) {
   RFM_REQUIRE(ctx && d_A && d_LU && d_B && d_LI && d_c, "null pointer");
   RFM_REQUIRE(n_factors >= 1 && n_factors <= RFM_MAX_FACTORS, "n_factors=%d unsupported (1..%d)",
               n_factors, RFM_MAX_FACTORS);
   RFM_REQUIRE(n_users >= 1 && n_items >= 1, "empty user or item table");
-  RFM_REQUIRE(n_sel >= 0 && n_sel <= (int64_t(65535) * kTile), "n_sel_users=%lld outside 0..%lld",
-              (long long)n_sel, (long long)(int64_t(65535) * kTile));
+  RFM_REQUIRE(n_sel >= 0 && n_sel <= kMaxSel, "n_sel_users=%lld outside 0..%lld", (long long)n_sel,
+              (long long)kMaxSel);
   RFM_REQUIRE(n_items < (int64_t(1) << 31) - kTile, "n_items=%lld does not fit int32 item ids",
               (long long)n_items);
+  RFM_REQUIRE(d_user_ids || n_sel == n_users, "without user ids every user is selected");
+  RFM_REQUIRE(!d_excl_indptr || d_excl_items, "exclusion lists without items");
+  PairArgs a{};
+  a.A = d_A, a.LU = d_LU, a.user_ids = d_user_ids, a.n_users = n_users, a.n_sel = n_sel;
+  a.B = d_B, a.LI = d_LI, a.n_items = n_items, a.kpad = int(pad4(n_factors)), a.c = d_c;
+  a.excl_indptr = d_excl_indptr, a.excl_items = d_excl_items;
+  return a;
 }
 
 // flags of a checked call (RFM_CHECK_IDS=1): read back after a synchronisation
@@ -749,17 +766,36 @@ struct IdCheck {
     RFM_HIP_CHECK(hipMemsetAsync(buf.p, 0, 4, ctx->stream));
   }
   int32_t* flags() const { return buf.as<int32_t>(); }
+  // Reports what the launches so far have flagged and arms the flags again.
   void finish() {
     if (!buf.p) return;
     int32_t h = 0;
     RFM_HIP_CHECK(hipMemcpyAsync(&h, buf.p, 4, hipMemcpyDeviceToHost, ctx->stream));
     RFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    RFM_HIP_CHECK(hipMemsetAsync(buf.p, 0, 4, ctx->stream));
     RFM_REQUIRE(!(h & 1), "a column index lies outside 0..n_features-1");
     RFM_REQUIRE(!(h & 2), "a user id lies outside 0..n_users-1");
     RFM_REQUIRE(!(h & 4), "the exclusion indptr is not monotone from 0");
     RFM_REQUIRE(!(h & 8), "an exclusion list is not strictly ascending inside 0..n_items-1");
     RFM_REQUIRE(!(h & 16), "the target indptr is not monotone from 0 to n_targets");
     RFM_REQUIRE(!(h & 32), "a target list is not ascending inside 0..n_items-1");
+  }
+  // The flags pointer of a pair launch and, before any of its lists is searched, their check.
+  void begin(PairArgs& a) {
+    a.flags = flags();
+    if (!a.flags || !a.excl_indptr) return;
+    hipLaunchKernelGGL(excl_check_kernel, dim3(capped_grid(ctx, a.n_users, kPairBlock, 16, 1)), dim3(kPairBlock),
+                       0, ctx->stream, a.excl_indptr, a.excl_items, a.n_users, a.n_items, a.flags);
+    RFM_HIP_CHECK(hipGetLastError());
+    finish();
+  }
+  void check_targets(const int64_t* d_indptr, const int32_t* d_items, int64_t n_sel, int64_t n_items,
+                     int64_t n_targets) {
+    if (!flags()) return;
+    hipLaunchKernelGGL(target_check_kernel, dim3(capped_grid(ctx, n_sel, kPairBlock, 16, 1)), dim3(kPairBlock), 0,
+                       ctx->stream, d_indptr, d_items, n_sel, n_items, n_targets, flags());
+    RFM_HIP_CHECK(hipGetLastError());
+    finish();
   }
 };
 
@@ -774,9 +810,8 @@ void pair_ranks_run(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t
                     const int32_t* d_excl_items, const int64_t* d_tgt_indptr, const int32_t* d_tgt_items,
                     const int64_t* h_n_targets, void* d_workspace, int32_t* d_out_ranks, double* d_out_scores,
                     int32_t* d_out_candidates) {
-  require_pair_args(ctx, d_A, d_LU, n_users, n_sel_users, d_B, d_LI, n_items, n_factors, d_c);
-  RFM_REQUIRE(d_user_ids || n_sel_users == n_users, "without user ids every user is selected");
-  RFM_REQUIRE(!d_excl_indptr || d_excl_items, "exclusion lists without items");
+  PairArgs a = pair_args(ctx, d_A, d_LU, n_users, d_user_ids, n_sel_users, d_B, d_LI, n_items, n_factors, d_c,
+                         d_excl_indptr, d_excl_items);
   if (n_sel_users == 0) return;
   RFM_REQUIRE(d_tgt_indptr && d_out_candidates, "null target indptr or candidates output");
   RFM_HIP_CHECK(hipSetDevice(ctx->device));
@@ -793,30 +828,13 @@ void pair_ranks_run(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t
   RFM_REQUIRE(n_targets == 0 || (d_tgt_items && d_workspace && d_out_ranks && d_out_scores),
               "null target items, workspace or output");
   IdCheck chk(ctx);
-  if (chk.flags()) {
-    if (d_excl_indptr) {
-      hipLaunchKernelGGL(excl_check_kernel, dim3(capped_grid(ctx, n_users, kPairBlock, 16, 1)),
-                         dim3(kPairBlock), 0, ctx->stream, d_excl_indptr, d_excl_items, n_users, n_items,
-                         chk.flags());
-      RFM_HIP_CHECK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(target_check_kernel, dim3(capped_grid(ctx, n_sel_users, kPairBlock, 16, 1)),
-                       dim3(kPairBlock), 0, ctx->stream, d_tgt_indptr, d_tgt_items, n_sel_users, n_items,
-                       n_targets, chk.flags());
-    RFM_HIP_CHECK(hipGetLastError());
-    chk.finish();  // (before any list is searched)
-    RFM_HIP_CHECK(hipMemsetAsync(chk.buf.p, 0, 4, ctx->stream));
-  }
+  chk.begin(a);
+  chk.check_targets(d_tgt_indptr, d_tgt_items, n_sel_users, n_items, n_targets);
   const Split sp = topk_split(n_sel_users, n_items);
-  PairArgs a{};
-  a.A = d_A, a.LU = d_LU, a.user_ids = d_user_ids, a.n_users = n_users, a.n_sel = n_sel_users;
-  a.B = d_B, a.LI = d_LI, a.n_items = n_items, a.kpad = int(pad4(n_factors)), a.c = d_c;
-  a.excl_indptr = d_excl_indptr, a.excl_items = d_excl_items;
   a.n_splits = sp.n_splits, a.tiles_per_split = sp.tiles_per_split;
   a.tgt_indptr = d_tgt_indptr, a.tgt_items = d_tgt_items, a.n_targets = n_targets;
   a.tgt_logit = static_cast<double*>(d_workspace);
   a.out_ranks = d_out_ranks, a.out_candidates = d_out_candidates;
-  a.flags = chk.flags();
   const dim3 grid((unsigned)sp.n_splits, (unsigned)((n_sel_users + kTile - 1) / kTile));
   RFM_HIP_CHECK(hipMemsetAsync(d_out_candidates, 0, size_t(n_sel_users) * 4, ctx->stream));
   if (n_targets > 0) {
@@ -982,17 +1000,6 @@ __global__ __launch_bounds__(kPairBlock) void rank_metrics_mean_kernel(
   }
 }
 
-// RFM_CHECK_IDS=1: target indptr monotone from 0 up to n_targets
-__global__ __launch_bounds__(kPairBlock) void indptr_check_kernel(const int64_t* indptr, int64_t n_sel,
-                                                                 int64_t n_targets, int32_t* flags) {
-  for (int64_t s = int64_t(blockIdx.x) * kPairBlock + threadIdx.x; s < n_sel;
-       s += int64_t(gridDim.x) * kPairBlock) {
-    const int64_t lo = indptr[s], hi = indptr[s + 1];
-    if ((s == 0 && lo != 0) || hi < lo || hi > n_targets || (s == n_sel - 1 && hi != n_targets))
-      atomicOr(flags, 16);
-  }
-}
-
 }  // namespace
 }  // namespace rfm
 
@@ -1026,16 +1033,14 @@ int32_t rfm_pair_scores(rfm_ctx* ctx, const double* d_A, const double* d_LU, int
                         const double* d_LI, int64_t n_items, int32_t n_factors, const double* d_c,
                         double* d_out) {
   return guarded([&] {
-    require_pair_args(ctx, d_A, d_LU, n_users, n_sel_users, d_B, d_LI, n_items, n_factors, d_c);
-    RFM_REQUIRE(d_user_ids || n_sel_users == n_users, "without user ids every user is selected");
+    PairArgs a = pair_args(ctx, d_A, d_LU, n_users, d_user_ids, n_sel_users, d_B, d_LI, n_items, n_factors, d_c,
+                           nullptr, nullptr);
     if (n_sel_users == 0) return;
     RFM_REQUIRE(d_out, "null output");
     RFM_HIP_CHECK(hipSetDevice(ctx->device));
     IdCheck chk(ctx);
-    PairArgs a{};
-    a.A = d_A, a.LU = d_LU, a.user_ids = d_user_ids, a.n_users = n_users, a.n_sel = n_sel_users;
-    a.B = d_B, a.LI = d_LI, a.n_items = n_items, a.kpad = int(pad4(n_factors)), a.c = d_c;
-    a.out = d_out, a.flags = chk.flags();
+    chk.begin(a);
+    a.out = d_out;
     const dim3 grid((unsigned)((n_items + kTile - 1) / kTile), (unsigned)((n_sel_users + kTile - 1) / kTile));
     hipLaunchKernelGGL(pair_tile_kernel<kScores>, grid, dim3(kPairBlock), size_t(kOperandDoubles) * 8,
                        ctx->stream, a);
@@ -1061,30 +1066,17 @@ int32_t rfm_pair_topk(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64
                       void* d_workspace, int32_t* d_out_items, double* d_out_scores) {
   return guarded([&] {
     RFM_REQUIRE(k >= 1 && k <= kMaxTopK, "k=%d outside 1..%d", k, kMaxTopK);
-    require_pair_args(ctx, d_A, d_LU, n_users, n_sel_users, d_B, d_LI, n_items, n_factors, d_c);
-    RFM_REQUIRE(d_user_ids || n_sel_users == n_users, "without user ids every user is selected");
-    RFM_REQUIRE(!d_excl_indptr || d_excl_items, "exclusion lists without items");
+    PairArgs a = pair_args(ctx, d_A, d_LU, n_users, d_user_ids, n_sel_users, d_B, d_LI, n_items, n_factors, d_c,
+                           d_excl_indptr, d_excl_items);
     if (n_sel_users == 0) return;
     RFM_REQUIRE(d_workspace && d_out_items && d_out_scores, "null workspace or output");
     RFM_HIP_CHECK(hipSetDevice(ctx->device));
     IdCheck chk(ctx);
-    if (chk.flags() && d_excl_indptr) {
-      hipLaunchKernelGGL(excl_check_kernel, dim3(capped_grid(ctx, n_users, kPairBlock, 16, 1)),
-                         dim3(kPairBlock), 0, ctx->stream, d_excl_indptr, d_excl_items, n_users, n_items,
-                         chk.flags());
-      RFM_HIP_CHECK(hipGetLastError());
-      chk.finish();  // (before any list is searched)
-      RFM_HIP_CHECK(hipMemsetAsync(chk.buf.p, 0, 4, ctx->stream));
-    }
+    chk.begin(a);
     const Split sp = topk_split(n_sel_users, n_items);
-    PairArgs a{};
-    a.A = d_A, a.LU = d_LU, a.user_ids = d_user_ids, a.n_users = n_users, a.n_sel = n_sel_users;
-    a.B = d_B, a.LI = d_LI, a.n_items = n_items, a.kpad = int(pad4(n_factors)), a.c = d_c;
-    a.excl_indptr = d_excl_indptr, a.excl_items = d_excl_items;
     a.K = k, a.n_splits = sp.n_splits, a.tiles_per_split = sp.tiles_per_split;
     a.ws_logit = static_cast<double*>(d_workspace);
     a.ws_item = reinterpret_cast<int32_t*>(a.ws_logit + int64_t(sp.n_splits) * n_sel_users * k);
-    a.flags = chk.flags();
     const size_t lds = topk_lds_bytes(k);
     allow_dynamic_lds(ctx, reinterpret_cast<const void*>(&pair_tile_kernel<kTopK>), lds, g_topk_lds);
     const dim3 grid((unsigned)sp.n_splits, (unsigned)((n_sel_users + kTile - 1) / kTile));
@@ -1149,8 +1141,8 @@ int32_t rfm_rank_metrics(rfm_ctx* ctx, const int64_t* d_tgt_indptr, int64_t n_se
   return guarded([&] {
     RFM_REQUIRE(ctx && h_K && d_workspace && d_out && d_out_counts, "null pointer");
     RFM_REQUIRE(n_K >= 1 && n_K <= kMaxMetricK, "n_K=%d outside 1..%d", n_K, kMaxMetricK);
-    RFM_REQUIRE(n_sel_users >= 0 && n_sel_users <= (int64_t(65535) * kTile), "n_sel_users=%lld outside 0..%lld",
-                (long long)n_sel_users, (long long)(int64_t(65535) * kTile));
+    RFM_REQUIRE(n_sel_users >= 0 && n_sel_users <= kMaxSel, "n_sel_users=%lld outside 0..%lld",
+                (long long)n_sel_users, (long long)kMaxSel);
     RFM_REQUIRE(n_targets >= 0 && n_targets < (int64_t(1) << 40), "n_targets=%lld", (long long)n_targets);
     RFM_REQUIRE(n_sel_users == 0 || (d_tgt_indptr && d_candidates), "null target indptr or candidates");
     RFM_REQUIRE(n_targets == 0 || d_ranks, "null ranks");
@@ -1163,12 +1155,7 @@ int32_t rfm_rank_metrics(rfm_ctx* ctx, const int64_t* d_tgt_indptr, int64_t n_se
     }
     RFM_HIP_CHECK(hipSetDevice(ctx->device));
     IdCheck chk(ctx);
-    if (chk.flags() && n_sel_users > 0) {
-      hipLaunchKernelGGL(indptr_check_kernel, dim3(capped_grid(ctx, n_sel_users, kPairBlock, 16, 1)),
-                         dim3(kPairBlock), 0, ctx->stream, d_tgt_indptr, n_sel_users, n_targets, chk.flags());
-      RFM_HIP_CHECK(hipGetLastError());
-      chk.finish();
-    }
+    if (n_sel_users > 0) chk.check_targets(d_tgt_indptr, nullptr, n_sel_users, 0, n_targets);
     a.tgt_indptr = d_tgt_indptr, a.ranks = d_ranks, a.candidates = d_candidates, a.weights = d_weights;
     a.n_sel = n_sel_users, a.n_targets = n_targets;
     const int cols = 3 * n_K + 2;
@@ -1207,9 +1194,8 @@ int32_t rfm_pair_order(rfm_ctx* ctx, const double* d_A, const double* d_LU, int6
                        double* d_out_scores, int32_t* d_out_n_ranked) {
   return guarded([&] {
     RFM_REQUIRE(depth >= 1, "depth=%lld: the ranking depth must be at least 1", (long long)depth);
-    require_pair_args(ctx, d_A, d_LU, n_users, n_sel_users, d_B, d_LI, n_items, n_factors, d_c);
-    RFM_REQUIRE(d_user_ids || n_sel_users == n_users, "without user ids every user is selected");
-    RFM_REQUIRE(!d_excl_indptr || d_excl_items, "exclusion lists without items");
+    PairArgs all = pair_args(ctx, d_A, d_LU, n_users, d_user_ids, n_sel_users, d_B, d_LI, n_items, n_factors, d_c,
+                             d_excl_indptr, d_excl_items);
     if (n_sel_users == 0) return;
     RFM_REQUIRE(d_workspace && d_out_items && d_out_scores && d_out_n_ranked, "null workspace or output");
     const int64_t block_rows = workspace_bytes / order_row_bytes(n_items) / kTile * kTile;
@@ -1217,14 +1203,7 @@ int32_t rfm_pair_order(rfm_ctx* ctx, const double* d_A, const double* d_LU, int6
                 (long long)workspace_bytes, kTile, (long long)(kTile * order_row_bytes(n_items)));
     RFM_HIP_CHECK(hipSetDevice(ctx->device));
     IdCheck chk(ctx);
-    if (chk.flags() && d_excl_indptr) {
-      hipLaunchKernelGGL(excl_check_kernel, dim3(capped_grid(ctx, n_users, kPairBlock, 16, 1)),
-                         dim3(kPairBlock), 0, ctx->stream, d_excl_indptr, d_excl_items, n_users, n_items,
-                         chk.flags());
-      RFM_HIP_CHECK(hipGetLastError());
-      chk.finish();  // (before any list is searched)
-      RFM_HIP_CHECK(hipMemsetAsync(chk.buf.p, 0, 4, ctx->stream));
-    }
+    chk.begin(all);
     // ranks beyond the catalogue are padding whatever the logits: they take no page of their own
     const int64_t n_ranks = std::min(depth, n_items);
     const int P = order_list_len(n_ranks);
@@ -1235,11 +1214,9 @@ int32_t rfm_pair_order(rfm_ctx* ctx, const double* d_A, const double* d_LU, int6
     int32_t* ws_cut_i = reinterpret_cast<int32_t*>(ws_cut_l + block_rows);
     for (int64_t first = 0; first < n_sel_users; first += block_rows) {
       const int64_t rows = std::min(block_rows, n_sel_users - first);
-      PairArgs a{};
-      a.A = d_A, a.LU = d_LU, a.user_ids = d_user_ids ? d_user_ids + first : nullptr, a.n_users = n_users;
-      a.n_sel = rows, a.sel_first = first;
-      a.B = d_B, a.LI = d_LI, a.n_items = n_items, a.kpad = int(pad4(n_factors)), a.c = d_c;
-      a.out = ws_logits, a.flags = chk.flags();
+      PairArgs a = all;  // this block of the selected users
+      a.user_ids = d_user_ids ? d_user_ids + first : nullptr, a.n_sel = rows, a.sel_first = first;
+      a.out = ws_logits;
       const dim3 grid((unsigned)((n_items + kTile - 1) / kTile), (unsigned)((rows + kTile - 1) / kTile));
       hipLaunchKernelGGL(pair_tile_kernel<kLogits>, grid, dim3(kPairBlock), size_t(kOperandDoubles) * 8,
                          ctx->stream, a);

@@ -30,6 +30,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
+from . import recommend as rec
 from .runtime import Runtime
 
 _COLUMNS = ("user", "label", "pscore", "ones_pscore")
@@ -662,8 +663,6 @@ class CatalogueValEvaluator:
 
     def __init__(self, positives, n_items: int, K, used_metrics, monitor, sides=None, exclude=None,
                  pscores=None, every: int = 1):
-        from . import recommend as rec
-
         base = CatalogueEvaluator(positives, n_items, K, used_metrics, exclude)  # (its checks)
         self.n_items, self.K, self.used_metrics, self.exclude = base.n_items, base.K, base.used_metrics, exclude
         if not 1 <= len(self.K) <= self.MAX_DEPTHS:
@@ -694,11 +693,11 @@ class CatalogueValEvaluator:
                 raise ValueError(f"monitor: {metric} has no depth, use ({metric!r}, None)")
             self._monitor = (metric, 0)
         else:
-            if isinstance(depth, (bool, np.bool_)) or not isinstance(depth, (int, np.integer)) or int(depth) not in self.K:
+            if not rec.is_int(depth) or int(depth) not in self.K:
                 raise ValueError(f"monitor: depth {depth!r} is not among K {self.K}")
             self._monitor = (metric, self.K.index(int(depth)))
         self.monitor = (metric, depth)
-        if isinstance(every, (bool, np.bool_)) or not isinstance(every, (int, np.integer)) or every < 1:
+        if not rec.is_int(every) or every < 1:
             raise ValueError(f"every must be an integer >= 1, got {every!r}")
         self.every = int(every)
         if sides is not None and not isinstance(sides, rec.Sides):
@@ -713,9 +712,7 @@ class CatalogueValEvaluator:
                 raise ValueError(f"positive (user {int(self.users[p])}, item {int(self.items[p])}) is in the "
                                  f"user's exclusion list: it has no rank")
         # the targets as rfm_pair_ranks takes them: the keys are sorted by (user, item)
-        sel, counts = np.unique(self.users, return_counts=True)
-        self._sel = sel.astype(np.int32)
-        self._indptr = np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
+        self._sel, self._indptr = rec.users_indptr(self.users)
         self._h_K = np.ascontiguousarray(self.K, dtype=np.int64)
         self.unranked = 0  # positives without a rank in the last evaluate()
         self.history: dict = {}
@@ -738,22 +735,13 @@ class CatalogueValEvaluator:
     def _bind(self, model):
         """The device-resident state for ``model`` (uploaded once, reused while the model's kind,
         runtime and shapes stay the same)."""
-        from . import recommend as rec
-
         torch = __import__("torch")
         is_fm = hasattr(model, "n_features")
-        if is_fm:
-            if self.sides is None:
-                raise ValueError("a FactorizationMachines needs sides=: its recommend.Sides")
-            if self.sides.n_features != model.n_features:
-                raise ValueError(f"sides have {self.sides.n_features} columns, model has {model.n_features}")
-            n_users, n_items = self.sides.n_users, self.sides.n_items
-        else:
-            if self.sides is not None:
-                raise ValueError("a LogisticMatrixFactorization takes no sides: give sides=None")
-            if not hasattr(model, "b"):
-                raise AttributeError("'LogisticMatrixFactorization' object has no attribute 'b'")
-            n_users, n_items = int(model.n_users), int(model.n_items)
+        if is_fm and self.sides is None:
+            raise ValueError("a FactorizationMachines needs sides=: its recommend.Sides")
+        if not is_fm and self.sides is not None:
+            raise ValueError("a LogisticMatrixFactorization takes no sides: give sides=None")
+        n_users, n_items = rec.catalogue_shape(model, self.sides)
         if n_items != self.n_items:
             raise ValueError(f"the model ranks {n_items} items, the evaluator was given n_items={self.n_items}")
         if self.users.size and self.users.max() >= n_users:
@@ -761,58 +749,33 @@ class CatalogueValEvaluator:
         if self._excl is not None and self._excl[0].shape[0] != n_users + 1:
             raise ValueError(f"exclude lists {self._excl[0].shape[0] - 1} users, the model has {n_users}")
         rt = model._rt
-        kf = int(model.n_factors)
-        key = (id(rt), is_fm, n_users, kf)
+        key = (id(rt), is_fm, n_users, int(model.n_factors))
         d = self._dev
         if d is None or d["key"] != key:
             n_sel, n_tgt = int(self._sel.shape[0]), int(self.items.shape[0])
-            i32 = lambda a: rt.upload(np.ascontiguousarray(a, dtype=np.int32) if len(a) else np.zeros(1, np.int32))  # noqa: E731
             ws_m = C.c_int64(0)
             _lib.check(rt.lib.rfm_rank_metrics_workspace(n_sel, n_tgt, len(self.K), C.byref(ws_m)))
-            d = {"key": key, "rt": rt, "n_users": n_users, "n_sel": n_sel, "n_tgt": n_tgt,
-                 "sel": i32(self._sel), "indptr": rt.upload(self._indptr), "items": i32(self.items),
+            d = {"key": key, "rt": rt, "n_sel": n_sel, "n_tgt": n_tgt, "ops": None,  # (the operands: the first _enqueue)
+                 "sel": rt.upload(self._sel if n_sel else np.zeros(1, np.int32)), "indptr": rt.upload(self._indptr),
+                 "items": rt.upload(self.items.astype(np.int32) if n_tgt else np.zeros(1, np.int32)),
                  "weights": None if self.pscores is None else rt.upload(1.0 / self.pscores if n_tgt else np.ones(1)),
-                 "excl": None if self._excl is None else (rt.upload(self._excl[0]), i32(self._excl[1])),
+                 "excl": rec._exclusions(rt, self._excl),
                  "ranks": rt.empty((max(n_tgt, 1),), torch.int32), "scores": rt.empty((max(n_tgt, 1),), torch.float64),
                  "cand": rt.empty((max(n_sel, 1),), torch.int32),
                  "ws_ranks": rt.empty((rec.ranks_workspace_bytes(n_sel, n_items, n_tgt),), torch.uint8),
                  "ws_metrics": rt.empty((int(ws_m.value),), torch.uint8),
                  "out": rt.empty((self.n_columns,), torch.float64), "counts": rt.empty((3,), torch.int64)}
-            kp = rec.pad4(kf)
-            if is_fm:
-                d["A"], d["LU"] = rt.empty((n_users, kp), torch.float64), rt.empty((n_users,), torch.float64)
-                d["B"], d["LI"] = rt.empty((n_items, kp), torch.float64), rt.empty((n_items,), torch.float64)
-            elif kp != kf:  # the tile's operands have a row stride of kpad: zero-padded copies of P, Q
-                d["A"] = torch.zeros((n_users, kp), dtype=torch.float64, device=rt.torch_device)
-                d["B"] = torch.zeros((n_items, kp), dtype=torch.float64, device=rt.torch_device)
             self._dev = d
-        if not is_fm:
-            d["c"] = rt.upload(np.array([float(model.b)], dtype=np.float64))
         return d
 
     def _enqueue(self, model, d, weighted: bool, out_ptr: int, counts_ptr: int) -> None:
-        """One evaluation of the model's current parameters, enqueued: side sums (FM), the two rank
-        passes, the metrics; the result row goes to ``out_ptr``, the three counts to ``counts_ptr``."""
-        rt, kf = d["rt"], int(model.n_factors)
-        if hasattr(model, "n_features"):
-            for X, A, L in zip(self.sides.device(rt), (d["A"], d["B"]), (d["LU"], d["LI"])):
-                _lib.check(rt.lib.rfm_fm_side_sums(
-                    rt.ctx, X.indptr.data_ptr(), X.indices.data_ptr(), X.values.data_ptr(), X.shape[0],
-                    model.w.dev.data_ptr(), model.V.dev.data_ptr(), model.n_features, kf, A.data_ptr(), L.data_ptr()))
-            A, LU, B, LI, c = d["A"], d["LU"], d["B"], d["LI"], model.w0.dev
-        else:
-            A, B = model.P.dev, model.Q.dev
-            if "A" in d:  # (device-to-device, on the same stream)
-                d["A"][:, :kf].copy_(A)
-                d["B"][:, :kf].copy_(B)
-                A, B = d["A"], d["B"]
-            LU, LI, c = model.b_u.dev, model.b_i.dev, d["c"]
-        excl = d["excl"]
-        _lib.check(rt.lib.rfm_pair_ranks_n(
-            rt.ctx, A.data_ptr(), LU.data_ptr(), d["n_users"], d["sel"].data_ptr(), d["n_sel"], B.data_ptr(),
-            LI.data_ptr(), self.n_items, kf, c.data_ptr(), None if excl is None else excl[0].data_ptr(),
-            None if excl is None else excl[1].data_ptr(), d["indptr"].data_ptr(), d["items"].data_ptr(), d["n_tgt"],
-            d["ws_ranks"].data_ptr(), d["ranks"].data_ptr(), d["scores"].data_ptr(), d["cand"].data_ptr()))
+        """One evaluation of the model's current parameters, enqueued: the operands refreshed in
+        place (FM: side sums), the two rank passes, the metrics; the result row goes to ``out_ptr``,
+        the three counts to ``counts_ptr``."""
+        rt = d["rt"]
+        d["ops"] = rec.operands(model, self.sides, into=d["ops"])
+        rec.enqueue_ranks(d["ops"], d["sel"], d["n_sel"], d["excl"], d["indptr"], d["items"], d["n_tgt"],
+                          d["ws_ranks"], d["ranks"], d["scores"], d["cand"])
         _lib.check(rt.lib.rfm_rank_metrics(
             rt.ctx, d["indptr"].data_ptr(), d["n_sel"], d["n_tgt"], d["ranks"].data_ptr(), d["cand"].data_ptr(),
             d["weights"].data_ptr() if weighted and d["weights"] is not None else None, self._h_K.ctypes.data,

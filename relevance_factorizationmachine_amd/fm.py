@@ -354,8 +354,7 @@ class FactorizationMachines(PointwiseBaseRecommender):
         sums + one dense product (recommend.py; src/fm.py:114-133 restated)."""
         from . import recommend as rec
 
-        A, LU, B, LI, c = rec.fm_operands(self, sides)
-        return rec.score_pairs(self._rt, A, LU, B, LI, c, self.n_factors, users)
+        return rec.score_pairs(*rec.operands(self, sides), users)
 
     def recommend(self, sides, k: int, users=None, exclude=None):
         """The ``k`` (1..64) best items of the catalogue per user: ``(items int32 [n, k], scores
@@ -363,8 +362,7 @@ class FactorizationMachines(PointwiseBaseRecommender):
         ``predict()`` gives them; ``exclude``: items never to return, CSR by user id."""
         from . import recommend as rec
 
-        A, LU, B, LI, c = rec.fm_operands(self, sides)
-        return rec.topk(self._rt, A, LU, B, LI, c, self.n_factors, k, users, exclude)
+        return rec.topk(*rec.operands(self, sides), k, users, exclude)
 
     def rank_items(self, sides, users, items, exclude=None):
         """Where the pairs ``(users[n], items[n])`` land in their users' ranking of the whole
@@ -373,8 +371,7 @@ class FactorizationMachines(PointwiseBaseRecommender):
         ``candidates`` (logit not NaN, not in ``exclude``), at any depth (recommend.py)."""
         from . import recommend as rec
 
-        A, LU, B, LI, c = rec.fm_operands(self, sides)
-        return rec.rank_items(self._rt, A, LU, B, LI, c, self.n_factors, users, items, exclude)
+        return rec.rank_items(*rec.operands(self, sides), users, items, exclude)
 
     def rank_catalogue(self, sides, depth: int, users=None, exclude=None):
         """Every user's ranking of the catalogue of ``sides`` down to ``depth`` (any integer >= 1;
@@ -383,5 +380,4 @@ class FactorizationMachines(PointwiseBaseRecommender):
         item -1 / score NaN; the first 64 columns are ``recommend(k=64)``'s (recommend.py)."""
         from . import recommend as rec
 
-        A, LU, B, LI, c = rec.fm_operands(self, sides)
-        return rec.rank_catalogue(self._rt, A, LU, B, LI, c, self.n_factors, depth, users, exclude)
+        return rec.rank_catalogue(*rec.operands(self, sides), depth, users, exclude)

@@ -322,16 +322,14 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
         matrix: one dense product (recommend.py; src/mf.py:136-170 restated)."""
         from . import recommend as rec
 
-        P, bu, Q, bi, c = rec.mf_operands(self)
-        return rec.score_pairs(self._rt, P, bu, Q, bi, c, self.n_factors, users)
+        return rec.score_pairs(*rec.operands(self), users)
 
     def recommend(self, k: int, users=None, exclude=None):
         """The ``k`` (1..64) best items per user: ``(items int32 [n, k], scores float64 [n, k])``,
         ranked by logit (ties: higher item index first); ``exclude``: CSR by user id."""
         from . import recommend as rec
 
-        P, bu, Q, bi, c = rec.mf_operands(self)
-        return rec.topk(self._rt, P, bu, Q, bi, c, self.n_factors, k, users, exclude)
+        return rec.topk(*rec.operands(self), k, users, exclude)
 
     def rank_items(self, users, items, exclude=None):
         """Where the pairs ``(users[n], items[n])`` land in their users' ranking of all items:
@@ -339,8 +337,7 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
         0-based under ``recommend()``'s order, at any depth (recommend.py)."""
         from . import recommend as rec
 
-        P, bu, Q, bi, c = rec.mf_operands(self)
-        return rec.rank_items(self._rt, P, bu, Q, bi, c, self.n_factors, users, items, exclude)
+        return rec.rank_items(*rec.operands(self), users, items, exclude)
 
     def rank_catalogue(self, depth: int, users=None, exclude=None):
         """Every user's ranking of all items down to ``depth`` (any integer >= 1): ``(items int32
@@ -348,5 +345,4 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
         order, short rows padded with item -1 / score NaN (recommend.py)."""
         from . import recommend as rec
 
-        P, bu, Q, bi, c = rec.mf_operands(self)
-        return rec.rank_catalogue(self._rt, P, bu, Q, bi, c, self.n_factors, depth, users, exclude)
+        return rec.rank_catalogue(*rec.operands(self), depth, users, exclude)

@@ -22,7 +22,7 @@ given (user, item) pairs in the user's ranking of the whole catalogue, at any de
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -88,52 +88,135 @@ class Sides:
         return self._dev
 
 
-def side_sums(rt: Runtime, X: DeviceCSR, w, V, n_features: int, n_factors: int):
-    """``(A [n, kpad], L [n])`` of a side matrix for the parameters ``w``, ``V`` (device tensors)."""
+class Operands(NamedTuple):
+    """The dense problem ``logit(u,i) = c + LU[u] + LI[i] + A[u,:].B[i,:]`` on the device, ``A
+    [n_users, kpad]``, ``B [n_items, kpad]``, ``c`` a device scalar: what every ``rfm_pair_*`` entry
+    takes, in the order it takes it (``operands`` builds one)."""
+    rt: Runtime
+    A: object
+    LU: object
+    B: object
+    LI: object
+    c: object
+    n_factors: int
+
+    @property
+    def n_users(self) -> int:
+        return int(self.A.shape[0])
+
+    @property
+    def n_items(self) -> int:
+        return int(self.B.shape[0])
+
+    def pair_args(self, ids, n_sel: int) -> tuple:
+        """The leading arguments of a ``rfm_pair_*`` call; ``ids``: device user ids, None = every user."""
+        return (self.rt.ctx, self.A.data_ptr(), self.LU.data_ptr(), self.n_users,
+                None if ids is None else ids.data_ptr(), n_sel, self.B.data_ptr(), self.LI.data_ptr(),
+                self.n_items, self.n_factors, self.c.data_ptr())
+
+
+def excl_args(excl) -> tuple:
+    """The two exclusion pointers of a ``rfm_pair_*`` call for device lists ``excl`` (or None)."""
+    return (None, None) if excl is None else (excl[0].data_ptr(), excl[1].data_ptr())
+
+
+def side_sums(rt: Runtime, X: DeviceCSR, w, V, n_features: int, n_factors: int, A=None, L=None):
+    """``(A [n, kpad], L [n])`` of a side matrix for ``w``, ``V`` (device tensors), into ``A``, ``L`` if given."""
     torch = __import__("torch")
-    n = X.shape[0]
-    A = rt.empty((n, pad4(n_factors)), torch.float64)
-    L = rt.empty((n,), torch.float64)
+    n, kp = X.shape[0], pad4(n_factors)
+    if A is None:
+        A, L = rt.empty((n, kp), torch.float64), rt.empty((n,), torch.float64)
+    elif tuple(A.shape) != (n, kp) or tuple(L.shape) != (n,):
+        raise ValueError(f"side sums of {n} rows x {kp} into buffers of {tuple(A.shape)}, {tuple(L.shape)}")
     _lib.check(rt.lib.rfm_fm_side_sums(rt.ctx, X.indptr.data_ptr(), X.indices.data_ptr(), X.values.data_ptr(), n,
                                        w.data_ptr(), V.data_ptr(), n_features, n_factors, A.data_ptr(),
                                        L.data_ptr()))
     return A, L
 
 
-def padded(rt: Runtime, M, n_factors: int):
-    """A dense ``[n, k]`` device matrix as ``[n, kpad]`` (itself when ``k % 4 == 0``)."""
+def padded(rt: Runtime, M, n_factors: int, out=None):
+    """A dense ``[n, k]`` device matrix as ``[n, kpad]`` (itself when ``k % 4 == 0``), into ``out`` if
+    given: an earlier result, whose columns past k stay zero."""
     torch = __import__("torch")
     kp = pad4(n_factors)
     if kp == n_factors:
         return M
-    out = torch.zeros((M.shape[0], kp), dtype=torch.float64, device=rt.torch_device)
+    if out is None:
+        out = torch.zeros((M.shape[0], kp), dtype=torch.float64, device=rt.torch_device)
     out[:, :n_factors] = M
     return out
+
+
+def catalogue_shape(model, sides=None) -> Tuple[int, int]:
+    """``(n_users, n_items)`` of a model's catalogue, after the checks that need no device."""
+    if hasattr(model, "n_features"):
+        if not isinstance(sides, Sides):
+            raise TypeError("sides must be a recommend.Sides")
+        if sides.n_features != model.n_features:
+            raise ValueError(f"sides have {sides.n_features} columns, model has {model.n_features}")
+        return sides.n_users, sides.n_items
+    if not hasattr(model, "b"):
+        # the reference's global bias exists only after fit() (src/mf.py:84)
+        raise AttributeError("'LogisticMatrixFactorization' object has no attribute 'b'")
+    return int(model.n_users), int(model.n_items)
+
+
+def operands(model, sides=None, into: Optional[Operands] = None) -> Operands:
+    """The ``Operands`` of a model as it stands.  FM (``sides``: its ``Sides``): two side-sum
+    launches per call.  MF: ``P, b_u, Q, b_i``, the uploaded ``b``, zero-padded copies of P, Q when
+    ``n_factors % 4``.  ``into``: an earlier result for the same shapes, whose buffers are refreshed
+    in place on the runtime's stream -- no allocation, no host wait."""
+    catalogue_shape(model, sides)
+    rt, kf = model._rt, int(model.n_factors)
+    _, A, LU, B, LI, c, _ = into or (None,) * 7
+    if hasattr(model, "n_features"):
+        XU, XI = sides.device(rt)
+        A, LU = side_sums(rt, XU, model.w.dev, model.V.dev, model.n_features, kf, A, LU)
+        B, LI = side_sums(rt, XI, model.w.dev, model.V.dev, model.n_features, kf, B, LI)
+        return Operands(rt, A, LU, B, LI, model.w0.dev, kf)
+    b = float(model.b)
+    if c is None:
+        c = rt.upload(np.array([b], dtype=np.float64))
+    elif c.holds != b:  # (a fit does not change b: no launch between its iterations)
+        c.fill_(b)
+    c.holds = b
+    return Operands(rt, padded(rt, model.P.dev, kf, A), model.b_u.dev, padded(rt, model.Q.dev, kf, B),
+                    model.b_i.dev, c, kf)
+
+
+def is_int(v) -> bool:  # an integer argument: a Python or NumPy integer, not a bool
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def _id_array(a, what: str, n: int) -> np.ndarray:
+    """``a`` (``what``: "users" / "items") as int64; ``ValueError`` unless 1-d integers inside 0 .. n-1."""
+    a = np.asarray(a)
+    if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+        raise ValueError(f"{what} must be a 1-d array of integer ids")
+    if a.size and (a.min() < 0 or a.max() >= n):
+        raise ValueError(f"{'a user' if what == 'users' else 'an item'} id lies outside 0..{n - 1}")
+    return a.astype(np.int64)
 
 
 def _users(rt: Runtime, users, n_users: int):
     if users is None:
         return None, n_users
-    ids = np.asarray(users)
-    if ids.ndim != 1 or (ids.size and not np.issubdtype(ids.dtype, np.integer)):
-        raise ValueError("users must be a 1-d array of user ids")
-    if ids.size and (ids.min() < 0 or ids.max() >= n_users):
-        raise ValueError(f"a user id lies outside 0..{n_users - 1}")
-    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    ids = _id_array(users, "users", n_users).astype(np.int32)
     return rt.upload(ids if ids.size else np.zeros(1, np.int32)), int(ids.shape[0])
 
 
-def _exclusions(rt: Runtime, exclude, n_users: int, n_items: int):
-    """``exclude``: scipy sparse matrix (row = user id, stored columns = items) or
-    ``(indptr, indices)``; device ``(indptr int64, items int32)`` with ascending items per user."""
-    if exclude is None:
+def _exclusions(rt: Runtime, excl):
+    """The checked host lists ``excl`` (``_host_exclusions``) on the device, or None."""
+    if excl is None:
         return None
-    indptr, items = _host_exclusions(exclude, n_users, n_items)
-    return rt.upload(indptr), rt.upload(items if items.size else np.zeros(1, np.int32))
+    return rt.upload(excl[0]), rt.upload(excl[1] if excl[1].size else np.zeros(1, np.int32))
 
 
 def _host_exclusions(exclude, n_users: int, n_items: int):
-    """The checked host arrays ``(indptr int64, items int32)`` of ``exclude``."""
+    """``exclude``: scipy sparse matrix (row = user id, stored columns = items), ``(indptr, indices)``
+    or None; the checked host arrays ``(indptr int64, items int32)``, items ascending per user, or None."""
+    if exclude is None:
+        return None
     if isinstance(exclude, (tuple, list)):
         indptr, items = (np.asarray(a) for a in exclude)
     else:
@@ -162,12 +245,10 @@ def _host_exclusions(exclude, n_users: int, n_items: int):
 def score_pairs(rt: Runtime, A, LU, B, LI, c, n_factors: int, users=None) -> np.ndarray:
     """Probabilities of every (selected user, item) pair, ``float64 [n_sel, n_items]``."""
     torch = __import__("torch")
-    n_users, n_items = int(A.shape[0]), int(B.shape[0])
-    ids, n_sel = _users(rt, users, n_users)
-    out = rt.empty((n_sel, n_items), torch.float64)
-    _lib.check(rt.lib.rfm_pair_scores(rt.ctx, A.data_ptr(), LU.data_ptr(), n_users,
-                                      None if ids is None else ids.data_ptr(), n_sel, B.data_ptr(),
-                                      LI.data_ptr(), n_items, n_factors, c.data_ptr(), out.data_ptr()))
+    ops = Operands(rt, A, LU, B, LI, c, n_factors)
+    ids, n_sel = _users(rt, users, ops.n_users)
+    out = rt.empty((n_sel, ops.n_items), torch.float64)
+    _lib.check(rt.lib.rfm_pair_scores(*ops.pair_args(ids, n_sel), out.data_ptr()))
     rt.sync()
     return out.cpu().numpy()
 
@@ -177,20 +258,16 @@ def topk(rt: Runtime, A, LU, B, LI, c, n_factors: int, k: int, users=None, exclu
     logit (ties: higher item index first), scores = sigmoid(logit); fewer than k rankable items
     pads with item -1 / score NaN."""
     torch = __import__("torch")
-    n_users, n_items = int(A.shape[0]), int(B.shape[0])
+    ops = Operands(rt, A, LU, B, LI, c, n_factors)
     k = int(k)
     if not 1 <= k <= MAX_K:
         raise ValueError(f"k={k} outside 1..{MAX_K}")
-    ids, n_sel = _users(rt, users, n_users)
-    excl = _exclusions(rt, exclude, n_users, n_items)
-    ws = rt.empty((topk_workspace_bytes(n_sel, n_items, k),), torch.uint8)
+    ids, n_sel = _users(rt, users, ops.n_users)
+    excl = _exclusions(rt, _host_exclusions(exclude, ops.n_users, ops.n_items))
+    ws = rt.empty((topk_workspace_bytes(n_sel, ops.n_items, k),), torch.uint8)
     items = rt.empty((n_sel, k), torch.int32)
     scores = rt.empty((n_sel, k), torch.float64)
-    _lib.check(rt.lib.rfm_pair_topk(rt.ctx, A.data_ptr(), LU.data_ptr(), n_users,
-                                    None if ids is None else ids.data_ptr(), n_sel, B.data_ptr(),
-                                    LI.data_ptr(), n_items, n_factors, c.data_ptr(),
-                                    None if excl is None else excl[0].data_ptr(),
-                                    None if excl is None else excl[1].data_ptr(), k, ws.data_ptr(),
+    _lib.check(rt.lib.rfm_pair_topk(*ops.pair_args(ids, n_sel), *excl_args(excl), k, ws.data_ptr(),
                                     items.data_ptr(), scores.data_ptr()))
     rt.sync()
     return items.cpu().numpy(), scores.cpu().numpy()
@@ -203,11 +280,10 @@ def ranks_workspace_bytes(n_sel_users: int, n_items: int, n_targets: int) -> int
     return int(out.value)
 
 
-def _id_array(a, what: str) -> np.ndarray:
-    a = np.asarray(a)
-    if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
-        raise ValueError(f"{what} must be a 1-d array of integer ids")
-    return a.astype(np.int64)
+def users_indptr(users) -> Tuple[np.ndarray, np.ndarray]:
+    """``(sel int32, indptr int64)``: the unique user ids ascending and, for sorted ``users``, their runs."""
+    sel, counts = np.unique(users, return_counts=True)
+    return sel.astype(np.int32), np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
 
 
 def group_pairs(users, items, n_users: int, n_items: int):
@@ -216,17 +292,12 @@ def group_pairs(users, items, n_users: int, n_items: int):
     the items of selected user s ascending in ``tgt_items[tgt_indptr[s]:tgt_indptr[s + 1]]``, and
     ``order`` with grouped target t = input pair ``order[t]``.  ``ValueError`` for anything but two
     equal-length 1-d integer arrays of ids inside their tables."""
-    users, items = _id_array(users, "users"), _id_array(items, "items")
+    users, items = _id_array(users, "users", n_users), _id_array(items, "items", n_items)
     if users.shape != items.shape:
         raise ValueError(f"{users.shape[0]} users for {items.shape[0]} items: the pairs need one of each")
-    if users.size and (users.min() < 0 or users.max() >= n_users):
-        raise ValueError(f"a user id lies outside 0..{n_users - 1}")
-    if items.size and (items.min() < 0 or items.max() >= n_items):
-        raise ValueError(f"an item id lies outside 0..{n_items - 1}")
     order = np.lexsort((items, users))
-    sel, counts = np.unique(users, return_counts=True)
-    indptr = np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
-    return sel.astype(np.int32), indptr, items[order].astype(np.int32), order
+    sel, indptr = users_indptr(users)
+    return sel, indptr, items[order].astype(np.int32), order
 
 
 def _first_excluded_pair(users, items, excl, n_items: int):
@@ -237,25 +308,26 @@ def _first_excluded_pair(users, items, excl, n_items: int):
     return int(hit[0]) if hit.size else None
 
 
+def enqueue_ranks(ops: Operands, sel, n_sel: int, excl, tgt_indptr, tgt_items, n_targets: int, ws, ranks, scores,
+                  cand) -> None:
+    """The rank passes enqueued (``rfm_pair_ranks_n``: the host knows the number of targets) on device tensors."""
+    _lib.check(ops.rt.lib.rfm_pair_ranks_n(*ops.pair_args(sel, n_sel), *excl_args(excl), tgt_indptr.data_ptr(),
+                                           tgt_items.data_ptr(), n_targets, ws.data_ptr(), ranks.data_ptr(),
+                                           scores.data_ptr(), cand.data_ptr()))
+
+
 def _rank_grouped(rt: Runtime, A, LU, B, LI, c, n_factors: int, sel, tgt_indptr, tgt_items, excl):
-    """One ``rfm_pair_ranks`` call for grouped targets (``group_pairs``); ``excl``: host lists or
-    None.  ``(ranks [n_targets], scores [n_targets], candidates [n_sel])``."""
+    """``(ranks [n_targets], scores [n_targets], candidates [n_sel])`` of grouped targets (``group_pairs``)."""
     torch = __import__("torch")
-    n_users, n_items = int(A.shape[0]), int(B.shape[0])
+    ops = Operands(rt, A, LU, B, LI, c, n_factors)
     n_sel, n_tgt = int(sel.shape[0]), int(tgt_items.shape[0])
     if n_sel == 0:
         return np.zeros(0, np.int32), np.zeros(0, np.float64), np.zeros(0, np.int32)
-    d_excl = None if excl is None else (rt.upload(excl[0]), rt.upload(excl[1] if excl[1].size else np.zeros(1, np.int32)))
-    d_sel, d_indptr, d_items = rt.upload(sel), rt.upload(tgt_indptr), rt.upload(tgt_items)
-    ws = rt.empty((ranks_workspace_bytes(n_sel, n_items, n_tgt),), torch.uint8)
+    ws = rt.empty((ranks_workspace_bytes(n_sel, ops.n_items, n_tgt),), torch.uint8)
     ranks, scores = rt.empty((n_tgt,), torch.int32), rt.empty((n_tgt,), torch.float64)
     cand = rt.empty((n_sel,), torch.int32)
-    _lib.check(rt.lib.rfm_pair_ranks(rt.ctx, A.data_ptr(), LU.data_ptr(), n_users, d_sel.data_ptr(), n_sel,
-                                     B.data_ptr(), LI.data_ptr(), n_items, n_factors, c.data_ptr(),
-                                     None if d_excl is None else d_excl[0].data_ptr(),
-                                     None if d_excl is None else d_excl[1].data_ptr(), d_indptr.data_ptr(),
-                                     d_items.data_ptr(), ws.data_ptr(), ranks.data_ptr(), scores.data_ptr(),
-                                     cand.data_ptr()))
+    enqueue_ranks(ops, rt.upload(sel), n_sel, _exclusions(rt, excl), rt.upload(tgt_indptr), rt.upload(tgt_items),
+                  n_tgt, ws, ranks, scores, cand)
     rt.sync()
     return ranks.cpu().numpy(), scores.cpu().numpy(), cand.cpu().numpy()
 
@@ -267,15 +339,15 @@ def rank_items(rt: Runtime, A, LU, B, LI, c, n_factors: int, users, items, exclu
     user's ``exclude`` list) that are better than ``items[p]`` under ``topk``'s order, so that
     ``rank_items`` of ``topk``'s r-th item is r; ``candidates[p]`` = how many such items the user
     has; scores = sigmoid(logit).  A pair that ``exclude`` lists is a ``ValueError``."""
-    n_users, n_items = int(A.shape[0]), int(B.shape[0])
-    sel, tgt_indptr, tgt_items, order = group_pairs(users, items, n_users, n_items)
-    excl = None if exclude is None else _host_exclusions(exclude, n_users, n_items)
+    ops = Operands(rt, A, LU, B, LI, c, n_factors)
+    sel, tgt_indptr, tgt_items, order = group_pairs(users, items, ops.n_users, ops.n_items)
+    excl = _host_exclusions(exclude, ops.n_users, ops.n_items)
     if excl is not None:
-        p = _first_excluded_pair(users, items, excl, n_items)
+        p = _first_excluded_pair(users, items, excl, ops.n_items)
         if p is not None:
             raise ValueError(f"pair {p} (user {int(np.asarray(users)[p])}, item {int(np.asarray(items)[p])}) "
                              f"is in the user's exclusion list: it has no rank")
-    g_ranks, g_scores, g_cand = _rank_grouped(rt, A, LU, B, LI, c, n_factors, sel, tgt_indptr, tgt_items, excl)
+    g_ranks, g_scores, g_cand = _rank_grouped(*ops, sel, tgt_indptr, tgt_items, excl)
     n = order.shape[0]
     ranks, scores, cand = np.empty(n, np.int32), np.empty(n, np.float64), np.empty(n, np.int32)
     ranks[order], scores[order] = g_ranks, g_scores
@@ -293,7 +365,7 @@ def order_workspace_bytes(n_sel_users: int, n_items: int, depth: int) -> Tuple[i
 
 
 def _depth(depth) -> int:
-    if isinstance(depth, (bool, np.bool_)) or not isinstance(depth, (int, np.integer)):
+    if not is_int(depth):
         raise ValueError(f"depth must be an integer, got {depth!r}")
     if depth < 1:
         raise ValueError(f"depth={int(depth)}: the ranking depth must be at least 1")
@@ -313,13 +385,13 @@ def rank_catalogue(rt: Runtime, A, LU, B, LI, c, n_factors: int, depth: int, use
     ``workspace_bytes``: device memory for the logits of a block of users (``order_workspace_bytes``;
     default: the preferred size, at most ``ORDER_WORKSPACE_BYTES``); the result does not depend on it."""
     torch = __import__("torch")
-    n_users, n_items = int(A.shape[0]), int(B.shape[0])
+    ops = Operands(rt, A, LU, B, LI, c, n_factors)
     depth = _depth(depth)
-    ids, n_sel = _users(rt, users, n_users)
-    excl = _exclusions(rt, exclude, n_users, n_items)
+    ids, n_sel = _users(rt, users, ops.n_users)
+    excl = _exclusions(rt, _host_exclusions(exclude, ops.n_users, ops.n_items))
     if n_sel == 0:
         return np.zeros((0, depth), np.int32), np.zeros((0, depth), np.float64), np.zeros(0, np.int32)
-    least, preferred = order_workspace_bytes(n_sel, n_items, depth)
+    least, preferred = order_workspace_bytes(n_sel, ops.n_items, depth)
     if workspace_bytes is None:
         workspace_bytes = max(least, min(preferred, ORDER_WORKSPACE_BYTES))
     workspace_bytes = int(workspace_bytes)
@@ -329,36 +401,7 @@ def rank_catalogue(rt: Runtime, A, LU, B, LI, c, n_factors: int, depth: int, use
     items = rt.empty((n_sel, depth), torch.int32)
     scores = rt.empty((n_sel, depth), torch.float64)
     n_ranked = rt.empty((n_sel,), torch.int32)
-    _lib.check(rt.lib.rfm_pair_order(rt.ctx, A.data_ptr(), LU.data_ptr(), n_users,
-                                     None if ids is None else ids.data_ptr(), n_sel, B.data_ptr(),
-                                     LI.data_ptr(), n_items, n_factors, c.data_ptr(),
-                                     None if excl is None else excl[0].data_ptr(),
-                                     None if excl is None else excl[1].data_ptr(), depth, ws.data_ptr(),
+    _lib.check(rt.lib.rfm_pair_order(*ops.pair_args(ids, n_sel), *excl_args(excl), depth, ws.data_ptr(),
                                      workspace_bytes, items.data_ptr(), scores.data_ptr(), n_ranked.data_ptr()))
     rt.sync()
     return items.cpu().numpy(), scores.cpu().numpy(), n_ranked.cpu().numpy()
-
-
-def fm_operands(model, sides: Sides):
-    """``(A, LU, B, LI, c)`` of an FM model for ``sides``: two side-sum launches per call (they
-    depend on the parameters)."""
-    rt = model._rt
-    if not isinstance(sides, Sides):
-        raise TypeError("sides must be a recommend.Sides")
-    if sides.n_features != model.n_features:
-        raise ValueError(f"sides have {sides.n_features} columns, model has {model.n_features}")
-    XU, XI = sides.device(rt)
-    A, LU = side_sums(rt, XU, model.w.dev, model.V.dev, model.n_features, model.n_factors)
-    B, LI = side_sums(rt, XI, model.w.dev, model.V.dev, model.n_features, model.n_factors)
-    return A, LU, B, LI, model.w0.dev
-
-
-def mf_operands(model):
-    """``(P, b_u, Q, b_i, b)`` of an MF model (padded copies of P, Q when ``n_factors % 4``)."""
-    rt = model._rt
-    if not hasattr(model, "b"):
-        # the reference's global bias exists only after fit() (src/mf.py:84)
-        raise AttributeError("'LogisticMatrixFactorization' object has no attribute 'b'")
-    c = rt.upload(np.array([float(model.b)], dtype=np.float64))
-    return (padded(rt, model.P.dev, model.n_factors), model.b_u.dev, padded(rt, model.Q.dev, model.n_factors),
-            model.b_i.dev, c)

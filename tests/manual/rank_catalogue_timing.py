@@ -143,14 +143,14 @@ def main():
             model = pkg.FactorizationMachines(estimator="IPS", n_epochs=1, n_factors=k, lr=1e-4, batch_size=1, seed=7,
                                               n_features=synth.n_features_of(synth.SHAPES[name]), alpha=2.0)
             sides = features.sides_kuairec(model._rt, nu, ni, ctx, user, item)
-            run(name, f"FM k = {k}, alpha = 2.0", nu, ni, lambda: recommend.fm_operands(model, sides), k,
+            run(name, f"FM k = {k}, alpha = 2.0", nu, ni, lambda: recommend.operands(model, sides)[1:6], k,
                 (lambda d: model.rank_catalogue(sides, d), lambda: model.recommend(sides, 64),
                  lambda: model.score_pairs(sides)), model._rt, args, plan)
         # MF at k = 400: P, Q as they are initialised, b as fit() would set it
         mf = pkg.LogisticMatrixFactorization(estimator="IPS", n_epochs=1, n_factors=400, n_users=nu, n_items=ni, lr=0.02,
                                              reg=0.5, batch_size=1, seed=7)
         mf.b = 0.5
-        run(name, "MF k = 400", nu, ni, lambda: recommend.mf_operands(mf), 400,
+        run(name, "MF k = 400", nu, ni, lambda: recommend.operands(mf)[1:6], 400,
             (mf.rank_catalogue, lambda: mf.recommend(64), mf.score_pairs), mf._rt, args, plan)
     if args.device_only:
         with open(args.device_only, "w") as f:

@@ -435,3 +435,52 @@ def test_mf_curve_inside_fit(rfm, gold, held, k):
     assert not np.allclose(weighted.history["DCG"], first["DCG"])
     cv.assert_same_bits(cv.row(weighted.history, n_iters - 1), weighted.evaluate(mw, estimator="IPS"), "weighted, last row")
     cv.assert_same_bits(cv.row(first, n_iters - 1), weighted.evaluate(mw, estimator="Naive"), "unweighted, last row")
+
+
+# --------------------------------------------------------------------------- 8
+@pytest.mark.parametrize("kind,k", [("mf", 33), ("fm", 6)])
+def test_operands_refreshed_in_place_are_fresh_operands(rfm, kind, k):
+    """``recommend.operands(into=)``, what the evaluator does between iterations: after the
+    parameters changed on the device, every tensor of the refreshed operands has the bytes of
+    operands built anew -- the zero columns k .. kpad-1 included (MF k = 33: kpad = 36, the padded
+    copies; FM k = 6: kpad = 8) -- in the memory the first call allocated.  65 users x 70 items:
+    two tiles a side, the second partial."""
+    pkg, _, recommend, rt = rfm
+    nu, ni, kp = 65, 70, recommend.pad4(k)
+    rng = np.random.default_rng(k)
+    if kind == "fm":
+        cu, ci = 9, 12  # user columns, then item columns: disjoint
+        XU = sp.hstack([sp.random(nu, cu, 0.5, random_state=1, data_rvs=rng.standard_normal), sp.csr_matrix((nu, ci))])
+        XI = sp.hstack([sp.csr_matrix((ni, cu)), sp.random(ni, ci, 0.5, random_state=2, data_rvs=rng.standard_normal)])
+        sides = recommend.Sides(XU.tocsr(), XI.tocsr())
+        model = tgr._fm_model(pkg, cu + ci, k, 2.0, 0.25, rng.standard_normal(cu + ci), rng.standard_normal((cu + ci, k)))
+        params, owned = (model.w0, model.w, model.V), ("A", "LU", "B", "LI")
+    else:
+        sides = None
+        model = pkg.LogisticMatrixFactorization(estimator="IPS", n_epochs=1, n_factors=k, n_users=nu, n_items=ni, lr=0.02,
+                                                reg=0.5, batch_size=1, seed=12345)
+        for p, shape in ((model.P, (nu, k)), (model.Q, (ni, k)), (model.b_u, nu), (model.b_i, ni)):
+            p.set(rng.standard_normal(shape))
+        model.b = 0.375
+        params, owned = (model.P, model.Q, model.b_u, model.b_i), ("A", "B", "c")
+    first = recommend.operands(model, sides)
+    rt.sync()
+    before = [t.cpu().numpy().copy() for t in first[1:6]]
+    for p, scale in zip(params, (2.0, 0.5, 4.0, 0.25)):  # exact: powers of two
+        p.dev.mul_(scale)
+    if kind == "mf":
+        model.b = 3.0
+    again = recommend.operands(model, sides, into=first)
+    fresh = recommend.operands(model, sides)
+    rt.sync()
+    assert again.A.shape == (nu, kp) and again.B.shape == (ni, kp) and kp > k
+    for name, a, f, b in zip(("A", "LU", "B", "LI", "c"), again[1:6], fresh[1:6], before):
+        a, f = a.cpu().numpy(), f.cpu().numpy()
+        assert a.shape == f.shape and a.tobytes() == f.tobytes(), name
+        assert a.tobytes() != b.tobytes(), (name, "the refresh changed nothing")
+    for M in (again.A, again.B):
+        assert not M.cpu().numpy()[:, k:].any()
+    for name in owned:
+        assert getattr(again, name).data_ptr() == getattr(first, name).data_ptr(), name
+        assert getattr(fresh, name).data_ptr() != getattr(first, name).data_ptr(), name
+    assert (again.rt, again.n_factors, again.n_users, again.n_items) == (rt, k, nu, ni)

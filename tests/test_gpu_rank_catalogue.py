@@ -250,9 +250,9 @@ def test_methods_take_exclusions_and_subsets_and_reject_bad_arguments(rfm, model
                                             lr=0.02, reg=0.5, batch_size=1, seed=12345)
     with pytest.raises(AttributeError):
         fresh.rank_catalogue(3)
-    operands = recommend.fm_operands(model, sides)
+    operands = recommend.operands(model, sides)
     with pytest.raises(ValueError, match="less than one block"):
-        recommend.rank_catalogue(rt, *operands, 16, 5, workspace_bytes=recommend.order_workspace_bytes(NU, NI, 5)[0] - 1)
+        recommend.rank_catalogue(*operands, 5, workspace_bytes=recommend.order_workspace_bytes(NU, NI, 5)[0] - 1)
 
 
 # --------------------------------------------------------------------------- 3
@@ -299,14 +299,14 @@ def test_agreement_with_recommend_and_rank_items(rfm, models, model):
 def test_determinism_block_cuts_and_user_subsets(rfm):
     _, _, recommend, rt = rfm
     model, sides, _, _ = tgr._fixture_model(rfm, rcc.gold(), "kuairec", 33, 2.0)
-    operands = recommend.fm_operands(model, sides)
+    operands = recommend.operands(model, sides)
     E = sp.csr_matrix(rcc.train_mask().astype(np.float64))
     users = np.tile(np.arange(NU), 4)[:200]
     least, preferred = recommend.order_workspace_bytes(200, NI, NI)
     assert 3 * least < preferred  # 200 users at the minimum: four blocks of 64, 64, 64 and 8
 
     def call(**kw):
-        return recommend.rank_catalogue(rt, *operands, 33, NI, exclude=E, **kw)
+        return recommend.rank_catalogue(*operands, NI, exclude=E, **kw)
 
     full = call(users=users)
     again = call(users=users)

@@ -135,11 +135,10 @@ def test_consistency_with_recommend_at_catalogue_size(rfm, k, alpha):
     # the user list three times over: 67 user tiles instead of 23, so another cut of the items into
     # splits (the number of splits goes by the number of user tiles) -- the counts are integers
     order = np.argsort(items, axis=1)
-    A, LU, B, LI, c = recommend.fm_operands(model, sides)
     sel = np.tile(np.arange(nu), 3).astype(np.int32)
     indptr = np.arange(3 * nu + 1, dtype=np.int64) * K
     tgt = np.tile(np.take_along_axis(items, order, axis=1), (3, 1)).astype(np.int32).ravel()
-    r3, s3, c3 = recommend._rank_grouped(rt, A, LU, B, LI, c, k, sel, indptr, tgt, None)
+    r3, s3, c3 = recommend._rank_grouped(*recommend.operands(model, sides), sel, indptr, tgt, None)
     np.testing.assert_array_equal(r3.reshape(3 * nu, K), np.tile(order, (3, 1)))
     np.testing.assert_array_equal(c3, ni)
     assert s3.reshape(3 * nu, K).tobytes() == np.tile(np.take_along_axis(scores, order, axis=1), (3, 1)).tobytes()
