@@ -255,7 +255,9 @@ int32_t rfm_fm_apply(rfm_ctx* ctx, double* d_w0, double* d_w, double* d_V,
  * the shard's g_w0.  Optional owner ranges for the exchange: d_range_lo[n_ranges]
  * (ascending first columns, n_ranges <= 64) -> d_range_bounds[n_ranges + 1]:
  * position in the list of the first record with column >= range_lo[i], and the
- * total.  Nothing of size n_features is cleared or moved per call: the kernels
+ * total.  Range starts may repeat (more ranks than columns: n_features * r / n_ranks
+ * gives the same first column to several ranks; their bounds are then equal).
+ * Nothing of size n_features is cleared or moved per call: the kernels
  * stamp the columns they write, and a count / scan / gather over the stamps
  * builds the list. */
 int32_t rfm_fm_grad_rows(rfm_ctx* ctx, rfm_fm_plan* plan, const int32_t* d_row_ids, int64_t batch,

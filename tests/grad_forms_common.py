@@ -1,0 +1,231 @@
+"""Shared by the tests of the FM gradient forms (test_grad_oracle_host.py, test_gpu_grad_forms.py)
+and by test_gpu_parity.py: the small random logs, the long-double statement of the batch-SUM
+gradients with the magnitude every sum adds up, and thin wrappers of the raw ABI calls
+(rfm_fm_grad, rfm_fm_grad_rows, ...) that fill their outputs with NaN first and keep guard
+records behind them.  Importing this module touches neither the GPU nor the package under test.
+
+Tolerance of a device gradient against ``fm_gradients_ld``: element-wise
+``|got - want| <= GRAD_TOL * S`` with S the sum of the absolute values of the terms of that
+element's sum.  A float64 sum of n terms in any order is off by at most (n-1) * 2^-53 * sum|terms|,
+i.e. 4.4e-12 * S at 40 000 rows, the largest batch used; the residuals and row sums carry a few
+row lengths of 2^-53 relative on top.  1e-11 covers both; it is derived, not measured."""
+import numpy as np
+from scipy.sparse import csr_matrix, random as sprandom
+
+from oracle import cpu_ref
+
+GRAD_TOL = 1e-11
+GRAD_TOL_ROWS = 40_000  # batch rows GRAD_TOL is derived for
+GUARD = 8               # records kept behind a record list's capacity
+LD = np.longdouble
+
+
+# --------------------------------------------------------------------------
+# logs
+# --------------------------------------------------------------------------
+def _random_log(rng, n_rows, n_cols, density, dense_cols=0):
+    X = sprandom(n_rows, n_cols, density=density, format="csr", random_state=rng,
+                 data_rvs=lambda s: rng.standard_normal(s)).tolil()
+    for c in range(dense_cols):  # a few columns present in every row (long column lists)
+        X[:, c] = rng.standard_normal(n_rows)[:, None]
+    X = X.tocsr()
+    X.sort_indices()
+    y = (rng.random(n_rows) < 0.5).astype(np.int64)
+    p = rng.uniform(0.1, 1.0, size=n_rows) ** 0.5
+    return {"features": X, "labels": y, "pscores": p}
+
+
+def _bounded_log(rng, n_rows, n_cols, max_len, dense_cols):
+    """Rows of 0..max_len entries (a few empty), `dense_cols` columns in (almost) every row."""
+    lens = rng.integers(0, max_len + 1, size=n_rows)
+    lens[rng.integers(0, n_rows, size=5)] = 0
+    lens[rng.integers(0, n_rows, size=5)] = max_len
+    indptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    cols = np.empty(indptr[-1], dtype=np.int32)
+    for r in range(n_rows):
+        m = lens[r]
+        if m:
+            d = min(dense_cols, m)
+            rest = rng.choice(np.arange(dense_cols, n_cols), size=m - d, replace=False) if m > d else []
+            cols[indptr[r]: indptr[r + 1]] = np.sort(np.concatenate([np.arange(d), rest]).astype(np.int32))
+    X = csr_matrix((rng.standard_normal(indptr[-1]), cols, indptr), shape=(n_rows, n_cols))
+    y = (rng.random(n_rows) < 0.5).astype(np.int64)
+    p = rng.uniform(0.1, 1.0, size=n_rows) ** 0.5
+    return {"features": X, "labels": y, "pscores": p}
+
+
+def perturbed_init(seed, n, k):
+    """cpu_ref.fm_init with w0 and every w[c] moved off zero."""
+    w0, w, V = cpu_ref.fm_init(seed, n, k)
+    rng = np.random.default_rng(seed + 1)
+    w0 = np.array([0.37])
+    w = w + np.where(rng.random(n) < 0.5, -1.0, 1.0) * rng.uniform(0.05, 0.3, size=n)
+    return w0, w, V
+
+
+# --------------------------------------------------------------------------
+# the oracle
+# --------------------------------------------------------------------------
+def fm_logit_ld(X, w0, w, V):
+    """Logit of dense long-double X [m, n] (src/fm.py:124-131), and q = X V."""
+    q = X @ V
+    pair = (q * q).sum(axis=1) - (X * X) @ (V * V).sum(axis=1)
+    return w0 + X @ w + pair / 2, q
+
+
+def fm_gradients_ld(Xb, yb, pb, w0, w, V):
+    """Closed form of cpu_ref.fm_gradients (batch-SUM gradients, no 1/|B|) in np.longdouble on
+    dense arrays.  Returns ``(g_w0, g_w, G_V, (S_0, S_w, S_V))``, the last the sum of the absolute
+    values of the terms each sum adds:
+        S_V[c, f] = sum_t |e_t| (|x_tc| |q_tf| + x_tc^2 |V_cf|),  S_w[c] = sum_t |e_t x_tc|,
+        S_0 = sum_t |e_t|."""
+    X = np.asarray(Xb.toarray() if hasattr(Xb, "toarray") else Xb).astype(LD)
+    w0 = LD(np.asarray(w0, dtype=np.float64).reshape(-1)[0])
+    w, V = np.asarray(w).astype(LD), np.asarray(V).astype(LD)
+    z, q = fm_logit_ld(X, w0, w, V)
+    z = np.clip(z, -LD(cpu_ref.LOGIT_CLIP), LD(cpu_ref.LOGIT_CLIP))
+    e = np.asarray(yb).astype(LD) / np.asarray(pb).astype(LD) - 1 / (1 + np.exp(-z))
+    Xsq, ae, aX = X * X, np.abs(e), np.abs(X)
+    g_w0 = -e.sum()
+    g_w = -(X.T @ e)
+    G_V = -(X.T @ (e[:, None] * q)) + (Xsq.T @ e)[:, None] * V
+    S_0 = ae.sum()
+    S_w = aX.T @ ae
+    S_V = aX.T @ (ae[:, None] * np.abs(q)) + (Xsq.T @ ae)[:, None] * np.abs(V)
+    return g_w0, g_w, G_V, (S_0, S_w, S_V)
+
+
+def grad_tol(n_rows):
+    """GRAD_TOL, scaled with the rows of the batch where they exceed what it is derived for."""
+    return GRAD_TOL * max(1.0, n_rows / GRAD_TOL_ROWS)
+
+
+def assert_within_scale(got, want, scale, tol, what):
+    """Element-wise ``|got - want| <= tol * scale`` (NaN anywhere counts as outside)."""
+    got = np.asarray(got, dtype=np.float64)
+    want, scale = np.asarray(want), np.asarray(scale)
+    assert got.shape == want.shape == scale.shape, (what, got.shape, want.shape, scale.shape)
+    bad = ~(np.abs(got.astype(LD) - want) <= LD(tol) * scale)
+    if bad.any():
+        ratio = np.where(scale > 0, np.abs(got.astype(LD) - want) / np.where(scale > 0, scale, 1), np.inf)
+        i = np.unravel_index(int(np.argmax(np.where(bad, ratio, -1))), got.shape) if got.ndim else ()
+        raise AssertionError(f"{what}: {int(bad.sum())} of {got.size} elements outside {tol} * S; worst at "
+                             f"{i}: got {got[i]!r}, want {float(want[i])!r}, S {float(scale[i])!r}")
+
+
+def split_grad(g, n, k):
+    """[G_V (n*k) | g_w (n) | g_w0] -> (G_V [n, k], g_w [n], g_w0)."""
+    return g[: n * k].reshape(n, k), g[n * k: n * k + n], g[n * k + n]
+
+
+# --------------------------------------------------------------------------
+# the raw ABI calls
+# --------------------------------------------------------------------------
+class Params:
+    """w0, w, V on the device (plain torch tensors: what the ABI takes)."""
+
+    def __init__(self, rt, w0, w, V):
+        self.rt = rt
+        self.w0, self.w, self.V = rt.upload(w0, dtype=np.float64), rt.upload(w, dtype=np.float64), rt.upload(
+            V, dtype=np.float64)
+        self.n, self.k = V.shape
+
+    def ptrs(self):
+        return self.w0.data_ptr(), self.w.data_ptr(), self.V.data_ptr()
+
+    def host(self):
+        self.rt.sync()
+        return self.w0.cpu().numpy(), self.w.cpu().numpy(), self.V.cpu().numpy()
+
+
+class DeviceLog:
+    """A log on the device with one plan: ``max_batch`` rows at most per step."""
+
+    def __init__(self, rt, log, k, max_batch, hot=0):
+        from relevance_factorizationmachine_amd.fm import FmPlan
+        from relevance_factorizationmachine_amd.runtime import DeviceCSR
+
+        self.rt, self.k = rt, k
+        self.X = log["features"]
+        self.n_rows, self.n = self.X.shape
+        self.csr = DeviceCSR(rt, self.X)
+        self.y = rt.upload(log["labels"], dtype=np.float64)
+        self.p = rt.upload(log["pscores"], dtype=np.float64)
+        self.plan = FmPlan(rt, self.csr, self.y, self.p, k, max_batch, hot)
+
+    def log_ptrs(self):
+        c = self.csr
+        return c.indptr.data_ptr(), c.indices.data_ptr(), c.values.data_ptr(), self.y.data_ptr(), self.p.data_ptr()
+
+    def geometry(self):
+        """Plan geometry from the public calls: lane groups of a workgroup, slots of a workgroup."""
+        info = self.plan.info()
+        gpb = 256 // self.plan.layout()["lanes_per_row"]
+        return {"GPB": gpb, "BC": info["slots"] // (info["tasks"] // gpb)}
+
+    def partial_rows(self, col):
+        """Partial rows of a column of the sparse class: ceil(len / BC)."""
+        length = int(self.X.getnnz(axis=0)[col])
+        return -(-length // self.geometry()["BC"])
+
+    def close(self):
+        self.plan.close()
+
+
+def step(dev, ids, params, lr):
+    from relevance_factorizationmachine_amd import _lib
+    d_ids = dev.rt.upload(np.asarray(ids, dtype=np.int32))
+    _lib.check(dev.rt.lib.rfm_fm_step(dev.rt.ctx, dev.plan.handle, *dev.log_ptrs(), d_ids.data_ptr(), len(ids),
+                                      *params.ptrs(), lr))
+    dev.rt.sync()
+
+
+def dense_grad(dev, ids, params):
+    """rfm_fm_grad into a buffer filled with NaN beforehand -> host array [n*(k+1)+1]."""
+    import torch
+    from relevance_factorizationmachine_amd import _lib
+    rt = dev.rt
+    d_ids = rt.upload(np.asarray(ids, dtype=np.int32))
+    grad = torch.full((dev.n * (dev.k + 1) + 1,), float("nan"), dtype=torch.float64, device=rt.torch_device)
+    _lib.check(rt.lib.rfm_fm_grad(rt.ctx, dev.plan.handle, *dev.log_ptrs(), d_ids.data_ptr(), len(ids),
+                                  *params.ptrs(), grad.data_ptr()))
+    rt.sync()
+    return grad.cpu().numpy(), grad
+
+
+class Records:
+    """What rfm_fm_grad_rows left: ``count`` (the true number), ``rec`` = all cap + GUARD records of
+    the NaN-filled buffer, ``gw0``, ``bounds`` (or None), and the device tensors of the call."""
+
+    def filled(self):
+        return self.rec[: min(self.count, self.cap)]
+
+    def assert_rest_untouched(self):
+        rest = self.rec[min(self.count, self.cap):]
+        assert np.isnan(rest).all(), "a record past the count (or a guard record) was written"
+
+
+def grad_rows(dev, ids, params, cap, ranges=None):
+    """rfm_fm_grad_rows with room for ``cap`` records, in a NaN-filled buffer of cap + GUARD."""
+    import torch
+    from relevance_factorizationmachine_amd import _lib
+    rt, k = dev.rt, dev.k
+    out = Records()
+    out.cap = cap
+    out.d_rows = torch.full((cap + GUARD, k + 2), float("nan"), dtype=torch.float64, device=rt.torch_device)
+    out.d_n = torch.full((1,), -7, dtype=torch.int32, device=rt.torch_device)
+    out.d_gw0 = torch.full((1,), float("nan"), dtype=torch.float64, device=rt.torch_device)
+    nr = 0 if ranges is None else len(ranges)
+    d_lo = rt.upload(np.asarray(ranges, dtype=np.int32)) if nr else None
+    d_bounds = torch.full((nr + 1,), -7, dtype=torch.int32, device=rt.torch_device) if nr else None
+    d_ids = rt.upload(np.asarray(ids, dtype=np.int32)) if len(ids) else None
+    _lib.check(rt.lib.rfm_fm_grad_rows(
+        rt.ctx, dev.plan.handle, d_ids.data_ptr() if d_ids is not None else None, len(ids), *params.ptrs(),
+        out.d_rows.data_ptr(), cap, out.d_n.data_ptr(), out.d_gw0.data_ptr(),
+        d_lo.data_ptr() if nr else None, nr, d_bounds.data_ptr() if nr else None))
+    rt.sync()
+    out.count = int(out.d_n.cpu()[0])
+    out.rec = out.d_rows.cpu().numpy()
+    out.gw0 = float(out.d_gw0.cpu()[0])
+    out.bounds = d_bounds.cpu().numpy() if nr else None
+    return out

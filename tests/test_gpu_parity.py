@@ -13,6 +13,7 @@ import pytest
 from scipy.sparse import csr_matrix, random as sprandom, vstack
 
 from conftest import assert_elementwise, load_golden, rel_err
+from grad_forms_common import _bounded_log, _random_log
 from oracle import cpu_ref
 from relevance_factorizationmachine_amd import synth
 
@@ -247,18 +248,6 @@ def test_fm_one_step_known_answer(rfm):
 # --------------------------------------------------------------------------
 # edge cases: ragged / empty rows, odd and large k, full batch, untouched columns
 # --------------------------------------------------------------------------
-def _random_log(rng, n_rows, n_cols, density, dense_cols=0):
-    X = sprandom(n_rows, n_cols, density=density, format="csr", random_state=rng,
-                 data_rvs=lambda s: rng.standard_normal(s)).tolil()
-    for c in range(dense_cols):  # a few columns present in every row (long column lists)
-        X[:, c] = rng.standard_normal(n_rows)[:, None]
-    X = X.tocsr()
-    X.sort_indices()
-    y = (rng.random(n_rows) < 0.5).astype(np.int64)
-    p = rng.uniform(0.1, 1.0, size=n_rows) ** 0.5
-    return {"features": X, "labels": y, "pscores": p}
-
-
 @pytest.mark.parametrize("k", [1, 2, 3, 7, 8, 16, 30, 32, 33, 64, 100, 128, 129, 300, 400])
 def test_fm_forward_all_factor_counts(rfm, k):
     pkg = rfm[0]
@@ -315,25 +304,6 @@ def test_fm_fit_full_chip_batches(rfm, k, density, dense_cols, hot):
     assert rel_err(model.w(), ref["w"]) < TIGHT
     assert rel_err(model.w0(), ref["w0"]) < TIGHT
     assert rel_err(tr, ref["train_loss"]) < TIGHT and rel_err(va, ref["val_loss"]) < TIGHT
-
-
-def _bounded_log(rng, n_rows, n_cols, max_len, dense_cols):
-    """Rows of 0..max_len entries (a few empty), `dense_cols` columns in (almost) every row."""
-    lens = rng.integers(0, max_len + 1, size=n_rows)
-    lens[rng.integers(0, n_rows, size=5)] = 0
-    lens[rng.integers(0, n_rows, size=5)] = max_len
-    indptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-    cols = np.empty(indptr[-1], dtype=np.int32)
-    for r in range(n_rows):
-        m = lens[r]
-        if m:
-            d = min(dense_cols, m)
-            rest = rng.choice(np.arange(dense_cols, n_cols), size=m - d, replace=False) if m > d else []
-            cols[indptr[r]: indptr[r + 1]] = np.sort(np.concatenate([np.arange(d), rest]).astype(np.int32))
-    X = csr_matrix((rng.standard_normal(indptr[-1]), cols, indptr), shape=(n_rows, n_cols))
-    y = (rng.random(n_rows) < 0.5).astype(np.int64)
-    p = rng.uniform(0.1, 1.0, size=n_rows) ** 0.5
-    return {"features": X, "labels": y, "pscores": p}
 
 
 @pytest.mark.parametrize("hot", [0, -1, -2])
