@@ -496,7 +496,12 @@ int32_t rfm_mf_schedule_ex(const int32_t* h_users, const int32_t* h_items, const
                            int32_t* h_level_ptr, int32_t* h_n_levels, int32_t* h_cache_items,
                            int32_t* h_n_cached);
 /* rfm_mf_sgd_levels on those records (d_ex = device copy of h_ex, d_cache_items of
- * h_cache_items; n_cached rows of n_factors+2 doubles must fit 32 KiB of LDS). */
+ * h_cache_items; n_cached rows of n_factors+2 doubles must fit 32 KiB of LDS).
+ * Pinned by tests/test_gpu_mf_step.py: level sizes may grow as well as shrink (small and
+ * large levels alternate in any order); every factor count 1..RFM_MAX_FACTORS is served;
+ * one call may take several launches, and the cached rows are consistent in memory between
+ * them (written back at the end of a launch, loaded again at the start of the next), so a
+ * level launched grid-wide in between reads and writes them through memory. */
 int32_t rfm_mf_sgd_levels_ex(rfm_ctx* ctx, const void* d_ex, const int32_t* h_level_ptr,
                              const int32_t* d_level_ptr, int32_t n_levels,
                              const int32_t* d_cache_items, int32_t n_cached, double* d_P,

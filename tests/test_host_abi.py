@@ -7,6 +7,7 @@ import re
 import numpy as np
 import pytest
 
+from mf_step_common import levels_py as _levels_py
 from relevance_factorizationmachine_amd import _lib
 from relevance_factorizationmachine_amd.runtime import mf_schedule, mf_schedule_ex, sample_batches
 
@@ -53,15 +54,6 @@ def test_sampler_rejects_oversized_batch():
     # the reference's resample raises ValueError (sklearn) when B > N
     with pytest.raises(ValueError, match="Cannot sample 11 out of arrays with dim 10"):
         sample_batches(10, 11, 0, 1)
-
-
-def _levels_py(users, items):
-    lu, li, lev = {}, {}, []
-    for u, i in zip(users, items):
-        l = max(lu.get(u, -1), li.get(i, -1)) + 1
-        lu[u] = li[i] = l
-        lev.append(l)
-    return np.asarray(lev)
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2])
