@@ -133,6 +133,70 @@ static void sample_one(int64_t n_rows, int64_t batch, uint32_t seed, int32_t* sc
   std::memcpy(out, scratch, size_t(batch) * sizeof(int32_t));
 }
 
+// --------------------------------------------------------------------------
+// The level pass of the MF schedule, once for both schedulers.  An example's level is one more than
+// the last level that touched its user or its item, so the examples of a level touch disjoint rows;
+// the batch positions are sorted by level, stably, into h_level_ptr[n_levels + 1], and `use(pass)`
+// writes the caller's form of the schedule.  The per-user / per-item tables are thread-local; only
+// the entries a batch touched are reset, on every exit: an id out of range (nothing has been
+// written then) leaves them clean for the next call.
+// --------------------------------------------------------------------------
+struct MfLevelPass {
+  std::vector<int32_t> dst;  // [batch] place in level order (ascending batch position inside a level)
+  std::vector<int32_t> gap;  // with_items: levels back to the previous writer of the user row
+                             // (RFM_MF_NO_WRITER if none): the row is final that far ahead
+  std::vector<int32_t>&cnt_i, &slot_i;  // with_items: occurrences of an item in the batch; -1, the caller's to mark
+};
+
+template <class Use>
+static void mf_level_pass(const int32_t* h_users, const int32_t* h_items, int64_t batch,
+                          int32_t n_users, int32_t n_items, bool with_items, int32_t* h_level_ptr,
+                          int32_t* h_n_levels, Use use) {
+  static thread_local std::vector<int32_t> last_u, last_i, cnt_i, slot_i;
+  if (int64_t(last_u.size()) < n_users) last_u.assign(size_t(n_users), -1);
+  if (int64_t(last_i.size()) < n_items) last_i.assign(size_t(n_items), -1);
+  if (with_items && int64_t(cnt_i.size()) < n_items) {
+    cnt_i.assign(size_t(n_items), 0);
+    slot_i.assign(size_t(n_items), -1);
+  }
+  int64_t seen = 0;  // examples taken: their ids were in range and their table entries written
+  struct Reset {
+    const int32_t *users, *items;
+    const int64_t& seen;
+    bool with_items;
+    ~Reset() {
+      for (int64_t s = 0; s < seen; ++s) {
+        last_u[users[s]] = last_i[items[s]] = -1;
+        if (with_items) cnt_i[items[s]] = 0, slot_i[items[s]] = -1;
+      }
+    }
+  } reset{h_users, h_items, seen, with_items};
+  MfLevelPass pass{std::vector<int32_t>(size_t(batch)), std::vector<int32_t>(with_items ? size_t(batch) : 0),
+                   cnt_i, slot_i};
+  std::vector<int32_t>& level = pass.dst;  // the level first, the place once the levels are counted
+  int32_t n_levels = 0;
+  for (; seen < batch; ++seen) {
+    const int32_t u = h_users[seen], i = h_items[seen];
+    RFM_REQUIRE(u >= 0 && u < n_users && i >= 0 && i < n_items, "user/item id out of range");
+    const int32_t lv = std::max(last_u[u], last_i[i]) + 1;
+    level[size_t(seen)] = lv;
+    if (with_items) {
+      pass.gap[size_t(seen)] = last_u[u] < 0 ? RFM_MF_NO_WRITER : lv - last_u[u];
+      cnt_i[i]++;
+    }
+    last_u[u] = last_i[i] = lv;
+    n_levels = std::max(n_levels, lv + 1);
+  }
+  // stable counting sort of batch positions by level
+  std::vector<int32_t> cnt(size_t(n_levels) + 1, 0);
+  for (int64_t s = 0; s < batch; ++s) cnt[size_t(level[size_t(s)]) + 1]++;
+  for (int32_t l = 0; l < n_levels; ++l) cnt[size_t(l) + 1] += cnt[size_t(l)];
+  for (int32_t l = 0; l <= n_levels; ++l) h_level_ptr[l] = cnt[size_t(l)];
+  for (int64_t s = 0; s < batch; ++s) pass.dst[size_t(s)] = cnt[size_t(level[size_t(s)])]++;
+  use(pass);
+  *h_n_levels = n_levels;
+}
+
 }  // namespace rfm
 
 using namespace rfm;
@@ -188,38 +252,10 @@ int32_t rfm_mf_schedule(const int32_t* h_users, const int32_t* h_items, int64_t 
   return guarded([&] {
     RFM_REQUIRE(h_users && h_items && h_order && h_level_ptr && h_n_levels, "null pointer");
     RFM_REQUIRE(batch >= 0 && batch < (int64_t(1) << 31), "batch out of range");
-    // last level seen per user / item; only touched entries are reset afterwards
-    static thread_local std::vector<int32_t> last_u, last_i;
-    if (int64_t(last_u.size()) < n_users) last_u.assign(size_t(n_users), -1);
-    if (int64_t(last_i.size()) < n_items) last_i.assign(size_t(n_items), -1);
-    std::vector<int32_t> level(static_cast<size_t>(batch), 0);
-    int32_t n_levels = 0;
-    bool bad = false;
-    for (int64_t s = 0; s < batch; ++s) {
-      int32_t u = h_users[s], i = h_items[s];
-      if (u < 0 || u >= n_users || i < 0 || i >= n_items) {
-        bad = true;
-        break;
-      }
-      int32_t lv = std::max(last_u[u], last_i[i]) + 1;
-      level[s] = lv;
-      last_u[u] = lv;
-      last_i[i] = lv;
-      n_levels = std::max(n_levels, lv + 1);
-    }
-    for (int64_t s = 0; s < batch; ++s) {
-      int32_t u = h_users[s], i = h_items[s];
-      if (u >= 0 && u < n_users) last_u[u] = -1;
-      if (i >= 0 && i < n_items) last_i[i] = -1;
-    }
-    RFM_REQUIRE(!bad, "user/item id out of range");
-    // stable counting sort of batch positions by level
-    std::vector<int32_t> cnt(static_cast<size_t>(n_levels) + 1, 0);
-    for (int64_t s = 0; s < batch; ++s) cnt[size_t(level[s]) + 1]++;
-    for (int32_t l = 0; l < n_levels; ++l) cnt[size_t(l) + 1] += cnt[size_t(l)];
-    for (int32_t l = 0; l <= n_levels; ++l) h_level_ptr[l] = cnt[size_t(l)];
-    for (int64_t s = 0; s < batch; ++s) h_order[cnt[size_t(level[s])]++] = int32_t(s);
-    *h_n_levels = n_levels;
+    mf_level_pass(h_users, h_items, batch, n_users, n_items, false, h_level_ptr, h_n_levels,
+                  [&](const MfLevelPass& lp) {
+                    for (int64_t s = 0; s < batch; ++s) h_order[lp.dst[size_t(s)]] = int32_t(s);
+                  });
   });
 }
 
@@ -239,35 +275,10 @@ int32_t rfm_mf_schedule_ex(const int32_t* h_users, const int32_t* h_items, const
                     h_cache_items && h_n_cached,
                 "null pointer");
     RFM_REQUIRE(batch >= 0 && batch < (int64_t(1) << 31) && cache_cap >= 0, "bad shape");
-    static thread_local std::vector<int32_t> last_u, last_i, cnt_i, slot_i;
-    if (int64_t(last_u.size()) < n_users) last_u.assign(size_t(n_users), -1);
-    if (int64_t(last_i.size()) < n_items) {
-      last_i.assign(size_t(n_items), -1);
-      cnt_i.assign(size_t(n_items), 0);
-      slot_i.assign(size_t(n_items), -1);
-    }
-    std::vector<int32_t> level(static_cast<size_t>(batch), 0), gap(static_cast<size_t>(batch), 0);
-    int32_t n_levels = 0;
-    bool bad = false;
-    for (int64_t s = 0; s < batch; ++s) {
-      const int32_t u = h_users[s], i = h_items[s];
-      if (u < 0 || u >= n_users || i < 0 || i >= n_items) {
-        bad = true;
-        break;
-      }
-      const int32_t lv = std::max(last_u[u], last_i[i]) + 1;
-      level[size_t(s)] = lv;
-      // levels back to the previous writer of the user row: the row is final, and may be
-      // read, that far ahead of lv
-      gap[size_t(s)] = last_u[u] < 0 ? RFM_MF_NO_WRITER : lv - last_u[u];
-      last_u[u] = lv;
-      last_i[i] = lv;
-      cnt_i[i]++;
-      n_levels = std::max(n_levels, lv + 1);
-    }
-    // items that occur more than once, most frequent first, get the LDS slots
-    std::vector<int32_t> repeated;
-    if (!bad)
+    const auto records = [&](const MfLevelPass& lp) {
+      std::vector<int32_t>&cnt_i = lp.cnt_i, &slot_i = lp.slot_i;
+      // items that occur more than once, most frequent first, get the LDS slots
+      std::vector<int32_t> repeated;
       for (int64_t s = 0; s < batch; ++s) {
         const int32_t i = h_items[s];
         if (cnt_i[i] >= 2 && slot_i[i] == -1) {
@@ -275,40 +286,23 @@ int32_t rfm_mf_schedule_ex(const int32_t* h_users, const int32_t* h_items, const
           repeated.push_back(i);
         }
       }
-    std::stable_sort(repeated.begin(), repeated.end(),
-                     [&](int32_t x, int32_t y) { return cnt_i[x] > cnt_i[y]; });
-    const int32_t n_cached = int32_t(std::min<size_t>(repeated.size(), size_t(cache_cap)));
-    for (int32_t c = 0; c < n_cached; ++c) {
-      slot_i[repeated[size_t(c)]] = c;
-      h_cache_items[c] = repeated[size_t(c)];
-    }
-    // level-ordered records (stable: ascending batch position inside a level)
-    std::vector<int32_t> cnt(static_cast<size_t>(n_levels) + 1, 0);
-    if (!bad) {
-      for (int64_t s = 0; s < batch; ++s) cnt[size_t(level[size_t(s)]) + 1]++;
-      for (int32_t l = 0; l < n_levels; ++l) cnt[size_t(l) + 1] += cnt[size_t(l)];
-      for (int32_t l = 0; l <= n_levels; ++l) h_level_ptr[l] = cnt[size_t(l)];
+      std::stable_sort(repeated.begin(), repeated.end(),
+                       [&](int32_t x, int32_t y) { return cnt_i[x] > cnt_i[y]; });
+      const int32_t n_cached = int32_t(std::min<size_t>(repeated.size(), size_t(cache_cap)));
+      for (int32_t c = 0; c < n_cached; ++c) {
+        slot_i[repeated[size_t(c)]] = c;
+        h_cache_items[c] = repeated[size_t(c)];
+      }
+      // level-ordered records
       HostMfEx* ex = static_cast<HostMfEx*>(h_ex);
       for (int64_t s = 0; s < batch; ++s) {
         const int32_t i = h_items[s];
         const int32_t cs = cnt_i[i] >= 2 ? slot_i[i] : -1;  // -2: repeated, no slot
-        ex[cnt[size_t(level[size_t(s)])]++] =
-            HostMfEx{h_users[s], i, cs, gap[size_t(s)], h_y[s] / h_pscore[s]};
+        ex[lp.dst[size_t(s)]] = HostMfEx{h_users[s], i, cs, lp.gap[size_t(s)], h_y[s] / h_pscore[s]};
       }
-    }
-    // reset only what this batch touched
-    for (int64_t s = 0; s < batch; ++s) {
-      const int32_t u = h_users[s], i = h_items[s];
-      if (u >= 0 && u < n_users) last_u[u] = -1;
-      if (i >= 0 && i < n_items) {
-        last_i[i] = -1;
-        cnt_i[i] = 0;
-        slot_i[i] = -1;
-      }
-    }
-    RFM_REQUIRE(!bad, "user/item id out of range");
-    *h_n_levels = n_levels;
-    *h_n_cached = n_cached;
+      *h_n_cached = n_cached;
+    };
+    mf_level_pass(h_users, h_items, batch, n_users, n_items, true, h_level_ptr, h_n_levels, records);
   });
 }
 

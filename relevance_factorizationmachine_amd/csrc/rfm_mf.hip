@@ -11,6 +11,14 @@
 // examples get a grid-wide launch each; runs of small levels are executed by
 // ONE workgroup that walks the levels with a barrier in between, so a batch
 // whose popular item forms a long chain costs one launch, not one per level.
+//
+// The schedule comes in two forms: the plain form (an order of batch positions,
+// rfm_mf_sgd_levels; rfm_mf_sgd_hogwild is its wide kernel on the whole batch)
+// and the record form the fits use (level-ordered MfEx records, an item cache
+// and a read-ahead ring in the sequential kernel, rfm_mf_sgd_levels_ex).  Both
+// run the same example update (mf_load_row, mf_update, mf_store_row), the same
+// host walk over the level pointers (mf_walk_levels) and fill the model's
+// fields of their argument blocks in one place (set_model).
 #include <algorithm>
 #include <cmath>
 
@@ -113,6 +121,56 @@ __global__ __launch_bounds__(kMfBlock) void mf_loss_finish_kernel(const double* 
   if (threadIdx.x == 0) out[0] = -lds[0] / double(n_rows);
 }
 
+// the arithmetic of one example on rows already in registers (src/mf.py:99-108,
+// 172-216): returns the residual, rows and biases are updated in place
+template <int LPR, int VEC, int NC>
+__device__ inline void mf_update(Pack<VEC> (&pp)[NC], Pack<VEC> (&pq)[NC], double& bu,
+                                 double& bi, double ry, double b, double lr, double reg, int k,
+                                 int l) {
+  double dot = 0.0;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const int f = (c * LPR + l) * VEC;
+    if (f < k) {
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) dot += pp[c].v[v] * pq[c].v[v];
+    }
+  }
+  dot = group_sum<LPR>(dot);
+  const double err = ry - sigmoid_clipped(dot + bu + bi + b);
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      const double p_new = pp[c].v[v] - lr * (-err * pq[c].v[v] + reg * pp[c].v[v]);
+      // the item row sees the user row this example has just updated (src/mf.py:193)
+      const double q_new = pq[c].v[v] - lr * (-err * p_new + reg * pq[c].v[v]);
+      pp[c].v[v] = p_new;
+      pq[c].v[v] = q_new;
+    }
+  }
+  bu = bu - lr * (-err + reg * bu);
+  bi = bi - lr * (-err + reg * bi);
+}
+
+template <int LPR, int VEC, int NC>
+__device__ inline void mf_load_row(Pack<VEC> (&dst)[NC], const double* row, int k, int l) {
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const int f = (c * LPR + l) * VEC;
+    dst[c].load(row + (f < k ? f : 0));
+  }
+}
+
+template <int LPR, int VEC, int NC>
+__device__ inline void mf_store_row(const Pack<VEC> (&src)[NC], double* row, int k, int l) {
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const int f = (c * LPR + l) * VEC;
+    if (f < k) src[c].store(row + f);
+  }
+}
+
 struct MfSgdArgs {
   const int32_t* users;
   const int32_t* items;
@@ -131,48 +189,22 @@ struct MfSgdArgs {
   double lr, reg;
 };
 
-// one example, LPR lanes: src/mf.py:99-108 with :172-216
+// one example of the plain form, LPR lanes
 template <int LPR, int VEC, int NC>
 __device__ inline void mf_example(const MfSgdArgs& a, int32_t s, int l) {
   const int k = a.k;
   const int64_t r = a.pos_rows[s];
   const int32_t u = a.users[r], i = a.items[r];
-  double* pu = a.P + int64_t(u) * k;
-  double* qi = a.Q + int64_t(i) * k;
   Pack<VEC> pp[NC], pq[NC];
-  double dot = 0.0;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int f = (c * LPR + l) * VEC;
-    if (f < k) {
-      pp[c].load(pu + f);
-      pq[c].load(qi + f);
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) dot += pp[c].v[v] * pq[c].v[v];
-    }
-  }
-  dot = group_sum<LPR>(dot);
-  const double bu = a.bu[u], bi = a.bi[i];
-  const double err = a.y[r] / a.pscore[r] - sigmoid_clipped(dot + bu + bi + a.b);
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int f = (c * LPR + l) * VEC;
-    if (f < k) {
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) {
-        const double p_new = pp[c].v[v] - a.lr * (-err * pq[c].v[v] + a.reg * pp[c].v[v]);
-        // the item row sees the user row this example has just updated (src/mf.py:193)
-        const double q_new = pq[c].v[v] - a.lr * (-err * p_new + a.reg * pq[c].v[v]);
-        pp[c].v[v] = p_new;
-        pq[c].v[v] = q_new;
-      }
-      pp[c].store(pu + f);
-      pq[c].store(qi + f);
-    }
-  }
+  mf_load_row<LPR, VEC, NC>(pp, a.P + int64_t(u) * k, k, l);
+  mf_load_row<LPR, VEC, NC>(pq, a.Q + int64_t(i) * k, k, l);
+  double bu = a.bu[u], bi = a.bi[i];
+  mf_update<LPR, VEC, NC>(pp, pq, bu, bi, a.y[r] / a.pscore[r], a.b, a.lr, a.reg, k, l);
+  mf_store_row<LPR, VEC, NC>(pp, a.P + int64_t(u) * k, k, l);
+  mf_store_row<LPR, VEC, NC>(pq, a.Q + int64_t(i) * k, k, l);
   if (l == 0) {
-    a.bu[u] = bu - a.lr * (-err + a.reg * bu);
-    a.bi[i] = bi - a.lr * (-err + a.reg * bi);
+    a.bu[u] = bu;
+    a.bi[i] = bi;
   }
 }
 
@@ -227,56 +259,6 @@ struct MfExArgs {
   int32_t k;
   double lr, reg;
 };
-
-// the arithmetic of one example on rows already in registers (src/mf.py:99-108,
-// 172-216): returns the residual, rows and biases are updated in place
-template <int LPR, int VEC, int NC>
-__device__ inline void mf_update(Pack<VEC> (&pp)[NC], Pack<VEC> (&pq)[NC], double& bu,
-                                 double& bi, double ry, double b, double lr, double reg, int k,
-                                 int l) {
-  double dot = 0.0;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int f = (c * LPR + l) * VEC;
-    if (f < k) {
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) dot += pp[c].v[v] * pq[c].v[v];
-    }
-  }
-  dot = group_sum<LPR>(dot);
-  const double err = ry - sigmoid_clipped(dot + bu + bi + b);
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {
-      const double p_new = pp[c].v[v] - lr * (-err * pq[c].v[v] + reg * pp[c].v[v]);
-      // the item row sees the user row this example has just updated (src/mf.py:193)
-      const double q_new = pq[c].v[v] - lr * (-err * p_new + reg * pq[c].v[v]);
-      pp[c].v[v] = p_new;
-      pq[c].v[v] = q_new;
-    }
-  }
-  bu = bu - lr * (-err + reg * bu);
-  bi = bi - lr * (-err + reg * bi);
-}
-
-template <int LPR, int VEC, int NC>
-__device__ inline void mf_load_row(Pack<VEC> (&dst)[NC], const double* row, int k, int l) {
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int f = (c * LPR + l) * VEC;
-    dst[c].load(row + (f < k ? f : 0));
-  }
-}
-
-template <int LPR, int VEC, int NC>
-__device__ inline void mf_store_row(const Pack<VEC> (&src)[NC], double* row, int k, int l) {
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int f = (c * LPR + l) * VEC;
-    if (f < k) src[c].store(row + f);
-  }
-}
 
 // one level, many workgroups (examples of a level touch disjoint rows)
 template <int LPR, int VEC, int NC>
@@ -493,23 +475,104 @@ static void launch_seq_ex(rfm_ctx* ctx, const MfExArgs& a, int threads, size_t l
   hipLaunchKernelGGL(kern, dim3(1), dim3(threads), lds, ctx->stream, a);
 }
 
-static void mf_predict_launch(rfm_ctx* ctx, MfPredArgs a, double* d_out_loss) {
-  if (a.n_rows <= 0) return;
-  const Shape s = shape_for(a.k);
-  const int gpb = kMfBlock / s.lpr;
-  const int grid = capped_grid(ctx, a.n_rows, gpb, 8, 1);
-  if (d_out_loss) {
-    ctx->loss_partials.ensure(size_t(ctx->n_cu) * 8 * sizeof(double));
-    a.loss_partial = ctx->loss_partials.as<double>();
-  }
+// the model's fields of a kernel argument block (MfPredArgs, MfSgdArgs, MfExArgs)
+template <class Args>
+static void set_model(Args& a, decltype(Args::P) P, decltype(Args::P) Q, decltype(Args::P) bu,
+                      decltype(Args::P) bi, double b, int32_t k) {
+  RFM_REQUIRE(P && Q && bu && bi, "null pointer");
+  a.P = P;
+  a.Q = Q;
+  a.bu = bu;
+  a.bi = bi;
+  a.b = b;
+  a.k = k;
+}
+template <class Args>
+static void set_model(Args& a, double* P, double* Q, double* bu, double* bi, double b, int32_t k,
+                      double lr, double reg) {
+  set_model(a, P, Q, bu, bi, b, k);
+  a.lr = lr;
+  a.reg = reg;
+}
+
+// rfm_mf_predict (scores of any number of rows) and, with want_loss, rfm_mf_predict_loss (the
+// loss of at least one row; the scores only where d_out_pred is given)
+static int32_t mf_predict(rfm_ctx* ctx, const int32_t* d_users, const int32_t* d_items,
+                          const double* d_y, const double* d_pscore, const int32_t* d_row_ids,
+                          int64_t n_rows, const double* d_P, const double* d_Q,
+                          const double* d_bu, const double* d_bi, double b, int32_t n_factors,
+                          double eps, double* d_out_pred, double* d_out_loss, bool want_loss) {
+  return guarded([&] {
+    RFM_REQUIRE(ctx, "null ctx");
+    RFM_REQUIRE(n_rows >= (want_loss ? 1 : 0), "n_rows=%lld out of range", (long long)n_rows);
+    if (n_rows == 0) return;
+    RFM_REQUIRE(d_users && d_items && (want_loss ? d_y && d_pscore && d_out_loss : d_out_pred != nullptr),
+                "null pointer");
+    MfPredArgs a{};
+    set_model(a, d_P, d_Q, d_bu, d_bi, b, n_factors);
+    a.users = d_users;
+    a.items = d_items;
+    a.row_ids = d_row_ids;
+    a.n_rows = n_rows;
+    a.y = d_y;
+    a.pscore = d_pscore;
+    a.eps = eps;
+    a.out_pred = d_out_pred;
+    const Shape s = shape_for(a.k);
+    const int grid = capped_grid(ctx, n_rows, kMfBlock / s.lpr, 8, 1);
+    if (want_loss) {
+      ctx->loss_partials.ensure(size_t(ctx->n_cu) * 8 * sizeof(double));
+      a.loss_partial = ctx->loss_partials.as<double>();
+    }
 #define RFM_CALL_MFP(L, Vv, N) \
   hipLaunchKernelGGL((mf_predict_kernel<L, Vv, N>), dim3(grid), dim3(kMfBlock), 0, ctx->stream, a)
-  RFM_FOR_SHAPE(s, RFM_CALL_MFP);
+    RFM_FOR_SHAPE(s, RFM_CALL_MFP);
 #undef RFM_CALL_MFP
-  if (d_out_loss)
-    hipLaunchKernelGGL(mf_loss_finish_kernel, dim3(1), dim3(kMfBlock), 0, ctx->stream,
-                       ctx->loss_partials.as<double>(), grid, a.n_rows, d_out_loss);
-  RFM_HIP_CHECK(hipGetLastError());
+    if (want_loss)
+      hipLaunchKernelGGL(mf_loss_finish_kernel, dim3(1), dim3(kMfBlock), 0, ctx->stream,
+                         a.loss_partial, grid, n_rows, d_out_loss);
+    RFM_HIP_CHECK(hipGetLastError());
+  });
+}
+
+// the plain form's wide kernel on a.order[a.lo, a.hi) (a null order: batch positions lo .. hi)
+static void launch_wide(rfm_ctx* ctx, const Shape& s, const MfSgdArgs& a) {
+  const int grid = capped_grid(ctx, int64_t(a.hi) - a.lo, kMfBlock / s.lpr, 8, 0);
+#define RFM_CALL_WIDE(L, Vv, N) \
+  hipLaunchKernelGGL((mf_sgd_wide_kernel<L, Vv, N>), dim3(grid), dim3(kMfBlock), 0, ctx->stream, a)
+  RFM_FOR_SHAPE(s, RFM_CALL_WIDE);
+#undef RFM_CALL_WIDE
+}
+
+// The launches of one batch from its level pointers: a level of more than seq_cap examples (more
+// than the sequential workgroup takes) is one grid-wide launch, wide(rec_lo, rec_hi); a run of
+// smaller levels is one sequential launch, seq(lev_lo, lev_hi), that ends before a wide level,
+// after max_levels levels and before the level that would take it past max_recs examples (the
+// two LDS tables of the record form's kernel; the plain form has neither: kNoLimit).
+constexpr int kNoLimit = INT32_MAX;
+
+template <class Wide, class Seq>
+static void mf_walk_levels(const int32_t* h_level_ptr, int n_levels, int seq_cap, int max_levels,
+                           int max_recs, Wide wide, Seq seq) {
+  const auto count = [&](int lev) {
+    const int cnt = h_level_ptr[lev + 1] - h_level_ptr[lev];
+    RFM_REQUIRE(cnt >= 0, "level_ptr not monotone");
+    return cnt;
+  };
+  int lev = 0;
+  while (lev < n_levels) {
+    if (count(lev) > seq_cap) {
+      wide(h_level_ptr[lev], h_level_ptr[lev + 1]);
+      ++lev;
+      continue;
+    }
+    int end = lev;
+    while (end < n_levels && end - lev < max_levels && count(end) <= seq_cap &&
+           h_level_ptr[end + 1] - h_level_ptr[lev] <= max_recs)
+      ++end;
+    seq(lev, end);
+    lev = end;
+  }
 }
 
 }  // namespace rfm
@@ -541,26 +604,8 @@ int32_t rfm_mf_predict(rfm_ctx* ctx, const int32_t* d_users, const int32_t* d_it
                        const int32_t* d_row_ids, int64_t n_rows, const double* d_P,
                        const double* d_Q, const double* d_bu, const double* d_bi, double b,
                        int32_t n_factors, double* d_out_pred) {
-  return guarded([&] {
-    RFM_REQUIRE(ctx, "null ctx");
-    RFM_REQUIRE(n_rows >= 0, "negative n_rows");
-    if (n_rows == 0) return;
-    RFM_REQUIRE(d_P && d_Q && d_bu && d_bi && d_out_pred, "null pointer");
-    RFM_REQUIRE(d_users && d_items, "null pair arrays");
-    MfPredArgs a{};
-    a.users = d_users;
-    a.items = d_items;
-    a.row_ids = d_row_ids;
-    a.n_rows = n_rows;
-    a.P = d_P;
-    a.Q = d_Q;
-    a.bu = d_bu;
-    a.bi = d_bi;
-    a.b = b;
-    a.k = n_factors;
-    a.out_pred = d_out_pred;
-    mf_predict_launch(ctx, a, nullptr);
-  });
+  return mf_predict(ctx, d_users, d_items, nullptr, nullptr, d_row_ids, n_rows, d_P, d_Q, d_bu, d_bi,
+                    b, n_factors, 0.0, d_out_pred, nullptr, false);
 }
 
 int32_t rfm_mf_predict_loss(rfm_ctx* ctx, const int32_t* d_users, const int32_t* d_items,
@@ -569,28 +614,8 @@ int32_t rfm_mf_predict_loss(rfm_ctx* ctx, const int32_t* d_users, const int32_t*
                             const double* d_Q, const double* d_bu, const double* d_bi,
                             double b, int32_t n_factors, double eps, double* d_out_pred,
                             double* d_out_loss) {
-  return guarded([&] {
-    RFM_REQUIRE(ctx && d_users && d_items && d_y && d_pscore && d_P && d_Q && d_bu && d_bi &&
-                    d_out_loss,
-                "null pointer");
-    RFM_REQUIRE(n_rows >= 1, "loss of zero rows");
-    MfPredArgs a{};
-    a.users = d_users;
-    a.items = d_items;
-    a.row_ids = d_row_ids;
-    a.n_rows = n_rows;
-    a.P = d_P;
-    a.Q = d_Q;
-    a.bu = d_bu;
-    a.bi = d_bi;
-    a.b = b;
-    a.k = n_factors;
-    a.y = d_y;
-    a.pscore = d_pscore;
-    a.eps = eps;
-    a.out_pred = d_out_pred;
-    mf_predict_launch(ctx, a, d_out_loss);
-  });
+  return mf_predict(ctx, d_users, d_items, d_y, d_pscore, d_row_ids, n_rows, d_P, d_Q, d_bu, d_bi, b,
+                    n_factors, eps, d_out_pred, d_out_loss, true);
 }
 
 int32_t rfm_mf_sgd_levels(rfm_ctx* ctx, const int32_t* d_users, const int32_t* d_items,
@@ -601,11 +626,12 @@ int32_t rfm_mf_sgd_levels(rfm_ctx* ctx, const int32_t* d_users, const int32_t* d
                           double* d_bi, double b, int32_t n_factors, double lr, double reg) {
   return guarded([&] {
     RFM_REQUIRE(ctx && d_users && d_items && d_y && d_pscore && d_pos_rows && d_order &&
-                    h_level_ptr && d_level_ptr && d_P && d_Q && d_bu && d_bi,
+                    h_level_ptr && d_level_ptr,
                 "null pointer");
     RFM_REQUIRE(n_levels >= 0, "negative n_levels");
     const Shape s = shape_for(n_factors);
     MfSgdArgs a{};
+    set_model(a, d_P, d_Q, d_bu, d_bi, b, n_factors, lr, reg);
     a.users = d_users;
     a.items = d_items;
     a.y = d_y;
@@ -613,43 +639,22 @@ int32_t rfm_mf_sgd_levels(rfm_ctx* ctx, const int32_t* d_users, const int32_t* d
     a.pos_rows = d_pos_rows;
     a.order = d_order;
     a.level_ptr = d_level_ptr;
-    a.P = d_P;
-    a.Q = d_Q;
-    a.bu = d_bu;
-    a.bi = d_bi;
-    a.b = b;
-    a.k = n_factors;
-    a.lr = lr;
-    a.reg = reg;
-    // a level is "small" when one pass of the sequential workgroup covers it
-    const int seq_cap = 2 * (kSeqBlock / s.lpr);
-    int lev = 0;
-    while (lev < n_levels) {
-      const int cnt = h_level_ptr[lev + 1] - h_level_ptr[lev];
-      RFM_REQUIRE(cnt >= 0, "level_ptr not monotone");
-      if (cnt > seq_cap) {
-        a.lo = h_level_ptr[lev];
-        a.hi = h_level_ptr[lev + 1];
-        const int gpb = kMfBlock / s.lpr;
-        const int grid = capped_grid(ctx, cnt, gpb, 8, 0);
-#define RFM_CALL_WIDE(L, Vv, N)                                                               \
-  hipLaunchKernelGGL((mf_sgd_wide_kernel<L, Vv, N>), dim3(grid), dim3(kMfBlock), 0, ctx->stream, \
-                     a)
-        RFM_FOR_SHAPE(s, RFM_CALL_WIDE);
-#undef RFM_CALL_WIDE
-        ++lev;
-      } else {
-        int end = lev;
-        while (end < n_levels && h_level_ptr[end + 1] - h_level_ptr[end] <= seq_cap) ++end;
-        a.lo = lev;
-        a.hi = end;
+    // a level is "small" when two passes of the sequential workgroup cover it
+    mf_walk_levels(
+        h_level_ptr, n_levels, 2 * (kSeqBlock / s.lpr), kNoLimit, kNoLimit,
+        [&](int32_t rec_lo, int32_t rec_hi) {
+          a.lo = rec_lo;
+          a.hi = rec_hi;
+          launch_wide(ctx, s, a);
+        },
+        [&](int32_t lev_lo, int32_t lev_hi) {
+          a.lo = lev_lo;
+          a.hi = lev_hi;
 #define RFM_CALL_SEQ(L, Vv, N) \
   hipLaunchKernelGGL((mf_sgd_seq_kernel<L, Vv, N>), dim3(1), dim3(kSeqBlock), 0, ctx->stream, a)
-        RFM_FOR_SHAPE(s, RFM_CALL_SEQ);
+          RFM_FOR_SHAPE(s, RFM_CALL_SEQ);
 #undef RFM_CALL_SEQ
-        lev = end;
-      }
-    }
+        });
     RFM_HIP_CHECK(hipGetLastError());
   });
 }
@@ -667,8 +672,7 @@ int32_t rfm_mf_sgd_levels_ex(rfm_ctx* ctx, const void* d_ex, const int32_t* h_le
                              double* d_Q, double* d_bu, double* d_bi, double b,
                              int32_t n_factors, double lr, double reg) {
   return guarded([&] {
-    RFM_REQUIRE(ctx && d_ex && h_level_ptr && d_level_ptr && d_P && d_Q && d_bu && d_bi,
-                "null pointer");
+    RFM_REQUIRE(ctx && d_ex && h_level_ptr && d_level_ptr, "null pointer");
     RFM_REQUIRE(n_levels >= 0 && n_cached >= 0 && (n_cached == 0 || d_cache_items),
                 "bad schedule");
     const Shape s = shape_for(n_factors);
@@ -676,57 +680,37 @@ int32_t rfm_mf_sgd_levels_ex(rfm_ctx* ctx, const void* d_ex, const int32_t* h_le
     RFM_REQUIRE(cache_bytes <= size_t(kSeqMaxCacheBytes),
                 "item cache of %d rows exceeds %d bytes of LDS", n_cached, kSeqMaxCacheBytes);
     MfExArgs a{};
+    set_model(a, d_P, d_Q, d_bu, d_bi, b, n_factors, lr, reg);
     a.ex = static_cast<const MfEx*>(d_ex);
     a.level_ptr = d_level_ptr;
     a.cache_items = d_cache_items;
     a.n_cached = n_cached;
-    a.P = d_P;
-    a.Q = d_Q;
-    a.bu = d_bu;
-    a.bi = d_bi;
-    a.b = b;
-    a.k = n_factors;
-    a.lr = lr;
-    a.reg = reg;
-    // a level is "small" when the sequential workgroup covers it in one pass
+    // a level is "small" when the sequential workgroup covers it in one pass; a launch takes a
+    // run of them that fits the kernel's LDS tables
     const int seq_threads = seq_block(s.nc);
-    const int seq_cap = seq_threads / s.lpr;
-    int lev = 0;
-    while (lev < n_levels) {
-      const int cnt = h_level_ptr[lev + 1] - h_level_ptr[lev];
-      RFM_REQUIRE(cnt >= 0, "level_ptr not monotone");
-      if (cnt > seq_cap) {
-        a.lo = h_level_ptr[lev];
-        a.hi = h_level_ptr[lev + 1];
-        const int gpb = kMfBlock / s.lpr;
-        const int grid = capped_grid(ctx, cnt, gpb, 8, 0);
+    mf_walk_levels(
+        h_level_ptr, n_levels, seq_threads / s.lpr, kSeqMaxLevels, kSeqMaxRecs,
+        [&](int32_t rec_lo, int32_t rec_hi) {
+          a.lo = rec_lo;
+          a.hi = rec_hi;
+          const int grid = capped_grid(ctx, rec_hi - rec_lo, kMfBlock / s.lpr, 8, 0);
 #define RFM_CALL_WIDE_EX(L, Vv, N)                                                            \
   hipLaunchKernelGGL((mf_sgd_wide_ex_kernel<L, Vv, N>), dim3(grid), dim3(kMfBlock), 0,        \
                      ctx->stream, a)
-        RFM_FOR_SHAPE(s, RFM_CALL_WIDE_EX);
+          RFM_FOR_SHAPE(s, RFM_CALL_WIDE_EX);
 #undef RFM_CALL_WIDE_EX
-        ++lev;
-      } else {
-        // a chunk of consecutive small levels that fits the kernel's LDS tables
-        int end = lev;
-        while (end < n_levels && end - lev < kSeqMaxLevels) {
-          const int c = h_level_ptr[end + 1] - h_level_ptr[end];
-          RFM_REQUIRE(c >= 0, "level_ptr not monotone");
-          if (c > seq_cap || h_level_ptr[end + 1] - h_level_ptr[lev] > kSeqMaxRecs) break;
-          ++end;
-        }
-        a.lo = lev;
-        a.hi = end;
-        a.rec_lo = h_level_ptr[lev];
-        a.rec_hi = h_level_ptr[end];
-        const size_t lds = size_t((end - lev + 2) / 2) * 8 + size_t(a.rec_hi - a.rec_lo) * sizeof(MfEx) +
-                           cache_bytes;
+        },
+        [&](int32_t lev_lo, int32_t lev_hi) {
+          a.lo = lev_lo;
+          a.hi = lev_hi;
+          a.rec_lo = h_level_ptr[lev_lo];
+          a.rec_hi = h_level_ptr[lev_hi];
+          const size_t lds = size_t((lev_hi - lev_lo + 2) / 2) * 8 +
+                             size_t(a.rec_hi - a.rec_lo) * sizeof(MfEx) + cache_bytes;
 #define RFM_CALL_SEQ_EX(L, Vv, N) launch_seq_ex<L, Vv, N>(ctx, a, seq_threads, lds)
-        RFM_FOR_SHAPE(s, RFM_CALL_SEQ_EX);
+          RFM_FOR_SHAPE(s, RFM_CALL_SEQ_EX);
 #undef RFM_CALL_SEQ_EX
-        lev = end;
-      }
-    }
+        });
     RFM_HIP_CHECK(hipGetLastError());
   });
 }
@@ -737,13 +721,11 @@ int32_t rfm_mf_sgd_hogwild(rfm_ctx* ctx, const int32_t* d_users, const int32_t* 
                            double* d_bu, double* d_bi, double b, int32_t n_factors, double lr,
                            double reg) {
   return guarded([&] {
-    RFM_REQUIRE(ctx && d_users && d_items && d_y && d_pscore && d_pos_rows && d_P && d_Q &&
-                    d_bu && d_bi,
-                "null pointer");
+    RFM_REQUIRE(ctx && d_users && d_items && d_y && d_pscore && d_pos_rows, "null pointer");
     RFM_REQUIRE(batch >= 0 && batch < (int64_t(1) << 31), "batch out of range");
-    if (batch == 0) return;
-    const Shape s = shape_for(n_factors);
     MfSgdArgs a{};
+    set_model(a, d_P, d_Q, d_bu, d_bi, b, n_factors, lr, reg);
+    if (batch == 0) return;
     a.users = d_users;
     a.items = d_items;
     a.y = d_y;
@@ -752,21 +734,7 @@ int32_t rfm_mf_sgd_hogwild(rfm_ctx* ctx, const int32_t* d_users, const int32_t* 
     a.order = nullptr;  // batch order, all examples at once
     a.lo = 0;
     a.hi = int32_t(batch);
-    a.P = d_P;
-    a.Q = d_Q;
-    a.bu = d_bu;
-    a.bi = d_bi;
-    a.b = b;
-    a.k = n_factors;
-    a.lr = lr;
-    a.reg = reg;
-    const int gpb = kMfBlock / s.lpr;
-    const int grid = capped_grid(ctx, batch, gpb, 8, 0);
-#define RFM_CALL_HOG(L, Vv, N)                                                                \
-  hipLaunchKernelGGL((mf_sgd_wide_kernel<L, Vv, N>), dim3(grid), dim3(kMfBlock), 0, ctx->stream, \
-                     a)
-    RFM_FOR_SHAPE(s, RFM_CALL_HOG);
-#undef RFM_CALL_HOG
+    launch_wide(ctx, shape_for(n_factors), a);
     RFM_HIP_CHECK(hipGetLastError());
   });
 }

@@ -53,12 +53,12 @@ LOGIT_CLIP = 700                      # src/base.py:65 (rfm_device_utils.hpp:10 
 MAX_FACTORS = 1024                    # include/rfm_hip.h:49 RFM_MAX_FACTORS
 READ_AHEAD = 4                        # include/rfm_hip.h:51 RFM_MF_READ_AHEAD
 NO_WRITER = 1 << 30                   # include/rfm_hip.h:53 RFM_MF_NO_WRITER
-MF_BLOCK = 256                        # rfm_mf.hip:22 kMfBlock
-SEQ_BLOCK = 1024                      # rfm_mf.hip:23 kSeqBlock
-SEQ_BLOCK_CHUNKED = 512               # rfm_mf.hip:418 seq_block(nc > 1)
-SEQ_MAX_LEVELS = 1024                 # rfm_mf.hip:324 kSeqMaxLevels
-SEQ_MAX_RECS = 1024                   # rfm_mf.hip:325 kSeqMaxRecs
-GRID_PER_CU = 8                       # rfm_mf.hip:500, :634, :702, :764 capped_grid(..., 8, ...)
+MF_BLOCK = 256                        # rfm_mf.hip kMfBlock
+SEQ_BLOCK = 1024                      # rfm_mf.hip kSeqBlock
+SEQ_BLOCK_CHUNKED = 512               # rfm_mf.hip seq_block(nc > 1)
+SEQ_MAX_LEVELS = 1024                 # rfm_mf.hip kSeqMaxLevels
+SEQ_MAX_RECS = 1024                   # rfm_mf.hip kSeqMaxRecs
+GRID_PER_CU = 8                       # rfm_mf.hip capped_grid(..., 8, ...): mf_predict, launch_wide, the wide launch of rfm_mf_sgd_levels_ex
 ASSUMED_CUS = 256                     # CUs the host-side geometry test assumes (an MI355X has 256)
 
 
@@ -89,8 +89,9 @@ CLASS_RANGE = {
 
 
 def seq_cap(k, entry):
-    """Largest level the sequential workgroup takes: rfm_mf.hip:625 (rfm_mf_sgd_levels, two passes of
-    1024 threads) and :692-693 (rfm_mf_sgd_levels_ex, one pass of seq_block(nc) threads)."""
+    """Largest level the sequential workgroup takes, the seq_cap each entry hands mf_walk_levels in
+    rfm_mf.hip: rfm_mf_sgd_levels two passes of kSeqBlock threads, rfm_mf_sgd_levels_ex one pass of
+    seq_block(nc) threads."""
     lpr, _, nc = shape_class(k)
     if entry == "levels":
         return 2 * (SEQ_BLOCK // lpr)
@@ -105,9 +106,10 @@ def grid_pass(k, n_cu):
 
 def launch_plan(level_ptr, k, entry):
     """The launches of one call: ``("wide", rec_lo, rec_hi)`` for a level above seq_cap,
-    ``("seq", lev_lo, lev_hi)`` for a run of small levels.  Restates rfm_mf.hip:624-652 (``levels``:
-    the run ends only at a wide level) and :691-729 (``levels_ex``: it also ends after 1024 levels
-    and before the level that would take it past 1024 records)."""
+    ``("seq", lev_lo, lev_hi)`` for a run of small levels.  Restates mf_walk_levels of rfm_mf.hip as
+    the two entries call it (``levels``: no chunk limits, the run ends only at a wide level;
+    ``levels_ex``: it also ends after kSeqMaxLevels levels and before the level that would take it
+    past kSeqMaxRecs records)."""
     lp = [int(v) for v in level_ptr]
     n_levels, cap, plan, lev = len(lp) - 1, seq_cap(k, entry), [], 0
     while lev < n_levels:

@@ -48,14 +48,16 @@ def _check(rt, case, entries, want=None):
     runs = {"levels_ex": lambda: ms.run_levels_ex(rt, case, sched, init),
             "levels": lambda: ms.run_levels(rt, case, init),
             "hogwild": lambda: ms.run_hogwild(rt, case, init)}
+    out = {}
     for entry in entries:
-        got = _twice(runs[entry])
+        got = out[entry] = _twice(runs[entry])
         d = ms.assert_params_within(got, want, init, case.pairs, ms.MF_TOL, f"{case.name} {entry}")
         print(f"distance {case.name} {entry} {d:.3e}")
         # the ring's unused loads read row 0 of each array
         for absent, idx in ((not (case.users == 0).any(), (0, 2)), (not (case.items == 0).any(), (1, 3))):
             for j in idx if absent else ():
                 np.testing.assert_array_equal(got[j][0], init[j][0], err_msg=f"{case.name} {entry}: row 0 changed")
+    return out
 
 
 def _names(prefix):
@@ -69,7 +71,11 @@ def _names(prefix):
 def test_every_shape_class(rt, name):
     case = ms.step_cases()[name]
     assert [p[0] for p in case.want_plan["levels_ex"]] == [p[0] for p in case.want_plan["levels"]] == ["wide", "seq"]
-    _check(rt, case, ("levels_ex", "levels"))
+    got = _check(rt, case, ("levels_ex", "levels"))
+    # the two forms run the same mf_update on the same values in the same order, and label / propensity
+    # is the same IEEE division on the host (the records) and on the device (the plain form)
+    for name_, a, b in zip(("P", "Q", "b_u", "b_i"), got["levels"], got["levels_ex"]):
+        np.testing.assert_array_equal(a, b, err_msg=f"{case.name}: {name_} of levels and levels_ex differ")
 
 
 # --------------------------------------------------------------------------
