@@ -162,8 +162,9 @@ int32_t rfm_fm_forward_loss(rfm_ctx* ctx, const int64_t* d_indptr, const int32_t
  * reproducible results).  -2 = the default columns, summed in a fixed order as well
  * (each column's rows of a forward workgroup in row order, the workgroups in block
  * order): bitwise reproducible at a fraction of -1's cost; where the factor count has
- * no such kernel (more than 128 factors, or fewer than 17 at batches of the many-rows
- * shape) it means -1. */
+ * no such kernel (several chunks of factors per lane: more than 128 factors, or an odd
+ * count above 64; or, at batches of the many-rows shape, fewer than 16 lanes per row: an
+ * even count up to 16, an odd one up to 8) it means -1. */
 int32_t rfm_fm_plan_create(rfm_ctx* ctx, const int64_t* h_indptr, const int32_t* h_indices,
                            const double* h_values, const double* h_y, const double* h_pscore,
                            int64_t n_rows, int64_t n_features, int32_t n_factors,
@@ -327,6 +328,28 @@ int32_t rfm_fm_train_part(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indp
                           const double* d_val_values, const double* d_val_y,
                           const double* d_val_pscore, int64_t n_val, double eps,
                           double* d_out_train_loss, double* d_out_val_loss, int64_t call_iters);
+/* The launch shape of a forward of n_rows rows at n_factors factors (nothing is launched):
+ * h_out4[0]=threads per workgroup (1024: the many-rows shape, lane groups with several rows in
+ * flight; 256: one row per lane group), [1]=workgroups, [2]=rows of a workgroup's trip (lane
+ * groups * rows in flight), [3]=lanes per row.  records != 0: a forward through a plan's records
+ * (the training step, the train-loss forward); 0: through the caller's CSR arrays (rfm_fm_forward,
+ * rfm_fm_forward_loss, the validation-loss forward). */
+int32_t rfm_fm_forward_geometry(const rfm_ctx* ctx, int64_t n_rows, int32_t n_factors, int32_t records,
+                                int32_t* h_out4);
+/* The forms of the loss forwards that rfm_fm_train (call_iters = 0) or rfm_fm_train_part would
+ * take with this plan, batch, n_iters, call_iters and validation log, want_train / want_val saying
+ * which of d_out_train_loss / d_out_val_loss is given (nothing is launched; the environment
+ * switches are read as the call reads them): h_out8[0]=1 sliced by factors, [1]=1 both losses in
+ * one merged launch, [2]=1 the forwards leave scores and a run's logarithms come later, [3]=1 the
+ * train rows ride in the next step's forward launch, [4]=1 so do the validation rows, [5]=iterations
+ * of a run, [6]=threads per workgroup of the launch that scores the train-loss rows (0: not asked
+ * for), [7]=... the validation-loss rows.  Riding rows: [6] / [7] are the step's forward launch
+ * they ride in (256 threads); the rows of the call's LAST iteration, which has no next step, are
+ * scored by a launch of their own, of the one-row shape as well. */
+int32_t rfm_fm_train_forms(const rfm_ctx* ctx, const rfm_fm_plan* plan, int64_t batch, int64_t n_iters,
+                           int64_t call_iters, const int64_t* d_val_indptr, const int32_t* d_val_indices,
+                           const double* d_val_values, int64_t n_val, int32_t want_train, int32_t want_val,
+                           int32_t* h_out8);
 /* rfm_fm_train with the evaluator hook of the reference's search loop inside
  * (utils/search_params.py:96-111: fit(..., evaluator=ValEvaluator) -- after every iteration the
  * scores of the evaluation log, src/fm.py:104-110, and their IPS-DCG@k, utils/evaluate.py:160-207):

@@ -136,6 +136,8 @@ SIGNATURES = {
                      _vp, _vp, _vp, _vp, _vp, _i64, _f64, _vp, _vp],
     "rfm_fm_train_part": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _f64,
                           _vp, _vp, _vp, _vp, _vp, _i64, _f64, _vp, _vp, _i64],
+    "rfm_fm_forward_geometry": [_vp, _i64, _i32, _i32, _vp],
+    "rfm_fm_train_forms": [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
     "rfm_fm_train_eval": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _f64,
                      _vp, _vp, _vp, _vp, _vp, _i64, _f64, _vp, _vp,
                           _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _i64, _i64, _vp],

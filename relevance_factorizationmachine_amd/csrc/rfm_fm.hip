@@ -1064,6 +1064,73 @@ int32_t rfm_fm_train(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr,
   });
 }
 
+int32_t rfm_fm_forward_geometry(const rfm_ctx* ctx, int64_t n_rows, int32_t n_factors, int32_t records,
+                                int32_t* h_out4) {
+  return guarded([&] {
+    RFM_REQUIRE(ctx && h_out4, "null pointer");
+    RFM_REQUIRE(n_rows >= 1 && n_rows < (int64_t(1) << 31), "bad shape");
+    const Shape s = shape_for(n_factors);
+    const FwdGeom g = forward_geom(ctx, n_rows, s, records != 0);
+    const int r = g.block == kBigBlock ? (records ? rows_in_flight(s.nc) : rows_in_flight_plain(s.nc)) : 1;
+    h_out4[0] = g.block;
+    h_out4[1] = g.grid;
+    h_out4[2] = g.block / s.lpr * r;
+    h_out4[3] = s.lpr;
+  });
+}
+
+int32_t rfm_fm_train_forms(const rfm_ctx* ctx, const rfm_fm_plan* plan, int64_t batch, int64_t n_iters,
+                           int64_t call_iters, const int64_t* d_val_indptr, const int32_t* d_val_indices,
+                           const double* d_val_values, int64_t n_val, int32_t want_train, int32_t want_val,
+                           int32_t* h_out8) {
+  return guarded([&] {
+    RFM_REQUIRE(ctx && plan && h_out8, "null pointer");
+    RFM_REQUIRE(batch >= 1 && batch <= plan->max_batch, "batch=%lld outside 1..max_batch=%lld",
+                (long long)batch, (long long)plan->max_batch);
+    RFM_REQUIRE(n_iters >= 1 && (call_iters == 0 || call_iters >= n_iters), "bad iteration counts");
+    RFM_REQUIRE(!want_val || n_val >= 1, "validation arrays missing");
+    // (loss_forms only asks whether a loss is wanted: the outputs are never written through)
+    static double wanted;
+    FitCall c{};
+    c.ctx = const_cast<rfm_ctx*>(ctx);
+    c.plan = const_cast<rfm_fm_plan*>(plan);
+    c.batch = batch;
+    c.n_iters = n_iters;
+    c.val_indptr = d_val_indptr;
+    c.val_indices = d_val_indices;
+    c.val_values = d_val_values;
+    c.n_val = n_val;
+    c.out_train_loss = want_train ? &wanted : nullptr;
+    c.out_val_loss = want_val ? &wanted : nullptr;
+    c.form_iters = call_iters;
+    const LossForms f = loss_forms(c);
+    const Shape s = shape_for(plan->k);
+    // threads per workgroup of the launch that scores the rows of each loss (fit_loss_forwards,
+    // fit_step): the sliced kernel's, the merged launch's, the step's own forward for riding rows
+    // (whose last iteration is a launch of its own: loss_forms lets rows ride only where that
+    // launch takes the one-row shape too -- checked here, so that the answer holds for both)
+    const auto block_of = [&](int64_t rows, bool recs, bool rides) {
+      if (f.sliced.ok) return kSlBlock;
+      if (f.merge_call) return kBigBlock;
+      if (rides) return kSmallBlock;
+      return forward_geom(ctx, rows, s, recs).block;
+    };
+    if (f.ride)
+      RFM_REQUIRE(forward_geom(ctx, batch, s, true).block == kSmallBlock, "riding rows: unexpected geometry");
+    if (f.ride_val)
+      RFM_REQUIRE(forward_geom(ctx, n_val, s, false).block == kSmallBlock,
+                  "riding validation rows: unexpected geometry");
+    h_out8[0] = f.sliced.ok ? 1 : 0;
+    h_out8[1] = f.merge_call ? 1 : 0;
+    h_out8[2] = f.scores_only ? 1 : 0;
+    h_out8[3] = f.ride ? 1 : 0;
+    h_out8[4] = f.ride_val ? 1 : 0;
+    h_out8[5] = int32_t(f.run_len);
+    h_out8[6] = want_train ? block_of(batch, true, f.ride) : 0;
+    h_out8[7] = want_val ? block_of(n_val, false, f.ride_val) : 0;
+  });
+}
+
 int32_t rfm_fm_train_part(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indptr,
                           const int32_t* d_indices, const double* d_values, const double* d_y,
                           const double* d_pscore, const int32_t* d_ids, int64_t batch,

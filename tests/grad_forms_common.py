@@ -1,8 +1,10 @@
-"""Shared by the tests of the FM gradient forms (test_grad_oracle_host.py, test_gpu_grad_forms.py)
-and by test_gpu_parity.py: the small random logs, the long-double statement of the batch-SUM
-gradients with the magnitude every sum adds up, and thin wrappers of the raw ABI calls
-(rfm_fm_grad, rfm_fm_grad_rows, ...) that fill their outputs with NaN first and keep guard
-records behind them.  Importing this module touches neither the GPU nor the package under test.
+"""Shared by the tests of the FM gradient forms (test_grad_oracle_host.py, test_gpu_grad_forms.py),
+by the row-by-row tests of the FM forward (forward_rows_common.py, test_gpu_forward_rows.py) and
+by test_gpu_parity.py: the table of kernel classes, the small random logs, the long-double
+statement of the batch-SUM gradients with the magnitude every sum adds up, thin wrappers of the
+raw ABI calls (rfm_fm_grad, rfm_fm_grad_rows, ...) that fill their outputs with NaN first and keep
+guard records behind them, and the comparisons of a plan's dense gradient and record list.
+Importing this module touches neither the GPU nor the package under test.
 
 Tolerance of a device gradient against ``fm_gradients_ld``: element-wise
 ``|got - want| <= GRAD_TOL * S`` with S the sum of the absolute values of the terms of that
@@ -229,3 +231,90 @@ def grad_rows(dev, ids, params, cap, ranges=None):
     out.gw0 = float(out.d_gw0.cpu()[0])
     out.bounds = d_bounds.cpu().numpy() if nr else None
     return out
+
+
+# --------------------------------------------------------------------------
+# the kernel classes
+# --------------------------------------------------------------------------
+# (lanes per row, factors per lane and chunk, chunks per lane) of every factor count used by the tests:
+# one k per class that the dispatch on the factor count can return
+CLASS_OF = {
+    8: (4, 2, 1), 16: (8, 2, 1), 32: (16, 2, 1), 64: (32, 2, 1), 128: (64, 2, 1), 200: (64, 2, 2),
+    300: (64, 2, 3), 400: (64, 2, 4), 1024: (64, 2, 8),
+    1: (4, 1, 1), 3: (4, 1, 1), 7: (8, 1, 1), 13: (16, 1, 1), 31: (32, 1, 1), 63: (64, 1, 1), 65: (64, 1, 2),
+    191: (64, 1, 3), 255: (64, 1, 4), 511: (64, 1, 8), 513: (64, 1, 16),
+    33: (64, 1, 1),
+}
+
+
+def class_id(k):
+    lpr, vec, nc = CLASS_OF[k]
+    return f"lpr{lpr}-vec{vec}-nc{nc}-k{k}"
+
+
+def chunked(k):
+    return CLASS_OF[k][2] > 1
+
+
+def fixed_order(k, hot):
+    return hot in (-1, -2) or chunked(k)
+
+
+# --------------------------------------------------------------------------
+# the comparisons of a plan's gradient forms (test_gpu_grad_forms.py, test_gpu_forward_rows.py)
+# --------------------------------------------------------------------------
+def check_dense(g, dev, ids, oracle, hot_cols, what):
+    """A dense gradient against the oracle; exact zeros where no row of the batch holds the column."""
+    n, k = dev.n, dev.k
+    assert not np.isnan(g).any(), f"{what}: an element of d_grad was not written"
+    G_V, g_w, g_w0 = split_grad(g, n, k)
+    o_w0, o_w, o_V, (S_0, S_w, S_V) = oracle
+    tol = grad_tol(len(ids))
+    assert_within_scale(G_V, o_V, S_V, tol, f"{what} G_V")
+    assert_within_scale(g_w, o_w, S_w, tol, f"{what} g_w")
+    assert_within_scale(g_w0, o_w0, S_0, tol, f"{what} g_w0")
+    touched = np.unique(dev.X[ids].indices)
+    cold = np.setdiff1d(np.arange(n), np.union1d(touched, hot_cols))
+    assert not G_V[cold].any() and not g_w[cold].any(), f"{what}: an untouched column is not exactly zero"
+    return touched
+
+
+def check_records(rec, g, dev, touched, hot_cols, fixed, what):
+    """A record list against the dense gradient of the same rows."""
+    from conftest import rel_err
+    n, k = dev.n, dev.k
+    want_cols = np.union1d(touched, hot_cols)  # (a shard that is not empty lists every hot column)
+    assert rec.count == len(want_cols) <= rec.cap, (what, rec.count, len(want_cols))
+    r = rec.filled()
+    cols = r[:, 0].astype(np.int64)
+    np.testing.assert_array_equal(r[:, 0], cols.astype(np.float64))
+    assert np.all(np.diff(cols) > 0), f"{what}: records do not ascend strictly"
+    np.testing.assert_array_equal(cols, want_cols)
+    G_V, g_w, g_w0 = split_grad(g, n, k)
+    if fixed:  # every sum of a step has a fixed order: two calls give the same bits
+        np.testing.assert_array_equal(r[:, 1: k + 1], G_V[cols], err_msg=f"{what} G_V")
+        np.testing.assert_array_equal(r[:, k + 1], g_w[cols], err_msg=f"{what} g_w")
+        assert rec.gw0 == g_w0, what
+    else:
+        assert rel_err(r[:, 1: k + 1], G_V[cols]) < 1e-13, what
+        assert rel_err(r[:, k + 1], g_w[cols]) < 1e-13, what
+        assert abs(rec.gw0 - g_w0) <= 1e-13 * max(abs(g_w0), 1e-300), what
+    rec.assert_rest_untouched()
+
+
+def check_all_forms(dev, params, full_ids, shard_ids, oracle_full, oracle_shard, fixed):
+    """On ONE plan, in this order: dense gradient of the full batch, of the shard, then the records
+    of the full batch, of the shard."""
+    hot_cols = dev.plan.hot_columns()
+    g_full, _ = dense_grad(dev, full_ids, params)
+    g_shard, _ = dense_grad(dev, shard_ids, params)
+    rec_full = grad_rows(dev, full_ids, params, dev.n)
+    rec_shard = grad_rows(dev, shard_ids, params, dev.n)
+    t_full = check_dense(g_full, dev, full_ids, oracle_full, hot_cols, "full batch")
+    t_shard = check_dense(g_shard, dev, shard_ids, oracle_shard, hot_cols, "shard")
+    check_records(rec_full, g_full, dev, t_full, hot_cols, fixed, "full batch records")
+    check_records(rec_shard, g_shard, dev, t_shard, hot_cols, fixed, "shard records")
+
+
+def grad_oracle(log, ids, w0, w, V):
+    return fm_gradients_ld(log["features"][ids], log["labels"][ids], log["pscores"][ids], w0, w, V)
