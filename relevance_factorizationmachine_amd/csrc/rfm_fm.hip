@@ -356,27 +356,22 @@ int launch_step_forward(rfm_ctx* ctx, FwdArgs f, const XtraRows* xtra) {
 // the step's consume launch (fm_consume_kernel): the slot-ordered sums and the updates
 void launch_consume(rfm_ctx* ctx, ConsArgs c, const Shape& s) {
   const int grid = c.nb_tasks + c.n_hot + 1;  // tasks, then the hot columns, then w0
-  // LDS: the groups' lists + parked records + head rows, or the hot workgroups' scratch
-  const int gpb = kBlock / s.lpr;
-  const int win = s.lpr >= 32 ? 64 : 4 * s.lpr;  // WinShape<LPR>::WIN
-  const size_t lds = std::max<size_t>(size_t(gpb) * size_t(win) * (sizeof(WinRec) + 8) +
-                                          size_t(gpb) * size_t(c.k + 3) * 8,
-                                      size_t(kBlock + 1024 + 2) * 8);
+  const size_t lds = consume_lds_bytes(s.lpr, c.c.k);
   if (s.nc > 1) {
     // one workgroup per (four tasks, chunk of 64 lanes x vec factors)
-    const int n_chunks = ((c.k + s.vec - 1) / s.vec + 63) / 64;
+    const int n_chunks = fm_chunks(c.c.k, s.vec);
     c.n_chunks = n_chunks;
     // chunks dealt to XCDs (see the kernel): every chunk gets at least 8 / n_chunks XCDs
     c.xcd_chunks = n_chunks <= 8 ? 1 : 0;
     const int per_chunk = 8 / n_chunks;  // (the fewest XCDs a chunk gets)
     const dim3 g2 = c.xcd_chunks ? dim3(8 * ((grid + per_chunk - 1) / per_chunk)) : dim3(grid, n_chunks);
     if (s.vec == 2)
-      hipLaunchKernelGGL((fm_consume_kernel<64, 2, 1, true>), g2, dim3(kBlock), lds, ctx->stream, c);
+      hipLaunchKernelGGL((fm_consume_kernel<64, 2, true>), g2, dim3(kBlock), lds, ctx->stream, c);
     else
-      hipLaunchKernelGGL((fm_consume_kernel<64, 1, 1, true>), g2, dim3(kBlock), lds, ctx->stream, c);
+      hipLaunchKernelGGL((fm_consume_kernel<64, 1, true>), g2, dim3(kBlock), lds, ctx->stream, c);
   } else {
 #define RFM_CALL_CONS(L, Vv, N) \
-  hipLaunchKernelGGL((fm_consume_kernel<L, Vv, N>), dim3(grid), dim3(kBlock), lds, ctx->stream, c)
+  hipLaunchKernelGGL((fm_consume_kernel<L, Vv>), dim3(grid), dim3(kBlock), lds, ctx->stream, c)
     RFM_FOR_SINGLE_CHUNK_SHAPE(s, RFM_CALL_CONS);
 #undef RFM_CALL_CONS
   }
@@ -389,14 +384,14 @@ void launch_finalize(rfm_ctx* ctx, const FinArgs& fa, const Shape& s) {
   const int nb_short = (fa.n_split_short + gpb - 1) / gpb;
   const int grid = nb_short + fa.n_split_long;
   if (s.nc > 1) {
-    const dim3 g2(grid, ((fa.k + s.vec - 1) / s.vec + 63) / 64);
+    const dim3 g2(grid, fm_chunks(fa.c.k, s.vec));
     if (s.vec == 2)
       hipLaunchKernelGGL(fm_finalize_chunk_kernel<2>, g2, dim3(kBlock), 0, ctx->stream, fa, nb_short);
     else
       hipLaunchKernelGGL(fm_finalize_chunk_kernel<1>, g2, dim3(kBlock), 0, ctx->stream, fa, nb_short);
   } else {
-#define RFM_CALL_FIN(L, Vv, N)                                                                 \
-  hipLaunchKernelGGL((fm_finalize_kernel<L, Vv, N>), dim3(grid), dim3(kBlock), 0, ctx->stream, \
+#define RFM_CALL_FIN(L, Vv, N)                                                              \
+  hipLaunchKernelGGL((fm_finalize_kernel<L, Vv>), dim3(grid), dim3(kBlock), 0, ctx->stream, \
                      fa, nb_short)
     RFM_FOR_SINGLE_CHUNK_SHAPE(s, RFM_CALL_FIN);
 #undef RFM_CALL_FIN
@@ -432,8 +427,19 @@ void enqueue_step(rfm_ctx* ctx, rfm_fm_plan* plan, const int32_t* d_row_ids, int
     const size_t bytes = (size_t(plan->n_features) * (k + 1) + 1) * sizeof(double);
     RFM_HIP_CHECK(hipMemsetAsync(d_grad, 0, bytes, ctx->stream));
   }
-  const double stamp = double(++plan->step);
+  ColArgs col{};  // what both launches need to finish a column
+  col.V = d_V;
+  col.w = d_w;
+  col.k = k;
+  col.n = plan->n_features;
+  col.lr = lr;
+  col.grad = d_grad;
+  col.touch = d_touch;
+  col.touch_id = touch_id;
+  col.parts = plan->parts.as<double>();
+  col.stamp = double(++plan->step);
   ConsArgs c{};
+  c.c = col;
   c.tasks = plan->tasks.as<TaskRec>();
   c.task_words = plan->task_words;
   c.slot_bits = bits;
@@ -441,17 +447,7 @@ void enqueue_step(rfm_ctx* ctx, rfm_fm_plan* plan, const int32_t* d_row_ids, int
   c.slot_mark = plan->slot_t.as<SlotMark>();
   c.slots = plan->slots.as<SlotRec>();
   c.Q = plan->Q.as<double>();
-  c.k = k;
-  c.n = plan->n_features;
   c.w0 = d_w0;
-  c.V = d_V;
-  c.w = d_w;
-  c.lr = lr;
-  c.parts = plan->parts.as<double>();
-  c.stamp = stamp;
-  c.grad = d_grad;
-  c.touch = d_touch;
-  c.touch_id = touch_id;
   c.nb_tasks = plan->n_task_blocks;  // one task per lane group
   c.n_hot = plan->n_hot;
   c.hot_cols = plan->hot_cols.as<int32_t>();
@@ -463,19 +459,10 @@ void enqueue_step(rfm_ctx* ctx, rfm_fm_plan* plan, const int32_t* d_row_ids, int
   // columns cut into several tasks (none on most plans): their partial rows
   if (plan->n_split_short + plan->n_split_long > 0) {
     FinArgs fa{};
+    fa.c = col;
     fa.split = plan->split.as<SplitCol>();
     fa.n_split_short = plan->n_split_short;
     fa.n_split_long = plan->n_split_long;
-    fa.parts = plan->parts.as<double>();
-    fa.stamp = stamp;
-    fa.k = k;
-    fa.n = plan->n_features;
-    fa.w = d_w;
-    fa.V = d_V;
-    fa.lr = lr;
-    fa.grad = d_grad;
-    fa.touch = d_touch;
-    fa.touch_id = touch_id;
     launch_finalize(ctx, fa, s);
   }
   ctx->prof_mark();

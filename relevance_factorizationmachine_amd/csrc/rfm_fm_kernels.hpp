@@ -804,15 +804,13 @@ __global__ __launch_bounds__(kBlock) void logloss_kernel(const double* y, const 
 // ---------------------------------------------------------------------------
 // fixed-order reductions over rows of a table (used by launches 2 and 3)
 // ---------------------------------------------------------------------------
-// tot[f] = sum_{r<rows} base[r*width + f], f < width, rows contiguous, in a
-// fixed order: the block's threads split into row groups x factor lanes, each
-// group sums its rows in ascending order (16 loads in flight), the groups are
-// then added in group order.
-__device__ inline void ordered_rows_sum(const double* base, int rows, int width,
+// tot[f] = sum over the valid rows r < rows of row(r)[f], f < width, in a fixed order: the
+// block's threads split into row groups x factor lanes, each group sums its rows in ascending
+// order (U loads in flight per thread), the groups are then added in group order.
+// Rows: row(r) = where row r starts, valid(row) = whether it counts.
+template <int U, class Rows>
+__device__ inline void ordered_rows_sum(const Rows& from, int rows, int width,
                                         double* scratch /*[kBlock]*/, double* tot /*[width]*/) {
-  // (loads in flight per thread: one round covers the slabs of a small batch's forward --
-  // 125 workgroups at B = 2 000 -- with seven row groups at k = 32)
-  constexpr int U = 32;
   const int fw = width < kBlock ? width : kBlock;  // factor lanes per row group
   const int nsg = kBlock / fw;
   const int sg = threadIdx.x / fw, fl = threadIdx.x % fw;
@@ -822,15 +820,19 @@ __device__ inline void ordered_rows_sum(const double* base, int rows, int width,
     double acc = 0.0;
     if (live && f < width) {
       for (int r = sg; r < rows; r += nsg * U) {
+        const double* row[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) row[u] = from.row(r + u * nsg < rows ? r + u * nsg : r);
         double v[U];
+        bool ok[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-          const int rr = r + u * nsg;
-          v[u] = base[int64_t(rr < rows ? rr : r) * width + f];
-          if (rr >= rows) v[u] = 0.0;
+          v[u] = row[u][f];
+          const bool counts = from.valid(row[u]);  // (read whether or not the row is in range)
+          ok[u] = counts && r + u * nsg < rows;
         }
 #pragma unroll
-        for (int u = 0; u < U; ++u) acc += v[u];
+        for (int u = 0; u < U; ++u) acc += ok[u] ? v[u] : 0.0;
       }
     }
     __syncthreads();
@@ -845,48 +847,24 @@ __device__ inline void ordered_rows_sum(const double* base, int rows, int width,
   __syncthreads();
 }
 
-// Same for the stamped partial rows of one split column: rows first .. first+rows-1 of
-// `parts`, each valid iff its stamp is this step's.
-__device__ inline void ordered_part_sum(const double* parts, int first, int rows, int k,
-                                        double stamp, double* scratch, double* tot) {
-  constexpr int U = 8;
-  const int width = k + 2;
-  const int fw = width < kBlock ? width : kBlock;
-  const int nsg = kBlock / fw;
-  const int sg = threadIdx.x / fw, fl = threadIdx.x % fw;
-  const bool live = sg < nsg;
-  for (int f0 = 0; f0 < width; f0 += fw) {
-    const int f = f0 + fl;
-    double acc = 0.0;
-    if (live && f < width) {
-      for (int r = sg; r < rows; r += nsg * U) {
-        const double* row[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int rr = r + u * nsg;
-          row[u] = parts + int64_t(first + (rr < rows ? rr : r)) * (k + 3);
-        }
-        double v[U], st[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          v[u] = row[u][f];
-          st[u] = row[u][k + 2];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) acc += (r + u * nsg < rows && st[u] == stamp) ? v[u] : 0.0;
-      }
-    }
-    __syncthreads();
-    scratch[threadIdx.x] = acc;
-    __syncthreads();
-    if (sg == 0 && f < width) {
-      double s = 0.0;
-      for (int j = 0; j < nsg; ++j) s += scratch[j * fw + fl];
-      tot[f] = s;
-    }
-  }
-  __syncthreads();
-}
+// the forward workgroups' slabs of one hot column: contiguous rows of `width`, all of them valid
+// (32 loads in flight: one round covers the slabs of a small batch's forward -- 125 workgroups at
+// B = 2 000 -- with seven row groups at k = 32)
+struct SlabRows {
+  const double* base;
+  int width;
+  __device__ const double* row(int r) const { return base + int64_t(r) * width; }
+  __device__ bool valid(const double*) const { return true; }
+};
+
+// the partial rows first .. of one split column ([k+3] each), valid iff stamped with this step
+struct PartRows {
+  const double* parts;
+  int first, k;
+  double stamp;
+  __device__ const double* row(int r) const { return parts + int64_t(first + r) * (k + 3); }
+  __device__ bool valid(const double* row) const { return row[k + 2] == stamp; }
+};
 
 // ---------------------------------------------------------------------------
 // 2. sparse-class gradient + update (tasks of whole columns), hot columns, w0
@@ -898,7 +876,22 @@ struct WinRec {  // a marked slot of the word being processed, parked in LDS, 24
   double cx;     // err_t * x * x
 };
 
+// what launches 2 and 3 both need to finish a column
+struct ColArgs {
+  double* V;        // apply mode: updated in place; grad mode: read only
+  double* w;
+  int32_t k;
+  int64_t n;        // features
+  double lr;
+  double* grad;     // nullable: grad mode -> [G_V | g_w | g_w0]
+  int32_t* touch;   // nullable (grad mode): touch[col] = touch_id for every column written
+  int32_t touch_id;
+  double* parts;    // [n_parts][k+3]: M[0..k), sum coef, sum coef*x, step stamp (split columns)
+  double stamp;     // id of this step (a partial row is valid iff its stamp matches)
+};
+
 struct ConsArgs {
+  ColArgs c;
   const TaskRec* tasks;  // [nb_tasks * tasks per workgroup]
   int32_t task_words;    // 64-slot words of the slot bitmap per task
   unsigned long long* slot_bits;  // one bit per slot: set by the forward, cleared here
@@ -906,17 +899,7 @@ struct ConsArgs {
   const SlotMark* slot_mark;      // {batch position, residual} of a marked slot's row
   const SlotRec* slots;
   const double* Q;
-  int32_t k;
-  int64_t n;        // features
   double* w0;
-  double* V;        // apply mode: updated in place; grad mode: read only
-  double* w;
-  double lr;
-  double* parts;    // [n_parts][k+3]: M[0..k), sum coef, sum coef*x, step stamp (split columns)
-  double stamp;     // id of this step (a partial row is valid iff its stamp matches)
-  double* grad;     // nullable: grad mode -> [G_V | g_w | g_w0]
-  int32_t* touch;   // nullable (grad mode): touch[col] = touch_id for every column written
-  int32_t touch_id;
   // the hot columns and w0 ride in the same launch: the workgroups after the tasks reduce
   // the forward's slabs / residual sums (independent of the sparse class, so they overlap)
   int32_t nb_tasks;  // workgroups that process tasks
@@ -925,64 +908,128 @@ struct ConsArgs {
   const double* hot_slab;
   int32_t n_slabs;
   const double* err_partial;  // [n_slabs] per-workgroup sums of the residual
-  int32_t n_chunks;           // CH form: chunks of 64 lanes x VEC factors
+  int32_t n_chunks;           // CH form: chunks of 64 lanes x VEC factors (fm_chunks)
   int32_t xcd_chunks;         // CH form: 1 = chunks dealt to XCDs (1-D grid), 0 = blockIdx.y
 };
 
-template <int VEC, int NC>
+// chunks of 64 lanes x vec factors that cover a row of k factors
+inline int fm_chunks(int k, int vec) { return ((k + vec - 1) / vec + 63) / 64; }
+
+// The sums of one column in a lane group: the lane's VEC factors of M (factor f = first factor of
+// the group's chunk + lane * VEC on), sum coef, sum coef * x.  A [k+3] row -- a group's head row
+// in LDS, a partial row in memory -- holds the same: [0..k) M, [k] sum coef, [k+1] sum coef * x;
+// its word [k+2] belongs to the caller (flags of a head row, the stamp of a partial row).
+template <int VEC>
 struct ColAcc {
-  double m[NC][VEC];
+  double m[VEC];
   double gw, d;
   __device__ inline void clear() {
 #pragma unroll
-    for (int c = 0; c < NC; ++c)
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) m[c][v] = 0.0;
+    for (int v = 0; v < VEC; ++v) m[v] = 0.0;
     gw = 0.0;
     d = 0.0;
   }
+  // into a row; the scalar part by the one lane that has `scalars`
+  __device__ inline void store_row(double* row, int f, int k, bool scalars) const {
+    if (f < k) {
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) row[f + v] = m[v];
+    }
+    if (scalars) {
+      row[k] = gw;
+      row[k + 1] = d;
+    }
+  }
+  // += a row
+  __device__ inline void add_row(const double* row, int f, int k) {
+    if (f < k) {
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) m[v] += row[f + v];
+    }
+    gw += row[k];
+    d += row[k + 1];
+  }
+  // a row read whole before it is known whether it counts (fc = f, or 0 past the row's end), ...
+  __device__ inline void load_row(const double* row, int fc, int k) {
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) m[v] = row[fc + v];
+    gw = row[k];
+    d = row[k + 1];
+  }
+  // ... then added if it does
+  __device__ inline void add_if(bool ok, const ColAcc& o) {
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) m[v] += ok ? o.m[v] : 0.0;
+    gw += ok ? o.gw : 0.0;
+    d += ok ? o.d : 0.0;
+  }
 };
 
-// V[col,:] and w[col] from the sums of one column: update in place, or write the
-// gradient row (grad mode).  vold = the row as it was read before.
-// (fb: first factor of the chunk this lane group works on -- 0 unless the chunks of a row are
-// dealt to different workgroups; the scalar part, w / touch, is then written by chunk 0)
+// the lane's factors of V[col,:] (any factors of the row where the lane has none: f >= k)
+template <int VEC>
+__device__ inline Pack<VEC> load_v_row(const double* V, int32_t col, int k, int f) {
+  Pack<VEC> p;
+  p.load(V + int64_t(col) * k + (f < k ? f : 0));
+  return p;
+}
+
+// THE UPDATE RULE.  A factor of V from the sums of its column (m = sum coef * Q[t,f], d = sum
+// coef * x; vold = the factor as it was read before): its gradient g = d * vold - m, or its new
+// value vold - lr * g.  The roundings are spelled out, because the results are compared bit for
+// bit from build to build: the step is one fused multiply-add; so is g, except where `dv_rounded`
+// asks for the product d * vold rounded on its own before the subtraction.  That is the first
+// factor of a lane at the lane-group sites (apply_column), and a record of how the expression
+// came out of the compiler when every site spelled it for itself -- the product both branches
+// share was hoisted for the first factor only.  One rounding everywhere would be the better rule
+// and a change of results.
+__device__ inline double updated_factor(double vold, double m, double d, double lr, bool grad,
+                                        bool dv_rounded) {
+  double g;
+  if (dv_rounded) {
+#pragma clang fp contract(off)
+    const double dv = d * vold;
+    g = dv - m;
+  } else {
+    g = fma(d, vold, -m);
+  }
+  return grad ? g : fma(lr, -g, vold);
+}
+
 // *p += x by its only writer of the step.  As `*p += x` the wavefront stands still for the load of *p
 // (nothing else waits for it) -- once per finished column in the gradient launch, eight times per task
 // where columns are short, and one dependent level in the finalize; the no-return atomic add gives the
 // same sum without the wait.
 __device__ inline void add_by_only_writer(double* p, double x) { unsafeAtomicAdd(p, x); }
 
-template <int LPR, int VEC, int NC>
-__device__ inline void apply_column(const ColAcc<VEC, NC>& acc, const Pack<VEC> (&vold)[NC],
-                                    int32_t col, double* V, double* w, double* grad, int64_t n,
-                                    int k, double lr, int l, int32_t* touch = nullptr,
-                                    int32_t touch_id = 0, int fb = 0) {
+// ... and a scalar parameter from the sum s of its residual terms, by one thread: *p += lr * s in
+// place, or grad[n*k + at] = -s
+__device__ inline void apply_scalar(const ColArgs& c, double* p, int64_t at, double s) {
+  if (c.grad)
+    c.grad[c.n * c.k + at] = -s;
+  else
+    add_by_only_writer(p, c.lr * s);
+}
+
+// w[col] so, with the column's mark in touched-row mode (the row is valid for this step)
+__device__ inline void apply_w(const ColArgs& c, int32_t col, double gw) {
+  apply_scalar(c, c.w + col, col, gw);
+  if (c.grad && c.touch) c.touch[col] = c.touch_id;
+}
+
+// V[col,:] and w[col] from the sums of one column in a lane group: update in place, or write the
+// gradient row (grad mode).  vold = the lane's factors f.. of the row as they were read before;
+// `scalars`: this lane writes w / touch (lane 0 of the group that has the row's first chunk).
+template <int VEC>
+__device__ inline void apply_column(const ColArgs& c, int32_t col, const ColAcc<VEC>& acc,
+                                    const Pack<VEC>& vold, int f, bool scalars) {
+  if (f < c.k) {
+    Pack<VEC> out;
 #pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int f = fb + (c * LPR + l) * VEC;
-    if (f < k) {
-      Pack<VEC> out;
-      if (grad) {
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) out.v[v] = acc.d * vold[c].v[v] - acc.m[c][v];
-        out.store(grad + int64_t(col) * k + f);
-      } else {
-#pragma unroll
-        for (int v = 0; v < VEC; ++v)
-          out.v[v] = vold[c].v[v] + lr * (acc.m[c][v] - acc.d * vold[c].v[v]);
-        out.store(V + int64_t(col) * k + f);
-      }
-    }
+    for (int v = 0; v < VEC; ++v)
+      out.v[v] = updated_factor(vold.v[v], acc.m[v], acc.d, c.lr, c.grad != nullptr, v == 0);
+    out.store((c.grad ? c.grad : c.V) + int64_t(col) * c.k + f);
   }
-  if (l == 0 && fb == 0) {
-    if (grad) {
-      grad[n * k + col] = -acc.gw;
-      if (touch) touch[col] = touch_id;  // touched-row mode: the row is valid for this step
-    } else {
-      add_by_only_writer(w + col, lr * acc.gw);
-    }
-  }
+  if (scalars) apply_w(c, col, acc.gw);
 }
 
 // The same from a whole workgroup, sums in LDS: tot[0..k) = M, tot[k] = sum coef,
@@ -990,28 +1037,17 @@ __device__ inline void apply_column(const ColAcc<VEC, NC>& acc, const Pack<VEC> 
 // (vpre: the row as the caller read it before the sums were formed -- threadIdx.x + j * kBlock
 // -- so that the load is in flight beside the sums' own loads; null: read here)
 constexpr int kRowPre = (RFM_MAX_FACTORS + kBlock - 1) / kBlock;
-__device__ inline void apply_column_block(const double* tot, int32_t col, double* V, double* w,
-                                          double* grad, int64_t n, int k, double lr,
-                                          int32_t* touch, int32_t touch_id,
+__device__ inline void apply_column_block(const ColArgs& c, int32_t col, const double* tot,
                                           const double* vpre = nullptr) {
+  const int k = c.k;
   const double gw = tot[k], d = tot[k + 1];
   int j = 0;
   for (int f = threadIdx.x; f < k; f += kBlock, ++j) {
     const int64_t at = int64_t(col) * k + f;
-    const double vold = vpre ? vpre[j] : V[at];
-    if (grad)
-      grad[at] = d * vold - tot[f];
-    else
-      V[at] = vold + lr * (tot[f] - d * vold);
+    const double vold = vpre ? vpre[j] : c.V[at];
+    (c.grad ? c.grad : c.V)[at] = updated_factor(vold, tot[f], d, c.lr, c.grad != nullptr, false);
   }
-  if (threadIdx.x == 0) {
-    if (grad) {
-      grad[n * k + col] = -gw;
-      if (touch) touch[col] = touch_id;
-    } else {
-      add_by_only_writer(w + col, lr * gw);
-    }
-  }
+  if (threadIdx.x == 0) apply_w(c, col, gw);
 }
 
 // slots a lane group handles per pass over a 64-slot word of the bitmap: PLANES pieces of
@@ -1020,7 +1056,28 @@ template <int LPR>
 struct WinShape {
   static constexpr int PLANES = LPR >= 64 ? 1 : (LPR == 32 ? 2 : 4);
   static constexpr int WIN = PLANES * LPR;  // 64 for LPR >= 16; 16 / 32 for LPR = 4 / 8
+  // LDS of a lane group: the parked records and the list of the slots it has marked
+  static constexpr int kGroupBytes = WIN * (int(sizeof(WinRec)) + 8);
 };
+
+// LDS of a workgroup of fm_consume_kernel: per group the list of marked slots and their parked
+// records, then the groups' head rows; or (hot-column / w0 workgroups) reduction scratch and totals
+constexpr int kConsHotBytes = (kBlock + 1024 + 2) * int(sizeof(double));
+template <int LPR>
+constexpr size_t consume_lds_bytes_of(int k) {
+  constexpr size_t gpb = kBlock / LPR;
+  const size_t tasks = gpb * WinShape<LPR>::kGroupBytes + gpb * size_t(k + 3) * sizeof(double);
+  return tasks > size_t(kConsHotBytes) ? tasks : size_t(kConsHotBytes);
+}
+inline size_t consume_lds_bytes(int lpr, int k) {
+  switch (lpr) {
+    case 4: return consume_lds_bytes_of<4>(k);
+    case 8: return consume_lds_bytes_of<8>(k);
+    case 16: return consume_lds_bytes_of<16>(k);
+    case 32: return consume_lds_bytes_of<32>(k);
+    default: return consume_lds_bytes_of<64>(k);
+  }
+}
 
 // inclusive prefix sum over the LPR lanes of a lane group
 template <int LPR>
@@ -1031,6 +1088,31 @@ __device__ inline int group_scan(int v, int l) {
     if (l >= o) v += up;
   }
   return v;
+}
+
+// A hot column, by one workgroup: the forward workgroups' slabs, in block order; the column's row
+// of V is requested first, so that it arrives with the slabs and not after them.
+__device__ inline void consume_hot_column(const ConsArgs& a, int hb, double* lds) {
+  const int k = a.c.k;
+  const int32_t col = a.hot_cols[hb];
+  double vpre[kRowPre];
+#pragma unroll
+  for (int j = 0; j < kRowPre; ++j) {
+    const int f = int(threadIdx.x) + j * kBlock;
+    vpre[j] = a.c.V[int64_t(col) * k + (f < k ? f : 0)];
+  }
+  double* tot = lds + kBlock;
+  ordered_rows_sum<32>(SlabRows{a.hot_slab + int64_t(hb) * a.n_slabs * (k + 2), k + 2}, a.n_slabs,
+                       k + 2, lds, tot);
+  apply_column_block(a.c, col, tot, vpre);
+}
+
+// w0, by one workgroup, from the forward workgroups' residual sums
+__device__ inline void consume_w0(const ConsArgs& a, double* lds) {
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < a.n_slabs; i += kBlock) acc += a.err_partial[i];
+  const double s = block_sum<kBlock>(acc, lds);
+  if (threadIdx.x == 0) apply_scalar(a.c, a.w0, a.c.n, s);
 }
 
 // One TASK per lane group: `task_words` 64-slot words of the slot view, the same number for
@@ -1050,19 +1132,19 @@ __device__ inline int group_scan(int v, int l) {
 // launch follows the batch (marked slots): an untouched task reads its bitmap words and
 // waits at the barrier.
 // (The lane groups of a wave run in lock step: ballots and shuffles are wave-wide.)
-// CH (factor counts of more than one chunk per lane): the chunks of a row are dealt to
-// DIFFERENT workgroups -- blockIdx.y = chunk, LPR x VEC factors each, NC = 1 in registers -- so
-// that a task's chain is one 16-byte load per lane and entry instead of NC of them, NC times as
-// many lane groups share the step's entries (measured at k = 400, B = 2 000: equal to the
-// all-chunks-in-registers form within noise -- both wait on the same chain of dependent levels --
-// at half the registers and with one instantiation for every chunk count).  Every
+// A lane holds VEC factors of a row: one chunk of LPR x VEC factors covers it, or -- CH, factor
+// counts of more than one chunk per lane -- the chunks of a row are dealt to DIFFERENT workgroups
+// (blockIdx.y = chunk), so that a task's chain is one 16-byte load per lane and entry whatever
+// the chunk count, and that many times as many lane groups share the step's entries (measured at
+// k = 400, B = 2 000: equal to a form with all chunks in registers within noise -- both wait on the
+// same chain of dependent levels -- at half the registers and with one instantiation for every
+// chunk count).  Every
 // chunk lists the task's marks itself (same bitmap words: they hit in L2), so the words cannot be
 // cleared while a sibling may still read them: the bitmap is double-buffered by step parity and
 // chunk 0 clears the task's words of the OTHER buffer (the step before, long consumed).
 constexpr int kConsChBatch = 4;  // CH form: entries whose Q and V rows are in flight together
-template <int LPR, int VEC, int NC, bool CH = false>
+template <int LPR, int VEC, bool CH = false>
 __global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
-  static_assert(!CH || NC == 1, "the chunked form holds one chunk per lane group");
   constexpr int GPB = kBlock / LPR;  // tasks of a workgroup
   constexpr int PLANES = WinShape<LPR>::PLANES;
   constexpr int WIN = WinShape<LPR>::WIN;  // marked slots a group lists before it runs the chain
@@ -1085,49 +1167,26 @@ __global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
   }
   const int fb = chunk * (LPR * VEC);  // first factor of this workgroup's chunk
   constexpr int TRIPS = kTaskTrips;        // bitmap words a lane loads (task_words <= TRIPS*LPR)
-  // LDS: per group the list of marked slots and their parked records, then the head rows; or
-  // (hot-column / w0 workgroups) reduction scratch
-  constexpr int kGroupBytes = WIN * (int(sizeof(WinRec)) + 8);
-  constexpr int kHotBytes = (kBlock + 1024 + 2) * int(sizeof(double));
-  extern __shared__ double lds_raw[];  // max(GPB * kGroupBytes + GPB * (k+3) * 8, kHotBytes)
-  const int k = a.k;
-  // the hot-column workgroups come last in the grid (measured: first, they delay the
-  // tasks and the launch takes longer)
+  constexpr int kGroupBytes = WinShape<LPR>::kGroupBytes;
+  extern __shared__ double lds_raw[];  // consume_lds_bytes(LPR, k)
+  const ColArgs& c = a.c;
+  const int k = c.k;
+  // the hot-column workgroups and the one of w0 come last in the grid (measured: first, they
+  // delay the tasks and the launch takes longer)
   if (bx >= a.nb_tasks) {
     if (CH && chunk != 0) return;
     const int hb = bx - a.nb_tasks;
-    double* tot = lds_raw + kBlock;
-    if (hb < a.n_hot) {
-      // a hot column: the forward workgroups' slabs, in block order; the column's row of V is
-      // requested first, so that it arrives with the slabs and not after them
-      const int32_t col = a.hot_cols[hb];
-      double vpre[kRowPre];
-#pragma unroll
-      for (int j = 0; j < kRowPre; ++j) {
-        const int f = int(threadIdx.x) + j * kBlock;
-        vpre[j] = a.V[int64_t(col) * k + (f < k ? f : 0)];
-      }
-      ordered_rows_sum(a.hot_slab + int64_t(hb) * a.n_slabs * (k + 2), a.n_slabs, k + 2, lds_raw,
-                       tot);
-      apply_column_block(tot, col, a.V, a.w, a.grad, a.n, k, a.lr, a.touch, a.touch_id, vpre);
-    } else {
-      // w0 from the forward workgroups' residual sums
-      double acc = 0.0;
-      for (int i = threadIdx.x; i < a.n_slabs; i += kBlock) acc += a.err_partial[i];
-      const double s = block_sum<kBlock>(acc, lds_raw);
-      if (threadIdx.x == 0) {
-        if (a.grad)
-          a.grad[a.n * k + a.n] = -s;
-        else
-          add_by_only_writer(a.w0, a.lr * s);
-      }
-    }
+    if (hb < a.n_hot)
+      consume_hot_column(a, hb, lds_raw);
+    else
+      consume_w0(a, lds_raw);
     return;
   }
-  (void)kHotBytes;
   const int lane = threadIdx.x % kWave;
   const int l = lane % LPR;
   const int gb = threadIdx.x / LPR;  // group in the workgroup
+  const int f = fb + l * VEC;        // this lane's first factor
+  const bool scalars = l == 0 && fb == 0;  // the lane that writes a column's scalar part to memory
   const int task = bx * GPB + gb;
   const int W = a.task_words;
   const int32_t slot0 = task * W * 64;  // first slot of the task
@@ -1152,13 +1211,13 @@ __global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
   WinRec* wrec = reinterpret_cast<WinRec*>(gmem);
   int32_t* list = reinterpret_cast<int32_t*>(gmem + WIN * sizeof(WinRec));
   double* heads = reinterpret_cast<double*>(reinterpret_cast<char*>(lds_raw) + GPB * kGroupBytes);
-  double* head = heads + gb * (k + 3);  // [0..k) M, [k] sum coef, [k+1] sum coef*x, [k+2] flags
+  double* head = heads + gb * (k + 3);  // the group's head row; [k+2] flags
 
   const bool head_open = tk.flags & 1;  // first_col continues from the previous task
   const bool tail_open = tk.flags & 2;  // last_col continues into the next task
-  ColAcc<VEC, NC> acc;
+  ColAcc<VEC> acc;
   acc.clear();
-  Pack<VEC> vold[NC];   // V row of the column being accumulated
+  Pack<VEC> vold;       // V row of the column being accumulated
   int32_t cur = -1;     // that column (uniform in the lane group)
   int fill = 0;         // marked slots listed and not yet consumed (uniform in the lane group)
   bool head_done = false;
@@ -1167,22 +1226,10 @@ __global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
   // place; the last column of a tail-open task stays in `acc` for the combine below
   const auto finish = [&]() {
     if (head_open && cur == tk.first_col) {
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const int f = fb + (c * LPR + l) * VEC;
-        if (f < k) {
-#pragma unroll
-          for (int v = 0; v < VEC; ++v) head[f + v] = acc.m[c][v];
-        }
-      }
-      if (l == 0) {
-        head[k] = acc.gw;
-        head[k + 1] = acc.d;
-      }
+      acc.store_row(head, f, k, l == 0);
       head_done = true;
     } else {
-      apply_column<LPR, VEC, NC>(acc, vold, cur, a.V, a.w, a.grad, a.n, k, a.lr, l, a.touch,
-                                 a.touch_id, fb);
+      apply_column(c, cur, acc, vold, f, scalars);
     }
   };
 
@@ -1211,7 +1258,7 @@ __global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
     while (__ballot(at < fill)) {
       const int nb = max(min(BATCH, fill - at), 0);
       WinRec rec[BATCH];
-      Pack<VEC> qq[BATCH][NC], vv[BATCH][NC];
+      Pack<VEC> qq[BATCH], vv[BATCH];
 #pragma unroll
       for (int u = 0; u < BATCH; ++u) {
         rec[u] = wrec[u < nb ? at + u : 0];
@@ -1222,19 +1269,10 @@ __global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
         // the entry's Q row, and the V row of its column in case the entry starts a new
         // column: fetched together, so that a run of one-entry columns (one-hot users and
         // items in a small batch) costs one round trip, not one per column
-#pragma unroll
-        for (int ch = 0; ch < NC; ++ch) {
-          const int f = fb + (ch * LPR + l) * VEC;
-          qq[u][ch].load(a.Q + int64_t(rec[u].t) * k + (f < k ? f : 0));
-        }
+        qq[u].load(a.Q + int64_t(rec[u].t) * k + (f < k ? f : 0));
         // (an entry of the column the one before it belongs to needs no V row)
-        if (rec[u].col != (u == 0 ? cur : rec[u > 0 ? u - 1 : 0].col)) {
-#pragma unroll
-          for (int ch = 0; ch < NC; ++ch) {
-            const int f = fb + (ch * LPR + l) * VEC;
-            vv[u][ch].load(a.V + int64_t(rec[u].col) * k + (f < k ? f : 0));
-          }
-        }
+        if (rec[u].col != (u == 0 ? cur : rec[u > 0 ? u - 1 : 0].col))
+          vv[u] = load_v_row<VEC>(c.V, rec[u].col, k, f);
       }
 #pragma unroll
       for (int u = 0; u < BATCH; ++u) {
@@ -1243,14 +1281,11 @@ __global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
             if (cur >= 0) finish();
             acc.clear();
             cur = rec[u].col;
-#pragma unroll
-            for (int ch = 0; ch < NC; ++ch) vold[ch] = vv[u][ch];
+            vold = vv[u];
           }
           const double coef = rec[u].coef, cx = rec[u].cx;
 #pragma unroll
-          for (int ch = 0; ch < NC; ++ch)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc.m[ch][v] += coef * qq[u][ch].v[v];
+          for (int v = 0; v < VEC; ++v) acc.m[v] += coef * qq[u].v[v];
           acc.gw += coef;
           acc.d += cx;
         }
@@ -1306,11 +1341,7 @@ __global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
   if (own) {
     if (!own_acc) {
       acc.clear();
-#pragma unroll
-      for (int ch = 0; ch < NC; ++ch) {
-        const int f = fb + (ch * LPR + l) * VEC;
-        vold[ch].load(a.V + int64_t(tk.last_col) * k + (f < k ? f : 0));
-      }
+      vold = load_v_row<VEC>(c.V, tk.last_col, k, f);
     }
     bool any = own_acc;
     for (int g2 = gb + 1; g2 < GPB; ++g2) {
@@ -1318,38 +1349,17 @@ __global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
       const int fl = int(h2[k + 2]);
       if (fl & 1) {
         any = true;
-#pragma unroll
-        for (int ch = 0; ch < NC; ++ch) {
-          const int f = fb + (ch * LPR + l) * VEC;
-          if (f < k) {
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc.m[ch][v] += h2[f + v];
-          }
-        }
-        acc.gw += h2[k];
-        acc.d += h2[k + 1];
+        acc.add_row(h2, f, k);
       }
       if (!(fl & 2)) break;  // the column ends in that task
     }
     if (tk.part >= 0) {
       // a piece of a column longer than the workgroup's tasks: its sums for fm_finalize_kernel
-      double* row = a.parts + int64_t(tk.part) * (k + 3);
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const int f = fb + (c * LPR + l) * VEC;
-        if (f < k) {
-#pragma unroll
-          for (int v = 0; v < VEC; ++v) row[f + v] = acc.m[c][v];
-        }
-      }
-      if (l == 0 && fb == 0) {
-        row[k] = acc.gw;
-        row[k + 1] = acc.d;
-        row[k + 2] = any ? a.stamp : 0.0;
-      }
+      double* row = c.parts + int64_t(tk.part) * (k + 3);
+      acc.store_row(row, f, k, scalars);
+      if (scalars) row[k + 2] = any ? c.stamp : 0.0;
     } else if (any) {
-      apply_column<LPR, VEC, NC>(acc, vold, tk.last_col, a.V, a.w, a.grad, a.n, k, a.lr, l,
-                                 a.touch, a.touch_id, fb);
+      apply_column(c, tk.last_col, acc, vold, f, scalars);
     }
   }
 }
@@ -1358,130 +1368,109 @@ __global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
 // 3. columns split over several tasks: their partial rows, in slot order
 // ---------------------------------------------------------------------------
 struct FinArgs {
+  ColArgs c;
   const SplitCol* split;  // [n_split_short | n_split_long]
   int32_t n_split_short;  // few partial rows: one lane group per column
   int32_t n_split_long;   // many partial rows: one workgroup per column
-  const double* parts;
-  double stamp;
-  int32_t k;
-  int64_t n;
-  double* w;
-  double* V;
-  double lr;
-  double* grad;  // nullable
-  int32_t* touch;  // nullable (grad mode): see ConsArgs
-  int32_t touch_id;
 };
+
+// The short split columns, one per lane group (workgroup b takes kBlock / LPR of them), the
+// factors fb + lane * VEC on of each: the column's partial rows CB to a round of loads, read
+// unconditionally -- a stale row is masked by its stamp -- and added in row order.
+template <int LPR, int VEC, int CB>
+__device__ inline void finalize_short_columns(const FinArgs& a, int b, int fb) {
+  constexpr int GPB = kBlock / LPR;
+  const ColArgs& c = a.c;
+  const int k = c.k;
+  const int l = threadIdx.x % LPR;
+  const int ci = b * GPB + threadIdx.x / LPR;
+  if (ci >= a.n_split_short) return;
+  const SplitCol cc = a.split[ci];
+  const int f = fb + l * VEC;
+  const int fc = f < k ? f : 0;
+  ColAcc<VEC> acc;
+  acc.clear();
+  const Pack<VEC> vold = load_v_row<VEC>(c.V, cc.col, k, f);
+  bool any = false;
+  for (int i = 0; i < cc.part_count; i += CB) {
+    ColAcc<VEC> part[CB];
+    double ss[CB];
+#pragma unroll
+    for (int u = 0; u < CB; ++u) {
+      const double* row = c.parts + int64_t(cc.part_begin + (i + u < cc.part_count ? i + u : i)) * (k + 3);
+      part[u].load_row(row, fc, k);
+      ss[u] = row[k + 2];
+    }
+#pragma unroll
+    for (int u = 0; u < CB; ++u) {
+      const bool ok = i + u < cc.part_count && ss[u] == c.stamp;
+      any = any || ok;
+      acc.add_if(ok, part[u]);
+    }
+  }
+  if (any) apply_column(c, cc.col, acc, vold, f, l == 0 && fb == 0);
+}
 
 // blocks [0, nb_short): short split columns, one per lane group; then one block per long
 // split column.  Launched only when the plan has split columns.
-template <int LPR, int VEC, int NC>
+template <int LPR, int VEC>
 __global__ __launch_bounds__(kBlock) void fm_finalize_kernel(FinArgs a, int nb_short) {
   __shared__ double scratch[kBlock];
   __shared__ double tot[1024 + 2];
   __shared__ int touched;
-  const int k = a.k;
+  const ColArgs& c = a.c;
+  const int k = c.k;
   const int b = blockIdx.x;
-  if (b < nb_short) {
-    constexpr int GPB = kBlock / LPR;
-    const int l = threadIdx.x % LPR;
-    const int ci = b * GPB + threadIdx.x / LPR;
-    if (ci >= a.n_split_short) return;
-    const SplitCol cc = a.split[ci];
-
-    ColAcc<VEC, NC> acc;
-    acc.clear();
-    Pack<VEC> vold[NC];
-#pragma unroll
-    for (int ch = 0; ch < NC; ++ch) {
-      const int f = (ch * LPR + l) * VEC;
-      vold[ch].load(a.V + int64_t(cc.col) * k + (f < k ? f : 0));
-    }
-    bool any = false;
-    constexpr int CB = 4;  // partial rows per trip, loaded unconditionally; stale rows are masked
-    for (int i = 0; i < cc.part_count; i += CB) {
-      const double* row[CB];
-      bool in[CB];
-#pragma unroll
-      for (int u = 0; u < CB; ++u) {
-        in[u] = i + u < cc.part_count;
-        row[u] = a.parts + int64_t(cc.part_begin + (in[u] ? i + u : i)) * (k + 3);
-      }
-      double mm[CB][NC][VEC], gg[CB], dd[CB], ss[CB];
-#pragma unroll
-      for (int u = 0; u < CB; ++u) {
-#pragma unroll
-        for (int ch = 0; ch < NC; ++ch) {
-          const int f = (ch * LPR + l) * VEC;
-#pragma unroll
-          for (int v = 0; v < VEC; ++v) mm[u][ch][v] = row[u][(f < k ? f : 0) + v];
-        }
-        gg[u] = row[u][k];
-        dd[u] = row[u][k + 1];
-        ss[u] = row[u][k + 2];
-      }
-#pragma unroll
-      for (int u = 0; u < CB; ++u) {
-        const bool ok = in[u] && ss[u] == a.stamp;
-        any = any || ok;
-#pragma unroll
-        for (int ch = 0; ch < NC; ++ch)
-#pragma unroll
-          for (int v = 0; v < VEC; ++v) acc.m[ch][v] += ok ? mm[u][ch][v] : 0.0;
-        acc.gw += ok ? gg[u] : 0.0;
-        acc.d += ok ? dd[u] : 0.0;
-      }
-    }
-    if (any)
-      apply_column<LPR, VEC, NC>(acc, vold, cc.col, a.V, a.w, a.grad, a.n, k, a.lr, l, a.touch,
-                                 a.touch_id);
-    return;
-  }
+  if (b < nb_short) return finalize_short_columns<LPR, VEC, 4>(a, b, 0);
   const SplitCol cc = a.split[a.n_split_short + (b - nb_short)];
   // is any partial row of this step's?  (an untouched column is left alone)
   if (threadIdx.x == 0) touched = 0;
   __syncthreads();
   for (int r = threadIdx.x; r < cc.part_count; r += kBlock)
-    if (a.parts[int64_t(cc.part_begin + r) * (k + 3) + k + 2] == a.stamp) touched = 1;
+    if (c.parts[int64_t(cc.part_begin + r) * (k + 3) + k + 2] == c.stamp) touched = 1;
   __syncthreads();
   if (!touched) return;
-  ordered_part_sum(a.parts, cc.part_begin, cc.part_count, k, a.stamp, scratch, tot);
-  apply_column_block(tot, cc.col, a.V, a.w, a.grad, a.n, k, a.lr, a.touch, a.touch_id);
+  ordered_rows_sum<8>(PartRows{c.parts, cc.part_begin, k, c.stamp}, cc.part_count, k + 2, scratch, tot);
+  apply_column_block(c, cc.col, tot);
 }
 
 // The same for factor counts of several chunks per lane, one chunk of 64 x VEC factors per
 // workgroup (blockIdx.y), as fm_consume_kernel's CH form: a short column's partial rows (at
-// most kShortSplit = 8) are ONE round of loads, a long column's are summed by one thread per
+// most kShortSplit) are ONE round of loads, a long column's are summed by one thread per
 // factor of the chunk with 32 rows in flight; stamps ride with the rows and the column's row of
 // V is requested before the sums, so a workgroup's chain is two dependent levels instead of
 // eight (k = 400, B = 2 000: 8.1 -> 6.8 us per launch, profiles/r3j vs r3q).
 template <int VEC>
 __global__ __launch_bounds__(kBlock) void fm_finalize_chunk_kernel(FinArgs a, int nb_short) {
-  constexpr int LPR = kWave, CW = kWave * VEC;
+  constexpr int CW = kWave * VEC;
   __shared__ double tot[CW + 2];
-  const int k = a.k;
+  const ColArgs& c = a.c;
+  const int k = c.k;
   const int b = blockIdx.x;
   const int fb = int(blockIdx.y) * CW;
   if (b < nb_short) {
+    // finalize_short_columns<kWave, VEC, kShortSplit>, open-coded: through the shared routine this
+    // kernel measured 0.3 us slower at k = 400 (profiles/n11/bench_parent_vs_this.txt)
+    constexpr int LPR = kWave;
     constexpr int GPB = kBlock / LPR;
-    constexpr int CB = 8;  // = kShortSplit: every partial row of a short column in one round
+    constexpr int CB = 8;
     const int l = threadIdx.x % LPR;
     const int ci = b * GPB + threadIdx.x / LPR;
     if (ci >= a.n_split_short) return;
     const SplitCol cc = a.split[ci];
     const int f = fb + l * VEC;
     const int fc = f < k ? f : 0;
-    ColAcc<VEC, 1> acc;
+    ColAcc<VEC> acc;
     acc.clear();
-    Pack<VEC> vold[1];
-    vold[0].load(a.V + int64_t(cc.col) * k + fc);
+    Pack<VEC> vold;
+    vold.load(c.V + int64_t(cc.col) * k + fc);
     bool any = false;
     for (int i = 0; i < cc.part_count; i += CB) {
       Pack<VEC> mm[CB];
       double gg[CB], dd[CB], ss[CB];
 #pragma unroll
       for (int u = 0; u < CB; ++u) {
-        const double* row = a.parts + int64_t(cc.part_begin + (i + u < cc.part_count ? i + u : i)) * (k + 3);
+        const double* row = c.parts + int64_t(cc.part_begin + (i + u < cc.part_count ? i + u : i)) * (k + 3);
         mm[u].load(row + fc);
         gg[u] = row[k];
         dd[u] = row[k + 1];
@@ -1489,16 +1478,15 @@ __global__ __launch_bounds__(kBlock) void fm_finalize_chunk_kernel(FinArgs a, in
       }
 #pragma unroll
       for (int u = 0; u < CB; ++u) {
-        const bool ok = i + u < cc.part_count && ss[u] == a.stamp;
+        const bool ok = i + u < cc.part_count && ss[u] == c.stamp;
         any = any || ok;
 #pragma unroll
-        for (int v = 0; v < VEC; ++v) acc.m[0][v] += ok ? mm[u].v[v] : 0.0;
+        for (int v = 0; v < VEC; ++v) acc.m[v] += ok ? mm[u].v[v] : 0.0;
         acc.gw += ok ? gg[u] : 0.0;
         acc.d += ok ? dd[u] : 0.0;
       }
     }
-    if (any)
-      apply_column<LPR, VEC, 1>(acc, vold, cc.col, a.V, a.w, a.grad, a.n, k, a.lr, l, a.touch, a.touch_id, fb);
+    if (any) apply_column(c, cc.col, acc, vold, f, l == 0 && fb == 0);
     return;
   }
   const SplitCol cc = a.split[a.n_split_short + (b - nb_short)];
@@ -1506,7 +1494,7 @@ __global__ __launch_bounds__(kBlock) void fm_finalize_chunk_kernel(FinArgs a, in
   const int j = threadIdx.x;                   // < fcnt: factor fb + j; fcnt, fcnt + 1: sum coef, sum coef * x
   const bool live = j < fcnt + 2;
   const int cidx = j < fcnt ? fb + j : k + (j - fcnt);
-  const double vold = a.V[int64_t(cc.col) * k + (j < fcnt ? fb + j : 0)];
+  const double vold = c.V[int64_t(cc.col) * k + (j < fcnt ? fb + j : 0)];
   double acc = 0.0;
   bool any = false;
   constexpr int U = 32;
@@ -1514,13 +1502,13 @@ __global__ __launch_bounds__(kBlock) void fm_finalize_chunk_kernel(FinArgs a, in
     double v[U], st[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const double* row = a.parts + int64_t(cc.part_begin + (r0 + u < cc.part_count ? r0 + u : r0)) * (k + 3);
+      const double* row = c.parts + int64_t(cc.part_begin + (r0 + u < cc.part_count ? r0 + u : r0)) * (k + 3);
       v[u] = row[live ? cidx : 0];
       st[u] = row[k + 2];
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const bool ok = r0 + u < cc.part_count && st[u] == a.stamp;
+      const bool ok = r0 + u < cc.part_count && st[u] == c.stamp;
       any = any || ok;  // (the stamps are the same for every thread: uniform)
       acc += ok ? v[u] : 0.0;
     }
@@ -1531,17 +1519,17 @@ __global__ __launch_bounds__(kBlock) void fm_finalize_chunk_kernel(FinArgs a, in
   const double gw = tot[fcnt], d = tot[fcnt + 1];
   if (j < fcnt) {
     const int64_t at = int64_t(cc.col) * k + fb + j;
-    if (a.grad)
-      a.grad[at] = d * vold - acc;
+    if (c.grad)
+      c.grad[at] = updated_factor(vold, acc, d, c.lr, true, false);
     else
-      a.V[at] = vold + a.lr * (acc - d * vold);
+      c.V[at] = updated_factor(vold, acc, d, c.lr, false, false);
   }
   if (j == 0 && fb == 0) {
-    if (a.grad) {
-      a.grad[a.n * k + cc.col] = -gw;
-      if (a.touch) a.touch[cc.col] = a.touch_id;
+    if (c.grad) {
+      c.grad[c.n * k + cc.col] = -gw;
+      if (c.touch) c.touch[cc.col] = c.touch_id;
     } else {
-      add_by_only_writer(a.w + cc.col, a.lr * gw);
+      add_by_only_writer(c.w + cc.col, c.lr * gw);
     }
   }
 }

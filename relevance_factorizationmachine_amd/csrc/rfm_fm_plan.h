@@ -82,7 +82,6 @@ constexpr size_t kHotLdsBudget = 56 << 10;
 constexpr size_t kHotLdsBudgetFixed = 40 << 10;  // ... when the fixed-order form shares the LDS
 constexpr int kMaxHot = 160;  // beyond this the slab traffic outweighs what the class saves
 constexpr int32_t kDefaultHotMinCount = 32;
-constexpr int32_t kShortSplit = 8;   // split columns up to this many partial rows: one lane group
 // fm_consume_kernel's tasks: task_words is the power of two for which a task expects about
 // kTaskMarks marked slots per max_batch step (at most kTaskTrips words per lane of a group)
 constexpr int kTaskMarks = 8;

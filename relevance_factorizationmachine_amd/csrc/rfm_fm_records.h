@@ -50,6 +50,7 @@ struct SplitCol {      // a sparse-class column longer than a whole workgroup's 
   int32_t part_count;
   int32_t pad;
 };
+constexpr int32_t kShortSplit = 8;  // split columns up to this many partial rows: one lane group
 
 // Sliced loss forwards (rfm_fm_sliced.hpp): LDS of a workgroup (the cached columns' slices)
 constexpr int kSlicedLds = 160 << 10;

@@ -10,7 +10,16 @@ Tolerance of a device gradient against ``fm_gradients_ld``: element-wise
 ``|got - want| <= GRAD_TOL * S`` with S the sum of the absolute values of the terms of that
 element's sum.  A float64 sum of n terms in any order is off by at most (n-1) * 2^-53 * sum|terms|,
 i.e. 4.4e-12 * S at 40 000 rows, the largest batch used; the residuals and row sums carry a few
-row lengths of 2^-53 relative on top.  1e-11 covers both; it is derived, not measured."""
+row lengths of 2^-53 relative on top.  1e-11 covers both; it is derived, not measured.
+
+Tolerance of a parameter after one in-place step of learning rate lr against theta - lr * g, g the
+oracle's gradient: element-wise ``lr * GRAD_TOL * S + 2^-52 * (|theta| + lr * S)`` (`step_bound`).
+The device forms theta + lr * (-g_dev) from the same sums as its gradient, so |g_dev - g| <=
+GRAD_TOL * S carries over scaled by lr: the first term.  The product lr * g_dev is exact for a
+power of two lr, else within 2^-53 * lr * |g_dev| <= 2^-53 * lr * S; the final addition rounds
+its result, of magnitude at most |theta| + lr * S, by 2^-53 relative (whether or not the product
+was fused into it); rounding the long-double reference to compare adds less.  Together under
+2^-52 * (|theta| + lr * S): the second term."""
 import numpy as np
 from scipy.sparse import csr_matrix, random as sprandom
 
@@ -54,6 +63,20 @@ def _bounded_log(rng, n_rows, n_cols, max_len, dense_cols):
     y = (rng.random(n_rows) < 0.5).astype(np.int64)
     p = rng.uniform(0.1, 1.0, size=n_rows) ** 0.5
     return {"features": X, "labels": y, "pscores": p}
+
+
+def split_case(k, n_rows, n_cols, dense_cols, seed):
+    """A log whose first `dense_cols` columns are in every row but two (a split column once the
+    rows outnumber a workgroup's slots), parameters, the full batch in shuffled order, a shard."""
+    rng = np.random.default_rng(seed)
+    log = _random_log(rng, n_rows, n_cols, 0.05, dense_cols)
+    D = log["features"].toarray()
+    D[[3, n_rows // 2], :] = 0.0  # empty rows (the dense columns miss them)
+    log["features"] = csr_matrix(D)
+    w0, w, V = perturbed_init(seed, n_cols, k)
+    full = rng.permutation(n_rows).astype(np.int32)
+    shard = np.array([n_rows - 1, 3, 0, n_rows // 3, 17], dtype=np.int32)
+    return log, (w0, w, V), full, shard
 
 
 def perturbed_init(seed, n, k):
@@ -100,6 +123,26 @@ def fm_gradients_ld(Xb, yb, pb, w0, w, V):
 def grad_tol(n_rows):
     """GRAD_TOL, scaled with the rows of the batch where they exceed what it is derived for."""
     return GRAD_TOL * max(1.0, n_rows / GRAD_TOL_ROWS)
+
+
+def step_bound(theta, scale, lr, n_rows):
+    """Element-wise bound of a parameter after one in-place step against theta - lr * g (see the
+    module's docstring); `scale` = that element's S."""
+    return lr * LD(grad_tol(n_rows)) * scale + LD(2.0) ** -52 * (np.abs(theta) + lr * scale)
+
+
+def step_excess(got, theta, oracle, lr, n_rows):
+    """``|got - (theta - lr * g)| / step_bound`` element by element, for (w0, w, V) in that order:
+    a step holds where every ratio is <= 1.  got, theta: (w0 [1], w [n], V [n, k])."""
+    g_w0, g_w, G_V, (S_0, S_w, S_V) = oracle
+    out = []
+    for x, t, g, S in zip(got, theta, (g_w0, g_w, G_V), (S_0, S_w, S_V)):
+        x, t = np.asarray(x, dtype=np.float64), np.asarray(t).astype(LD)
+        g, S = np.broadcast_to(g, t.shape), np.broadcast_to(S, t.shape)
+        assert x.shape == t.shape and not np.isnan(x).any()
+        err, bound = np.abs(x.astype(LD) - (t - lr * g)), step_bound(t, S, lr, n_rows)
+        out.append(np.where(bound > 0, err / np.where(bound > 0, bound, 1), np.where(err > 0, np.inf, 0)))
+    return out
 
 
 def assert_within_scale(got, want, scale, tol, what):
@@ -247,6 +290,13 @@ CLASS_OF = {
 }
 
 
+def full_batch_workgroup_slots(k):
+    """Slots of a workgroup of the gradient launch on a plan whose batch is the whole log: every
+    slot is then expected marked, a task is one 64-slot word, and a workgroup has one task per
+    lane group of its 256 threads.  (test_gpu_grad_forms.py holds the plans to it.)"""
+    return 256 // CLASS_OF[k][0] * 64
+
+
 def class_id(k):
     lpr, vec, nc = CLASS_OF[k]
     return f"lpr{lpr}-vec{vec}-nc{nc}-k{k}"
@@ -254,6 +304,10 @@ def class_id(k):
 
 def chunked(k):
     return CLASS_OF[k][2] > 1
+
+
+# split columns in gradient mode (test_gpu_grad_forms.py): (factor count, hot mode)
+CASES_B = [(8, -1), (33, -1), (128, -1), (65, 0), (300, 0)]
 
 
 def fixed_order(k, hot):

@@ -100,27 +100,17 @@ def _workgroup_slots(k):
     rng = np.random.default_rng(1)
     dev = gf.DeviceLog(runtime.Runtime.get(), gf._random_log(rng, 64, 6, 0.3), k, 64, -1)
     try:
+        assert dev.geometry()["BC"] == gf.full_batch_workgroup_slots(k)
         return dev.geometry()["BC"]
     finally:
         dev.close()
 
 
-def _split_case(rt, k, hot, n_rows, n_cols, dense_cols, seed):
-    rng = np.random.default_rng(seed)
-    log = gf._random_log(rng, n_rows, n_cols, 0.05, dense_cols)
-    D = log["features"].toarray()
-    D[[3, n_rows // 2], :] = 0.0  # empty rows (the dense columns miss them)
-    log["features"] = csr_matrix(D)
-    w0, w, V = gf.perturbed_init(seed, n_cols, k)
-    full = rng.permutation(n_rows).astype(np.int32)
-    shard = np.array([n_rows - 1, 3, 0, n_rows // 3, 17], dtype=np.int32)
-    return log, (w0, w, V), full, shard
-
-
 # the smallest row counts that reach the form: one workgroup's slots + a few rows -> 2 partial rows
 # (short form), 8 workgroups' + a few -> 9 (long form).  At 4 lanes per row (k = 8) a workgroup has
 # 4 096 slots: the long form needs about 33 000 rows, inside the 40 000 the tolerance is derived for.
-CASES_B = [(8, -1), (33, -1), (128, -1), (65, 0), (300, 0)]
+CASES_B = gf.CASES_B
+STEP_LR = 2.0 ** -3  # an update the size of the parameters
 
 
 @pytest.mark.parametrize("form", ["short", "long"])
@@ -129,7 +119,7 @@ def test_split_columns_in_gradient_mode(rt, k, hot, form):
     bc = _workgroup_slots(k)
     n_rows = (bc if form == "short" else K_SHORT_SPLIT * bc) + 37
     assert n_rows <= gf.GRAD_TOL_ROWS
-    log, theta, full, shard = _split_case(rt, k, hot, n_rows, 24 if n_rows > 5000 else 60, 1, 7 * k + len(form))
+    log, theta, full, shard = gf.split_case(k, n_rows, 24 if n_rows > 5000 else 60, 1, 7 * k + len(form))
     dev = gf.DeviceLog(rt, log, k, n_rows, hot)
     try:
         assert dev.geometry()["BC"] == bc
@@ -137,8 +127,17 @@ def test_split_columns_in_gradient_mode(rt, k, hot, form):
         assert (2 <= parts <= K_SHORT_SPLIT) if form == "short" else parts > K_SHORT_SPLIT, parts
         info = dev.plan.info()
         assert info["split_columns"] >= 1 and info["hot_columns"] == 0
-        _check_all_forms(dev, gf.Params(rt, *theta), full, shard, _oracle(log, full, *theta),
-                         _oracle(log, shard, *theta), True)
+        o_full = _oracle(log, full, *theta)
+        _check_all_forms(dev, gf.Params(rt, *theta), full, shard, o_full, _oracle(log, shard, *theta), True)
+        # ... and in place: one step on the full batch against theta - lr * g, element by element
+        # (grad_forms_common.step_bound); the split column's row goes through the finalize launch
+        params = gf.Params(rt, *theta)
+        gf.step(dev, full, params, STEP_LR)
+        got = params.host()
+        assert not np.array_equal(got[2][0], theta[2][0])  # the split column moved
+        for name, ratio in zip(("w0", "w", "V"), gf.step_excess(got, theta, o_full, STEP_LR, n_rows)):
+            print(f"{name}: worst |got - (theta - lr g)| / bound = {float(ratio.max()):.3g}")
+            assert (ratio <= 1).all(), (name, np.argwhere(ratio > 1)[:5], float(ratio.max()))
     finally:
         dev.close()
 
@@ -151,7 +150,7 @@ def test_hot_class_overflow_leaves_dense_columns_split(rt):
     bc = _workgroup_slots(k)
     n_rows, n_cols, dense = bc + 37, 150, hot_cap + 7
     assert dense < n_cols
-    log, theta, full, shard = _split_case(rt, k, 0, n_rows, n_cols, dense, 64)
+    log, theta, full, shard = gf.split_case(k, n_rows, n_cols, dense, 64)
     dev = gf.DeviceLog(rt, log, k, n_rows, 0)
     try:
         info = dev.plan.info()

@@ -97,3 +97,47 @@ def test_within_scale_is_elementwise():
     with pytest.raises(AssertionError):
         gf.assert_within_scale(np.array([1e6, np.nan]), want, scale, 1e-11, "NaN")
     assert gf.grad_tol(1_500) == gf.GRAD_TOL and gf.grad_tol(80_000) == 2 * gf.GRAD_TOL
+
+
+def _step_f64(log, theta, lr, order, drop=None):
+    """One in-place step on the whole log in float64, every column's sums (m = sum coef * q_t,
+    sum coef, sum coef * x) added one term at a time in the row order `order`; `drop` = (column,
+    rows): that column's sums miss those rows' terms."""
+    w0, w, V = theta
+    X = log["features"].toarray()
+    q = X @ V
+    z = w0[0] + X @ w + ((q * q).sum(axis=1) - (X * X) @ (V * V).sum(axis=1)) / 2
+    e = log["labels"] / log["pscores"] - 1 / (1 + np.exp(-np.clip(z, -cpu_ref.LOGIT_CLIP, cpu_ref.LOGIT_CLIP)))
+    new_w, new_V = w.copy(), V.copy()
+    for c in range(X.shape[1]):
+        rows = [t for t in order if X[t, c] != 0 and not (drop and drop[0] == c and t in drop[1])]
+        coef = e[rows] * X[rows, c]
+        m = np.cumsum(coef[:, None] * q[rows], axis=0)[-1] if rows else np.zeros(V.shape[1])
+        gw, d = (np.cumsum(coef)[-1], np.cumsum(coef * X[rows, c])[-1]) if rows else (0.0, 0.0)
+        new_V[c] = V[c] + lr * (m - d * V[c])
+        new_w[c] = w[c] + lr * gw
+    return np.array([w0[0] + lr * np.cumsum(e[order])[-1]]), new_w, new_V
+
+
+def test_step_bound_on_the_smallest_split_geometry():
+    """grad_forms_common.step_bound on the smallest case of test_split_columns_in_gradient_mode (64
+    lanes per row, short form: 256 slots to a workgroup, column 0 in two partial rows): a float64
+    step with every sum's terms in shuffled order stays below HALF the bound on every element; a
+    step that loses one partial row of the split column is outside it on that column's V row and
+    w, and nowhere else."""
+    k = min(k for k, _ in gf.CASES_B if gf.CLASS_OF[k][0] == 64)
+    bc = gf.full_batch_workgroup_slots(k)
+    assert bc == min(gf.full_batch_workgroup_slots(k2) for k2, _ in gf.CASES_B)
+    n_rows, lr = bc + 37, 2.0 ** -3
+    log, theta, full, _ = gf.split_case(k, n_rows, 60, 1, 7 * k + len("short"))
+    oracle = gf.grad_oracle(log, full, *theta)
+    order = [int(t) for t in np.random.default_rng(5).permutation(n_rows)]
+    for ratio in gf.step_excess(_step_f64(log, theta, lr, order), theta, oracle, lr, n_rows):
+        assert (ratio < 0.5).all(), float(ratio.max())
+    # column 0's entries in row (= slot) order: a workgroup's slots to a partial row
+    holders = np.flatnonzero(log["features"].toarray()[:, 0])
+    assert bc < len(holders) <= 2 * bc
+    lost = _step_f64(log, theta, lr, order, drop=(0, set(holders[bc:].tolist())))
+    r_w0, r_w, r_V = gf.step_excess(lost, theta, oracle, lr, n_rows)
+    assert (r_V[0] > 1).all() and r_w[0] > 1
+    assert (r_V[1:] <= 1).all() and (r_w[1:] <= 1).all() and (r_w0 <= 1).all()
