@@ -466,7 +466,11 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? kBigWaves : 1)) void f
               Pack<VEC> pq;
 #pragma unroll
               for (int v = 0; v < VEC; ++v) pq.v[v] = q[i][c][v];
-              pq.store(a.out_Q + (qoff + uint32_t(fo[c])));
+              // (training: the gradient launch reads the row next, nothing here does)
+              if (REC)
+                pq.store_through(a.out_Q + (qoff + uint32_t(fo[c])));
+              else
+                pq.store(a.out_Q + (qoff + uint32_t(fo[c])));
             }
           }
         }
@@ -540,10 +544,19 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? kBigWaves : 1)) void f
 #pragma unroll
           for (int i = 0; i < R; ++i) {
             if (pb + l < len[i] && em[i].slot >= 0) {
-              // the row's batch position and residual at the entry's slot (plain store: the
+              // the row's batch position and residual at the entry's slot (no atomic: the
               // row ids of a step are distinct), and the slot's bit in the map the gradient
-              // launch scans (no-return atomic)
-              a.slot_mark[em[i].slot] = SlotMark{int32_t(t[i]), 0, err[i]};
+              // launch scans (no-return atomic).  The mark is written through like the Q row,
+              // as the two words {t, 0} and the residual; the fixed-order forms keep the plain
+              // store (the other costs them two VGPRs, or 8 bytes of scratch at k = 32)
+              if (!DET) {
+                Pack<2> pm;
+                pm.v[0] = __hiloint2double(0, int32_t(t[i]));
+                pm.v[1] = err[i];
+                pm.store_through(reinterpret_cast<double*>(a.slot_mark + em[i].slot));
+              } else {
+                a.slot_mark[em[i].slot] = SlotMark{int32_t(t[i]), 0, err[i]};
+              }
               atomicOr(a.slot_bits + (em[i].slot >> 6), 1ull << (em[i].slot & 63));
             }
           }
@@ -743,10 +756,21 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? kBigWaves : 1)) void f
 
   if (H > 0) {
     __syncthreads();
-    // slab layout [H][gridDim.x][k+2]: the slabs of one column are contiguous
-    for (int i = tid; i < H * hot_w; i += BLOCK) {
-      const int h = i / hot_w, f = i % hot_w;
-      a.hot_slab[(int64_t(h) * gx + bx) * hot_w + f] = hot[i];
+    // slab layout [H][gridDim.x][k+2]: the slabs of one column are contiguous.  An even k makes
+    // a row of k + 2 doubles whole 16-byte pairs, here and in LDS: one write-through store each
+    // (the gradient launch reads the slabs next)
+    if constexpr (REC && VEC == 2) {
+      for (int i = 2 * tid; i < H * hot_w; i += 2 * BLOCK) {
+        const int h = i / hot_w, f = i % hot_w;
+        Pack<2> ps;
+        ps.load(hot + i);
+        ps.store_through(a.hot_slab + (int64_t(h) * gx + bx) * hot_w + f);
+      }
+    } else {
+      for (int i = tid; i < H * hot_w; i += BLOCK) {
+        const int h = i / hot_w, f = i % hot_w;
+        a.hot_slab[(int64_t(h) * gx + bx) * hot_w + f] = hot[i];
+      }
     }
   }
   if (a.err_partial) {
