@@ -51,6 +51,9 @@ enum {
 #define RFM_MF_READ_AHEAD 4
 /* rfm_mf_schedule_ex: gap of an example whose user row no earlier example of the batch writes */
 #define RFM_MF_NO_WRITER (1 << 30)
+/* steps rfm_mf_fold_in reads a chain's fixed rows ahead (and its ids twice as far); measured:
+ * profiles/n13/ */
+#define RFM_MF_FOLD_READ_AHEAD 4
 
 typedef struct rfm_ctx rfm_ctx;
 typedef struct rfm_fm_plan rfm_fm_plan;
@@ -530,6 +533,33 @@ int32_t rfm_mf_sgd_levels_ex(rfm_ctx* ctx, const void* d_ex, const int32_t* h_le
                              const int32_t* d_cache_items, int32_t n_cached, double* d_P,
                              double* d_Q, double* d_bu, double* d_bi, double b,
                              int32_t n_factors, double lr, double reg);
+
+/* ---- MF fold-in: new rows of one side against the fixed other side ----------------
+ * The per-example update of src/mf.py:99-108 with _update_P / _update_b_u (src/mf.py:172-216)
+ * restricted to ONE side: new row r has factors x_r = d_rows[r][0..k) and bias c_r = d_bias[r]
+ * (in / out; the caller's initial values, zeros for a cold start).  Its examples are
+ * e = d_row_ptr[r] .. d_row_ptr[r+1]-1 in that order; example e names row d_ids[e] of the fixed
+ * side d_F [n_fixed][k], d_fb [n_fixed] (Q, b_i for new users; P, b_u for new items -- the same
+ * rule with the sides exchanged) and carries d_ry[e] = label / propensity.  n_passes passes are
+ * made over the row's examples, each in order:
+ *   err = ry_e - sigmoid(clip(x_r . F[j] + c_r + fb[j] + b));
+ *   x_r -= lr (-err F[j] + reg x_r);  c_r -= lr (-err + reg c_r)   (err from before the row update)
+ * Nothing of the fixed side is written; a row without examples keeps its bits.  For new users,
+ * one pass and all item ids of the call distinct this is what the reference's sequential batch
+ * does to those user rows.  One lane group per new row, one launch for any n_new; d_order
+ * [n_new] hands the rows to the lane groups: the rows by descending example count (stable), so
+ * that the lane groups of a wavefront have chains of similar length and the longest start first.
+ * The ids are not checked on the device: every d_ids[e] must lie in 0 .. n_fixed-1, d_order must
+ * be a permutation of 0 .. n_new-1.  n_new == 0 or n_passes == 0: no launch. */
+int32_t rfm_mf_fold_in(rfm_ctx* ctx, const int64_t* d_row_ptr, const int32_t* d_ids, const double* d_ry,
+                       const int32_t* d_order, int64_t n_new, const double* d_F, const double* d_fb,
+                       int64_t n_fixed, double b, int32_t n_factors, double lr, double reg,
+                       int32_t n_passes, double* d_rows, double* d_bias);
+/* The launch shape of rfm_mf_fold_in for n_new rows at n_factors factors (host only, nothing is
+ * launched): h_out6[0]=lanes per row, [1]=adjacent factors a lane owns per chunk, [2]=chunks per
+ * lane, [3]=new rows per workgroup, [4]=workgroups, [5]=read-ahead depth in steps
+ * (RFM_MF_FOLD_READ_AHEAD).  ctx == NULL: the grid on a device of 256 CUs (an MI355X). */
+int32_t rfm_mf_fold_geometry(const rfm_ctx* ctx, int64_t n_new, int32_t n_factors, int32_t* h_out6);
 
 /* ---- MF across GPUs: user-range partition ------------------
  * NOT the reference's semantics (its batch is strictly sequential, src/mf.py:97-108;

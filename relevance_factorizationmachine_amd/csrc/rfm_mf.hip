@@ -19,6 +19,10 @@
 // run the same example update (mf_load_row, mf_update, mf_store_row), the same
 // host walk over the level pointers (mf_walk_levels) and fill the model's
 // fields of their argument blocks in one place (set_model).
+//
+// Fold-in (rfm_mf_fold_in, mf_fold_kernel) trains new rows of one side against the fixed
+// other side by the same update restricted to that side: independent chains, one lane group
+// per new row, no schedule.
 #include <algorithm>
 #include <cmath>
 
@@ -575,6 +579,165 @@ static void mf_walk_levels(const int32_t* h_level_ptr, int n_levels, int seq_cap
   }
 }
 
+// ---------------------------------------------------------------------------
+// Fold-in (rfm_mf_fold_in): new rows of one side trained against the fixed other side by
+// the same per-example update restricted to that side (src/mf.py:99-108, 172-216).  New rows
+// are independent of each other and each is one sequential chain, so there is no level
+// schedule: ONE LANE GROUP PER NEW ROW, the row and its bias in registers for all of its
+// examples and passes, written once at the end; no barrier, atomic or LDS hand-off.
+//  * A step is one example of one pass; a chain of n examples and p passes has n * p steps and
+//    step s reads example s % n, so the rings below run across a pass boundary unchanged.
+//  * The chain is latency-bound, so a lane group reads ahead through two rings of kFoldAhead
+//    register slots: the id and weight of the step 2 * kFoldAhead ahead, and -- from the id that
+//    arrived one turn of the ring earlier -- the fixed row and bias of the step kFoldAhead ahead.
+//    No step waits for an index load and then a row load in sequence.
+//  * Lane groups of one wavefront have chains of different length (the host orders the rows by
+//    descending length, so neighbours are close).  The wavefront walks to its longest chain with
+//    a wave-uniform trip count, so the cross-lane sums run converged; a group past its own chain
+//    is predicated off: its loads read row 0 of the fixed side, its update is not applied.
+// ---------------------------------------------------------------------------
+constexpr int kFoldAhead = RFM_MF_FOLD_READ_AHEAD;
+
+struct MfFoldArgs {
+  const int64_t* row_ptr;  // [n_new + 1]: examples of new row r are row_ptr[r] .. row_ptr[r + 1]
+  const int32_t* ids;      // fixed-side row of every example, chain order
+  const double* ry;        // label / propensity of every example
+  const int32_t* order;    // [n_new]: new rows by descending chain length
+  int64_t n_new;
+  const double* F;   // the fixed side: Q, b_i for new users; P, b_u for new items
+  const double* fb;
+  double b;
+  int32_t k;
+  double lr, reg;
+  int32_t n_passes;
+  double* rows;  // [n_new][k] in / out
+  double* bias;  // [n_new] in / out
+};
+
+struct FoldChain {
+  int64_t e0, n, total;  // first example, examples, steps = n * n_passes
+  int64_t step, e;       // the next step whose id is fetched, and its example
+};
+
+template <int VEC, int NC>
+struct FoldSlot {
+  // the step 2 * kFoldAhead ahead: id and weight on their way
+  int32_t j_far;
+  double ry_far;
+  bool live_far;
+  // the step kFoldAhead ahead: the fixed row and bias on their way
+  Pack<VEC> q[NC];
+  double fb, ry;
+  bool live;  // the lane group has that step (its chain is not over)
+};
+
+template <int VEC, int NC>
+__device__ __forceinline__ void fold_fetch_id(const MfFoldArgs& a, FoldChain& ch, FoldSlot<VEC, NC>& s) {
+  s.live_far = ch.step < ch.total;
+  s.j_far = 0;  // past the chain: row 0, a valid address
+  s.ry_far = 0.0;
+  if (s.live_far) {
+    s.j_far = a.ids[ch.e0 + ch.e];
+    s.ry_far = a.ry[ch.e0 + ch.e];
+  }
+  ++ch.step;
+  if (++ch.e == ch.n) ch.e = 0;  // the next pass
+}
+
+template <int LPR, int VEC, int NC>
+__device__ __forceinline__ void fold_fetch_row(const MfFoldArgs& a, int l, FoldSlot<VEC, NC>& s) {
+  s.live = s.live_far;
+  s.ry = s.ry_far;
+  mf_load_row<LPR, VEC, NC>(s.q, a.F + int64_t(s.j_far) * a.k, a.k, l);
+  s.fb = a.fb[s.j_far];
+}
+
+// one step on the row in registers; every lane of the wavefront takes part in the sum.  A chunk
+// past k holds what mf_load_row put there (row[0 .. VEC), not zeros) and is updated along with the
+// rest: it stays out of the dot product and mf_store_row never writes it.
+template <int LPR, int VEC, int NC>
+__device__ __forceinline__ void fold_step(const MfFoldArgs& a, int l, const FoldSlot<VEC, NC>& s,
+                                          Pack<VEC> (&x)[NC], double& c) {
+  double dot = 0.0;
+#pragma unroll
+  for (int ch = 0; ch < NC; ++ch) {
+    const int f = (ch * LPR + l) * VEC;
+    if (f < a.k) {
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) dot += x[ch].v[v] * s.q[ch].v[v];
+    }
+  }
+  dot = group_sum<LPR>(dot);
+  const double err = s.ry - sigmoid_clipped(dot + c + s.fb + a.b);
+#pragma unroll
+  for (int ch = 0; ch < NC; ++ch) {
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      const double x_new = x[ch].v[v] - a.lr * (-err * s.q[ch].v[v] + a.reg * x[ch].v[v]);
+      x[ch].v[v] = s.live ? x_new : x[ch].v[v];
+    }
+  }
+  const double c_new = c - a.lr * (-err + a.reg * c);
+  c = s.live ? c_new : c;
+}
+
+// the largest value among the 64 lanes, as a scalar
+__device__ inline int64_t wave_max(int64_t v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const int64_t o = __shfl_xor(static_cast<long long>(v), m, 64);
+    v = o > v ? o : v;
+  }
+  const uint32_t lo = __builtin_amdgcn_readfirstlane(int(uint32_t(v)));
+  const uint32_t hi = __builtin_amdgcn_readfirstlane(int(uint32_t(uint64_t(v) >> 32)));
+  return int64_t((uint64_t(hi) << 32) | lo);
+}
+
+template <int LPR, int VEC, int NC>
+__global__ __launch_bounds__(kMfBlock) void mf_fold_kernel(MfFoldArgs a) {
+  constexpr int GPB = kMfBlock / LPR;
+  const int l = threadIdx.x % LPR;
+  const int g = threadIdx.x / LPR;
+  const int k = a.k;
+  for (int64_t base = int64_t(blockIdx.x) * GPB; base < a.n_new; base += int64_t(gridDim.x) * GPB) {
+    const bool valid = base + g < a.n_new;
+    // a lane group without a row walks along on row 0 with a chain of no examples
+    const int64_t r = valid ? int64_t(a.order[base + g]) : 0;
+    FoldChain ch;
+    ch.e0 = a.row_ptr[r];
+    ch.n = valid ? a.row_ptr[r + 1] - ch.e0 : 0;
+    ch.total = ch.n * a.n_passes;
+    ch.step = ch.e = 0;
+    const int64_t steps = wave_max(ch.total);
+    Pack<VEC> x[NC];
+    mf_load_row<LPR, VEC, NC>(x, a.rows + r * k, k, l);
+    double c = a.bias[r];
+    FoldSlot<VEC, NC> s[kFoldAhead];
+#pragma unroll
+    for (int d = 0; d < kFoldAhead; ++d) fold_fetch_id(a, ch, s[d]);
+#pragma unroll
+    for (int d = 0; d < kFoldAhead; ++d) {
+      fold_fetch_row<LPR>(a, l, s[d]);
+      fold_fetch_id(a, ch, s[d]);
+    }
+    for (int64_t t = 0; t < steps; t += kFoldAhead) {
+#pragma unroll
+      for (int d = 0; d < kFoldAhead; ++d) {
+        if (t + d >= steps) break;
+        fold_step<LPR>(a, l, s[d], x, c);
+        fold_fetch_row<LPR>(a, l, s[d]);
+        fold_fetch_id(a, ch, s[d]);
+      }
+    }
+    if (valid) {
+      mf_store_row<LPR, VEC, NC>(x, a.rows + r * k, k, l);
+      if (l == 0) a.bias[r] = c;
+    }
+  }
+}
+
+constexpr int kFoldPerCu = 8;  // workgroups per CU of the capped grid, as the other MF launches
+
 }  // namespace rfm
 
 using namespace rfm;
@@ -735,6 +898,59 @@ int32_t rfm_mf_sgd_hogwild(rfm_ctx* ctx, const int32_t* d_users, const int32_t* 
     a.lo = 0;
     a.hi = int32_t(batch);
     launch_wide(ctx, shape_for(n_factors), a);
+    RFM_HIP_CHECK(hipGetLastError());
+  });
+}
+
+int32_t rfm_mf_fold_geometry(const rfm_ctx* ctx, int64_t n_new, int32_t n_factors, int32_t* h_out6) {
+  return guarded([&] {
+    RFM_REQUIRE(h_out6, "null pointer");
+    RFM_REQUIRE(n_new >= 0 && n_new < (int64_t(1) << 31), "n_new=%lld out of range", (long long)n_new);
+    const Shape s = shape_for(n_factors);
+    const rfm_ctx assumed{};  // (the CU count of an MI355X)
+    h_out6[0] = s.lpr;
+    h_out6[1] = s.vec;
+    h_out6[2] = s.nc;
+    h_out6[3] = kMfBlock / s.lpr;
+    h_out6[4] = capped_grid(ctx ? ctx : &assumed, n_new, kMfBlock / s.lpr, kFoldPerCu, 0);
+    h_out6[5] = kFoldAhead;
+  });
+}
+
+int32_t rfm_mf_fold_in(rfm_ctx* ctx, const int64_t* d_row_ptr, const int32_t* d_ids, const double* d_ry,
+                       const int32_t* d_order, int64_t n_new, const double* d_F, const double* d_fb,
+                       int64_t n_fixed, double b, int32_t n_factors, double lr, double reg,
+                       int32_t n_passes, double* d_rows, double* d_bias) {
+  return guarded([&] {
+    RFM_REQUIRE(ctx, "null ctx");
+    RFM_REQUIRE(n_new >= 0 && n_new < (int64_t(1) << 31), "n_new=%lld out of range", (long long)n_new);
+    RFM_REQUIRE(n_fixed >= 0 && n_fixed < (int64_t(1) << 31), "n_fixed=%lld out of range", (long long)n_fixed);
+    RFM_REQUIRE(n_passes >= 0, "negative n_passes");
+    const Shape s = shape_for(n_factors);
+    RFM_REQUIRE(d_row_ptr && d_ids && d_ry && d_order && d_F && d_fb && d_rows && d_bias, "null pointer");
+    if (n_new == 0 || n_passes == 0) return;
+    // (a lane group past its chain reads row 0 of the fixed side)
+    RFM_REQUIRE(n_fixed >= 1, "a fixed side without rows");
+    MfFoldArgs a{};
+    a.row_ptr = d_row_ptr;
+    a.ids = d_ids;
+    a.ry = d_ry;
+    a.order = d_order;
+    a.n_new = n_new;
+    a.F = d_F;
+    a.fb = d_fb;
+    a.b = b;
+    a.k = n_factors;
+    a.lr = lr;
+    a.reg = reg;
+    a.n_passes = n_passes;
+    a.rows = d_rows;
+    a.bias = d_bias;
+    const int grid = capped_grid(ctx, n_new, kMfBlock / s.lpr, kFoldPerCu, 0);
+#define RFM_CALL_FOLD(L, Vv, N) \
+  hipLaunchKernelGGL((mf_fold_kernel<L, Vv, N>), dim3(grid), dim3(kMfBlock), 0, ctx->stream, a)
+    RFM_FOR_SHAPE(s, RFM_CALL_FOLD);
+#undef RFM_CALL_FOLD
     RFM_HIP_CHECK(hipGetLastError());
   });
 }

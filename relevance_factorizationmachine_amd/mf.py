@@ -115,6 +115,57 @@ class DevicePairs:
         self.items = rt.upload(self.h_items if self.n else np.zeros(1, np.int32))
 
 
+def fold_examples(data: dict, n_new: int, n_fixed: int, new_col: int, n_passes: int):
+    """The examples of a fold-in call as ``rfm_mf_fold_in`` takes them (host only): ``data`` as
+    ``fit()`` takes it, column ``new_col`` of ``features`` holding new-row indices 0..n_new-1 and the
+    other column known ids 0..n_fixed-1.  Returns ``(row_ptr int64 [n_new+1], ids int32, ry float64,
+    order int32 [n_new])``: the examples grouped by new row with a stable sort (a row's examples
+    keep their input order), ``ry`` = label / propensity as ``fit()`` divides them, and the new rows
+    by descending example count (stable) -- the order in which lane groups take them."""
+    pairs = np.asarray(data["features"])
+    if pairs.ndim != 2 or pairs.shape[1] < 2:
+        raise ValueError("MF features must be an (N, 2) array of [user, item]")
+    labels, pscores = np.asarray(data["labels"]), np.asarray(data["pscores"])
+    if not (labels.ndim == pscores.ndim == 1 and labels.shape[0] == pscores.shape[0] == pairs.shape[0]):
+        raise ValueError(f"{pairs.shape[0]} pairs, {labels.shape[0] if labels.ndim else 0} labels and "
+                         f"{pscores.shape[0] if pscores.ndim else 0} pscores: one of each per example")
+    n_new, n_passes = int(n_new), int(n_passes)
+    if n_new < 0 or n_passes < 0:
+        raise ValueError(f"n_new={n_new}, n_passes={n_passes}: neither may be negative")
+    new, other = pairs[:, new_col].astype(np.int64), pairs[:, 1 - new_col].astype(np.int64)
+    names = ("user", "item")
+    if new.size:
+        if new.min() < 0 or new.max() >= n_new:
+            raise IndexError(f"new {names[new_col]} index out of range")
+        if other.min() < 0 or other.max() >= n_fixed:
+            raise IndexError(f"{names[1 - new_col]} id out of range")
+    by_row = np.argsort(new, kind="stable")
+    counts = np.bincount(new, minlength=n_new)
+    row_ptr = np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
+    ry = (labels.astype(np.float64) / pscores.astype(np.float64))[by_row]
+    order = np.argsort(-counts, kind="stable").astype(np.int32)
+    return row_ptr, other[by_row].astype(np.int32), ry, order
+
+
+@dataclass
+class FoldedRows:
+    """New rows of one side of a trained MF model (``fold_in_users`` / ``fold_in_items``): device
+    tensors ``rows [n_new, k]`` and ``bias [n_new]``, ``side`` "user" or "item"."""
+
+    side: str
+    rows: object
+    bias: object
+    rt: Runtime
+
+    def __len__(self) -> int:
+        return int(self.rows.shape[0])
+
+    def numpy(self):
+        """``(rows, bias)`` on the host, after the work enqueued so far."""
+        self.rt.sync()
+        return self.rows.cpu().numpy(), self.bias.cpu().numpy()
+
+
 @dataclass
 class LogisticMatrixFactorization(PointwiseBaseRecommender):
     """Logistic matrix factorisation trained by per-example SGD on an MI355X.
@@ -316,33 +367,101 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
         rt.sync()
         return out.cpu().numpy()
 
+    # -------------------------------------------------------------- fold-in
+    def _fold_in(self, side: int, data: dict, n_new: int, n_passes: int, init) -> FoldedRows:
+        """New rows of ``side`` (0: users, 1: items) trained against the fixed other side
+        (``rfm_mf_fold_in``): enqueued on the runtime's stream, no host wait."""
+        import torch
+
+        rt = self._rt
+        if not hasattr(self, "b"):
+            # the reference's global bias exists only after fit() (src/mf.py:84)
+            raise AttributeError("'LogisticMatrixFactorization' object has no attribute 'b'")
+        F, fb, n_fixed = ((self.Q, self.b_i, self.n_items), (self.P, self.b_u, self.n_users))[side]
+        row_ptr, ids, ry, order = fold_examples(data, n_new, n_fixed, side, n_passes)
+        n_new, kf = int(n_new), int(self.n_factors)
+        if init is None:
+            rows = torch.zeros((n_new, kf), dtype=torch.float64, device=rt.torch_device)
+            bias = torch.zeros((n_new,), dtype=torch.float64, device=rt.torch_device)
+        else:
+            rows0, bias0 = (np.asarray(a, dtype=np.float64) for a in init)
+            if rows0.shape != (n_new, kf) or bias0.shape != (n_new,):
+                raise ValueError(f"init must be (rows [{n_new}, {kf}], bias [{n_new}]), got {rows0.shape}, "
+                                 f"{bias0.shape}")
+            rows, bias = rt.upload(rows0), rt.upload(bias0)
+        if n_new and int(n_passes):
+            dev = [rt.upload(a if a.size else np.zeros(1, a.dtype)) for a in (row_ptr, ids, ry, order)]
+            _lib.check(rt.lib.rfm_mf_fold_in(
+                rt.ctx, *(d.data_ptr() for d in dev), n_new, F.dev.data_ptr(), fb.dev.data_ptr(), n_fixed,
+                float(self.b), kf, float(self.lr), float(self.reg), int(n_passes), rows.data_ptr(),
+                bias.data_ptr()))
+        return FoldedRows(("user", "item")[side], rows, bias, rt)
+
+    def fold_in_users(self, data: dict, n_new: int, n_passes: int, init=None) -> FoldedRows:
+        """Rows and biases for ``n_new`` users who arrived after the fit, by the reference's own
+        per-example update (``src/mf.py:99-108``) with ``Q, b_i`` held fixed.  ``data`` as ``fit()``
+        takes it: the user column of ``features`` holds new-user indices 0..n_new-1, the item column
+        known item ids; a user's examples are taken in input order, ``n_passes`` times.  ``init``:
+        ``(rows [n_new, k], bias [n_new])`` to start from (default zeros).  The model is not
+        written; serve the result through ``new_users=`` or ``append_users`` it."""
+        return self._fold_in(0, data, n_new, n_passes, init)
+
+    def fold_in_items(self, data: dict, n_new: int, n_passes: int, init=None) -> FoldedRows:
+        """``fold_in_users`` with the sides exchanged: the item column of ``features`` holds new-item
+        indices, the user column known user ids, and ``P, b_u`` are held fixed."""
+        return self._fold_in(1, data, n_new, n_passes, init)
+
+    def _append(self, folded: FoldedRows, side: str, M: DeviceSGD, bias: DeviceSGD) -> np.ndarray:
+        if not isinstance(folded, FoldedRows) or folded.side != side:
+            raise TypeError(f"append_{side}s takes the FoldedRows of fold_in_{side}s")
+        if tuple(folded.rows.shape[1:]) != (self.n_factors,):
+            raise ValueError(f"folded rows of {tuple(folded.rows.shape)} for a model of {self.n_factors} factors")
+        first = int(M.dev.shape[0])
+        M.append(folded.rows)
+        bias.append(folded.bias)
+        return np.arange(first, first + len(folded))
+
+    def append_users(self, folded: FoldedRows) -> np.ndarray:
+        """Grows ``P, b_u`` and ``n_users`` by folded user rows; returns their user ids."""
+        ids = self._append(folded, "user", self.P, self.b_u)
+        self.n_users += len(folded)
+        return ids
+
+    def append_items(self, folded: FoldedRows) -> np.ndarray:
+        """Grows ``Q, b_i`` and ``n_items`` by folded item rows; returns their item ids."""
+        ids = self._append(folded, "item", self.Q, self.b_i)
+        self.n_items += len(folded)
+        return ids
+
     # ------------------------------------------------------------ catalogue
-    def score_pairs(self, users=None) -> np.ndarray:
+    # new_users: the FoldedRows of fold_in_users stand in for P, b_u -- ``users`` and ``exclude``
+    # then index the folded rows, and the model is not touched
+    def score_pairs(self, users=None, new_users=None) -> np.ndarray:
         """``predict()`` of every (user, item) pair as a ``[n_users (or len(users)), n_items]``
         matrix: one dense product (recommend.py; src/mf.py:136-170 restated)."""
         from . import recommend as rec
 
-        return rec.score_pairs(*rec.operands(self), users)
+        return rec.score_pairs(*rec.operands(self, new_users=new_users), users)
 
-    def recommend(self, k: int, users=None, exclude=None):
+    def recommend(self, k: int, users=None, exclude=None, new_users=None):
         """The ``k`` (1..64) best items per user: ``(items int32 [n, k], scores float64 [n, k])``,
         ranked by logit (ties: higher item index first); ``exclude``: CSR by user id."""
         from . import recommend as rec
 
-        return rec.topk(*rec.operands(self), k, users, exclude)
+        return rec.topk(*rec.operands(self, new_users=new_users), k, users, exclude)
 
-    def rank_items(self, users, items, exclude=None):
+    def rank_items(self, users, items, exclude=None, new_users=None):
         """Where the pairs ``(users[n], items[n])`` land in their users' ranking of all items:
         ``(ranks int32 [n], scores float64 [n], candidates int32 [n])`` in input order, ranks
         0-based under ``recommend()``'s order, at any depth (recommend.py)."""
         from . import recommend as rec
 
-        return rec.rank_items(*rec.operands(self), users, items, exclude)
+        return rec.rank_items(*rec.operands(self, new_users=new_users), users, items, exclude)
 
-    def rank_catalogue(self, depth: int, users=None, exclude=None):
+    def rank_catalogue(self, depth: int, users=None, exclude=None, new_users=None):
         """Every user's ranking of all items down to ``depth`` (any integer >= 1): ``(items int32
         [n, depth], scores float64 [n, depth], n_ranked int32 [n])`` under ``recommend()``'s
         order, short rows padded with item -1 / score NaN (recommend.py)."""
         from . import recommend as rec
 
-        return rec.rank_catalogue(*rec.operands(self), depth, users, exclude)
+        return rec.rank_catalogue(*rec.operands(self, new_users=new_users), depth, users, exclude)

@@ -34,6 +34,13 @@ class DeviceSGD:
             p[index] -= self.lr * grad
         self.set(p)
 
+    def append(self, dev_rows) -> None:
+        """Grows the parameters by the device tensor ``dev_rows`` along the first axis (fold-in)."""
+        import torch
+
+        self.dev = torch.cat([self.dev, dev_rows.to(self.dev.dtype)], dim=0).contiguous()
+        self._shape = tuple(self.dev.shape)
+
     def set(self, params: np.ndarray) -> None:
         host = np.ascontiguousarray(params, dtype=np.float64).reshape(self._shape)
         self.dev.copy_(self._rt.upload(host))

@@ -143,6 +143,8 @@ def padded(rt: Runtime, M, n_factors: int, out=None):
         return M
     if out is None:
         out = torch.zeros((M.shape[0], kp), dtype=torch.float64, device=rt.torch_device)
+    elif tuple(out.shape) != (M.shape[0], kp):  # (an earlier result for other rows, new_users= among them)
+        raise ValueError(f"{M.shape[0]} rows x {kp} into a buffer of {tuple(out.shape)}")
     out[:, :n_factors] = M
     return out
 
@@ -161,11 +163,24 @@ def catalogue_shape(model, sides=None) -> Tuple[int, int]:
     return int(model.n_users), int(model.n_items)
 
 
-def operands(model, sides=None, into: Optional[Operands] = None) -> Operands:
+def operands(model, sides=None, into: Optional[Operands] = None, new_users=None) -> Operands:
     """The ``Operands`` of a model as it stands.  FM (``sides``: its ``Sides``): two side-sum
     launches per call.  MF: ``P, b_u, Q, b_i``, the uploaded ``b``, zero-padded copies of P, Q when
     ``n_factors % 4``.  ``into``: an earlier result for the same shapes, whose buffers are refreshed
-    in place on the runtime's stream -- no allocation, no host wait."""
+    in place on the runtime's stream -- no allocation, no host wait; buffers of another shape (the
+    operands of the model's own users as ``into`` of a call with ``new_users``, say) are a
+    ``ValueError``.  ``new_users`` (MF): the
+    ``FoldedRows`` of ``fold_in_users``, whose rows and biases stand in for ``P, b_u`` (DESIGN.md 8
+    N13): the operands' users are then the folded rows, and the model is not touched."""
+    if new_users is not None:
+        if hasattr(model, "n_features"):
+            raise TypeError("new_users is for LogisticMatrixFactorization: the new rows of an FM model go "
+                            "into its recommend.Sides")
+        if getattr(new_users, "side", None) != "user":
+            raise TypeError("new_users takes the FoldedRows of fold_in_users")
+        if tuple(new_users.rows.shape[1:]) != (int(model.n_factors),):
+            raise ValueError(f"folded rows of {tuple(new_users.rows.shape)} for a model of {int(model.n_factors)} "
+                             f"factors")
     catalogue_shape(model, sides)
     rt, kf = model._rt, int(model.n_factors)
     _, A, LU, B, LI, c, _ = into or (None,) * 7
@@ -180,7 +195,8 @@ def operands(model, sides=None, into: Optional[Operands] = None) -> Operands:
     elif c.holds != b:  # (a fit does not change b: no launch between its iterations)
         c.fill_(b)
     c.holds = b
-    return Operands(rt, padded(rt, model.P.dev, kf, A), model.b_u.dev, padded(rt, model.Q.dev, kf, B),
+    user_rows, user_bias = (model.P.dev, model.b_u.dev) if new_users is None else (new_users.rows, new_users.bias)
+    return Operands(rt, padded(rt, user_rows, kf, A), user_bias, padded(rt, model.Q.dev, kf, B),
                     model.b_i.dev, c, kf)
 
 
