@@ -66,6 +66,10 @@ constexpr int rows_in_flight_plain(int nc) { return nc == 1 ? kFwdRowsPlain : 1;
 constexpr bool hot_fixed_order(int lpr, int nc, int block, int rows) {
   return nc == 1 && (block / lpr) * rows <= 128;
 }
+// Hot tile (arrival-order hot sums, 16 lanes x 2 factors per row): the kTileRanks most frequent
+// hot columns' err * x * q are summed on the matrix core, see the kernel's hot pass
+constexpr int kTileRanks = 16;  // 16 or 32: tiles of 16 ranks (32 measured no faster: DESIGN.md section 7)
+constexpr bool hot_tile(int lpr, int vec, int nc) { return lpr == 16 && vec == 2 && nc == 1; }
 constexpr int kHotUnroll = 2;  // rows of a fixed-order hot sum whose LDS reads are in flight together
 constexpr int kHotPosPad = 4;  // bytes between the position rows of two columns (bank spread)
 // LDS bytes of the forward kernel (what a launch asks for)
@@ -76,6 +80,9 @@ inline size_t forward_lds_bytes(int block, int lpr, int vec, int nc, int rows, i
   // (many-rows shape without a hot class -- the loss forwards: two stages of a trip's
   // {score, label, propensity}, see the kernel)
   if (block == kBigBlock && n_hot == 0) bytes += 2 * size_t(block / lpr) * rows * 24;
+  // (hot tile: a lane group's coefficients by rank, one strip per row in flight)
+  if (!fixed_order && n_hot > 0 && hot_tile(lpr, vec, nc))
+    bytes += size_t(block / lpr) * rows * kTileRanks * 8;
   if (fixed_order && n_hot > 0 && hot_fixed_order(lpr, nc, block, rows)) {
     const size_t rt = size_t(block / lpr) * rows;
     bytes += rt * size_t(lpr * vec) * 8;                                 // Q rows of the trip
@@ -172,6 +179,8 @@ static_assert(sizeof(HotEnt) == sizeof(Entry), "HotEnt replaces an Entry in plac
 // REC: read the training plan's records (RowRec / Entry); otherwise the
 // caller's CSR arrays.
 // LDS (dynamic): red[BLOCK] f64 | entry buffer [BLOCK/LPR][R*LPR+1] Entry | hot sums [H][k+2] f64
+//   | hot tile: coefficient strips [R][BLOCK/LPR][kTileRanks] f64 (hot_tile shapes, REC && !DET)
+//   | fixed-order hot sums (DET): Q rows, cell sums, row sets, entry positions
 // ELL (with REC): the records come as padded row blocks (a.ell).
 // DET (with REC): the hot-class sums in a fixed order (hot_fixed_order) instead of LDS atomics.
 // SEG (without REC, many-rows shape): two logs in one launch, see FwdArgs.
@@ -228,6 +237,9 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? kBigWaves : 1)) void f
   constexpr int NHV = NCELL > 1 ? GPB / NCELL : 0;  // columns cut into cells: one cell per group
   constexpr int PS = RT + kHotPosPad;    // bytes of a column's position row
   double* Qs = hot + H * hot_w;
+  // hot tile (see the arrival-order hot pass): the kTileRanks most frequent hot columns' factor
+  // sums go through the matrix core
+  constexpr bool TILE = REC && !DET && hot_tile(LPR, VEC, NC);
   double* part = Qs + RT * KS;           // [GPB][k+2] cell sums (NCELL > 1)
   unsigned int* hbits = reinterpret_cast<unsigned int*>(part + (NCELL > 1 ? GPB * hot_w : 0));
   uint8_t* hpos = reinterpret_cast<uint8_t*>(hbits + ((H * NW + 1) & ~1));
@@ -528,7 +540,9 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? kBigWaves : 1)) void f
       // of the plan's longest row, whatever its own rows need)
       const bool fix_hot = FIX && H > 0;
       const int rounds_len = fix_hot ? a.hot_rounds * LPR : maxlen;
-      for (int pb = 0; pb < rounds_len; pb += LPR) {
+      // (hot tile: the matrix core ignores the execution mask, so the lane groups of a wavefront
+      // make the rounds of its longest row together; a group past its own rows has no live entry)
+      for (int pb = 0; TILE ? __ballot(pb < rounds_len) != 0 : pb < rounds_len; pb += LPR) {
         Entry em[R];
 #pragma unroll
         for (int i = 0; i < R; ++i) {
@@ -687,6 +701,118 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? kBigWaves : 1)) void f
 #pragma unroll
                 for (int c = 0; c < NCELL; ++c) sum += part[(g * NCELL + c) * hot_w + f];
                 hrow[f] = sum;
+              }
+            }
+          }
+          continue;
+        }
+        if constexpr (TILE) {
+          // ---- arrival-order hot sums, the most frequent columns on the matrix core ----
+          // A live hot entry of rank h < kTileRanks is a TILE entry: its err * x * q goes into
+          // G[rank][factor] += C[rank][row] * Q[row][factor], one v_mfma_f64_16x16x4 per row in
+          // flight, tile of 16 ranks and factor parity -- the wavefront's four lane groups are
+          // the four k-slots, lane j of a group holds factors 2j, 2j + 1 (the B operand as it
+          // stands) -- and the tile is flushed into the LDS sums once per round.  The other
+          // live hot entries are walked as before, compacted to the front of the round.
+          constexpr int GPW = kWave / LPR;  // lane groups of a wave
+          constexpr int NT = kTileRanks / 16;
+          typedef double tile_acc __attribute__((ext_vector_type(4)));
+          // (the lane's constants of this pass are derived here, from a value the compiler cannot
+          // see through: hoisted out of the trip loop they would hold registers under the gathers)
+          int tid_here = tid;
+          asm volatile("" : "+v"(tid_here));
+          const int lh = tid_here % LPR, gh = tid_here / LPR, gw = gh % GPW;
+          HotEnt* const hbuf = reinterpret_cast<HotEnt*>(ebuf);
+          double* const strip = hot + H * hot_w;  // [R][GPB][kTileRanks], behind the hot sums
+          bool rowok[R], won[R];
+          unsigned long long walked[R];  // the wave's lanes whose entry of row i is walked
+#pragma unroll
+          for (int i = 0; i < R; ++i) {
+            const bool live = pb + l < len[i] && em[i].slot < 0;
+            const int h = -1 - em[i].slot;
+            // Containment: a non-finite row of V reaches only the columns of the rows that hold
+            // it, and 0 * NaN inside the tile would spread it.  A row that is not valid, or whose
+            // residual is not finite, gives zeros to B and keeps all its hot entries on the walk.
+            // A finite residual implies a finite q: any non-finite q[f] makes `pair` NaN.
+            rowok[i] = valid[i] && __builtin_isfinite(err[i]);
+            const bool tile_e = live && rowok[i] && h < kTileRanks;
+            won[i] = live && !tile_e;
+            walked[i] = __ballot(won[i]);
+            const double coef = err[i] * em[i].x;
+            if (live) {  // the [k] / [k+1] sums by the entry's own lane, tile entry or not
+              double* const hsum = hot + (-em[i].slot * hot_w - 2);
+              unsafeAtomicAdd(hsum, coef);
+              unsafeAtomicAdd(hsum + 1, coef * em[i].x);
+            }
+            // A operand: lane r of the group gets the coefficient of the row's entry of rank r
+            // (+ 16 per tile), 0 where the row has none -- through the group's strip (same
+            // wavefront, program order; read back where the products are issued)
+            double* const st = strip + (i * GPB + gh) * kTileRanks;
+#pragma unroll
+            for (int tl = 0; tl < NT; ++tl) st[tl * 16 + lh] = 0.0;
+            if (tile_e) st[h] = coef;
+          }
+          // the entries the wave walks: the largest count of a row of its groups (scalar)
+          int wcnt = 0;
+#pragma unroll
+          for (int i = 0; i < R; ++i)
+#pragma unroll
+            for (int gq = 0; gq < GPW; ++gq)
+              wcnt = max(wcnt, __popc(unsigned(walked[i] >> (gq * LPR)) & ((1u << LPR) - 1u)));
+          // (the lane groups of a wave start at different entries, as adds to one LDS address
+          // from several groups in one instruction serialise)
+          const int rot = (gw * wcnt) / GPW;
+#pragma unroll
+          for (int i = 0; i < R; ++i) {
+            // walked entries first, in lane order (an entry's place: the walked entries of its
+            // row in lower lanes); the other lanes fill the positions behind them
+            const unsigned bits = unsigned(walked[i] >> (gw * LPR)) & ((1u << LPR) - 1u);
+            const int below = __popc(bits & ((1u << lh) - 1u));
+            const int p = won[i] ? below : __popc(bits) + lh - below;
+            const int at = p - rot < 0 ? p - rot + wcnt : p - rot;
+            if (p < wcnt)
+              hbuf[i * LPR + at] = HotEnt{won[i] ? (-1 - em[i].slot) * hot_w : -1, 0, err[i] * em[i].x};
+          }
+          // one factor parity at a time (the tile's registers are the pass's widest item)
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) {
+            tile_acc D[NT];
+#pragma unroll
+            for (int tl = 0; tl < NT; ++tl) D[tl] = tile_acc{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int i = 0; i < R; ++i) {
+              const double* const st = strip + (i * GPB + gh) * kTileRanks;
+              const double b = rowok[i] ? q[i][0][v] : 0.0;
+#pragma unroll
+              for (int tl = 0; tl < NT; ++tl)
+                D[tl] = __builtin_amdgcn_mfma_f64_16x16x4f64(st[tl * 16 + lh], b, D[tl], 0, 0, 0);
+            }
+            // flush: D register `reg` of a lane is rank (lane >> 4) + 4 reg, factor 2 (lane & 15) + v
+#pragma unroll
+            for (int tl = 0; tl < NT; ++tl)
+#pragma unroll
+              for (int reg = 0; reg < 4; ++reg) {
+                const int rank = tl * 16 + gw + 4 * reg;
+                if (rank < H && fok[0]) unsafeAtomicAdd(hot + rank * hot_w + fo[0] + v, D[tl][reg]);
+              }
+          }
+          for (int j = 0; j < wcnt; ++j) {
+            HotEnt eh[R];
+#pragma unroll
+            for (int i = 0; i < R; ++i) eh[i] = hbuf[i * LPR + j];  // broadcast in the group
+            // two rows of the group holding the same hot column: one add for both
+            const bool pair01 = R == 2 && eh[0].off >= 0 && eh[0].off == eh[R - 1].off;
+            const double coef2 = pair01 ? eh[R - 1].coef : 0.0;
+            if (pair01) eh[R - 1].off = -1;
+#pragma unroll
+            for (int i = 0; i < R; ++i) {
+              if (eh[i].off >= 0 && fok[0]) {
+                double* hrow = hot + eh[i].off + fo[0];
+#pragma unroll
+                for (int v = 0; v < VEC; ++v)
+                  unsafeAtomicAdd(hrow + v, R == 2 && i == 0
+                                                ? eh[0].coef * q[0][0][v] + coef2 * q[R - 1][0][v]
+                                                : eh[i].coef * q[i][0][v]);
               }
             }
           }
