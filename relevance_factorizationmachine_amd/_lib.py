@@ -97,7 +97,22 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
 _i32, _i64, _f64, _vp = C.c_int32, C.c_int64, C.c_double, C.c_void_p
 
-# name -> argtypes; every function returns int32.  Mirrors include/rfm_hip.h.
+# argument groups that several entries share, each named once
+_CSR = [_vp, _vp, _vp]                     # indptr, indices, values
+_FM_PARAMS = [_vp, _vp, _vp]               # w0, w, V
+# what every training entry ends its own arguments with (fm.FmFit.tail): parameters, lr, the
+# validation split (CSR, labels, pscores, n_val), eps, the two loss outputs
+_TRAIN_TAIL = _FM_PARAMS + [_f64] + _CSR + [_vp, _vp, _i64, _f64, _vp, _vp]
+# rfm_fm_train and its kin: ctx, plan, the training log, labels, pscores, ids, batch, n_iters
+_TRAIN = [_vp, _vp] + _CSR + [_vp, _vp, _vp, _i64, _i64] + _TRAIN_TAIL
+# rfm_fm_fit_dp and its kin: ctx, plan, transport, exchange, ids, global_batch, n_iters
+_FIT_DP = [_vp, _vp, _vp, _i32, _vp, _i64, _i64] + _TRAIN_TAIL
+# every rfm_pair_* entry (recommend.Operands.pair_args): ctx, A, LU, n_users, user ids, n_sel, B,
+# LI, n_items, n_factors, c
+_PAIR = [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp]
+
+# name -> argtypes; every function returns int32.  Mirrors include/rfm_hip.h
+# (tests/test_host_abi.py compares the two, argument by argument).
 SIGNATURES = {
     "rfm_version": [],
     "rfm_last_error": [C.c_char_p, C.c_size_t],
@@ -132,21 +147,14 @@ SIGNATURES = {
     "rfm_fm_apply_rows": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _f64],
     "rfm_fm_reduce_rows": [_vp, _vp, _vp, _i32, _i64, _vp, _vp, _i64, _i32, _f64, _vp],
     "rfm_fm_set_rows": [_vp, _vp, _i64, _vp, _i32, _i64, _vp, _vp, _vp, _i64, _i32, _f64],
-    "rfm_fm_train": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _f64,
-                     _vp, _vp, _vp, _vp, _vp, _i64, _f64, _vp, _vp],
-    "rfm_fm_train_part": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _f64,
-                          _vp, _vp, _vp, _vp, _vp, _i64, _f64, _vp, _vp, _i64],
+    "rfm_fm_train": _TRAIN,
+    "rfm_fm_train_part": _TRAIN + [_i64],
     "rfm_fm_forward_geometry": [_vp, _i64, _i32, _i32, _vp],
     "rfm_fm_train_forms": [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
-    "rfm_fm_train_eval": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _f64,
-                     _vp, _vp, _vp, _vp, _vp, _i64, _f64, _vp, _vp,
-                          _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _i64, _i64, _vp],
-    "rfm_fm_fit_dp": [_vp, _vp, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _f64, _vp, _vp, _vp, _vp, _vp,
-                      _i64, _f64, _vp, _vp],
-    "rfm_fm_fit_dp_eval": [_vp, _vp, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _f64, _vp, _vp, _vp, _vp, _vp,
-                           _i64, _f64, _vp, _vp,
-                           _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _i64,
-                           _i64, _vp, _i32, _i32, _vp, _vp],
+    "rfm_fm_train_eval": _TRAIN + _CSR + [_i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _i64, _i64, _vp],
+    "rfm_fm_fit_dp": _FIT_DP,
+    "rfm_fm_fit_dp_eval": _FIT_DP + _CSR + [_i64, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _i64, _i64, _vp,
+                                     _i32, _i32, _vp, _vp],
     "rfm_mf_predict": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _i32, _vp],
     "rfm_mf_predict_loss": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _i32,
                             _f64, _vp, _vp],
@@ -173,22 +181,17 @@ SIGNATURES = {
     "rfm_csr_assemble_fill": [_vp, _vp, _i32, _i64, _vp, _vp, _vp],
     "rfm_topk_users": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
     "rfm_fm_side_sums": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp],
-    "rfm_pair_scores": [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp],
+    "rfm_pair_scores": _PAIR + [_vp],
     "rfm_pair_topk_workspace": [_i64, _i64, _i32, C.POINTER(_i64)],
-    "rfm_pair_topk": [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _vp,
-                      _vp],
+    "rfm_pair_topk": _PAIR + [_vp, _vp, _i32, _vp, _vp, _vp],
     "rfm_pair_ranks_workspace": [_i64, _i64, _i64, C.POINTER(_i64)],
-    "rfm_pair_ranks": [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                       _vp, _vp],
-    "rfm_pair_ranks_n": [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp,
-                         _vp, _vp, _vp],
+    "rfm_pair_ranks": _PAIR + [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "rfm_pair_ranks_n": _PAIR + [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
     "rfm_rank_metrics_workspace": [_i64, _i64, _i32, C.POINTER(_i64)],
     "rfm_rank_metrics": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
     "rfm_pair_order_workspace": [_i64, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64)],
-    "rfm_pair_order": [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
-                       _vp, _vp],
+    "rfm_pair_order": _PAIR + [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
 }
-
 
 
 # ``rfm_transport`` of include/rfm_hip.h: the collectives of rfm_fm_fit_dp as caller functions

@@ -16,6 +16,8 @@ from __future__ import annotations
 
 from typing import Callable, Tuple
 
+from .evaluate import CatalogueValEvaluator, FitHook, SlotLoop, host_frame, leave_y_score, runs
+
 
 def shard_bounds(batch: int, world: int, rank: int) -> Tuple[int, int]:
     """Contiguous shard [lo, hi) of ``batch`` rows for ``rank``; the first
@@ -605,7 +607,7 @@ def choose_exchange(n_features: int, n_factors: int, global_batch: int) -> str:
     return "rows" if 4 * touched * (n_factors + 2) * 2 < n_features * (n_factors + 1) else "dense"
 
 
-class DpEvalLoop:
+class DpEvalLoop(SlotLoop):
     """The evaluator of a data-parallel fit on the device (``rfm_fm_fit_dp_eval``): ``EvalLoop``
     with the evaluation log cut by user groups.
 
@@ -617,15 +619,15 @@ class DpEvalLoop:
     recomputes it from its own shard's scores (``ValFrame.host_user_values``), the ranks swap those
     few values (``all_gather_object``), and every rank forms the mean ``ValFrame.resolve`` would."""
 
-    def __init__(self, rt, plan, frame, ev, evaluator, world: int, rank: int, n_epochs: int, group=None):
+    def __init__(self, st, frame, ev, evaluator, world: int, rank: int, group=None):
         import numpy as np
         import torch
 
         from . import _lib
-        from .evaluate import EvalLoop
         from .features import take_rows
 
-        self.rt, self.frame, self.evaluator, self.world, self.rank, self.group = rt, frame, evaluator, world, rank, group
+        rt = st.rt
+        self.st, self.frame, self.evaluator, self.world, self.rank, self.group = st, frame, evaluator, world, rank, group
         self.ev = ev  # the whole log on the device (the scores left behind at the end)
         seg = frame.h_seg_ptr
         self.group_lo = np.ascontiguousarray(group_shard_bounds(seg, world), dtype=np.int32)
@@ -639,7 +641,7 @@ class DpEvalLoop:
         self.csr = take_rows(rt, ev, frame.h_order[r0: r0 + self.n_rows]) if self.n_rows else None
         if self.csr is not None:  # (the plan translates the shard once, not once per iteration)
             _lib.check(rt.lib.rfm_fm_plan_register_log(
-                rt.ctx, plan.handle, 1, self.csr.indptr.data_ptr(), self.csr.indices.data_ptr(),
+                rt.ctx, st.plan.handle, 1, self.csr.indptr.data_ptr(), self.csr.indices.data_ptr(),
                 self.csr.values.data_ptr(), self.n_rows))
         loc = self.local
         self.seg_ptr = rt.upload(loc.h_seg_ptr)
@@ -649,21 +651,11 @@ class DpEvalLoop:
         # every rank cuts its runs at the same iterations (the collectives pair up): the chunk is
         # sized by the largest shard, not by this one
         n = frame.n_segments
-        per_iter = 8 * (max_rows + self.user_stride + 3 * n) + 16
-        self.chunk = int(max(1, min(max(n_epochs, 1), EvalLoop.CHUNK_BYTES // per_iter)))
+        super().__init__(rt, st.model.n_epochs, 8 * (max_rows + self.user_stride + 3 * n) + 16)
         f64 = torch.float64
         self.scores = rt.empty((self.chunk, max(self.n_rows, 1)), f64)
         self.slots = rt.empty((self.chunk, self.user_stride), f64)
         self.full = rt.empty((self.chunk, max(3 * n, 1)), f64)
-        self.out = rt.empty((max(n_epochs, 1), 2), f64)
-        self.values: list = []
-        self.host_calls = 0
-        self.host_users = 0
-        self._flushed = 0
-
-    def room(self, epoch: int) -> int:
-        """Iterations from ``epoch`` on that fit the current chunk of score slots."""
-        return self.chunk - epoch % self.chunk
 
     def call_args(self, first: int) -> tuple:
         """The evaluation arguments of ``rfm_fm_fit_dp_eval`` for a run that starts at ``first``."""
@@ -677,22 +669,12 @@ class DpEvalLoop:
                 self.group_lo.ctypes.data, self.pad, n, self.full.data_ptr() + slot * self.full.shape[1] * 8,
                 self.out.data_ptr() + first * 16)
 
-    def ran(self, first: int, count: int) -> None:
-        """Iterations ``first .. first + count`` (inside one chunk) were scored and measured."""
-        if (first + count) % self.chunk == 0:
-            self._flush(first + count)
-
-    def _flush(self, upto: int) -> None:
+    def _resolve(self, flagged: list) -> dict:
         import numpy as np
 
-        if upto <= self._flushed:
-            return
-        self.rt.sync()
+        # (the table of values and its means are the same on every rank, bit for bit: so is
+        # `flagged`, and every rank takes part in the one exchange below or none does)
         n = self.frame.n_segments
-        o = self.out[self._flushed:upto].cpu().numpy()
-        # (the table and its means are the same on every rank, bit for bit: so is this list, and
-        # every rank takes part in the exchange below or none does)
-        flagged = [e for i, e in enumerate(range(self._flushed, upto)) if o[i, 1] != 0.0]
         tables, mine = {}, []
         for e in flagged:
             t = self.full[e % self.chunk][: 3 * n].cpu().numpy()
@@ -708,100 +690,83 @@ class DpEvalLoop:
 
             parts = [None] * self.world
             dist.all_gather_object(parts, mine, group=self.group)
-        fixed = {}
+        vals = {e: t[:n].copy() for e, t in tables.items()}
         for part in parts:
-            for e, groups, vals in part:
-                fixed.setdefault(e, []).append((groups, vals))
-        for i, e in enumerate(range(self._flushed, upto)):
-            if o[i, 1] == 0.0:
-                self.values.append(float(o[i, 0]))
-                continue
-            t = tables[e]
-            vals = t[:n].copy()
-            counted = t[n: 2 * n] != 0.0
-            for groups, v in fixed.get(e, []):
-                vals[groups] = v
-            self.values.append(float(np.mean(vals[counted])))
-            self.host_calls += 1
-            self.host_users += int(o[i, 1])
-        self._flushed = upto
+            for e, groups, v in part:
+                vals[e][groups] = v
+        return {e: float(np.mean(vals[e][tables[e][n: 2 * n] != 0.0])) for e in flagged}
 
-    def finish(self, n_done: int) -> list:
-        self._flush(n_done)
-        return self.values
+    def leave_scores(self, epoch: int) -> None:
+        """The whole log's scores with the final parameters into the evaluator's frame
+        (``evaluate.leave_y_score``): one ``rfm_fm_plan_forward``, the same on every rank."""
+        import torch
+
+        from . import _lib
+
+        rt, ev, m = self.rt, self.ev, self.st.model
+        n = ev.shape[0]
+        out = rt.empty((max(n, 1),), torch.float64)
+        if n:
+            _lib.check(rt.lib.rfm_fm_plan_forward(
+                rt.ctx, self.st.plan.handle, ev.indptr.data_ptr(), ev.indices.data_ptr(), ev.values.data_ptr(), n,
+                m.w0.dev.data_ptr(), m.w.dev.data_ptr(), m.V.dev.data_ptr(), out.data_ptr()))
+        rt.sync()
+        leave_y_score(self.evaluator, out[:n].cpu().numpy())
 
 
 class HipDpEngine:
     """One rank's side of ``fit_data_parallel`` on the HIP kernels: the log replicated in HBM,
-    a training plan for this rank's shard size, and runs of iterations handed to
+    a training plan for this rank's shard size (``fm.FmFit``), and runs of iterations handed to
     ``rfm_fm_fit_dp`` (gradients, exchange, update and both losses enqueued on the stream)."""
 
     def __init__(self, model, train, val, world: int, rank: int, exchange: str, transport):
-        import numpy as np
-
-        from . import _lib
-        from .fm import FmPlan
-        from .runtime import BatchIdStream, DeviceCSR
+        from .fm import FmFit
+        from .runtime import BatchIdStream
 
         rt = model._rt
         self.rt, self.model, self.world, self.rank = rt, model, world, rank
         X = train["features"]
         if X.shape[1] != model.n_features:
             raise ValueError(f"train features have {X.shape[1]} columns, model has {model.n_features}")
-        self.global_batch = model.batch_size
-        self.ids = BatchIdStream(rt, X.shape[0], self.global_batch, model.n_epochs, need_host=False,
+        self.ids = BatchIdStream(rt, X.shape[0], model.batch_size, model.n_epochs, need_host=False,
                                  device_sampler=getattr(model, "device_sampler", False))
         try:
-            self.tr = X if isinstance(X, DeviceCSR) else DeviceCSR(rt, X)
-            self.y = rt.upload(np.asarray(train["labels"]), dtype=np.float64)
-            self.p = rt.upload(np.asarray(train["pscores"]), dtype=np.float64)
-            vX = val["features"]
-            self.va = vX if isinstance(vX, DeviceCSR) else DeviceCSR(rt, vX)
-            self.vy = rt.upload(np.asarray(val["labels"]), dtype=np.float64)
-            self.vp = rt.upload(np.asarray(val["pscores"]), dtype=np.float64)
-            lo, hi = shard_bounds(self.global_batch, world, 0)  # rank 0 holds a largest shard
-            hot = -2 if model.deterministic else model.hot_min_count
-            self.plan = FmPlan(rt, self.tr, self.y, self.p, model.n_factors, max(hi - lo, 1), hot)
+            lo, hi = shard_bounds(model.batch_size, world, 0)  # rank 0 holds a largest shard
+            self.st = FmFit(model, train, val, max(hi - lo, 1), cached=False)
         except BaseException:
             self.ids.close()
             raise
         self.exchange = {"dense": 0, "rows": 1}[exchange]
         self.transport = transport
         self._c_transport = transport.c_struct() if transport is not None else None
-        self.tl = rt.empty((model.n_epochs,), self.y.dtype)
-        self.vl = rt.empty((model.n_epochs,), self.y.dtype)
-        self.has_val = self.va.shape[0] > 0
-        if not self.has_val:
-            self.vl.fill_(float("nan"))
-        self._lib = _lib
+        self._loop = None
 
     def chunks(self):
         for first, _host, dev_ids in self.ids.chunks():
             yield first, dev_ids.shape[0], dev_ids
 
-    def run(self, first: int, count: int, chunk_first: int, dev_ids) -> None:
+    def run(self, first: int, count: int, chunk_first: int, dev_ids, loop=None) -> None:
+        """Iterations ``first .. first + count`` of the ids ``dev_ids`` (from ``chunk_first`` on):
+        ``rfm_fm_fit_dp``, or with ``loop`` its evaluator after every update
+        (``rfm_fm_fit_dp_eval``; ``count <= loop.room(first)``)."""
         import ctypes as C
 
-        from .base import LOSS_EPS
+        from . import _lib
 
-        m, rt, B = self.model, self.rt, self.global_batch
-        ids_ptr = dev_ids.data_ptr() + (first - chunk_first) * B * 4
+        rt, st = self.rt, self.st
         tp = C.byref(self._c_transport) if self._c_transport is not None else None
-        rc = rt.lib.rfm_fm_fit_dp(
-            rt.ctx, self.plan.handle, tp, self.exchange, ids_ptr, B, count,
-            m.w0.dev.data_ptr(), m.w.dev.data_ptr(), m.V.dev.data_ptr(), float(m.lr),
-            self.va.indptr.data_ptr(), self.va.indices.data_ptr(), self.va.values.data_ptr(),
-            self.vy.data_ptr(), self.vp.data_ptr(), self.va.shape[0], LOSS_EPS,
-            self.tl.data_ptr() + first * 8, self.vl.data_ptr() + first * 8 if self.has_val else None)
+        args = (rt.ctx, st.plan.handle, tp, self.exchange, st.ids_ptr(first, chunk_first, dev_ids),
+                self.model.batch_size, count, *st.tail(first))
+        rc = rt.lib.rfm_fm_fit_dp(*args) if loop is None else rt.lib.rfm_fm_fit_dp_eval(*args, *loop.call_args(first))
         if rc != 0 and self.transport is not None and self.transport.error is not None:
             raise self.transport.error
-        self._lib.check(rc)
+        _lib.check(rc)
+
+    run_eval = run  # (an engine with a device evaluator: fit_data_parallel looks for the name)
 
     def eval_loop(self, evaluator):
         """The device form of ``evaluator`` for ``run_eval`` (``DpEvalLoop``), or ``None`` when it is
         not recognised -- the rule of the single-GPU ``fit()`` (``evaluate.device_frame``)."""
-        from .evaluate import host_frame
-
         m = self.model
         ev_X = evaluator.features[m.model_name]
         frame = host_frame(evaluator, m.estimator, ev_X.shape[0])
@@ -809,65 +774,24 @@ class HipDpEngine:
             return None
         if ev_X.shape[1] != m.n_features:
             raise ValueError(f"X has {ev_X.shape[1]} columns, model has {m.n_features}")
-        ev = m._csr_cache.get(ev_X)
-        self._loop = DpEvalLoop(self.rt, self.plan, frame, ev, evaluator, self.world, self.rank, m.n_epochs,
+        self._loop = DpEvalLoop(self.st, frame, m._csr_cache.get(ev_X), evaluator, self.world, self.rank,
                                 getattr(self.transport, "group", None))
         return self._loop
-
-    def run_eval(self, first: int, count: int, chunk_first: int, dev_ids, loop) -> None:
-        """``run`` with the evaluator of ``loop`` after every update (``rfm_fm_fit_dp_eval``);
-        ``count <= loop.room(first)``."""
-        import ctypes as C
-
-        from .base import LOSS_EPS
-
-        m, rt, B = self.model, self.rt, self.global_batch
-        ids_ptr = dev_ids.data_ptr() + (first - chunk_first) * B * 4
-        tp = C.byref(self._c_transport) if self._c_transport is not None else None
-        rc = rt.lib.rfm_fm_fit_dp_eval(
-            rt.ctx, self.plan.handle, tp, self.exchange, ids_ptr, B, count,
-            m.w0.dev.data_ptr(), m.w.dev.data_ptr(), m.V.dev.data_ptr(), float(m.lr),
-            self.va.indptr.data_ptr(), self.va.indices.data_ptr(), self.va.values.data_ptr(),
-            self.vy.data_ptr(), self.vp.data_ptr(), self.va.shape[0], LOSS_EPS,
-            self.tl.data_ptr() + first * 8, self.vl.data_ptr() + first * 8 if self.has_val else None,
-            *loop.call_args(first))
-        if rc != 0 and self.transport is not None and self.transport.error is not None:
-            raise self.transport.error
-        self._lib.check(rc)
-
-    def leave_scores(self, loop) -> None:
-        """The reference's ``evaluate`` leaves the scores it was given in its frame
-        (``interaction_df["y_score"]``, utils/evaluate.py:224): the whole log's scores with the
-        final parameters, one ``rfm_fm_plan_forward`` (the same on every rank)."""
-        import torch
-
-        m, rt, ev = self.model, self.rt, loop.ev
-        n = ev.shape[0]
-        out = rt.empty((max(n, 1),), torch.float64)
-        if n:
-            self._lib.check(rt.lib.rfm_fm_plan_forward(
-                rt.ctx, self.plan.handle, ev.indptr.data_ptr(), ev.indices.data_ptr(), ev.values.data_ptr(), n,
-                m.w0.dev.data_ptr(), m.w.dev.data_ptr(), m.V.dev.data_ptr(), out.data_ptr()))
-        rt.sync()
-        try:
-            loop.evaluator.interaction_df["y_score"] = out[:n].cpu().numpy()
-        except Exception:  # noqa: BLE001 -- a read-only or exotic frame: nothing to leave
-            pass
 
     def predict(self, X):
         return self.model.predict(X=X)
 
     def losses(self):
         self.rt.sync()
-        return self.tl.cpu().numpy().tolist(), self.vl.cpu().numpy().tolist()
+        return self.st.losses()
 
     def close(self) -> None:
         self.ids.close()
         self.rt.sync()
-        if getattr(self, "_loop", None) is not None:  # (the shard's registration ends with the fit)
-            self.rt.lib.rfm_fm_plan_register_log(self.rt.ctx, self.plan.handle, 1, None, None, None, 0)
+        if self._loop is not None:  # (the shard's registration ends with the fit)
+            self.rt.lib.rfm_fm_plan_register_log(self.rt.ctx, self.st.plan.handle, 1, None, None, None, 0)
             self._loop = None
-        self.plan.close()
+        self.st.release()
 
 
 def fit_data_parallel(model, train: dict, val: dict, exchange: str = "auto", transport=None,
@@ -894,8 +818,6 @@ def fit_data_parallel(model, train: dict, val: dict, exchange: str = "auto", tra
     evaluator -- or an engine without ``run_eval`` -- is called after every iteration on every rank
     (the replicas are identical, so are the metrics).  ``engine_factory`` replaces the arithmetic
     (tests)."""
-    from .evaluate import CatalogueValEvaluator
-
     if isinstance(getattr(model, "evaluator", None), CatalogueValEvaluator):
         # (its users would have to be shared out over the ranks: DESIGN.md 8 N8, not built)
         raise NotImplementedError("fit_data_parallel does not take a CatalogueValEvaluator: the catalogue "
@@ -920,31 +842,17 @@ def fit_data_parallel(model, train: dict, val: dict, exchange: str = "auto", tra
         engine_factory = HipDpEngine
     engine = engine_factory(model, train, val, world, rank, exchange, transport)
     try:
-        evaluator = getattr(model, "evaluator", None)
-        loop = None
-        if evaluator is not None and getattr(model, "device_evaluator", False) and hasattr(engine, "run_eval"):
-            loop = engine.eval_loop(evaluator)
+        hook = FitHook(model, model.n_epochs, engine.predict,
+                       engine.eval_loop if hasattr(engine, "run_eval") else None)
         for chunk_first, count, ids in engine.chunks():
-            if evaluator is None:
-                engine.run(chunk_first, count, chunk_first, ids)
-            elif loop is not None:
-                # one library call per run of iterations that fits the chunk of score slots
-                at = chunk_first
-                while at < chunk_first + count:
-                    n = min(chunk_first + count - at, loop.room(at), 1 << 15)
-                    engine.run_eval(at, n, chunk_first, ids, loop)
-                    loop.ran(at, n)
-                    at += n
-            else:
-                for epoch in range(chunk_first, chunk_first + count):
-                    engine.run(epoch, 1, chunk_first, ids)
-                    scores = engine.predict(evaluator.features[model.model_name])
-                    model.val_metrics.append(evaluator.evaluate(y_scores=scores, estimator=model.estimator))
-        if loop is not None:
-            model.val_metrics.extend(loop.finish(model.n_epochs))
-            model.evaluator_host_calls = loop.host_calls
-            model.evaluator_host_users = loop.host_users
-            engine.leave_scores(loop)
+            # one library call per run of iterations (FitHook.limit), of at most 2^15
+            for at, n in runs(chunk_first, count, lambda at: min(hook.limit(at), 1 << 15)):
+                if hook.loop is None:
+                    engine.run(at, n, chunk_first, ids)
+                else:
+                    engine.run_eval(at, n, chunk_first, ids, hook.loop)
+                hook.ran(at, n)
+        hook.finish()
         return engine.losses()
     finally:
         engine.close()

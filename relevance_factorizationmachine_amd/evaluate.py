@@ -187,40 +187,42 @@ class DeviceValFrame(ValFrame):
         return s[:n].copy(), s[n: 2 * n] != 0.0, s[2 * n: 3 * n] != 0.0
 
 
-class EvalLoop:
-    """The evaluator hook of a ``fit()`` loop, computed on the device.
+def runs(first: int, count: int, limit):
+    """``(at, n)`` of consecutive runs that cover iterations ``first .. first + count``, the run
+    that starts at ``at`` no longer than ``limit(at)``: how every fit cuts an id chunk into
+    library calls."""
+    at, end = first, first + count
+    while at < end:
+        n = min(end - at, limit(at))
+        yield at, n
+        at += n
 
-    Per iteration the caller writes the evaluator's scores into ``slot(epoch)`` and
-    calls ``done(epoch)``; nothing returns to the host until a chunk of iterations is
-    complete.  For an iteration with tie-order dependent users, the scores and the
-    per-user results come back and those users are redone the reference's way
-    (``DeviceValFrame.resolve``) -- the list ``finish()`` returns is what calling the
-    evaluator every iteration would have produced on this machine."""
 
-    CHUNK_BYTES = 1 << 30
+def leave_y_score(evaluator, y_scores: np.ndarray) -> None:
+    """The reference's ``evaluate`` stores the scores it was given in its frame
+    (``interaction_df["y_score"] = y_scores``, utils/evaluate.py:224): so does a fit that never
+    called it."""
+    try:
+        evaluator.interaction_df["y_score"] = y_scores
+    except Exception:  # noqa: BLE001 -- a read-only or exotic frame: nothing to leave
+        pass
 
-    def __init__(self, rt: Runtime, frame: DeviceValFrame, evaluator, estimator: str, n_epochs: int):
-        self.rt, self.frame, self.evaluator, self.estimator = rt, frame, evaluator, estimator
-        self.n_epochs = n_epochs
-        per_iter = 8 * (frame.n_rows + 3 * frame.n_segments) + 8
-        self.chunk = int(max(1, min(max(n_epochs, 1), self.CHUNK_BYTES // per_iter)))
-        self.scores = rt.empty((self.chunk, max(frame.n_rows, 1)), frame.labels.dtype)
-        self.users = rt.empty((self.chunk, max(3 * frame.n_segments, 1)), frame.labels.dtype)
-        self.out = rt.empty((max(n_epochs, 1), 2), frame.labels.dtype)
+
+class SlotLoop:
+    """Chunks of per-iteration score slots on the device and the metric list they become: what
+    ``EvalLoop`` and ``dist.DpEvalLoop`` share.  ``out [n_epochs, 2]`` receives every iteration's
+    value and the number of users it is tie-order dependent for; nothing returns to the host until
+    a chunk of iterations is complete (``_flush``), and the flagged iterations of a chunk are then
+    resolved by one ``_resolve`` call of the subclass."""
+
+    def __init__(self, rt: Runtime, n_epochs: int, per_iter_bytes: int):
+        self.rt, self.n_epochs = rt, n_epochs
+        self.chunk = int(max(1, min(max(n_epochs, 1), EvalLoop.CHUNK_BYTES // per_iter_bytes)))
+        self.out = rt.empty((max(n_epochs, 1), 2), __import__("torch").float64)
         self.values: list = []
         self.host_calls = 0   # iterations that needed host work
         self.host_users = 0   # users redone on the host, over all iterations
         self._flushed = 0
-
-    def slot(self, epoch: int):
-        """Device tensor the scores of iteration ``epoch`` go to."""
-        return self.scores[epoch % self.chunk]
-
-    def done(self, epoch: int) -> None:
-        self.frame.dcg_into(self.slot(epoch), self.out.data_ptr() + epoch * 16,
-                            self.users[epoch % self.chunk].data_ptr())
-        if (epoch + 1) % self.chunk == 0:
-            self._flush(epoch + 1)
 
     def room(self, epoch: int) -> int:
         """Iterations from ``epoch`` on that fit the current chunk of score slots."""
@@ -228,20 +230,24 @@ class EvalLoop:
 
     def ran(self, first: int, count: int) -> None:
         """Iterations ``first .. first + count`` (inside one chunk: ``count <= room(first)``) were
-        scored and measured by the library itself (``rfm_fm_train_eval``)."""
+        scored and measured."""
         if (first + count) % self.chunk == 0:
             self._flush(first + count)
+
+    def _resolve(self, flagged: list) -> dict:
+        """``{iteration: value}`` of the iterations with tie-order dependent users."""
+        raise NotImplementedError
 
     def _flush(self, upto: int) -> None:
         if upto <= self._flushed:
             return
         self.rt.sync()
         o = self.out[self._flushed:upto].cpu().numpy()
-        for i, epoch in enumerate(range(self._flushed, upto)):
-            if o[i, 1] != 0.0:
-                y_scores = self.slot(epoch)[: self.frame.n_rows].cpu().numpy()
-                per_user = self.users[epoch % self.chunk].cpu().numpy()
-                self.values.append(self.frame.resolve(y_scores, per_user))
+        epochs = range(self._flushed, upto)
+        fixed = self._resolve([e for i, e in enumerate(epochs) if o[i, 1] != 0.0])
+        for i, e in enumerate(epochs):
+            if e in fixed:
+                self.values.append(fixed[e])
                 self.host_calls += 1
                 self.host_users += int(o[i, 1])
             else:
@@ -252,17 +258,55 @@ class EvalLoop:
         self._flush(n_done)
         return self.values
 
+
+class EvalLoop(SlotLoop):
+    """The evaluator hook of a ``fit()`` loop, computed on the device.
+
+    Per iteration the caller writes the evaluator's scores into ``slot(epoch)`` and calls
+    ``measure(epoch)`` (MF), or the library does both (``rfm_fm_train_eval`` with ``call_args``);
+    either way ``ran`` follows.  For an iteration with tie-order dependent users, the scores
+    and the per-user results come back and those users are redone the reference's way
+    (``DeviceValFrame.resolve``) -- the list ``finish()`` returns is what calling the
+    evaluator every iteration would have produced on this machine.  ``log``: the evaluator's
+    features on the device -- FM's matrix (``call_args``), MF's pairs."""
+
+    CHUNK_BYTES = 1 << 30
+
+    def __init__(self, rt: Runtime, frame: DeviceValFrame, evaluator, estimator: str, n_epochs: int, log=None):
+        super().__init__(rt, n_epochs, 8 * (frame.n_rows + 3 * frame.n_segments) + 8)
+        self.frame, self.evaluator, self.estimator, self.log = frame, evaluator, estimator, log
+        self.scores = rt.empty((self.chunk, max(frame.n_rows, 1)), frame.labels.dtype)
+        self.users = rt.empty((self.chunk, max(3 * frame.n_segments, 1)), frame.labels.dtype)
+
+    def slot(self, epoch: int):
+        """Device tensor the scores of iteration ``epoch`` go to."""
+        return self.scores[epoch % self.chunk]
+
+    def measure(self, epoch: int) -> None:
+        """Enqueue the metric of the scores in ``slot(epoch)``; the caller then reports ``ran(epoch, 1)``."""
+        self.frame.dcg_into(self.slot(epoch), self.out.data_ptr() + epoch * 16,
+                            self.users[epoch % self.chunk].data_ptr())
+
+    def call_args(self, first: int) -> tuple:
+        """The evaluation arguments of ``rfm_fm_train_eval`` for a run that starts at ``first``."""
+        ev, fr = self.log, self.frame
+        return (ev.indptr.data_ptr(), ev.indices.data_ptr(), ev.values.data_ptr(), ev.shape[0],
+                fr.seg_ptr.data_ptr(), fr.rows.data_ptr(), fr.labels.data_ptr(),
+                None if fr.pscores is None else fr.pscores.data_ptr(), fr.n_segments, fr.k,
+                self.scores.data_ptr(), self.scores.shape[1], self.users.data_ptr(), self.users.shape[1],
+                first % self.chunk, self.out.data_ptr() + first * 16)
+
+    def _resolve(self, flagged: list) -> dict:
+        return {e: self.frame.resolve(self.slot(e)[: self.frame.n_rows].cpu().numpy(),
+                                      self.users[e % self.chunk].cpu().numpy()) for e in flagged}
+
     def leave_scores(self, epoch: int) -> None:
-        """The reference's ``evaluate`` stores the scores it was given in its frame
-        (``interaction_df["y_score"] = y_scores``, utils/evaluate.py:224): leave the last
-        iteration's there, as the last host callback would have."""
+        """The last iteration's scores into the evaluator's frame, as the last host callback
+        would have left them (``leave_y_score``)."""
         if epoch < 0:
             return
-        try:
-            self.rt.sync()
-            self.evaluator.interaction_df["y_score"] = self.slot(epoch)[: self.frame.n_rows].cpu().numpy()
-        except Exception:  # noqa: BLE001 -- a read-only or exotic frame: nothing to leave
-            pass
+        self.rt.sync()
+        leave_y_score(self.evaluator, self.slot(epoch)[: self.frame.n_rows].cpu().numpy())
 
 
 def known_implementation(evaluator) -> bool:
@@ -321,6 +365,64 @@ def device_frame(rt: Runtime, evaluator, estimator: str, n_scores: int) -> Optio
         return None
     users, labels, pscores, k = got
     return DeviceValFrame(rt, users, labels, pscores, k)
+
+
+class FitHook:
+    """What one fit does about ``model.evaluator``: the one place where its path is chosen, for
+    ``FactorizationMachines.fit``, ``LogisticMatrixFactorization.fit`` and
+    ``dist.fit_data_parallel``.
+
+    - ``cat``: a ``CatalogueValEvaluator`` is given the model and enqueues its own evaluations
+      (DESIGN.md 8 N8);
+    - ``loop``: with ``model.device_evaluator``, ``make_loop(evaluator)`` -- the driver's score-slot
+      loop (``EvalLoop``, ``dist.DpEvalLoop``) -- or ``None`` when the driver has no device path
+      (``make_loop=None``) or does not recognise the evaluator (``device_frame`` / ``host_frame``);
+    - otherwise an evaluator is a host callback after every iteration, on ``predict``'s scores.
+
+    The driver cuts its id chunks with ``runs(first, count, hook.limit)``, calls ``ran`` after
+    enqueueing each run and ``finish`` once the stream is idle."""
+
+    def __init__(self, model, n_epochs: int, predict, make_loop=None):
+        self.model, self.n_epochs, self.predict = model, n_epochs, predict
+        self.evaluator = getattr(model, "evaluator", None)
+        self.cat = self.loop = None
+        if isinstance(self.evaluator, CatalogueValEvaluator):
+            self.cat = self.evaluator
+            self.cat.fit_begin(model, n_epochs)
+        elif self.evaluator is not None and make_loop is not None and getattr(model, "device_evaluator", False):
+            self.loop = make_loop(self.evaluator)
+
+    def limit(self, at: int) -> int:
+        """How many iterations the run that starts at ``at`` may hold."""
+        if self.cat is not None:
+            return self.cat.fit_run_length(at)  # (ends at the next evaluation point)
+        if self.loop is not None:
+            return self.loop.room(at)
+        return self.n_epochs if self.evaluator is None else 1
+
+    def ran(self, at: int, n: int) -> None:
+        """Iterations ``at .. at + n`` were enqueued."""
+        last = at + n - 1
+        if self.cat is not None:
+            if self.cat.fit_due(last):
+                self.cat.fit_enqueue(last)  # (behind the iteration, on the same stream)
+        elif self.loop is not None:
+            self.loop.ran(at, n)
+        elif self.evaluator is not None:
+            m = self.model
+            y_scores = self.predict(self.evaluator.features[m.model_name])
+            m.val_metrics.append(self.evaluator.evaluate(y_scores=y_scores, estimator=m.estimator))
+
+    def finish(self) -> None:
+        """The metric list into ``model.val_metrics``; the device loop's counters and last scores."""
+        m = self.model
+        if self.cat is not None:
+            m.val_metrics.extend(self.cat.fit_end())
+        elif self.loop is not None:
+            m.val_metrics.extend(self.loop.finish(self.n_epochs))
+            m.evaluator_host_calls = self.loop.host_calls
+            m.evaluator_host_users = self.loop.host_users
+            self.loop.leave_scores(self.n_epochs - 1)
 
 
 # ---------------------------------------------------------------------------

@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _lib
 from .base import LOSS_EPS, PointwiseBaseRecommender
-from .evaluate import CatalogueValEvaluator, EvalLoop, device_frame
+from .evaluate import EvalLoop, FitHook, device_frame, runs
 from .optimizer import DeviceSGD
 from .runtime import BatchIdStream, CsrCache, DeviceCSR, Runtime
 
@@ -130,6 +130,65 @@ class FmPlan:
             pass
 
 
+class FmFit:
+    """What a fit of FM holds on the device -- the split, the training plan, the two loss lists --
+    and the arguments that every training entry of the library shares (``rfm_fm_train``,
+    ``rfm_fm_train_part``, ``rfm_fm_train_eval``, ``rfm_fm_fit_dp``, ``rfm_fm_fit_dp_eval``).
+
+    ``cached``: the uploads and the plan come from the runtime's caches (``log_cache``,
+    ``upload_cached``, ``plan_cache``; subject to ``Runtime.remember_splits``) -- the single-GPU
+    fit, whose drivers fit several models on one split; else plain uploads and a plan of its own
+    (``dist.HipDpEngine``: ``max_batch`` is the largest shard)."""
+
+    def __init__(self, model, train: dict, val: dict, max_batch: int, cached: bool):
+        rt = self.rt = model._rt
+        self.model = model
+        self.keep = keep = cached and rt.remember_splits
+
+        # a log that is already in HBM (features.assemble / load_csr_to_device) is used as it is
+        # (cached: device copies of the split are remembered per device; an array edited in place
+        # is uploaded again -- CsrCache._fingerprint)
+        def log(X):
+            return X if isinstance(X, DeviceCSR) else (rt.log_cache().get(X) if keep else DeviceCSR(rt, X))
+
+        def vec(a):
+            return rt.upload_cached(a, np.float64) if keep else rt.upload(np.asarray(a), dtype=np.float64)
+
+        self.tr, self.y, self.p = log(train["features"]), vec(train["labels"]), vec(train["pscores"])
+        self.va, self.vy, self.vp = log(val["features"]), vec(val["labels"]), vec(val["pscores"])
+        hot = -2 if model.deterministic else model.hot_min_count
+        plan_args = (rt, self.tr, self.y, self.p, model.n_factors, max_batch, hot)
+        self.plan = plan_cache(rt).take(*plan_args) if keep else FmPlan(*plan_args)
+        self.tl = rt.empty((model.n_epochs,), self.y.dtype)
+        self.vl = rt.empty((model.n_epochs,), self.y.dtype)
+        # an empty validation set: the reference's mean over no rows is nan (src/base.py:61)
+        self.has_val = self.va.shape[0] > 0
+        if not self.has_val:
+            self.vl.fill_(float("nan"))
+
+    def ids_ptr(self, first: int, chunk_first: int, dev_ids) -> int:
+        """Address of iteration ``first``'s batch in ``dev_ids``, the ids from ``chunk_first`` on."""
+        return dev_ids.data_ptr() + (first - chunk_first) * self.model.batch_size * 4
+
+    def tail(self, first: int) -> tuple:
+        """The arguments every training entry ends its own with, for a run that starts at ``first``:
+        parameters, step size, validation split, and where the two losses go."""
+        m, va = self.model, self.va
+        return (m.w0.dev.data_ptr(), m.w.dev.data_ptr(), m.V.dev.data_ptr(), float(m.lr),
+                va.indptr.data_ptr(), va.indices.data_ptr(), va.values.data_ptr(),
+                self.vy.data_ptr(), self.vp.data_ptr(), va.shape[0], LOSS_EPS,
+                self.tl.data_ptr() + first * 8, self.vl.data_ptr() + first * 8 if self.has_val else None)
+
+    def losses(self) -> tuple:
+        return self.tl.cpu().numpy().tolist(), self.vl.cpu().numpy().tolist()
+
+    def release(self) -> None:
+        if self.keep:
+            plan_cache(self.rt).give_back(self.plan)
+        else:
+            self.plan.close()
+
+
 @dataclass
 class FactorizationMachines(PointwiseBaseRecommender):
     """Factorization Machines trained by mini-batch SGD on an MI355X.
@@ -204,132 +263,59 @@ class FactorizationMachines(PointwiseBaseRecommender):
 
     def _fit(self, train: dict, val: dict, id_stream: BatchIdStream) -> tuple:
         rt = self._rt
-        X = train["features"]
-
-        # a log that is already in HBM (features.assemble / load_csr_to_device) is used as it is
-        # (device copies of the split are remembered per device: the drivers fit several models
-        # on it; an array edited in place is uploaded again -- CsrCache._fingerprint)
-        keep = rt.remember_splits
-        tr = X if isinstance(X, DeviceCSR) else (rt.log_cache().get(X) if keep else DeviceCSR(rt, X))
-        y = rt.upload_cached(train["labels"], np.float64)
-        p = rt.upload_cached(train["pscores"], np.float64)
-        va = (val["features"] if isinstance(val["features"], DeviceCSR) else
-              (rt.log_cache().get(val["features"]) if keep else DeviceCSR(rt, val["features"])))
-        vy = rt.upload_cached(val["labels"], np.float64)
-        vp = rt.upload_cached(val["pscores"], np.float64)
-        hot = -2 if self.deterministic else self.hot_min_count
-        plan = (plan_cache(rt).take(rt, tr, y, p, self.n_factors, self.batch_size, hot) if keep
-                else FmPlan(rt, tr, y, p, self.n_factors, self.batch_size, hot))
+        st = FmFit(self, train, val, self.batch_size, cached=True)
+        plan, tr, va = st.plan, st.tr, st.va
         self.plan_info = dict(plan.info(), **plan.layout(), **plan.sliced())  # (what the last fit trained with)
-        if va.shape[0] > 0:  # (the split's device copy does not change during this fit)
+        if st.has_val:  # (the split's device copy does not change during this fit)
             _lib.check(rt.lib.rfm_fm_plan_register_log(
                 rt.ctx, plan.handle, 0, va.indptr.data_ptr(), va.indices.data_ptr(), va.values.data_ptr(),
                 va.shape[0]))
-        tl = rt.empty((self.n_epochs,), y.dtype)
-        vl = rt.empty((self.n_epochs,), y.dtype)
-        # an empty validation set: the reference's mean over no rows is nan (src/base.py:61)
-        has_val = va.shape[0] > 0
-        if not has_val:
-            vl.fill_(float("nan"))
 
-        chunk = {"first": 0, "ids": None}
-
-        def run(first: int, count: int, loop=None, part_of: int = 0) -> None:
-            ids_ptr = chunk["ids"].data_ptr() + (first - chunk["first"]) * self.batch_size * 4
-            args = (rt.ctx, plan.handle, tr.indptr.data_ptr(), tr.indices.data_ptr(), tr.values.data_ptr(),
-                    y.data_ptr(), p.data_ptr(), ids_ptr, self.batch_size, count,
-                    self.w0.dev.data_ptr(), self.w.dev.data_ptr(), self.V.dev.data_ptr(), float(self.lr),
-                    va.indptr.data_ptr(), va.indices.data_ptr(), va.values.data_ptr(),
-                    vy.data_ptr(), vp.data_ptr(), va.shape[0], LOSS_EPS,
-                    tl.data_ptr() + first * 8, vl.data_ptr() + first * 8 if has_val else None)
-            if part_of:
-                # a piece of the call of `part_of` iterations that a fit without an evaluator makes:
-                # the same loss forms, hence the same losses bit for bit
-                _lib.check(rt.lib.rfm_fm_train_part(*args, part_of))
-                return
-            if loop is None:
-                _lib.check(rt.lib.rfm_fm_train(*args))
-                return
-            fr = loop.frame
-            _lib.check(rt.lib.rfm_fm_train_eval(
-                *args, ev.indptr.data_ptr(), ev.indices.data_ptr(), ev.values.data_ptr(), ev.shape[0],
-                fr.seg_ptr.data_ptr(), fr.rows.data_ptr(), fr.labels.data_ptr(),
-                None if fr.pscores is None else fr.pscores.data_ptr(), fr.n_segments, fr.k,
-                loop.scores.data_ptr(), loop.scores.shape[1], loop.users.data_ptr(), loop.users.shape[1],
-                first % loop.chunk, loop.out.data_ptr() + first * 16))
+        def make_loop(evaluator):
+            # ValEvaluator's IPS-DCG@k from the scores in HBM (rfm_val_dcg), inside the library's
+            # loop (rfm_fm_train_eval); only the users whose value hangs on the order of tied
+            # scores are redone on the host
+            ev_X = evaluator.features[self.model_name]
+            frame = device_frame(rt, evaluator, self.estimator, ev_X.shape[0])
+            if frame is None:
+                return None
+            if ev_X.shape[1] != self.n_features:
+                raise ValueError(f"X has {ev_X.shape[1]} columns, model has {self.n_features}")
+            ev = self._csr_cache.get(ev_X)
+            _lib.check(rt.lib.rfm_fm_plan_register_log(
+                rt.ctx, plan.handle, 1, ev.indptr.data_ptr(), ev.indices.data_ptr(), ev.values.data_ptr(),
+                ev.shape[0]))
+            return EvalLoop(rt, frame, evaluator, self.estimator, self.n_epochs, log=ev)
 
         try:
-            frame = loop = ev = ev_X = None
-            # catalogue metrics per iteration: the evaluator is given the model,
-            # not scores of a feature matrix
-            cat = self.evaluator if isinstance(self.evaluator, CatalogueValEvaluator) else None
-            if cat is not None:
-                cat.fit_begin(self, self.n_epochs)
-            elif self.evaluator is not None:
-                ev_X = self.evaluator.features[self.model_name]
-                frame = (device_frame(rt, self.evaluator, self.estimator, ev_X.shape[0])
-                         if self.device_evaluator else None)
-                if frame is not None:
-                    # ValEvaluator's IPS-DCG@k from the scores in HBM (rfm_val_dcg); only the
-                    # users whose value hangs on the order of tied scores are redone on the host
-                    if ev_X.shape[1] != self.n_features:
-                        raise ValueError(
-                            f"X has {ev_X.shape[1]} columns, model has {self.n_features}")
-                    ev = self._csr_cache.get(ev_X)
-                    _lib.check(rt.lib.rfm_fm_plan_register_log(
-                        rt.ctx, plan.handle, 1, ev.indptr.data_ptr(), ev.indices.data_ptr(),
-                        ev.values.data_ptr(), ev.shape[0]))
-                    loop = EvalLoop(rt, frame, self.evaluator, self.estimator, self.n_epochs)
+            hook = FitHook(self, self.n_epochs, self.predict, make_loop)
             for first, host_ids, dev_ids in id_stream.chunks():
-                chunk["first"], chunk["ids"] = first, dev_ids
                 count = dev_ids.shape[0]
-                if self.evaluator is None:
-                    run(first, count)
-                elif cat is not None:
-                    # runs of iterations that end at the next evaluation point, the evaluation
-                    # enqueued behind each on the same stream
-                    at = first
-                    while at < first + count:
-                        n = min(first + count - at, cat.fit_run_length(at))
-                        run(at, n, part_of=count)
-                        at += n
-                        if cat.fit_due(at - 1):
-                            cat.fit_enqueue(at - 1)
-                elif frame is None:
-                    # an evaluator of unknown kind is a host callback: one iteration per enqueue
-                    for epoch in range(first, first + count):
-                        run(epoch, 1)
-                        y_scores = self.predict(X=ev_X)
-                        self.val_metrics.append(
-                            self.evaluator.evaluate(y_scores=y_scores, estimator=self.estimator))
-                else:
-                    # the recognised evaluator: scores + IPS-DCG@k inside the library's loop
-                    # (rfm_fm_train_eval), one enqueue per run of iterations that fits the chunk
-                    # of score slots
-                    at = first
-                    while at < first + count:
-                        n = min(first + count - at, loop.room(at))
-                        run(at, n, loop)
-                        loop.ran(at, n)
-                        at += n
-            if loop is not None:
-                self.val_metrics.extend(loop.finish(self.n_epochs))
-                self.evaluator_host_calls = loop.host_calls
-                self.evaluator_host_users = loop.host_users
-                loop.leave_scores(self.n_epochs - 1)
+                # one enqueue per run of iterations: the whole chunk without an evaluator, else up
+                # to the next evaluation point, the end of the chunk of score slots, or one
+                # iteration for a host callback (FitHook.limit)
+                for at, n in runs(first, count, hook.limit):
+                    args = (rt.ctx, plan.handle, tr.indptr.data_ptr(), tr.indices.data_ptr(), tr.values.data_ptr(),
+                            st.y.data_ptr(), st.p.data_ptr(), st.ids_ptr(at, first, dev_ids), self.batch_size, n,
+                            *st.tail(at))
+                    if hook.cat is not None:
+                        # a piece of the call of `count` iterations that a fit without an evaluator
+                        # makes: the same loss forms, hence the same losses bit for bit
+                        _lib.check(rt.lib.rfm_fm_train_part(*args, count))
+                    elif hook.loop is not None:
+                        _lib.check(rt.lib.rfm_fm_train_eval(*args, *hook.loop.call_args(at)))
+                    else:
+                        _lib.check(rt.lib.rfm_fm_train(*args))
+                    hook.ran(at, n)
             rt.sync()
-            if cat is not None:
-                self.val_metrics.extend(cat.fit_end())
+            hook.finish()
         finally:
             rt.sync()
             # (the registration ends with the fit: the plan may outlive this split's device copy)
             for log_slot in (0, 1):
                 rt.lib.rfm_fm_plan_register_log(rt.ctx, plan.handle, log_slot, None, None, None, 0)
-            if keep:
-                plan_cache(rt).give_back(plan)
-            else:
-                plan.close()
-        return tl.cpu().numpy().tolist(), vl.cpu().numpy().tolist()
+            st.release()
+        return st.losses()
 
     # -------------------------------------------------------------- predict
     def predict(self, X) -> np.ndarray:

@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _lib
 from .base import LOSS_EPS, PointwiseBaseRecommender
-from .evaluate import CatalogueValEvaluator, EvalLoop, device_frame
+from .evaluate import EvalLoop, FitHook, device_frame
 from .optimizer import DeviceSGD
 from .runtime import BatchIdStream, Runtime, mf_cache_capacity, mf_schedule_ex
 
@@ -257,21 +257,17 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
         # item rows the sequential kernel may keep in LDS (rows + bias, 32 KiB)
         cache_cap = mf_cache_capacity(self.n_factors)
 
-        ev_frame = ev_pairs = ev_loop = None
-        # catalogue metrics per iteration: the evaluator is given the model, not
-        # scores of a list of pairs
-        cat = self.evaluator if isinstance(self.evaluator, CatalogueValEvaluator) else None
-        if cat is not None:
-            cat.fit_begin(self, self.n_epochs)
-        elif self.evaluator is not None:
-            ev_X = self.evaluator.features[self.model_name]
-            if self.device_evaluator:
-                ev_frame = device_frame(rt, self.evaluator, self.estimator, int(np.asarray(ev_X).shape[0]))
-            if ev_frame is not None:
-                # ValEvaluator's IPS-DCG@k from scores that stay in HBM (rfm_val_dcg)
-                ev_pairs = DevicePairs(rt, ev_X)
-                self._check_ids(ev_pairs)
-                ev_loop = EvalLoop(rt, ev_frame, self.evaluator, self.estimator, self.n_epochs)
+        def make_loop(evaluator):
+            # ValEvaluator's IPS-DCG@k from scores that stay in HBM (rfm_val_dcg)
+            ev_X = evaluator.features[self.model_name]
+            frame = device_frame(rt, evaluator, self.estimator, int(np.asarray(ev_X).shape[0]))
+            if frame is None:
+                return None
+            ev_pairs = DevicePairs(rt, ev_X)
+            self._check_ids(ev_pairs)
+            return EvalLoop(rt, frame, evaluator, self.estimator, self.n_epochs, log=ev_pairs)
+
+        hook = FitHook(self, self.n_epochs, self.predict, make_loop)
 
         def after_sgd(epoch: int, ids_ptr: int) -> None:
             # train loss on the same batch with the updated parameters (src/mf.py:110-116)
@@ -283,18 +279,13 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
                 _lib.check(rt.lib.rfm_mf_predict_loss(
                     rt.ctx, va.users.data_ptr(), va.items.data_ptr(), vy.data_ptr(), vp.data_ptr(),
                     None, va.n, *params, b, self.n_factors, LOSS_EPS, None, vl.data_ptr() + epoch * 8))
-            if ev_frame is not None:
+            if hook.loop is not None:
+                ev_pairs = hook.loop.log
                 _lib.check(rt.lib.rfm_mf_predict(
                     rt.ctx, ev_pairs.users.data_ptr(), ev_pairs.items.data_ptr(), None, ev_pairs.n,
-                    *params, b, self.n_factors, ev_loop.slot(epoch).data_ptr()))
-                ev_loop.done(epoch)
-            elif cat is not None:
-                if cat.fit_due(epoch):
-                    cat.fit_enqueue(epoch)  # (behind the iteration, on the same stream)
-            elif self.evaluator is not None:
-                y_scores = self.predict(self.evaluator.features[self.model_name])
-                self.val_metrics.append(
-                    self.evaluator.evaluate(y_scores=y_scores, estimator=self.estimator))
+                    *params, b, self.n_factors, hook.loop.slot(epoch).data_ptr()))
+                hook.loop.measure(epoch)
+            hook.ran(epoch, 1)
 
         if self.hogwild:
             for epoch, rows, ids_ptr in self._epochs(id_stream):
@@ -334,13 +325,7 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
                 worker.join(timeout=5.0)
         rt.sync()
         self._keep_ids = []
-        if cat is not None:
-            self.val_metrics.extend(cat.fit_end())
-        if ev_frame is not None:
-            self.val_metrics.extend(ev_loop.finish(self.n_epochs))
-            self.evaluator_host_calls = ev_loop.host_calls
-            self.evaluator_host_users = ev_loop.host_users
-            ev_loop.leave_scores(self.n_epochs - 1)
+        hook.finish()
         return tl.cpu().numpy().tolist(), vl.cpu().numpy().tolist()
 
     def _epochs(self, id_stream: BatchIdStream):

@@ -8,9 +8,14 @@ order, the mean over users is a different (fixed) summation order: 1e-12 relativ
 import numpy as np
 import pytest
 
+import catalogue_val_common as cv
+import rank_items_common as rk
+import test_gpu_catalogue_val as tcv
 from conftest import load_golden
 from oracle import cpu_ref
 from relevance_factorizationmachine_amd import synth
+
+from test_gpu_catalogue_val import gold, held, rfm  # noqa: F401 -- its fixtures: the catalogue's models and split
 
 pytestmark = pytest.mark.gpu
 
@@ -285,6 +290,112 @@ def test_eval_loop_chunks(ev):
     host.device_evaluator = False
     host.fit(train, val)
     assert len(dev.val_metrics) == 7
+    np.testing.assert_allclose(dev.val_metrics, host.val_metrics, rtol=TOL)
+
+
+def _three_per_chunk(frame):
+    """``EvalLoop.CHUNK_BYTES`` at which a chunk of score slots holds exactly three iterations of ``frame``."""
+    n_rows, n_groups = len(frame["user"]), np.unique(frame["user"]).shape[0]
+    return 3 * (8 * (n_rows + 3 * n_groups) + 8)
+
+
+def _record_runs(monkeypatch, rt, entry):
+    """The argument lists of every call of library entry ``entry`` from here on."""
+    calls, real = [], getattr(rt.lib, entry)
+
+    def recorded(*args):
+        calls.append(args)
+        return real(*args)
+
+    monkeypatch.setattr(rt.lib, entry, recorded)
+    return calls
+
+
+def test_fm_runs_cut_by_id_chunks_and_score_slots(ev, monkeypatch):
+    """19 iterations: the sampler hands out 16 ids first, the score slots hold three iterations, so
+    the runs of ``rfm_fm_train_eval`` end at 3, 6, .. 15, at 16 (the id chunk), at 18 and at 19 --
+    and the metrics are the host callback's, iteration by iteration."""
+    import relevance_factorizationmachine_amd as pkg
+    evaluate, rt = ev
+    sh = synth.SHAPES["coat"]
+    train, val = synth.make_log(sh, "FM", "IPS", seed=0)
+    _, val_mf = synth.make_log(sh, "MF", "IPS", seed=0)
+    frame = synth.interaction_frame(val_mf, val_mf["features"])
+    E = 19
+    kw = dict(estimator="IPS", n_epochs=E, n_factors=8, n_features=train["features"].shape[1], lr=1e-4,
+              batch_size=500, seed=12345)
+    monkeypatch.setattr(evaluate.EvalLoop, "CHUNK_BYTES", _three_per_chunk(frame))
+    calls = _record_runs(monkeypatch, rt, "rfm_fm_train_eval")
+    hook = _ValEvaluatorLike(frame, {"FM": val["features"]})
+    dev = pkg.FactorizationMachines(evaluator=hook, **kw)
+    dev.fit(train, val)
+    monkeypatch.undo()
+    ends = np.cumsum([c[9] for c in calls]).tolist()  # (n_iters of every call)
+    assert ends == [3, 6, 9, 12, 15, 16, 18, 19]
+    assert [c[-2] for c in calls] == [0, 0, 0, 0, 0, 0, 1, 0]  # slot_first: the run's place in its chunk
+    assert len(dev.val_metrics) == E
+    assert hook.calls == 0 and dev.evaluator_host_calls <= E  # the evaluator object is never called
+    hook2 = _ValEvaluatorLike(frame, {"FM": val["features"]})
+    host = pkg.FactorizationMachines(evaluator=hook2, **kw)
+    host.device_evaluator = False
+    host.fit(train, val)
+    assert hook2.calls == E
+    np.testing.assert_allclose(dev.val_metrics, host.val_metrics, rtol=TOL)
+    np.testing.assert_allclose(dev.V(), host.V(), rtol=1e-11, atol=1e-14)  # the evaluator never touches training
+
+
+def test_fm_runs_cut_by_id_chunks_and_evaluation_points(rfm, gold, held, monkeypatch):
+    """The same 19 iterations with a ``CatalogueValEvaluator`` every 5 (5 does not divide 16): the
+    runs of ``rfm_fm_train_part`` end at 5, 10, 15, at 16 (the id chunk) and at 19, each a piece of
+    its id chunk's call, and every evaluated row is the evaluation of a fresh model fitted that long
+    (the helpers and fixture models of test_gpu_catalogue_val.py)."""
+    rt = rfm[3]
+    case, E, every = ("coat", 16, 2.0), 19, 5
+    split = cv.fixture_split(gold[0], case[0])
+    cat = tcv._fm_evaluator(rfm, gold, held, case, every=every)
+    m = tcv._fm(rfm, gold, case, E, cat)
+    calls = _record_runs(monkeypatch, rt, "rfm_fm_train_part")
+    m.fit(*split)
+    monkeypatch.undo()
+    assert np.cumsum([c[9] for c in calls]).tolist() == [5, 10, 15, 16, 19]
+    assert [c[-1] for c in calls] == [16, 16, 16, 16, 3]  # call_iters: the id chunk each run is a piece of
+    assert len(m.val_metrics) == E
+    due = [4, 9, 14, 18]
+    one_shot = tcv._fm_evaluator(rfm, gold, held, case)
+    for e in range(E):
+        if e in due:
+            fresh = tcv._fm(rfm, gold, case, e + 1)
+            fresh.fit(*split)
+            cv.assert_same_bits(cv.row(cat.history, e), one_shot.evaluate(fresh, estimator="IPS"), f"iteration {e}")
+            assert cat.unranked_history[e] == 0
+        else:
+            assert all(np.isnan(v[e]).all() for v in cat.history.values()) and cat.unranked_history[e] == -1
+    col = cat.history["DCG"][:, rk.K_LIST.index(5)]
+    assert np.asarray(m.val_metrics)[due].tobytes() == col[due].tobytes() and np.unique(col[due]).shape[0] > 1
+
+
+def test_mf_device_evaluator_over_several_chunks_of_score_slots(ev, monkeypatch):
+    """19 iterations of MF, three per chunk of score slots, over two id chunks (16 + 3): the device
+    evaluator against the host callback, as test_mf_fit_device_evaluator compares them."""
+    import relevance_factorizationmachine_amd as pkg
+    evaluate, rt = ev
+    sh = synth.SHAPES["kuairec_small"]
+    train, val = synth.make_log(sh, "MF", "IPS", seed=0)
+    frame = synth.interaction_frame(val, val["features"])
+    E = 19
+    kw = dict(estimator="IPS", n_epochs=E, n_factors=16, n_users=sh.n_users, n_items=sh.n_items, lr=0.01,
+              reg=0.5, batch_size=2000, seed=12345)
+    monkeypatch.setattr(evaluate.EvalLoop, "CHUNK_BYTES", _three_per_chunk(frame))
+    hook = _ValEvaluatorLike(frame, {"MF": val["features"]})
+    dev = pkg.LogisticMatrixFactorization(evaluator=hook, **kw)
+    dev.fit(train, val)
+    monkeypatch.undo()
+    assert len(dev.val_metrics) == E and hook.calls == 0 and dev.evaluator_host_calls <= E
+    hook2 = _ValEvaluatorLike(frame, {"MF": val["features"]})
+    host = pkg.LogisticMatrixFactorization(evaluator=hook2, **kw)
+    host.device_evaluator = False
+    host.fit(train, val)
+    assert hook2.calls == E
     np.testing.assert_allclose(dev.val_metrics, host.val_metrics, rtol=TOL)
 
 

@@ -25,6 +25,43 @@ def test_library_exports_every_declared_symbol():
     assert lib.rfm_version() == 100
 
 
+def test_ctypes_table_matches_the_header_argument_by_argument():
+    """Every ``int32_t rfm_*(...);`` of the header against ``SIGNATURES``: a parameter with a ``*`` is a
+    pointer (``c_void_p``, ``c_char_p``, ``POINTER(..)``), the scalars are ``int32_t``, ``int64_t``,
+    ``double`` and ``size_t`` themselves."""
+    import ctypes as C
+
+    header = open(os.path.join(ROOT, "include", "rfm_hip.h")).read()
+    header = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    header = re.sub(r"//[^\n]*", " ", header)
+    scalars = {"int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double, "size_t": C.c_size_t}
+
+    def header_kind(param):
+        if "*" in param:
+            return "pointer"
+        kinds = [name for name in scalars if re.search(r"\b%s\b" % name, param)]
+        assert len(kinds) == 1, f"cannot classify parameter {param!r}"
+        return kinds[0]
+
+    def table_kind(ctype):
+        for name, scalar in scalars.items():
+            if ctype is scalar:
+                return name
+        assert ctype in (C.c_void_p, C.c_char_p) or issubclass(ctype, C._Pointer), ctype
+        return "pointer"
+
+    declared = re.findall(r"^int32_t\s+(rfm_\w+)\s*\(([^)]*)\)\s*;", header, flags=re.M)
+    assert len(declared) == 70 == len(_lib.SIGNATURES)
+    mismatches = []
+    for name, params in declared:
+        params = [p.strip() for p in params.split(",") if p.strip() not in ("", "void")]
+        want = [header_kind(p) for p in params]
+        got = [table_kind(t) for t in _lib.SIGNATURES[name]]
+        if want != got:
+            mismatches.append((name, want, got))
+    assert not mismatches, mismatches
+
+
 @pytest.mark.parametrize("n,batch", [(1, 1), (2, 2), (7, 3), (1000, 64), (3660, 500), (43036, 2000), (65537, 100)])
 def test_sampler_bit_exact_vs_numpy(n, batch):
     got = sample_batches(n, batch, 0, 5, n_threads=3)
