@@ -690,6 +690,10 @@ int32_t rfm_csr_assemble_fill(rfm_ctx* ctx, const rfm_csr_segment* h_segments, i
 int32_t rfm_fm_side_sums(rfm_ctx* ctx, const int64_t* d_indptr, const int32_t* d_indices,
                          const double* d_values, int64_t n_rows, const double* d_w, const double* d_V,
                          int64_t n_features, int32_t n_factors, double* d_A, double* d_L);
+/* ---- FM fold-in: the id column of new rows of one side against the fixed other side ----
+ * rfm_fm_fold_in and rfm_fm_fold_geometry: semantics and declarations in rfm_fm_fold.h (a part of this
+ * ABI in a file of its own, with a ctypes table of its own: _lib.FOLD_SIGNATURES). */
+#include "rfm_fm_fold.h"
 /* d_out[s][i] = sigmoid(clip(*d_c + LU[u] + LI[i] + A[u,:].B[i,:], +-700)) (src/base.py:63-66; a
  * NaN logit stays NaN) for every item i and selected user s, u = d_user_ids ? d_user_ids[s] : s
  * (any order, repeats allowed; NULL needs n_sel_users == n_users).  A is [n_users][kpad], B is

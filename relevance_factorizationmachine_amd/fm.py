@@ -7,6 +7,10 @@ Same dataclass fields, same ``fit(train, val) -> (train_loss, val_loss)`` and
 host only prepares inputs (parameter init with the reference's NumPy calls,
 mini-batch ids, uploads) and enqueues; every floating-point operation of the
 loop runs in the kernels of ``csrc/rfm_fm.hip``.
+
+Beyond the reference: the catalogue methods (``recommend.py``) and fold-in of
+users and items that arrive after the fit (``fold_in_users`` / ``fold_in_items``
+/ ``append_columns``, ``csrc/rfm_fm_fold.hip``).
 """
 from __future__ import annotations
 
@@ -190,6 +194,48 @@ class FmFit:
 
 
 @dataclass
+class FoldedColumns:
+    """The id columns of new rows of one side of a trained FM model (``fold_in_users`` /
+    ``fold_in_items``): device tensors ``w [n_new]`` and ``V [n_new, k]`` (the new
+    columns' weights and factor rows) and the served operands of the grown rows, ``A [n_new, kpad]``
+    and ``L [n_new]`` (``recommend.Operands``); ``side`` "user" or "item"."""
+
+    side: str
+    w: object
+    V: object
+    A: object
+    L: object
+    rt: Runtime
+
+    def __len__(self) -> int:
+        return int(self.w.shape[0])
+
+    def numpy(self):
+        """``(V, w)`` on the host, after the work enqueued so far."""
+        self.rt.sync()
+        return self.V.cpu().numpy(), self.w.cpu().numpy()
+
+
+def fold_rows(sides, new_rows, side: int, n_features: int):
+    """The feature entries of the new rows of ``side`` (0: users, 1: items) as a canonical CSR
+    ``[n_new, n_features]`` (host only).  ``ValueError`` for another width, and for a column that
+    the OTHER side of ``sides`` stores: the pair rows would not be user row + item row."""
+    from . import recommend as rec
+
+    if len(new_rows.shape) != 2 or int(new_rows.shape[1]) != int(n_features):
+        raise ValueError(f"new_rows of shape {tuple(new_rows.shape)} for a model of {int(n_features)} columns")
+    X = new_rows.tocsr()
+    if not X.has_canonical_format:
+        X = X.copy()
+        X.sum_duplicates()
+    both = np.intersect1d(rec._stored_columns(X), rec._stored_columns(sides._host[1 - side]))
+    if both.size:
+        raise ValueError(f"column {int(both[0])} of new_rows is stored on the {('item', 'user')[side]} side "
+                         f"({both.size} such columns): pair rows are not user_rows[u] + item_rows[i]")
+    return X
+
+
+@dataclass
 class FactorizationMachines(PointwiseBaseRecommender):
     """Factorization Machines trained by mini-batch SGD on an MI355X.
 
@@ -333,37 +379,119 @@ class FactorizationMachines(PointwiseBaseRecommender):
         rt.sync()
         return out.cpu().numpy()
 
+    # -------------------------------------------------------------- fold-in
+    def _fold_in(self, side: int, sides, new_rows, data: dict, n_passes: int, init, lr, ops) -> FoldedColumns:
+        """The id columns of new rows of ``side`` (0: users, 1: items) trained against the fixed
+        other side (``rfm_fm_fold_in``): every check on the host first, then the
+        side sums of ``new_rows`` and the fold launch enqueued on the runtime's stream, no host wait."""
+        from . import recommend as rec
+        from .mf import fold_examples
+
+        n_users, n_items = rec.catalogue_shape(self, sides)
+        kf, kp = int(self.n_factors), rec.pad4(self.n_factors)
+        X = fold_rows(sides, new_rows, side, self.n_features)
+        n_new, n_fixed = int(X.shape[0]), (n_items, n_users)[side]
+        row_ptr, ids, ry, order = fold_examples(data, n_new, n_fixed, side, n_passes)
+        lr = float(self.lr if lr is None else lr)
+        if init is not None:
+            V0, w0 = (np.asarray(a, dtype=np.float64) for a in init)
+            if V0.shape != (n_new, kf) or w0.shape != (n_new,):
+                raise ValueError(f"init must be (V [{n_new}, {kf}], w [{n_new}]), got {V0.shape}, {w0.shape}")
+        if ops is not None and (tuple(ops.A.shape) != (n_users, kp) or tuple(ops.B.shape) != (n_items, kp)):
+            raise ValueError(f"ops of {tuple(ops.A.shape)}, {tuple(ops.B.shape)} for sides of {n_users} users and "
+                             f"{n_items} items at {kf} factors")
+        import torch
+
+        rt = self._rt
+        if init is None:
+            V_new = torch.zeros((n_new, kf), dtype=torch.float64, device=rt.torch_device)
+            w_new = torch.zeros((n_new,), dtype=torch.float64, device=rt.torch_device)
+        else:
+            V_new, w_new = rt.upload(V0), rt.upload(w0)
+        A_new, L_new = rt.empty((n_new, kp), torch.float64), rt.empty((n_new,), torch.float64)
+        if n_new:
+            if ops is None:
+                ops = rec.operands(self, sides)
+            F, fL = ((ops.B, ops.LI), (ops.A, ops.LU))[side]
+            g, l = rec.side_sums(rt, DeviceCSR(rt, X), self.w.dev, self.V.dev, self.n_features, kf)
+            dev = [rt.upload(a if a.size else np.zeros(1, a.dtype)) for a in (row_ptr, ids, ry, order)]
+            _lib.check(rt.lib.rfm_fm_fold_in(
+                rt.ctx, *(d.data_ptr() for d in dev), n_new, g.data_ptr(), l.data_ptr(), F.data_ptr(), fL.data_ptr(),
+                n_fixed, self.w0.dev.data_ptr(), kf, lr, int(n_passes), w_new.data_ptr(), V_new.data_ptr(),
+                A_new.data_ptr(), L_new.data_ptr()))
+        return FoldedColumns(("user", "item")[side], w_new, V_new, A_new, L_new, rt)
+
+    def fold_in_users(self, sides, new_rows, data: dict, n_passes: int, init=None, lr=None, ops=None) -> FoldedColumns:
+        """Id columns for users who arrived after the fit: each new user's one-hot
+        id column -- its weight and factor row -- is learned from the user's interactions by the
+        reference's batch-sum step (``src/fm.py:80-88``) with the trained model held fixed.
+        ``sides``: the catalogue the model serves; ``new_rows``: CSR ``[n_new, n_features]`` of the
+        new users' FEATURE entries (a column stored on the item side is a ``ValueError``); ``data``
+        as ``fit()`` of the MF model takes it: ``features`` ``(N, 2)`` of ``[user, item]`` with
+        new-user indices 0..n_new-1 in the user column and item rows of ``sides`` in the item
+        column, ``labels``, ``pscores``.  One pass is one full-batch step over a user's examples;
+        ``lr``: the model's unless given; ``init``: ``(V [n_new, k], w [n_new])`` to start from
+        (default zeros); ``ops``: ``recommend.operands(self, sides)`` to reuse.  The model is not
+        written; serve the result through ``new_users=`` or ``append_columns`` it."""
+        return self._fold_in(0, sides, new_rows, data, n_passes, init, lr, ops)
+
+    def fold_in_items(self, sides, new_rows, data: dict, n_passes: int, init=None, lr=None, ops=None) -> FoldedColumns:
+        """``fold_in_users`` with the sides exchanged: ``new_rows`` holds new items' feature entries,
+        the item column of ``features`` new-item indices and the user column user rows of ``sides``."""
+        return self._fold_in(1, sides, new_rows, data, n_passes, init, lr, ops)
+
+    def append_columns(self, folded: FoldedColumns) -> np.ndarray:
+        """Grows ``w``, ``V`` and ``n_features`` by folded id columns, at the end; returns their
+        column ids.  Rows that store those columns (entry 1 next to the row's feature entries) are
+        then scored by ``predict``, served by the catalogue methods on a ``Sides`` of the grown
+        width and trained by a further ``fit``; where a loader's id segment sits is the loader's
+        business, nothing is inserted mid-matrix."""
+        if not isinstance(folded, FoldedColumns):
+            raise TypeError("append_columns takes the FoldedColumns of fold_in_users / fold_in_items")
+        if tuple(folded.V.shape[1:]) != (int(self.n_factors),):
+            raise ValueError(f"folded columns of {tuple(folded.V.shape)} for a model of {int(self.n_factors)} factors")
+        first = int(self.n_features)
+        self.w.append(folded.w)
+        self.V.append(folded.V)
+        self.n_features = first + len(folded)
+        # (matrices of the old width are refused from here on; training plans are keyed on the log
+        # they were built from, and a log of the grown width is another log)
+        self._csr_cache = CsrCache(self._rt)
+        return np.arange(first, first + len(folded))
+
     # ------------------------------------------------------------ catalogue
-    def score_pairs(self, sides, users=None) -> np.ndarray:
+    # new_users: the FoldedColumns of fold_in_users stand in for the user side -- ``users`` and
+    # ``exclude`` then index the folded rows, and the model is not touched
+    def score_pairs(self, sides, users=None, new_users=None) -> np.ndarray:
         """``predict()`` of every (user, item) pair of ``sides`` (``recommend.Sides``) as a
         ``[n_users (or len(users)), n_items]`` matrix, without the pairs' design matrix: side
         sums + one dense product (recommend.py; src/fm.py:114-133 restated)."""
         from . import recommend as rec
 
-        return rec.score_pairs(*rec.operands(self, sides), users)
+        return rec.score_pairs(*rec.operands(self, sides, new_users=new_users), users)
 
-    def recommend(self, sides, k: int, users=None, exclude=None):
+    def recommend(self, sides, k: int, users=None, exclude=None, new_users=None):
         """The ``k`` (1..64) best items of the catalogue per user: ``(items int32 [n, k], scores
         float64 [n, k])``, ranked by logit (ties: higher item index first), scores as
         ``predict()`` gives them; ``exclude``: items never to return, CSR by user id."""
         from . import recommend as rec
 
-        return rec.topk(*rec.operands(self, sides), k, users, exclude)
+        return rec.topk(*rec.operands(self, sides, new_users=new_users), k, users, exclude)
 
-    def rank_items(self, sides, users, items, exclude=None):
+    def rank_items(self, sides, users, items, exclude=None, new_users=None):
         """Where the pairs ``(users[n], items[n])`` land in their users' ranking of the whole
         catalogue of ``sides``: ``(ranks int32 [n], scores float64 [n], candidates int32 [n])`` in
         input order -- ``ranks`` 0-based under ``recommend()``'s order among the user's
         ``candidates`` (logit not NaN, not in ``exclude``), at any depth (recommend.py)."""
         from . import recommend as rec
 
-        return rec.rank_items(*rec.operands(self, sides), users, items, exclude)
+        return rec.rank_items(*rec.operands(self, sides, new_users=new_users), users, items, exclude)
 
-    def rank_catalogue(self, sides, depth: int, users=None, exclude=None):
+    def rank_catalogue(self, sides, depth: int, users=None, exclude=None, new_users=None):
         """Every user's ranking of the catalogue of ``sides`` down to ``depth`` (any integer >= 1;
         ``depth >= n_items``: the full ordering): ``(items int32 [n, depth], scores float64
         [n, depth], n_ranked int32 [n])`` under ``recommend()``'s order, short rows padded with
         item -1 / score NaN; the first 64 columns are ``recommend(k=64)``'s (recommend.py)."""
         from . import recommend as rec
 
-        return rec.rank_catalogue(*rec.operands(self, sides), depth, users, exclude)
+        return rec.rank_catalogue(*rec.operands(self, sides, new_users=new_users), depth, users, exclude)

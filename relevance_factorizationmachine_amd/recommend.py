@@ -171,22 +171,42 @@ def operands(model, sides=None, into: Optional[Operands] = None, new_users=None)
     operands of the model's own users as ``into`` of a call with ``new_users``, say) are a
     ``ValueError``.  ``new_users`` (MF): the
     ``FoldedRows`` of ``fold_in_users``, whose rows and biases stand in for ``P, b_u`` (DESIGN.md 8
-    N13): the operands' users are then the folded rows, and the model is not touched."""
+    N13): the operands' users are then the folded rows, and the model is not touched.  ``new_users``
+    (FM): the ``FoldedColumns`` of ``fold_in_users``, whose served operands ``A, L`` stand in for the
+    user side sums -- one side-sum launch, for the items; with ``into`` they are
+    copied into its user buffers.  Folded items, and the folded rows of the other model class, are
+    a ``TypeError``."""
+    is_fm = hasattr(model, "n_features")
     if new_users is not None:
-        if hasattr(model, "n_features"):
-            raise TypeError("new_users is for LogisticMatrixFactorization: the new rows of an FM model go "
-                            "into its recommend.Sides")
-        if getattr(new_users, "side", None) != "user":
-            raise TypeError("new_users takes the FoldedRows of fold_in_users")
-        if tuple(new_users.rows.shape[1:]) != (int(model.n_factors),):
-            raise ValueError(f"folded rows of {tuple(new_users.rows.shape)} for a model of {int(model.n_factors)} "
-                             f"factors")
+        if is_fm:
+            # (FoldedColumns carry the served operands A, L; the FoldedRows of an MF model do not)
+            if getattr(new_users, "side", None) != "user" or not hasattr(new_users, "A"):
+                raise TypeError("new_users of an FM model takes the FoldedColumns of its fold_in_users; rows "
+                                "that are served from their features alone go into its recommend.Sides")
+            if tuple(new_users.A.shape[1:]) != (pad4(model.n_factors),):
+                raise ValueError(f"folded operands of {tuple(new_users.A.shape)} for a model of "
+                                 f"{int(model.n_factors)} factors")
+        else:
+            if getattr(new_users, "side", None) != "user" or not hasattr(new_users, "rows"):
+                raise TypeError("new_users takes the FoldedRows of fold_in_users")
+            if tuple(new_users.rows.shape[1:]) != (int(model.n_factors),):
+                raise ValueError(f"folded rows of {tuple(new_users.rows.shape)} for a model of "
+                                 f"{int(model.n_factors)} factors")
     catalogue_shape(model, sides)
     rt, kf = model._rt, int(model.n_factors)
     _, A, LU, B, LI, c, _ = into or (None,) * 7
-    if hasattr(model, "n_features"):
+    if is_fm:
         XU, XI = sides.device(rt)
-        A, LU = side_sums(rt, XU, model.w.dev, model.V.dev, model.n_features, kf, A, LU)
+        if new_users is None:
+            A, LU = side_sums(rt, XU, model.w.dev, model.V.dev, model.n_features, kf, A, LU)
+        elif A is None:
+            A, LU = new_users.A, new_users.L
+        else:  # refreshed in place, as every other buffer of `into`
+            if tuple(A.shape) != tuple(new_users.A.shape) or tuple(LU.shape) != tuple(new_users.L.shape):
+                raise ValueError(f"folded operands of {tuple(new_users.A.shape)} into a buffer of {tuple(A.shape)}")
+            if A.data_ptr() != new_users.A.data_ptr():
+                A.copy_(new_users.A)
+                LU.copy_(new_users.L)
         B, LI = side_sums(rt, XI, model.w.dev, model.V.dev, model.n_features, kf, B, LI)
         return Operands(rt, A, LU, B, LI, model.w0.dev, kf)
     b = float(model.b)
