@@ -561,6 +561,47 @@ int32_t rfm_mf_fold_in(rfm_ctx* ctx, const int64_t* d_row_ptr, const int32_t* d_
  * (RFM_MF_FOLD_READ_AHEAD).  ctx == NULL: the grid on a device of 256 CUs (an MI355X). */
 int32_t rfm_mf_fold_geometry(const rfm_ctx* ctx, int64_t n_new, int32_t n_factors, int32_t* h_out6);
 
+/* ---- FM fold-in: the id column of new rows of one side against the fixed other side ----
+ * The reference's loaders give every user and item a one-hot id column next to its feature columns;
+ * a user or item that arrived after the fit has none.  New row r of one side has
+ *   - its FEATURE SUMS, fixed: g_r = d_g[r][0..k), l_r = d_l[r], the A and L that rfm_fm_side_sums
+ *     gives for its feature entries (no id entry stored);
+ *   - its NEW ID COLUMN (entry 1), trained: weight w_r = d_w_new[r], factor row v_r = d_V_new[r][0..k)
+ *     (in / out; the caller's initial values, zeros for a cold start);
+ *   - its examples e = d_row_ptr[r] .. d_row_ptr[r+1]-1, each naming row j_e = d_ids[e] of the fixed
+ *     side d_F [n_fixed][kpad], d_fL [n_fixed] (B, LI of the operands for a new user; A, LU for a new
+ *     item) and carrying ry_e = d_ry[e] = label / propensity;  c = *d_c (w0), read on the device.
+ * One pass is the reference's batch-sum step (src/fm.py:80-88, 135-187) on the batch of all of r's
+ * examples, restricted to the new column:
+ *     h_e   = g_r + F[j_e]
+ *     z_e   = c + l_r + fL[j_e] + g_r.F[j_e] + w_r + v_r.h_e
+ *     err_e = ry_e - sigmoid(clip(z_e, +-700))
+ *     w_r  += lr * sum_e err_e;   v_r += lr * sum_e err_e h_e      (every err_e from before the update)
+ * n_passes passes are made; there is no regularisation (the reference's FM has none).  On the model
+ * grown by the new columns (stored last) one step of the reference on the batch of ALL examples of
+ * the call does to the new columns of w and V exactly one pass of this rule.  After the last pass
+ * the served operands of the row are written as well: d_A_new[r] = g_r + v_r (zero-padded to kpad),
+ * d_L_new[r] = l_r + w_r + g_r.v_r, so that c + L_new[r] + fL[j] + A_new[r].F[j] is the FM logit of
+ * the grown row.  A row without examples, or n_passes == 0, keeps the bits of w_r, v_r; A_new and
+ * L_new are still written.  Nothing of the model or of the fixed side is written.
+ * One workgroup per new row, its lane groups over the row's examples, partial sums added in a fixed
+ * order: no atomics, the same inputs give the same bits, and p passes in one call equal p calls of
+ * one pass bit for bit.  One launch for any n_new, no host wait; d_order [n_new] hands the rows to
+ * the workgroups: the rows by descending example count (stable).  The ids are not checked on the
+ * device (RFM_CHECK_IDS is not consulted: the check kernels belong to the pair entries): every
+ * d_ids[e] must lie in 0 .. n_fixed-1, d_order must be a permutation of 0 .. n_new-1.
+ * n_new == 0: no launch. */
+int32_t rfm_fm_fold_in(rfm_ctx* ctx, const int64_t* d_row_ptr, const int32_t* d_ids, const double* d_ry,
+                       const int32_t* d_order, int64_t n_new, const double* d_g, const double* d_l,
+                       const double* d_F, const double* d_fL, int64_t n_fixed, const double* d_c,
+                       int32_t n_factors, double lr, int32_t n_passes, double* d_w_new, double* d_V_new,
+                       double* d_A_new, double* d_L_new);
+/* The launch shape of rfm_fm_fold_in for n_new rows at n_factors factors (host only, nothing is
+ * launched): h_out5[0]=lanes per example, [1]=adjacent factors a lane owns per chunk, [2]=chunks per
+ * lane, [3]=lane groups per workgroup (examples of a row in flight), [4]=workgroups (one new row
+ * each per grid-stride turn).  ctx == NULL: the grid on a device of 256 CUs (an MI355X). */
+int32_t rfm_fm_fold_geometry(const rfm_ctx* ctx, int64_t n_new, int32_t n_factors, int32_t* h_out5);
+
 /* ---- MF across GPUs: user-range partition ------------------
  * NOT the reference's semantics (its batch is strictly sequential, src/mf.py:97-108;
  * exact mode = one GPU or independent replicas).  Throughput mode: rank r runs the exact
@@ -690,10 +731,6 @@ int32_t rfm_csr_assemble_fill(rfm_ctx* ctx, const rfm_csr_segment* h_segments, i
 int32_t rfm_fm_side_sums(rfm_ctx* ctx, const int64_t* d_indptr, const int32_t* d_indices,
                          const double* d_values, int64_t n_rows, const double* d_w, const double* d_V,
                          int64_t n_features, int32_t n_factors, double* d_A, double* d_L);
-/* ---- FM fold-in: the id column of new rows of one side against the fixed other side ----
- * rfm_fm_fold_in and rfm_fm_fold_geometry: semantics and declarations in rfm_fm_fold.h (a part of this
- * ABI in a file of its own, with a ctypes table of its own: _lib.FOLD_SIGNATURES). */
-#include "rfm_fm_fold.h"
 /* d_out[s][i] = sigmoid(clip(*d_c + LU[u] + LI[i] + A[u,:].B[i,:], +-700)) (src/base.py:63-66; a
  * NaN logit stays NaN) for every item i and selected user s, u = d_user_ids ? d_user_ids[s] : s
  * (any order, repeats allowed; NULL needs n_sel_users == n_users).  A is [n_users][kpad], B is

@@ -59,7 +59,7 @@ def main():
     import relevance_factorizationmachine_amd as pkg
     from relevance_factorizationmachine_amd import _lib
     from relevance_factorizationmachine_amd import recommend as rec
-    from relevance_factorizationmachine_amd.mf import fold_examples
+    from relevance_factorizationmachine_amd.fold import fold_examples
     from relevance_factorizationmachine_amd.runtime import DeviceCSR
 
     lines = []

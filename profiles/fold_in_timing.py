@@ -54,7 +54,7 @@ def main():
 
     import relevance_factorizationmachine_amd as pkg
     from relevance_factorizationmachine_amd import _lib
-    from relevance_factorizationmachine_amd.mf import fold_examples
+    from relevance_factorizationmachine_amd.fold import fold_examples
 
     lines = []
 

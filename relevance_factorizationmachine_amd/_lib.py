@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("RFM_LIB_PATH") or os.path.join(PKG_DIR, "librfm_hip.s
 SOURCES = ["rfm_capi.hip", "rfm_fm.hip", "rfm_fm_plan.hip", "rfm_mf.hip", "rfm_fm_fold.hip", "rfm_eval.hip", "rfm_csr.hip", "rfm_sample.hip", "rfm_pairs.hip", "rfm_host.cpp", "rfm_comm.cpp"]
 # every header under csrc/ (a change of any of them rebuilds every object) + the C ABI
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp"))) + [
-    os.path.join(os.path.dirname(PKG_DIR), "include", h) for h in ("rfm_hip.h", "rfm_fm_fold.h")]
+    os.path.join(os.path.dirname(PKG_DIR), "include", "rfm_hip.h")]
 
 RFM_OK, RFM_ERR_BAD_ARG, RFM_ERR_HIP, RFM_ERR_NO_DEVICE, RFM_ERR_INTERNAL = range(5)
 
@@ -172,6 +172,9 @@ SIGNATURES = {
                              _f64],
     "rfm_mf_fold_in": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _f64, _i32, _f64, _f64, _i32, _vp, _vp],
     "rfm_mf_fold_geometry": [_vp, _i64, _i32, _vp],
+    "rfm_fm_fold_in": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _f64, _i32, _vp, _vp, _vp,
+                       _vp],
+    "rfm_fm_fold_geometry": [_vp, _i64, _i32, _vp],
     "rfm_mf_delta": [_vp, _vp, _vp, _vp, _i64],
     "rfm_mf_merge": [_vp, _vp, _vp, _vp, _i64],
     "rfm_mf_sgd_hogwild": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _i32, _f64,
@@ -191,14 +194,6 @@ SIGNATURES = {
     "rfm_rank_metrics": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
     "rfm_pair_order_workspace": [_i64, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64)],
     "rfm_pair_order": _PAIR + [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
-}
-
-# FM fold-in, the part of the ABI that include/rfm_fm_fold.h declares (tests/test_fm_fold_host.py
-# compares the two, argument by argument)
-FOLD_SIGNATURES = {
-    "rfm_fm_fold_in": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _f64, _i32, _vp, _vp, _vp,
-                       _vp],
-    "rfm_fm_fold_geometry": [_vp, _i64, _i32, _vp],
 }
 
 
@@ -255,7 +250,7 @@ def load():
         lib = C.CDLL(path)
     except OSError as exc:
         raise RfmError(f"cannot load {path}: {exc}") from exc
-    for name, argtypes in {**SIGNATURES, **FOLD_SIGNATURES}.items():
+    for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError = header/library mismatch
         fn.argtypes = argtypes
         fn.restype = _i32

@@ -19,22 +19,18 @@
 //    0 .. GPB-1 and applies the update to its own copy: the copies stay identical bit for bit, and
 //    nothing depends on timing.  A second barrier frees the LDS for the next pass or row.
 //  * No atomics, plain loads and plain vector stores only.
+// The example layout and the entry's first checks are MF fold-in's too: rfm_fold.hpp.
 #include <algorithm>
 
 #include "rfm_common.h"
 #include "rfm_device_utils.hpp"
+#include "rfm_fold.hpp"
 
 namespace rfm {
 
 constexpr int kFmFoldBlock = 256;
-constexpr int kFmFoldPerCu = 8;  // workgroups per CU of the capped grid, as rfm_mf_fold_in
 
-struct FmFoldArgs {
-  const int64_t* row_ptr;  // [n_new + 1]: examples of new row r are row_ptr[r] .. row_ptr[r + 1]
-  const int32_t* ids;      // fixed-side row of every example
-  const double* ry;        // label / propensity of every example
-  const int32_t* order;    // [n_new]: new rows by descending example count
-  int64_t n_new;
+struct FmFoldArgs : FoldExamples {
   const double* g;   // [n_new][kpad]: the new rows' feature sums
   const double* l;   // [n_new]
   const double* F;   // [n_fixed][kpad]: the fixed side (B, LI for new users; A, LU for new items)
@@ -72,12 +68,6 @@ __device__ __forceinline__ void fold_store(const Pack<VEC> (&src)[NC], double* r
     if (f < k) src[ch].store(row + f);
   }
 }
-
-struct FoldEx {  // an example on its way: fixed row, weight, and whether the group has it
-  int32_t j;
-  double ry;
-  bool live;
-};
 
 __device__ __forceinline__ FoldEx fold_fetch_ex(const FmFoldArgs& a, int64_t e0, int64_t n, int64_t e) {
   FoldEx x;
@@ -218,11 +208,8 @@ int32_t rfm_fm_fold_geometry(const rfm_ctx* ctx, int64_t n_new, int32_t n_factor
     RFM_REQUIRE(n_new >= 0 && n_new < (int64_t(1) << 31), "n_new=%lld out of range", (long long)n_new);
     const Shape s = shape_for(n_factors);
     const rfm_ctx assumed{};  // (the CU count of an MI355X)
-    h_out5[0] = s.lpr;
-    h_out5[1] = s.vec;
-    h_out5[2] = s.nc;
-    h_out5[3] = kFmFoldBlock / s.lpr;
-    h_out5[4] = capped_grid(ctx ? ctx : &assumed, n_new, 1, kFmFoldPerCu, 0);
+    fold_shape_out(s, kFmFoldBlock, h_out5);
+    h_out5[4] = capped_grid(ctx ? ctx : &assumed, n_new, 1, kFoldPerCu, 0);
   });
 }
 
@@ -232,11 +219,8 @@ int32_t rfm_fm_fold_in(rfm_ctx* ctx, const int64_t* d_row_ptr, const int32_t* d_
                        int32_t n_factors, double lr, int32_t n_passes, double* d_w_new, double* d_V_new,
                        double* d_A_new, double* d_L_new) {
   return guarded([&] {
-    RFM_REQUIRE(ctx, "null ctx");
-    RFM_REQUIRE(n_new >= 0 && n_new < (int64_t(1) << 31), "n_new=%lld out of range", (long long)n_new);
-    RFM_REQUIRE(n_fixed >= 0 && n_fixed < (int64_t(1) << 31), "n_fixed=%lld out of range", (long long)n_fixed);
-    RFM_REQUIRE(n_passes >= 0, "negative n_passes");
-    const Shape s = shape_for(n_factors);
+    Shape s;
+    const FoldExamples x = fold_checked(ctx, d_row_ptr, d_ids, d_ry, d_order, n_new, n_fixed, n_factors, n_passes, &s);
     RFM_REQUIRE(d_row_ptr && d_ids && d_ry && d_order && d_g && d_l && d_F && d_fL && d_c && d_w_new && d_V_new &&
                     d_A_new && d_L_new,
                 "null pointer");
@@ -244,12 +228,7 @@ int32_t rfm_fm_fold_in(rfm_ctx* ctx, const int64_t* d_row_ptr, const int32_t* d_
     // (a lane group past the row's examples reads row 0 of the fixed side)
     RFM_REQUIRE(n_fixed >= 1, "a fixed side without rows");
     RFM_HIP_CHECK(hipSetDevice(ctx->device));
-    FmFoldArgs a{};
-    a.row_ptr = d_row_ptr;
-    a.ids = d_ids;
-    a.ry = d_ry;
-    a.order = d_order;
-    a.n_new = n_new;
+    FmFoldArgs a{x};
     a.g = d_g;
     a.l = d_l;
     a.F = d_F;
@@ -263,7 +242,7 @@ int32_t rfm_fm_fold_in(rfm_ctx* ctx, const int64_t* d_row_ptr, const int32_t* d_
     a.V_new = d_V_new;
     a.A_new = d_A_new;
     a.L_new = d_L_new;
-    const int grid = capped_grid(ctx, n_new, 1, kFmFoldPerCu, 0);
+    const int grid = capped_grid(ctx, n_new, 1, kFoldPerCu, 0);
 #define RFM_CALL_FM_FOLD(L, Vv, N) \
   hipLaunchKernelGGL((fm_fold_kernel<L, Vv, N>), dim3(grid), dim3(kFmFoldBlock), 0, ctx->stream, a)
     RFM_FOR_SHAPE(s, RFM_CALL_FM_FOLD);

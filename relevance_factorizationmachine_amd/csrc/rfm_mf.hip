@@ -22,12 +22,13 @@
 //
 // Fold-in (rfm_mf_fold_in, mf_fold_kernel) trains new rows of one side against the fixed
 // other side by the same update restricted to that side: independent chains, one lane group
-// per new row, no schedule.
+// per new row, no schedule.  What it shares with FM fold-in is in rfm_fold.hpp.
 #include <algorithm>
 #include <cmath>
 
 #include "rfm_common.h"
 #include "rfm_device_utils.hpp"
+#include "rfm_fold.hpp"
 
 namespace rfm {
 
@@ -598,12 +599,7 @@ static void mf_walk_levels(const int32_t* h_level_ptr, int n_levels, int seq_cap
 // ---------------------------------------------------------------------------
 constexpr int kFoldAhead = RFM_MF_FOLD_READ_AHEAD;
 
-struct MfFoldArgs {
-  const int64_t* row_ptr;  // [n_new + 1]: examples of new row r are row_ptr[r] .. row_ptr[r + 1]
-  const int32_t* ids;      // fixed-side row of every example, chain order
-  const double* ry;        // label / propensity of every example
-  const int32_t* order;    // [n_new]: new rows by descending chain length
-  int64_t n_new;
+struct MfFoldArgs : FoldExamples {  // (a row's examples in chain order)
   const double* F;   // the fixed side: Q, b_i for new users; P, b_u for new items
   const double* fb;
   double b;
@@ -621,10 +617,7 @@ struct FoldChain {
 
 template <int VEC, int NC>
 struct FoldSlot {
-  // the step 2 * kFoldAhead ahead: id and weight on their way
-  int32_t j_far;
-  double ry_far;
-  bool live_far;
+  FoldEx far;  // the step 2 * kFoldAhead ahead: id and weight on their way
   // the step kFoldAhead ahead: the fixed row and bias on their way
   Pack<VEC> q[NC];
   double fb, ry;
@@ -633,12 +626,12 @@ struct FoldSlot {
 
 template <int VEC, int NC>
 __device__ __forceinline__ void fold_fetch_id(const MfFoldArgs& a, FoldChain& ch, FoldSlot<VEC, NC>& s) {
-  s.live_far = ch.step < ch.total;
-  s.j_far = 0;  // past the chain: row 0, a valid address
-  s.ry_far = 0.0;
-  if (s.live_far) {
-    s.j_far = a.ids[ch.e0 + ch.e];
-    s.ry_far = a.ry[ch.e0 + ch.e];
+  s.far.live = ch.step < ch.total;
+  s.far.j = 0;  // past the chain: row 0, a valid address
+  s.far.ry = 0.0;
+  if (s.far.live) {
+    s.far.j = a.ids[ch.e0 + ch.e];
+    s.far.ry = a.ry[ch.e0 + ch.e];
   }
   ++ch.step;
   if (++ch.e == ch.n) ch.e = 0;  // the next pass
@@ -646,10 +639,10 @@ __device__ __forceinline__ void fold_fetch_id(const MfFoldArgs& a, FoldChain& ch
 
 template <int LPR, int VEC, int NC>
 __device__ __forceinline__ void fold_fetch_row(const MfFoldArgs& a, int l, FoldSlot<VEC, NC>& s) {
-  s.live = s.live_far;
-  s.ry = s.ry_far;
-  mf_load_row<LPR, VEC, NC>(s.q, a.F + int64_t(s.j_far) * a.k, a.k, l);
-  s.fb = a.fb[s.j_far];
+  s.live = s.far.live;
+  s.ry = s.far.ry;
+  mf_load_row<LPR, VEC, NC>(s.q, a.F + int64_t(s.far.j) * a.k, a.k, l);
+  s.fb = a.fb[s.far.j];
 }
 
 // one step on the row in registers; every lane of the wavefront takes part in the sum.  A chunk
@@ -735,8 +728,6 @@ __global__ __launch_bounds__(kMfBlock) void mf_fold_kernel(MfFoldArgs a) {
     }
   }
 }
-
-constexpr int kFoldPerCu = 8;  // workgroups per CU of the capped grid, as the other MF launches
 
 }  // namespace rfm
 
@@ -908,10 +899,7 @@ int32_t rfm_mf_fold_geometry(const rfm_ctx* ctx, int64_t n_new, int32_t n_factor
     RFM_REQUIRE(n_new >= 0 && n_new < (int64_t(1) << 31), "n_new=%lld out of range", (long long)n_new);
     const Shape s = shape_for(n_factors);
     const rfm_ctx assumed{};  // (the CU count of an MI355X)
-    h_out6[0] = s.lpr;
-    h_out6[1] = s.vec;
-    h_out6[2] = s.nc;
-    h_out6[3] = kMfBlock / s.lpr;
+    fold_shape_out(s, kMfBlock, h_out6);
     h_out6[4] = capped_grid(ctx ? ctx : &assumed, n_new, kMfBlock / s.lpr, kFoldPerCu, 0);
     h_out6[5] = kFoldAhead;
   });
@@ -922,21 +910,13 @@ int32_t rfm_mf_fold_in(rfm_ctx* ctx, const int64_t* d_row_ptr, const int32_t* d_
                        int64_t n_fixed, double b, int32_t n_factors, double lr, double reg,
                        int32_t n_passes, double* d_rows, double* d_bias) {
   return guarded([&] {
-    RFM_REQUIRE(ctx, "null ctx");
-    RFM_REQUIRE(n_new >= 0 && n_new < (int64_t(1) << 31), "n_new=%lld out of range", (long long)n_new);
-    RFM_REQUIRE(n_fixed >= 0 && n_fixed < (int64_t(1) << 31), "n_fixed=%lld out of range", (long long)n_fixed);
-    RFM_REQUIRE(n_passes >= 0, "negative n_passes");
-    const Shape s = shape_for(n_factors);
+    Shape s;
+    const FoldExamples x = fold_checked(ctx, d_row_ptr, d_ids, d_ry, d_order, n_new, n_fixed, n_factors, n_passes, &s);
     RFM_REQUIRE(d_row_ptr && d_ids && d_ry && d_order && d_F && d_fb && d_rows && d_bias, "null pointer");
     if (n_new == 0 || n_passes == 0) return;
     // (a lane group past its chain reads row 0 of the fixed side)
     RFM_REQUIRE(n_fixed >= 1, "a fixed side without rows");
-    MfFoldArgs a{};
-    a.row_ptr = d_row_ptr;
-    a.ids = d_ids;
-    a.ry = d_ry;
-    a.order = d_order;
-    a.n_new = n_new;
+    MfFoldArgs a{x};
     a.F = d_F;
     a.fb = d_fb;
     a.b = b;

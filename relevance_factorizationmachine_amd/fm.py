@@ -10,7 +10,8 @@ loop runs in the kernels of ``csrc/rfm_fm.hip``.
 
 Beyond the reference: the catalogue methods (``recommend.py``) and fold-in of
 users and items that arrive after the fit (``fold_in_users`` / ``fold_in_items``
-/ ``append_columns``, ``csrc/rfm_fm_fold.hip``).
+/ ``append_columns``, ``csrc/rfm_fm_fold.hip``, the host side shared with MF in
+``fold.py``).
 """
 from __future__ import annotations
 
@@ -21,7 +22,7 @@ from typing import Optional
 
 import numpy as np
 
-from . import _lib
+from . import _lib, fold
 from .base import LOSS_EPS, PointwiseBaseRecommender
 from .evaluate import EvalLoop, FitHook, device_frame, runs
 from .optimizer import DeviceSGD
@@ -385,36 +386,32 @@ class FactorizationMachines(PointwiseBaseRecommender):
         other side (``rfm_fm_fold_in``): every check on the host first, then the
         side sums of ``new_rows`` and the fold launch enqueued on the runtime's stream, no host wait."""
         from . import recommend as rec
-        from .mf import fold_examples
 
         n_users, n_items = rec.catalogue_shape(self, sides)
         kf, kp = int(self.n_factors), rec.pad4(self.n_factors)
         X = fold_rows(sides, new_rows, side, self.n_features)
         n_new, n_fixed = int(X.shape[0]), (n_items, n_users)[side]
-        row_ptr, ids, ry, order = fold_examples(data, n_new, n_fixed, side, n_passes)
+        row_ptr, ids, ry, order = fold.fold_examples(data, n_new, n_fixed, side, n_passes)
         lr = float(self.lr if lr is None else lr)
-        if init is not None:
-            V0, w0 = (np.asarray(a, dtype=np.float64) for a in init)
-            if V0.shape != (n_new, kf) or w0.shape != (n_new,):
-                raise ValueError(f"init must be (V [{n_new}, {kf}], w [{n_new}]), got {V0.shape}, {w0.shape}")
+        start = fold.initial_state(init, n_new, kf, ("V", "w"))
         if ops is not None and (tuple(ops.A.shape) != (n_users, kp) or tuple(ops.B.shape) != (n_items, kp)):
             raise ValueError(f"ops of {tuple(ops.A.shape)}, {tuple(ops.B.shape)} for sides of {n_users} users and "
                              f"{n_items} items at {kf} factors")
         import torch
 
         rt = self._rt
-        if init is None:
+        if start is None:
             V_new = torch.zeros((n_new, kf), dtype=torch.float64, device=rt.torch_device)
             w_new = torch.zeros((n_new,), dtype=torch.float64, device=rt.torch_device)
         else:
-            V_new, w_new = rt.upload(V0), rt.upload(w0)
+            V_new, w_new = rt.upload(start[0]), rt.upload(start[1])
         A_new, L_new = rt.empty((n_new, kp), torch.float64), rt.empty((n_new,), torch.float64)
         if n_new:
             if ops is None:
                 ops = rec.operands(self, sides)
             F, fL = ((ops.B, ops.LI), (ops.A, ops.LU))[side]
             g, l = rec.side_sums(rt, DeviceCSR(rt, X), self.w.dev, self.V.dev, self.n_features, kf)
-            dev = [rt.upload(a if a.size else np.zeros(1, a.dtype)) for a in (row_ptr, ids, ry, order)]
+            dev = fold.upload_examples(rt, row_ptr, ids, ry, order)
             _lib.check(rt.lib.rfm_fm_fold_in(
                 rt.ctx, *(d.data_ptr() for d in dev), n_new, g.data_ptr(), l.data_ptr(), F.data_ptr(), fL.data_ptr(),
                 n_fixed, self.w0.dev.data_ptr(), kf, lr, int(n_passes), w_new.data_ptr(), V_new.data_ptr(),

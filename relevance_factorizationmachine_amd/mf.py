@@ -14,7 +14,7 @@ from typing import Optional
 
 import numpy as np
 
-from . import _lib
+from . import _lib, fold
 from .base import LOSS_EPS, PointwiseBaseRecommender
 from .evaluate import EvalLoop, FitHook, device_frame
 from .optimizer import DeviceSGD
@@ -113,38 +113,6 @@ class DevicePairs:
         self.h_items = np.ascontiguousarray(pairs[:, 1], dtype=np.int32)
         self.users = rt.upload(self.h_users if self.n else np.zeros(1, np.int32))
         self.items = rt.upload(self.h_items if self.n else np.zeros(1, np.int32))
-
-
-def fold_examples(data: dict, n_new: int, n_fixed: int, new_col: int, n_passes: int):
-    """The examples of a fold-in call as ``rfm_mf_fold_in`` takes them (host only): ``data`` as
-    ``fit()`` takes it, column ``new_col`` of ``features`` holding new-row indices 0..n_new-1 and the
-    other column known ids 0..n_fixed-1.  Returns ``(row_ptr int64 [n_new+1], ids int32, ry float64,
-    order int32 [n_new])``: the examples grouped by new row with a stable sort (a row's examples
-    keep their input order), ``ry`` = label / propensity as ``fit()`` divides them, and the new rows
-    by descending example count (stable) -- the order in which lane groups take them."""
-    pairs = np.asarray(data["features"])
-    if pairs.ndim != 2 or pairs.shape[1] < 2:
-        raise ValueError("MF features must be an (N, 2) array of [user, item]")
-    labels, pscores = np.asarray(data["labels"]), np.asarray(data["pscores"])
-    if not (labels.ndim == pscores.ndim == 1 and labels.shape[0] == pscores.shape[0] == pairs.shape[0]):
-        raise ValueError(f"{pairs.shape[0]} pairs, {labels.shape[0] if labels.ndim else 0} labels and "
-                         f"{pscores.shape[0] if pscores.ndim else 0} pscores: one of each per example")
-    n_new, n_passes = int(n_new), int(n_passes)
-    if n_new < 0 or n_passes < 0:
-        raise ValueError(f"n_new={n_new}, n_passes={n_passes}: neither may be negative")
-    new, other = pairs[:, new_col].astype(np.int64), pairs[:, 1 - new_col].astype(np.int64)
-    names = ("user", "item")
-    if new.size:
-        if new.min() < 0 or new.max() >= n_new:
-            raise IndexError(f"new {names[new_col]} index out of range")
-        if other.min() < 0 or other.max() >= n_fixed:
-            raise IndexError(f"{names[1 - new_col]} id out of range")
-    by_row = np.argsort(new, kind="stable")
-    counts = np.bincount(new, minlength=n_new)
-    row_ptr = np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
-    ry = (labels.astype(np.float64) / pscores.astype(np.float64))[by_row]
-    order = np.argsort(-counts, kind="stable").astype(np.int32)
-    return row_ptr, other[by_row].astype(np.int32), ry, order
 
 
 @dataclass
@@ -363,19 +331,16 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
             # the reference's global bias exists only after fit() (src/mf.py:84)
             raise AttributeError("'LogisticMatrixFactorization' object has no attribute 'b'")
         F, fb, n_fixed = ((self.Q, self.b_i, self.n_items), (self.P, self.b_u, self.n_users))[side]
-        row_ptr, ids, ry, order = fold_examples(data, n_new, n_fixed, side, n_passes)
+        row_ptr, ids, ry, order = fold.fold_examples(data, n_new, n_fixed, side, n_passes)
         n_new, kf = int(n_new), int(self.n_factors)
-        if init is None:
+        start = fold.initial_state(init, n_new, kf, ("rows", "bias"))
+        if start is None:
             rows = torch.zeros((n_new, kf), dtype=torch.float64, device=rt.torch_device)
             bias = torch.zeros((n_new,), dtype=torch.float64, device=rt.torch_device)
         else:
-            rows0, bias0 = (np.asarray(a, dtype=np.float64) for a in init)
-            if rows0.shape != (n_new, kf) or bias0.shape != (n_new,):
-                raise ValueError(f"init must be (rows [{n_new}, {kf}], bias [{n_new}]), got {rows0.shape}, "
-                                 f"{bias0.shape}")
-            rows, bias = rt.upload(rows0), rt.upload(bias0)
+            rows, bias = rt.upload(start[0]), rt.upload(start[1])
         if n_new and int(n_passes):
-            dev = [rt.upload(a if a.size else np.zeros(1, a.dtype)) for a in (row_ptr, ids, ry, order)]
+            dev = fold.upload_examples(rt, row_ptr, ids, ry, order)
             _lib.check(rt.lib.rfm_mf_fold_in(
                 rt.ctx, *(d.data_ptr() for d in dev), n_new, F.dev.data_ptr(), fb.dev.data_ptr(), n_fixed,
                 float(self.b), kf, float(self.lr), float(self.reg), int(n_passes), rows.data_ptr(),

@@ -33,24 +33,20 @@ showed over the case list and the flows: 1.4e-15 (``GPU_MAX_SEEN``), below the C
 inside ``FMFOLD_TOL``."""
 import functools
 import types
-import zlib
 from dataclasses import dataclass
 
 import numpy as np
 import scipy.sparse as sp
 
+import fold_common
 import mf_step_common as ms
+from fold_common import FOLD_BLOCK, GRID_PER_CU, LD, N_FIXED, _chains, _sigmoid
 from mf_step_common import Guarded, PAD
-
-LD = np.longdouble
 
 FMFOLD_FLOOR = 2.7e-15                # measured CPU floor to two digits (test_tolerance_floor holds it within 5%)
 FMFOLD_TOL = min(64 * FMFOLD_FLOOR, 1e-11)
 GPU_MAX_SEEN = 1.4e-15                # largest distance an MI355X showed over the case list (shape-k3)
 
-FOLD_BLOCK = 256                      # rfm_fm_fold.hip kFmFoldBlock
-GRID_PER_CU = 8                       # rfm_fm_fold.hip kFmFoldPerCu
-N_FIXED = 23                          # rows of the fixed side of every case
 LONG_ROW = 1029                       # the long row of the narrowest classes
 C0 = 0.4                              # w0 of every case
 LR_CAP = 0.05
@@ -68,11 +64,6 @@ def groups(k):
 # --------------------------------------------------------------------------
 # the semantics: one row, pass by pass (the form the mutations are made in)
 # --------------------------------------------------------------------------
-def _sigmoid(z, dtype):
-    clip = dtype(ms.LOGIT_CLIP)
-    return 1 / (1 + np.exp(-np.clip(z, -clip, clip)))
-
-
 def _sum_rows_reversed(a):
     """Sum over the first axis, strictly from the last example to the first."""
     return np.cumsum(a[::-1], axis=0)[-1]
@@ -128,48 +119,7 @@ def served(g, l, nu, om):
 # cases
 # --------------------------------------------------------------------------
 @dataclass
-class FmFoldCase:
-    name: str
-    k: int
-    chains: list                         # per new row: the fixed-side rows of its examples, in order
-    n_passes: int
-    with_init: bool = False
-    n_fixed: int = N_FIXED
-    clip: bool = False                   # fixed rows 0 / 1 carry a linear term of +900 / -900
-
-    @property
-    def n_new(self):
-        return len(self.chains)
-
-    @property
-    def lengths(self):
-        return np.asarray([len(c) for c in self.chains], dtype=np.int64)
-
-    @property
-    def row_ptr(self):
-        return np.concatenate([[0], np.cumsum(self.lengths)]).astype(np.int64)
-
-    @property
-    def ids(self):
-        return (np.concatenate(self.chains) if self.n_new else np.zeros(0)).astype(np.int32)
-
-    @property
-    def order(self):
-        """New rows by descending example count, stable: what the host hands the kernel."""
-        return np.argsort(-self.lengths, kind="stable").astype(np.int32)
-
-    def _rng(self, tag=""):
-        return np.random.default_rng(zlib.crc32((tag + self.name).encode()))
-
-    def yp(self):
-        """(label, propensity) of every example in row order, drawn as the parity tests draw them."""
-        rng, n = self._rng(), int(self.lengths.sum())
-        return (rng.random(n) < 0.5).astype(np.float64), rng.uniform(0.1, 1.0, size=n) ** 0.5
-
-    def ry(self):
-        y, p = self.yp()
-        return y / p
-
+class FmFoldCase(fold_common.FoldCaseBase):
     def fixed(self):
         """The fixed side ``(F [n_fixed, k], fL [n_fixed])``: rows of squared length about 1."""
         rng = self._rng("fixed-")
@@ -206,16 +156,6 @@ class FmFoldCase:
     def lr(self):
         return _lr_for(self.step_bound())
 
-    def data(self, side="user", interleaved=False):
-        """The case as the dictionary ``fold_in_users`` (``side`` "item": ``fold_in_items``) takes.
-        ``interleaved``: the rows' examples take turns (each row's own order is kept)."""
-        y, p = self.yp()
-        new = np.repeat(np.arange(self.n_new), self.lengths)
-        pos = np.concatenate([np.arange(n) for n in self.lengths]) if self.n_new else np.zeros(0, np.int64)
-        take = np.lexsort((new, pos)) if interleaved else np.arange(len(new))
-        cols = (new, self.ids.astype(np.int64)) if side == "user" else (self.ids.astype(np.int64), new)
-        return {"features": np.stack(cols, axis=1)[take], "labels": y[take], "pscores": p[take]}
-
 
 def _lr_for(bound):
     """The largest power of two with lr * bound <= 1/2, at most LR_CAP."""
@@ -247,11 +187,6 @@ def served_all(case, V, w):
     for r in range(case.n_new):
         A[r], L[r] = served(g[r], l[r], V[r], w[r])
     return A, L
-
-
-def _chains(name, lengths, n_fixed=N_FIXED, lo=0):
-    rng = np.random.default_rng(zlib.crc32(("ids-" + name).encode()))
-    return [rng.integers(lo, n_fixed, size=int(n)) for n in lengths]
 
 
 SHAPE_KS = ms.SHAPE_KS                       # the lowest and highest k of the 19 classes, 300 and 400
@@ -317,14 +252,7 @@ def fold_cases():
     return {c.name: c for c in out}
 
 
-@functools.lru_cache(maxsize=None)
-def _oracle_by_name(name):
-    return fold_all(fold_cases()[name])
-
-
-def oracle(case):
-    """(nu, omega) in long double; computed once per listed case."""
-    return _oracle_by_name(case.name) if case.name in fold_cases() else fold_all(case)
+oracle = fold_common.cached_oracle(fold_cases, fold_all)  # (nu, omega) in long double
 
 
 def distance(got, want, lr):
@@ -517,14 +445,10 @@ def run_fold(rt, case, start=None, n_passes=None):
     d_F, d_fL, d_g, d_l, d_ry, d_c = (i[0] for i in inputs)
     d_V, d_w = Guarded(rt, nu0, k), Guarded(rt, om0, PAD)
     d_A, d_L = Guarded.blank(rt, n * kp, kp), Guarded.blank(rt, n)
-    ints = [rt.upload(a if a.size else np.zeros(1, a.dtype)) for a in (case.row_ptr, case.ids, case.order)]
+    ints = fold_common.upload_ints(rt, case)
     _lib.check(rt.lib.rfm_fm_fold_in(
         rt.ctx, ints[0].data_ptr(), ints[1].data_ptr(), d_ry.ptr, ints[2].data_ptr(), n, d_g.ptr, d_l.ptr, d_F.ptr,
         d_fL.ptr, case.n_fixed, d_c.ptr, k, case.lr, n_passes, d_w.ptr, d_V.ptr, d_A.ptr, d_L.ptr))
     rt.sync()
-    for dev, host, what in inputs:
-        np.testing.assert_array_equal(dev.host().view(np.uint64), np.ascontiguousarray(host).view(np.uint64),
-                                      err_msg=f"{case.name}: {what} changed")
-    for dev, host in zip(ints, (case.row_ptr, case.ids, case.order)):
-        np.testing.assert_array_equal(dev.cpu().numpy()[: host.size], host)
+    fold_common.assert_inputs_kept(case, inputs, ints)
     return d_V.host().reshape(n, k), d_w.host(), d_A.host().reshape(n, kp), d_L.host()

@@ -25,19 +25,16 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
+import fold_common
 import mf_step_common as ms
+from fold_common import FOLD_BLOCK, GRID_PER_CU, LD, N_FIXED, _chains, _sigmoid
 from mf_step_common import B0, INIT_SEED, LR, REG, Guarded, PAD
-
-LD = np.longdouble
 
 FOLD_FLOOR = 1.8e-15                  # measured CPU floor to two digits (test_tolerance_floor holds it within 5%)
 FOLD_TOL = min(64 * FOLD_FLOOR, 1e-11)
 GPU_MAX_SEEN = 1.3e-15                # largest distance an MI355X showed (the grid case; 6.7e-16 over the listed cases)
 
 DEPTH = 4                             # include/rfm_hip.h RFM_MF_FOLD_READ_AHEAD
-FOLD_BLOCK = 256                      # rfm_mf.hip kMfBlock
-GRID_PER_CU = 8                       # rfm_mf.hip kFoldPerCu
-N_FIXED = 23                          # rows of the fixed side of every case but the anchor's
 LONG_CHAIN = 1029                     # the long chain of the small classes
 
 
@@ -53,11 +50,6 @@ def grid_pass(k, n_cu):
 # --------------------------------------------------------------------------
 # the semantics: one row, example by example (the form the mutations are made in)
 # --------------------------------------------------------------------------
-def _sigmoid(z, dtype):
-    clip = dtype(ms.LOGIT_CLIP)
-    return 1 / (1 + np.exp(-np.clip(z, -clip, clip)))
-
-
 def fold_row(ids, ry, F, fb, x0, c0, n_passes, b=B0, lr=LR, reg=REG, dtype=LD, mutation=None):
     """One new row after ``n_passes`` passes over its examples: ``(x, c)`` in ``dtype``.
     ``mutation`` breaks the rule in one of four ways (test_fold_in_host.py): "stale" = the row
@@ -90,48 +82,8 @@ def fold_row(ids, ry, F, fb, x0, c0, n_passes, b=B0, lr=LR, reg=REG, dtype=LD, m
 # cases
 # --------------------------------------------------------------------------
 @dataclass
-class FoldCase:
-    name: str
-    k: int
-    chains: list                         # per new row: the fixed-side ids of its examples, in order
-    n_passes: int
-    with_init: bool = False
-    n_fixed: int = N_FIXED
-    clip: bool = False                   # fixed rows 0 / 1 carry a bias of +900 / -900
+class FoldCase(fold_common.FoldCaseBase):  # (N_FIXED fixed rows in every case but the anchor's)
     extra: dict = field(default_factory=dict)
-
-    @property
-    def n_new(self):
-        return len(self.chains)
-
-    @property
-    def lengths(self):
-        return np.asarray([len(c) for c in self.chains], dtype=np.int64)
-
-    @property
-    def row_ptr(self):
-        return np.concatenate([[0], np.cumsum(self.lengths)]).astype(np.int64)
-
-    @property
-    def ids(self):
-        return (np.concatenate(self.chains) if self.n_new else np.zeros(0)).astype(np.int32)
-
-    @property
-    def order(self):
-        """New rows by descending example count, stable: what the host hands the kernel."""
-        return np.argsort(-self.lengths, kind="stable").astype(np.int32)
-
-    def _rng(self):
-        return np.random.default_rng(zlib.crc32(self.name.encode()))
-
-    def yp(self):
-        """(label, propensity) of every example in chain order, drawn as the parity tests draw them."""
-        rng, n = self._rng(), int(self.lengths.sum())
-        return (rng.random(n) < 0.5).astype(np.float64), rng.uniform(0.1, 1.0, size=n) ** 0.5
-
-    def ry(self):
-        y, p = self.yp()
-        return y / p
 
     def fixed(self):
         """The fixed side ``(F [n_fixed, k], fb [n_fixed])``: the item side of the reference's init."""
@@ -147,16 +99,6 @@ class FoldCase:
             return np.zeros((self.n_new, self.k)), np.zeros(self.n_new)
         rng = np.random.default_rng(zlib.crc32(self.name.encode()) ^ 0x5EED)
         return rng.uniform(-1.0, 1.0, size=(self.n_new, self.k)), rng.normal(scale=0.1, size=self.n_new)
-
-    def data(self, side="user", interleaved=False):
-        """The case as the dictionary ``fold_in_users`` (``side`` "item": ``fold_in_items``) takes.
-        ``interleaved``: the rows' examples take turns (each row's own order is kept)."""
-        y, p = self.yp()
-        new = np.repeat(np.arange(self.n_new), self.lengths)
-        pos = np.concatenate([np.arange(n) for n in self.lengths]) if self.n_new else np.zeros(0, np.int64)
-        take = np.lexsort((new, pos)) if interleaved else np.arange(len(new))
-        cols = (new, self.ids.astype(np.int64)) if side == "user" else (self.ids.astype(np.int64), new)
-        return {"features": np.stack(cols, axis=1)[take], "labels": y[take], "pscores": p[take]}
 
 
 def fold_all(case, dtype=LD, reverse=False):
@@ -186,11 +128,6 @@ def fold_all(case, dtype=LD, reverse=False):
 def edge_lengths(depth=DEPTH):
     """Chain lengths around the read-ahead depth: its two rings are ``depth`` and ``2 * depth`` deep."""
     return [depth + 1, 0, 2 * depth, 1, depth - 1, 2 * depth + 1, depth, 2 * depth - 1]
-
-
-def _chains(name, lengths, n_fixed=N_FIXED, lo=0):
-    rng = np.random.default_rng(zlib.crc32(("ids-" + name).encode()))
-    return [rng.integers(lo, n_fixed, size=int(n)) for n in lengths]
 
 
 SHAPE_KS = ms.SHAPE_KS                       # the lowest and highest k of the 19 classes, 300 and 400
@@ -258,14 +195,7 @@ def fold_cases():
     return {c.name: c for c in out}
 
 
-@functools.lru_cache(maxsize=None)
-def _oracle_by_name(name):
-    return fold_all(fold_cases()[name])
-
-
-def oracle(case):
-    """(rows, bias) in long double; computed once per listed case."""
-    return _oracle_by_name(case.name) if case.name in fold_cases() else fold_all(case)
+oracle = fold_common.cached_oracle(fold_cases, fold_all)  # (rows, bias) in long double
 
 
 def distance(got, want):
@@ -311,14 +241,11 @@ def run_fold(rt, case, start=None, n_passes=None):
     k = case.k
     d_F, d_fb, d_ry = Guarded(rt, F, k), Guarded(rt, fb, PAD), Guarded(rt, ry, PAD)
     d_rows, d_bias = Guarded(rt, x0, k), Guarded(rt, c0, PAD)
-    ints = [rt.upload(a if a.size else np.zeros(1, a.dtype)) for a in (case.row_ptr, case.ids, case.order)]
+    ints = fold_common.upload_ints(rt, case)
     _lib.check(rt.lib.rfm_mf_fold_in(
         rt.ctx, ints[0].data_ptr(), ints[1].data_ptr(), d_ry.ptr, ints[2].data_ptr(), case.n_new, d_F.ptr, d_fb.ptr,
         case.n_fixed, B0, k, LR, REG, n_passes, d_rows.ptr, d_bias.ptr))
     rt.sync()
-    for dev, host, what in ((d_F, F, "the fixed rows"), (d_fb, fb, "the fixed bias"), (d_ry, ry, "the weights")):
-        np.testing.assert_array_equal(dev.host().view(np.uint64), np.ascontiguousarray(host).view(np.uint64),
-                                      err_msg=f"{case.name}: {what} changed")
-    for dev, host in zip(ints, (case.row_ptr, case.ids, case.order)):
-        np.testing.assert_array_equal(dev.cpu().numpy()[: host.size], host)
+    fold_common.assert_inputs_kept(case, ((d_F, F, "the fixed rows"), (d_fb, fb, "the fixed bias"), (d_ry, ry, "the weights")),
+                                   ints)
     return d_rows.host().reshape(case.n_new, k), d_bias.host()

@@ -189,9 +189,9 @@ def test_flow_logits_are_far_apart(k, side):
 # grouping, order array and argument checks of the Python entry (no device)
 # --------------------------------------------------------------------------
 def test_grouping_and_order_are_fold_examples():
-    """The host half reuses mf.fold_examples: grouped by new row with a stable sort, the rows by
+    """The host half is fold.fold_examples: grouped by new row with a stable sort, the rows by
     descending example count."""
-    from relevance_factorizationmachine_amd.mf import fold_examples
+    from relevance_factorizationmachine_amd.fold import fold_examples
     case = fc.fold_cases()["shape-k7"]
     for side, col in (("user", 0), ("item", 1)):
         for interleaved in (False, True):
@@ -311,36 +311,3 @@ def test_entry_points_reject_bad_arguments():
                               one) == _lib.RFM_ERR_BAD_ARG
     assert "ctx" in _lib.last_error()
 
-
-# --------------------------------------------------------------------------
-# the header of the two entries and their ctypes table
-# --------------------------------------------------------------------------
-def test_fold_header_and_ctypes_table_agree_argument_by_argument():
-    """include/rfm_fm_fold.h (included by rfm_hip.h) against ``_lib.FOLD_SIGNATURES``, as
-    test_host_abi.py holds rfm_hip.h against ``_lib.SIGNATURES``: a parameter with a ``*`` is a
-    pointer, the scalars are themselves; the library exports both entries and binds them on load."""
-    import os
-    import re
-
-    from relevance_factorizationmachine_amd import _lib
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    main = open(os.path.join(root, "include", "rfm_hip.h")).read()
-    assert re.search(r'^#include "rfm_fm_fold.h"$', main, flags=re.M)
-    header = open(os.path.join(root, "include", "rfm_fm_fold.h")).read()
-    header = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
-    scalars = {"int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double}
-    declared = re.findall(r"^int32_t\s+(rfm_\w+)\s*\(([^)]*)\)\s*;", header, flags=re.M)
-    assert sorted(n for n, _ in declared) == sorted(_lib.FOLD_SIGNATURES) == ["rfm_fm_fold_geometry", "rfm_fm_fold_in"]
-    assert not set(_lib.FOLD_SIGNATURES) & set(_lib.SIGNATURES)
-    lib = _lib.load()
-    for name, params in declared:
-        want = []
-        for p in (q.strip() for q in params.split(",")):
-            kinds = [n for n in scalars if re.search(r"\b%s\b" % n, p)]
-            want.append("pointer" if "*" in p else kinds[0])
-            assert "*" in p or len(kinds) == 1, p
-        got = ["pointer" if t is C.c_void_p else next(n for n, s in scalars.items() if t is s)
-               for t in _lib.FOLD_SIGNATURES[name]]
-        assert want == got, (name, want, got)
-        fn = getattr(lib, name)
-        assert fn.argtypes == _lib.FOLD_SIGNATURES[name] and fn.restype is C.c_int32

@@ -158,7 +158,7 @@ def test_oracle_catches_a_mutation_on_its_row_alone(mutation):
 # grouping, order array and argument checks of the Python entry (no device)
 # --------------------------------------------------------------------------
 def test_grouping_of_interleaved_input_is_stable():
-    from relevance_factorizationmachine_amd.mf import fold_examples
+    from relevance_factorizationmachine_amd.fold import fold_examples
     case = fc.fold_cases()["shape-k7"]
     for side, col in (("user", 0), ("item", 1)):
         for interleaved in (False, True):
@@ -184,7 +184,8 @@ def test_grouping_of_interleaved_input_is_stable():
 
 def test_argument_checks_need_no_device():
     from relevance_factorizationmachine_amd import recommend as rec
-    from relevance_factorizationmachine_amd.mf import FoldedRows, LogisticMatrixFactorization, fold_examples
+    from relevance_factorizationmachine_amd.fold import fold_examples
+    from relevance_factorizationmachine_amd.mf import FoldedRows, LogisticMatrixFactorization
     good = {"features": np.array([[0, 1], [1, 2]]), "labels": np.ones(2), "pscores": np.ones(2)}
     fold_examples(good, 2, 3, 0, 1)
     fold_examples(good, 2, 3, 0, 0)

@@ -19,6 +19,7 @@ import scipy.sparse as sp
 import fold_in_common as fc
 import mf_step_common as ms
 from conftest import rel_err
+from fold_common import _bits, _n_cu, _names, _twice
 from oracle import cpu_ref
 
 pytestmark = pytest.mark.gpu
@@ -30,22 +31,6 @@ TIGHT = 1e-9  # the norm-wise bound of the parity tests (test_gpu_parity.py), fo
 def rt():
     from relevance_factorizationmachine_amd import runtime
     return runtime.Runtime.get()
-
-
-def _n_cu(rt):
-    import torch
-    return int(torch.cuda.get_device_properties(rt.device).multi_processor_count)
-
-
-def _twice(run):
-    first, second = run(), run()
-    for a, b in zip(first, second):
-        np.testing.assert_array_equal(a, b, err_msg="two calls from the same start differ")
-    return first
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def _check(rt, case, want=None):
@@ -63,14 +48,10 @@ def _check(rt, case, want=None):
     return got, g
 
 
-def _names(prefix):
-    return [n for n in fc.fold_cases() if n.startswith(prefix)]
-
-
 # --------------------------------------------------------------------------
 # a. every shape class at its lowest and highest factor count
 # --------------------------------------------------------------------------
-@pytest.mark.parametrize("name", _names("shape-"))
+@pytest.mark.parametrize("name", _names("shape-", fc.fold_cases()))
 def test_every_shape_class(rt, name):
     case = fc.fold_cases()[name]
     _, g = _check(rt, case)
@@ -87,7 +68,7 @@ def test_every_shape_class(rt, name):
 # --------------------------------------------------------------------------
 # b. 0, 1, 2, 3 passes: the rings across the pass boundary
 # --------------------------------------------------------------------------
-@pytest.mark.parametrize("name", _names("passes"))
+@pytest.mark.parametrize("name", _names("passes", fc.fold_cases()))
 def test_passes(rt, name):
     case = fc.fold_cases()[name]
     got, _ = _check(rt, case)
@@ -106,7 +87,7 @@ def test_passes(rt, name):
 # --------------------------------------------------------------------------
 # c. row counts around a workgroup, and past one pass of the capped grid
 # --------------------------------------------------------------------------
-@pytest.mark.parametrize("name", _names("count"))
+@pytest.mark.parametrize("name", _names("count", fc.fold_cases()))
 def test_row_counts(rt, name):
     case = fc.fold_cases()[name]
     _, g = _check(rt, case)
@@ -123,7 +104,7 @@ def test_grid_stride(rt):
 # --------------------------------------------------------------------------
 # d. repeated and shared fixed rows, clipped logits, a caller's init
 # --------------------------------------------------------------------------
-@pytest.mark.parametrize("name", _names("special"))
+@pytest.mark.parametrize("name", _names("special", fc.fold_cases()))
 def test_special_chains(rt, name):
     case = fc.fold_cases()[name]
     got, _ = _check(rt, case)
