@@ -211,6 +211,9 @@ int32_t rfm_fm_plan_forward(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_in
                             double* d_out_pred);
 /* the hot columns (ascending), h_out[0 .. info[2]); capacity = room in h_out */
 int32_t rfm_fm_plan_hot_columns(const rfm_fm_plan* plan, int32_t* h_out, int32_t capacity);
+/* the columns whose slice a sliced forward's workgroup keeps in LDS, in their LDS order (most
+ * frequent first, ties ascending), h_out[0 .. sliced[2]); capacity = room in h_out */
+int32_t rfm_fm_plan_sliced_columns(const rfm_fm_plan* plan, int32_t* h_out, int32_t capacity);
 
 /* ---- FM: one training step ----------------------------------------------
  * Replaces lines src/fm.py:80-88 with _update_w0/_update_w/_update_V
@@ -339,6 +342,15 @@ int32_t rfm_fm_train_part(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indp
  * rfm_fm_forward_loss, the validation-loss forward). */
 int32_t rfm_fm_forward_geometry(const rfm_ctx* ctx, int64_t n_rows, int32_t n_factors, int32_t records,
                                 int32_t* h_out4);
+/* The launch of a sliced forward of n_rows rows through this plan (rfm_fm_plan_forward; the loss
+ * forwards of rfm_fm_train with n_rows = batch + n_val), form_rows >= 0: the decision between the
+ * sliced and the plain form taken for that many rows instead (a shard of a log), -1: for n_rows.
+ * Nothing is launched; the environment switches are read as the call reads them.  h_out4[0]=1 if
+ * the sliced form is taken (0: the plan has no slices, the rows are too few, RFM_SLICED_LOSS=0; the
+ * call then takes the plain forward and [1..3] say nothing), [1]=workgroups, [2]=rows per workgroup
+ * (a wavefront takes every 16th of them, in blocks of 64), [3]=bytes of LDS per workgroup. */
+int32_t rfm_fm_sliced_geometry(const rfm_ctx* ctx, const rfm_fm_plan* plan, int64_t n_rows, int64_t form_rows,
+                               int32_t* h_out4);
 /* The forms of the loss forwards that rfm_fm_train (call_iters = 0) or rfm_fm_train_part would
  * take with this plan, batch, n_iters, call_iters and validation log, want_train / want_val saying
  * which of d_out_train_loss / d_out_val_loss is given (nothing is launched; the environment

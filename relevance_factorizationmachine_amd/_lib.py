@@ -140,6 +140,7 @@ SIGNATURES = {
     "rfm_fm_plan_register_log": [_vp, _vp, _i32, _vp, _vp, _vp, _i64],
     "rfm_fm_plan_forward": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
     "rfm_fm_plan_hot_columns": [_vp, _vp, _i32],
+    "rfm_fm_plan_sliced_columns": [_vp, _vp, _i32],
     "rfm_fm_step": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _f64],
     "rfm_fm_grad": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
     "rfm_fm_apply": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f64],
@@ -150,6 +151,7 @@ SIGNATURES = {
     "rfm_fm_train": _TRAIN,
     "rfm_fm_train_part": _TRAIN + [_i64],
     "rfm_fm_forward_geometry": [_vp, _i64, _i32, _i32, _vp],
+    "rfm_fm_sliced_geometry": [_vp, _vp, _i64, _i64, _vp],
     "rfm_fm_train_forms": [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
     "rfm_fm_train_eval": _TRAIN + _CSR + [_i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _i64, _i64, _vp],
     "rfm_fm_fit_dp": _FIT_DP,

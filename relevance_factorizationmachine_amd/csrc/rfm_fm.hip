@@ -1066,6 +1066,19 @@ int32_t rfm_fm_forward_geometry(const rfm_ctx* ctx, int64_t n_rows, int32_t n_fa
   });
 }
 
+int32_t rfm_fm_sliced_geometry(const rfm_ctx* ctx, const rfm_fm_plan* plan, int64_t n_rows, int64_t form_rows,
+                               int32_t* h_out4) {
+  return guarded([&] {
+    RFM_REQUIRE(ctx && plan && h_out4, "null pointer");
+    RFM_REQUIRE(n_rows >= 1 && form_rows >= -1, "bad shape");
+    const SlicedGeom g = sliced_geom(ctx, plan, n_rows, form_rows);
+    h_out4[0] = g.ok ? 1 : 0;
+    h_out4[1] = g.grid;
+    h_out4[2] = g.rows_per_wg;
+    h_out4[3] = int32_t(g.lds);
+  });
+}
+
 int32_t rfm_fm_train_forms(const rfm_ctx* ctx, const rfm_fm_plan* plan, int64_t batch, int64_t n_iters,
                            int64_t call_iters, const int64_t* d_val_indptr, const int32_t* d_val_indices,
                            const double* d_val_values, int64_t n_val, int32_t want_train, int32_t want_val,

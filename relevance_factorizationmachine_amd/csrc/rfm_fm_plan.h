@@ -52,6 +52,7 @@ struct rfm_fm_plan {
   rfm::DevBuf sl_z;      // partial logits [iterations of a run][slices][rows]
   rfm::DevBuf sl_zf;     // ... of rfm_fm_plan_forward's rows
   std::vector<int32_t> h_hot_cols;  // host copy of hot_cols (rfm_fm_plan_hot_columns)
+  std::vector<int32_t> h_sl_cols;   // host copy of sl_cols (rfm_fm_plan_sliced_columns)
   // touched-row gradients (rfm_fm_grad_rows), allocated on first use: the gradient table
   // [G_V | g_w | g_w0] indexed by column, never cleared; touch[col] == touch_seq marks the
   // rows of the current step

@@ -422,6 +422,7 @@ rfm_fm_plan* build_plan(rfm_ctx* ctx, const int64_t* d_indptr, const int32_t* d_
       sl_rank.assign(nf, -1);
       for (size_t h = 0; h < sl_cols.size(); ++h) sl_rank[size_t(sl_cols[h])] = int32_t(h);
       plan->sl_n_cached = int32_t(sl_cols.size());
+      plan->h_sl_cols = sl_cols;
       if (sl_cols.empty())
         plan->sl_cols.alloc(4);
       else
@@ -597,6 +598,15 @@ int32_t rfm_fm_plan_hot_columns(const rfm_fm_plan* plan, int32_t* h_out, int32_t
     RFM_REQUIRE(plan && (h_out || capacity == 0), "null pointer");
     RFM_REQUIRE(capacity >= plan->n_hot, "capacity %d < %d hot columns", capacity, plan->n_hot);
     std::copy(plan->h_hot_cols.begin(), plan->h_hot_cols.end(), h_out);
+  });
+}
+
+int32_t rfm_fm_plan_sliced_columns(const rfm_fm_plan* plan, int32_t* h_out, int32_t capacity) {
+  return guarded([&] {
+    RFM_REQUIRE(plan && (h_out || capacity == 0), "null pointer");
+    const int32_t n = int32_t(plan->h_sl_cols.size());
+    RFM_REQUIRE(capacity >= n, "capacity %d < %d cached columns", capacity, n);
+    std::copy(plan->h_sl_cols.begin(), plan->h_sl_cols.end(), h_out);
   });
 }
 

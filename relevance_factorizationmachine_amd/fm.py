@@ -123,6 +123,20 @@ class FmPlan:
         _lib.check(self.rt.lib.rfm_fm_plan_hot_columns(self.handle, out.ctypes.data, out.shape[0]))
         return out[: self.info()["hot_columns"]]
 
+    def sliced_columns(self) -> np.ndarray:
+        """The columns a sliced forward's workgroup keeps in LDS, in their LDS order."""
+        n = self.sliced()["cached_columns"]
+        out = np.zeros(max(n, 1), dtype=np.int32)
+        _lib.check(self.rt.lib.rfm_fm_plan_sliced_columns(self.handle, out.ctypes.data, out.shape[0]))
+        return out[:n]
+
+    def sliced_geometry(self, n_rows: int, form_rows: int = -1) -> dict:
+        """The launch a sliced forward of ``n_rows`` rows takes (``rfm_fm_sliced_geometry``)."""
+        out = np.zeros(4, dtype=np.int32)
+        _lib.check(self.rt.lib.rfm_fm_sliced_geometry(self.rt.ctx, self.handle, int(n_rows), int(form_rows),
+                                                      out.ctypes.data))
+        return dict(zip(("sliced", "workgroups", "rows_per_workgroup", "lds_bytes"), (int(v) for v in out)))
+
     def close(self) -> None:
         if self.handle is not None:
             self.rt.lib.rfm_fm_plan_destroy(self.handle)

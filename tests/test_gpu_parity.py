@@ -1024,7 +1024,7 @@ def test_sliced_loss_forward_gives_the_same_losses(rfm, monkeypatch, k, n_cols, 
     """The loss forwards of fit() sliced by factors (rfm_fm_sliced.hpp: every even k > 128, taken when
     the batch and the validation log together have enough rows; RFM_SLICED_MIN_ROWS=1 forces it,
     RFM_SLICED_LOSS=0 forbids it): same parameters bit for bit, loss curves equal to the plain
-    forwards' up to the order of the sums, both against the oracle.  Slices of 2, 4 and 8 pieces with a
+    forwards' up to the order of the sums, both against the oracle.  Slices of 1, 2 and 4 pieces with a
     narrower last slice; staged rows of 16 / 32 / 64 entries; validation rows LONGER than the staging
     stride derived from the training log (read straight from the log), empty rows, rows of cached
     columns only and of uncached columns only; twice in a row (the second fit finds a warm plan)."""
