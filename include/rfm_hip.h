@@ -546,6 +546,12 @@ int32_t rfm_mf_sgd_levels_ex(rfm_ctx* ctx, const void* d_ex, const int32_t* h_le
                              double* d_Q, double* d_bu, double* d_bi, double b,
                              int32_t n_factors, double lr, double reg);
 
+/* ---- MF: several models on one schedule --------------------------------------------
+ * rfm_mf_schedule_rows, rfm_mf_sgd_levels_many, rfm_mf_predict_many, rfm_mf_predict_loss_many and
+ * rfm_mf_many_geometry: semantics and declarations in rfm_mf_many.h (a part of this ABI in a file of
+ * its own, with a ctypes table of its own: _lib.MF_MANY_SIGNATURES). */
+#include "rfm_mf_many.h"
+
 /* ---- MF fold-in: new rows of one side against the fixed other side ----------------
  * The per-example update of src/mf.py:99-108 with _update_P / _update_b_u (src/mf.py:172-216)
  * restricted to ONE side: new row r has factors x_r = d_rows[r][0..k) and bias c_r = d_bias[r]

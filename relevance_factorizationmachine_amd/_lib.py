@@ -20,9 +20,10 @@ LIB_PATH = os.environ.get("RFM_LIB_PATH") or os.path.join(PKG_DIR, "librfm_hip.s
 SOURCES = ["rfm_capi.hip", "rfm_fm.hip", "rfm_fm_plan.hip", "rfm_mf.hip", "rfm_fm_fold.hip", "rfm_eval.hip", "rfm_csr.hip", "rfm_sample.hip", "rfm_pairs.hip", "rfm_host.cpp", "rfm_comm.cpp"]
 # every header under csrc/ (a change of any of them rebuilds every object) + the C ABI
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp"))) + [
-    os.path.join(os.path.dirname(PKG_DIR), "include", "rfm_hip.h")]
+    os.path.join(os.path.dirname(PKG_DIR), "include", h) for h in ("rfm_hip.h", "rfm_mf_many.h")]
 
 RFM_OK, RFM_ERR_BAD_ARG, RFM_ERR_HIP, RFM_ERR_NO_DEVICE, RFM_ERR_INTERNAL = range(5)
+MF_MAX_MODELS = 1024  # RFM_MF_MAX_MODELS of include/rfm_mf_many.h
 
 
 class RfmError(RuntimeError):
@@ -198,6 +199,16 @@ SIGNATURES = {
     "rfm_pair_order": _PAIR + [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
 }
 
+# several MF models on one schedule, the part of the ABI that include/rfm_mf_many.h declares
+# (tests/test_mf_many_host.py compares the two, argument by argument)
+MF_MANY_SIGNATURES = {
+    "rfm_mf_schedule_rows": [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, C.POINTER(_i32), _vp,
+                             C.POINTER(_i32)],
+    "rfm_mf_sgd_levels_many": [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32],
+    "rfm_mf_predict_many": [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _i64],
+    "rfm_mf_predict_loss_many": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _f64, _vp, _i64, _vp, _i64],
+    "rfm_mf_many_geometry": [_vp, _i32, _i32, _i64, _vp],
+}
 
 # ``rfm_transport`` of include/rfm_hip.h: the collectives of rfm_fm_fit_dp as caller functions
 TRANSPORT_ALL_GATHER = C.CFUNCTYPE(_i32, _vp, _vp, _vp, _i64)
@@ -209,6 +220,19 @@ TRANSPORT_ALL_TO_ALL = C.CFUNCTYPE(_i32, _vp, _vp, C.POINTER(_i64), C.POINTER(_i
 class Transport(C.Structure):
     _fields_ = [("user", _vp), ("n_ranks", _i32), ("rank", _i32), ("all_gather", TRANSPORT_ALL_GATHER),
                 ("all_reduce_sum", TRANSPORT_ALL_REDUCE), ("all_to_all", TRANSPORT_ALL_TO_ALL)]
+
+
+class MfModel(C.Structure):
+    """``rfm_mf_model`` of include/rfm_hip.h."""
+
+    _fields_ = [("P", _vp), ("Q", _vp), ("bu", _vp), ("bi", _vp), ("ry", _vp), ("b", _f64), ("lr", _f64),
+                ("reg", _f64)]
+
+
+class MfLabels(C.Structure):
+    """``rfm_mf_labels`` of include/rfm_hip.h."""
+
+    _fields_ = [("y", _vp), ("pscore", _vp)]
 
 
 class CsrSegment(C.Structure):
@@ -252,7 +276,7 @@ def load():
         lib = C.CDLL(path)
     except OSError as exc:
         raise RfmError(f"cannot load {path}: {exc}") from exc
-    for name, argtypes in SIGNATURES.items():
+    for name, argtypes in {**SIGNATURES, **MF_MANY_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError = header/library mismatch
         fn.argtypes = argtypes
         fn.restype = _i32

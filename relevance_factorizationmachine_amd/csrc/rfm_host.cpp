@@ -2,6 +2,7 @@
 // and the order-preserving MF schedule.  No device code here.
 #include <algorithm>
 #include <atomic>
+#include <limits>
 #include <thread>
 
 #include "rfm_common.h"
@@ -197,6 +198,49 @@ static void mf_level_pass(const int32_t* h_users, const int32_t* h_items, int64_
   *h_n_levels = n_levels;
 }
 
+// the level-ordered record of rfm_mf.hip (MfEx)
+struct HostMfEx {
+  int32_t u, i, cslot, gap;
+  double ry;
+};
+
+// The records of both record-form schedulers from the level pass: the cache-slot rule, then the
+// examples in level order.  `ry_of(s)` is the label / propensity of batch position s and
+// `placed(s, dst)` tells the caller where position s went.
+template <class Ry, class Placed>
+static auto mf_ex_records(const int32_t* h_users, const int32_t* h_items, int64_t batch, int32_t cache_cap,
+                          void* h_ex, int32_t* h_cache_items, int32_t* h_n_cached, Ry ry_of, Placed placed) {
+  return [=](const MfLevelPass& lp) {
+    std::vector<int32_t>&cnt_i = lp.cnt_i, &slot_i = lp.slot_i;
+    // items that occur more than once, most frequent first, get the LDS slots
+    std::vector<int32_t> repeated;
+    for (int64_t s = 0; s < batch; ++s) {
+      const int32_t i = h_items[s];
+      if (cnt_i[i] >= 2 && slot_i[i] == -1) {
+        slot_i[i] = -2;  // seen
+        repeated.push_back(i);
+      }
+    }
+    std::stable_sort(repeated.begin(), repeated.end(),
+                     [&](int32_t x, int32_t y) { return cnt_i[x] > cnt_i[y]; });
+    const int32_t n_cached = int32_t(std::min<size_t>(repeated.size(), size_t(cache_cap)));
+    for (int32_t c = 0; c < n_cached; ++c) {
+      slot_i[repeated[size_t(c)]] = c;
+      h_cache_items[c] = repeated[size_t(c)];
+    }
+    // level-ordered records
+    HostMfEx* ex = static_cast<HostMfEx*>(h_ex);
+    for (int64_t s = 0; s < batch; ++s) {
+      const int32_t i = h_items[s];
+      const int32_t cs = cnt_i[i] >= 2 ? slot_i[i] : -1;  // -2: repeated, no slot
+      const int32_t dst = lp.dst[size_t(s)];
+      ex[dst] = HostMfEx{h_users[s], i, cs, lp.gap[size_t(s)], ry_of(s)};
+      placed(s, dst);
+    }
+    *h_n_cached = n_cached;
+  };
+}
+
 }  // namespace rfm
 
 using namespace rfm;
@@ -259,12 +303,6 @@ int32_t rfm_mf_schedule(const int32_t* h_users, const int32_t* h_items, int64_t 
   });
 }
 
-// the level-ordered record of rfm_mf.hip (MfEx)
-struct HostMfEx {
-  int32_t u, i, cslot, gap;
-  double ry;
-};
-
 int32_t rfm_mf_schedule_ex(const int32_t* h_users, const int32_t* h_items, const double* h_y,
                            const double* h_pscore, int64_t batch, int32_t n_users,
                            int32_t n_items, int32_t cache_cap, void* h_ex,
@@ -275,34 +313,28 @@ int32_t rfm_mf_schedule_ex(const int32_t* h_users, const int32_t* h_items, const
                     h_cache_items && h_n_cached,
                 "null pointer");
     RFM_REQUIRE(batch >= 0 && batch < (int64_t(1) << 31) && cache_cap >= 0, "bad shape");
-    const auto records = [&](const MfLevelPass& lp) {
-      std::vector<int32_t>&cnt_i = lp.cnt_i, &slot_i = lp.slot_i;
-      // items that occur more than once, most frequent first, get the LDS slots
-      std::vector<int32_t> repeated;
-      for (int64_t s = 0; s < batch; ++s) {
-        const int32_t i = h_items[s];
-        if (cnt_i[i] >= 2 && slot_i[i] == -1) {
-          slot_i[i] = -2;  // seen
-          repeated.push_back(i);
-        }
-      }
-      std::stable_sort(repeated.begin(), repeated.end(),
-                       [&](int32_t x, int32_t y) { return cnt_i[x] > cnt_i[y]; });
-      const int32_t n_cached = int32_t(std::min<size_t>(repeated.size(), size_t(cache_cap)));
-      for (int32_t c = 0; c < n_cached; ++c) {
-        slot_i[repeated[size_t(c)]] = c;
-        h_cache_items[c] = repeated[size_t(c)];
-      }
-      // level-ordered records
-      HostMfEx* ex = static_cast<HostMfEx*>(h_ex);
-      for (int64_t s = 0; s < batch; ++s) {
-        const int32_t i = h_items[s];
-        const int32_t cs = cnt_i[i] >= 2 ? slot_i[i] : -1;  // -2: repeated, no slot
-        ex[lp.dst[size_t(s)]] = HostMfEx{h_users[s], i, cs, lp.gap[size_t(s)], h_y[s] / h_pscore[s]};
-      }
-      *h_n_cached = n_cached;
-    };
-    mf_level_pass(h_users, h_items, batch, n_users, n_items, true, h_level_ptr, h_n_levels, records);
+    mf_level_pass(h_users, h_items, batch, n_users, n_items, true, h_level_ptr, h_n_levels,
+                  mf_ex_records(h_users, h_items, batch, cache_cap, h_ex, h_cache_items, h_n_cached,
+                                [=](int64_t s) { return h_y[s] / h_pscore[s]; }, [](int64_t, int32_t) {}));
+  });
+}
+
+int32_t rfm_mf_schedule_rows(const int32_t* h_users, const int32_t* h_items, const int32_t* h_rows,
+                             int64_t batch, int32_t n_users, int32_t n_items, int32_t cache_cap,
+                             void* h_ex, int32_t* h_ex_rows, int32_t* h_level_ptr,
+                             int32_t* h_n_levels, int32_t* h_cache_items, int32_t* h_n_cached) {
+  return guarded([&] {
+    RFM_REQUIRE(h_users && h_items && h_rows && h_ex && h_ex_rows && h_level_ptr && h_n_levels &&
+                    h_cache_items && h_n_cached,
+                "null pointer");
+    RFM_REQUIRE(batch >= 0 && batch < (int64_t(1) << 31) && cache_cap >= 0, "bad shape");
+    // no model's label / propensity belongs in a shared record: a quiet NaN until the kernel puts
+    // the model's own value there
+    const double no_ry = std::numeric_limits<double>::quiet_NaN();
+    mf_level_pass(h_users, h_items, batch, n_users, n_items, true, h_level_ptr, h_n_levels,
+                  mf_ex_records(h_users, h_items, batch, cache_cap, h_ex, h_cache_items, h_n_cached,
+                                [=](int64_t) { return no_ry; },
+                                [=](int64_t s, int32_t dst) { h_ex_rows[dst] = h_rows[s]; }));
   });
 }
 

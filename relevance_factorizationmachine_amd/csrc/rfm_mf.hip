@@ -20,11 +20,18 @@
 // host walk over the level pointers (mf_walk_levels) and fill the model's
 // fields of their argument blocks in one place (set_model).
 //
+// Several models on one schedule (rfm_mf_sgd_levels_many, rfm_mf_predict_many / _loss_many): models
+// fitted on one log with one batch size share the schedule, so the record form's kernels and the
+// scoring kernels exist a second time with a model dimension.  Their bodies are the single-model
+// kernels' (mf_seq_ex_body, mf_wide_ex_body, mf_predict_body, mf_loss_finish_body), run on an
+// argument block the workgroup fills from its model's row of a device table (rfm_mf_model).
+//
 // Fold-in (rfm_mf_fold_in, mf_fold_kernel) trains new rows of one side against the fixed
 // other side by the same update restricted to that side: independent chains, one lane group
 // per new row, no schedule.  What it shares with FM fold-in is in rfm_fold.hpp.
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 
 #include "rfm_common.h"
 #include "rfm_device_utils.hpp"
@@ -52,8 +59,9 @@ struct MfPredArgs {
   double eps;
 };
 
+// (the body of mf_predict_kernel and of mf_predict_many_kernel: blockIdx.x / gridDim.x walk the rows)
 template <int LPR, int VEC, int NC>
-__global__ __launch_bounds__(kMfBlock) void mf_predict_kernel(MfPredArgs a) {
+__device__ __forceinline__ void mf_predict_body(const MfPredArgs& a) {
   constexpr int GPB = kMfBlock / LPR;
   __shared__ double lds[kMfBlock];
   const int tid = threadIdx.x;
@@ -110,9 +118,13 @@ __global__ __launch_bounds__(kMfBlock) void mf_predict_kernel(MfPredArgs a) {
   }
 }
 
-__global__ __launch_bounds__(kMfBlock) void mf_loss_finish_kernel(const double* partial,
-                                                                 int n_partial, int64_t n_rows,
-                                                                 double* out) {
+template <int LPR, int VEC, int NC>
+__global__ __launch_bounds__(kMfBlock) void mf_predict_kernel(MfPredArgs a) {
+  mf_predict_body<LPR, VEC, NC>(a);
+}
+
+__device__ __forceinline__ void mf_loss_finish_body(const double* partial, int n_partial,
+                                                    int64_t n_rows, double* out) {
   __shared__ double lds[kMfBlock];
   double acc = 0.0;
   for (int i = threadIdx.x; i < n_partial; i += kMfBlock) acc += partial[i];
@@ -124,6 +136,58 @@ __global__ __launch_bounds__(kMfBlock) void mf_loss_finish_kernel(const double* 
     __syncthreads();
   }
   if (threadIdx.x == 0) out[0] = -lds[0] / double(n_rows);
+}
+
+__global__ __launch_bounds__(kMfBlock) void mf_loss_finish_kernel(const double* partial,
+                                                                 int n_partial, int64_t n_rows,
+                                                                 double* out) {
+  mf_loss_finish_body(partial, n_partial, n_rows, out);
+}
+
+// ---- several models on one log (rfm_mf_predict_many, rfm_mf_predict_loss_many): blockIdx.y is
+// the model, blockIdx.x walks the rows as in the single-model launch, so a model's scores and the
+// order of its partial sums are those of rfm_mf_predict / rfm_mf_predict_loss
+struct MfPredManyArgs {
+  const int32_t* users;
+  const int32_t* items;
+  const int32_t* row_ids;  // nullable
+  int64_t n_rows;
+  const rfm_mf_model* models;
+  const rfm_mf_labels* labels;  // nullable (scores only)
+  int32_t k;
+  double eps;
+  double* const* out_base;  // nullable: model m's scores go to out_base[m] + out_offset
+  int64_t out_offset;
+  double* loss_partial;  // nullable: [model][block]
+};
+
+template <int LPR, int VEC, int NC>
+__global__ __launch_bounds__(kMfBlock) void mf_predict_many_kernel(MfPredManyArgs m) {
+  const rfm_mf_model mod = m.models[blockIdx.y];
+  MfPredArgs a;
+  a.users = m.users;
+  a.items = m.items;
+  a.row_ids = m.row_ids;
+  a.n_rows = m.n_rows;
+  a.P = mod.P;
+  a.Q = mod.Q;
+  a.bu = mod.bu;
+  a.bi = mod.bi;
+  a.b = mod.b;
+  a.k = m.k;
+  a.y = m.labels ? m.labels[blockIdx.y].y : nullptr;
+  a.pscore = m.labels ? m.labels[blockIdx.y].pscore : nullptr;
+  a.out_pred = m.out_base ? m.out_base[blockIdx.y] + m.out_offset : nullptr;
+  a.loss_partial = m.loss_partial ? m.loss_partial + int64_t(blockIdx.y) * gridDim.x : nullptr;
+  a.eps = m.eps;
+  mf_predict_body<LPR, VEC, NC>(a);
+}
+
+__global__ __launch_bounds__(kMfBlock) void mf_loss_finish_many_kernel(const double* partial,
+                                                                      int n_partial, int64_t n_rows,
+                                                                      double* out, int64_t out_stride) {
+  mf_loss_finish_body(partial + int64_t(blockIdx.x) * n_partial, n_partial, n_rows,
+                      out + int64_t(blockIdx.x) * out_stride);
 }
 
 // the arithmetic of one example on rows already in registers (src/mf.py:99-108,
@@ -265,9 +329,23 @@ struct MfExArgs {
   double lr, reg;
 };
 
-// one level, many workgroups (examples of a level touch disjoint rows)
-template <int LPR, int VEC, int NC>
-__global__ __launch_bounds__(kMfBlock) void mf_sgd_wide_ex_kernel(MfExArgs a) {
+// where a record's label / propensity comes from: the record itself (one model), or the model's
+// own vector over the training log through the record's row (several models on one schedule)
+struct RyOfRecord {
+  static constexpr bool kInRecord = true;
+  __device__ __forceinline__ double operator()(int32_t, double ry) const { return ry; }
+};
+struct RyOfModel {
+  static constexpr bool kInRecord = false;
+  const double* ry;         // [rows of the training log]
+  const int32_t* ex_rows;   // [batch] training-log row of each record, level order
+  __device__ __forceinline__ double operator()(int32_t rec, double) const { return ry[ex_rows[rec]]; }
+};
+
+// one level, many workgroups (examples of a level touch disjoint rows); blockIdx.x / gridDim.x
+// walk the level
+template <int LPR, int VEC, int NC, class Ry>
+__device__ __forceinline__ void mf_wide_ex_body(const MfExArgs& a, Ry ry_of) {
   constexpr int GPB = kMfBlock / LPR;
   const int l = threadIdx.x % LPR;
   const int g = threadIdx.x / LPR;
@@ -279,7 +357,7 @@ __global__ __launch_bounds__(kMfBlock) void mf_sgd_wide_ex_kernel(MfExArgs a) {
     mf_load_row<LPR, VEC, NC>(pp, a.P + int64_t(e.u) * k, k, l);
     mf_load_row<LPR, VEC, NC>(pq, a.Q + int64_t(e.i) * k, k, l);
     double bu = a.bu[e.u], bi = a.bi[e.i];
-    mf_update<LPR, VEC, NC>(pp, pq, bu, bi, e.ry, a.b, a.lr, a.reg, k, l);
+    mf_update<LPR, VEC, NC>(pp, pq, bu, bi, ry_of(int32_t(idx), e.ry), a.b, a.lr, a.reg, k, l);
     mf_store_row<LPR, VEC, NC>(pp, a.P + int64_t(e.u) * k, k, l);
     mf_store_row<LPR, VEC, NC>(pq, a.Q + int64_t(e.i) * k, k, l);
     if (l == 0) {
@@ -287,6 +365,54 @@ __global__ __launch_bounds__(kMfBlock) void mf_sgd_wide_ex_kernel(MfExArgs a) {
       a.bi[e.i] = bi;
     }
   }
+}
+
+template <int LPR, int VEC, int NC>
+__global__ __launch_bounds__(kMfBlock) void mf_sgd_wide_ex_kernel(MfExArgs a) {
+  mf_wide_ex_body<LPR, VEC, NC>(a, RyOfRecord{});
+}
+
+// Several models on one schedule (rfm_mf_sgd_levels_many): the records, level pointers and cached
+// items are shared, the parameters, lr, reg, b and the label / propensity vector are the model's.
+// A workgroup builds its own MfExArgs from its model's row of the table and runs the bodies above.
+struct MfManyArgs {
+  const MfEx* ex;
+  const int32_t* ex_rows;    // [batch] training-log row of each record
+  const int32_t* level_ptr;
+  int32_t lo, hi;
+  int32_t rec_lo, rec_hi;
+  const int32_t* cache_items;
+  int32_t n_cached;
+  const rfm_mf_model* models;
+  int32_t k;
+};
+
+__device__ __forceinline__ MfExArgs mf_model_args(const MfManyArgs& m, const rfm_mf_model& mod) {
+  MfExArgs a;
+  a.ex = m.ex;
+  a.level_ptr = m.level_ptr;
+  a.lo = m.lo;
+  a.hi = m.hi;
+  a.rec_lo = m.rec_lo;
+  a.rec_hi = m.rec_hi;
+  a.cache_items = m.cache_items;
+  a.n_cached = m.n_cached;
+  a.P = mod.P;
+  a.Q = mod.Q;
+  a.bu = mod.bu;
+  a.bi = mod.bi;
+  a.b = mod.b;
+  a.k = m.k;
+  a.lr = mod.lr;
+  a.reg = mod.reg;
+  return a;
+}
+
+// one level of every model: blockIdx.y is the model
+template <int LPR, int VEC, int NC>
+__global__ __launch_bounds__(kMfBlock) void mf_sgd_wide_many_kernel(MfManyArgs m) {
+  const rfm_mf_model mod = m.models[blockIdx.y];
+  mf_wide_ex_body<LPR, VEC, NC>(mf_model_args(m, mod), RyOfModel{mod.ry, m.ex_rows});
 }
 
 // ---------------------------------------------------------------------------
@@ -404,8 +530,8 @@ __device__ __forceinline__ void mf_slot_run(const MfExArgs& a, const MfSeqLds& m
 // groups then, and more than four chunks run without the ring)
 constexpr int seq_block(int nc) { return nc > 1 ? 512 : kSeqBlock; }
 
-template <int LPR, int VEC, int NC>
-__global__ __launch_bounds__(seq_block(NC)) void mf_sgd_seq_ex_kernel(MfExArgs a) {
+template <int LPR, int VEC, int NC, class Ry>
+__device__ __forceinline__ void mf_seq_ex_body(const MfExArgs& a, Ry ry_of) {
   extern __shared__ double seq_lds[];
   constexpr int kSeqBlock = seq_block(NC);  // (shadows the one-chunk constant inside this kernel)
   // rows wider than four chunks per lane leave no registers for a ring of them
@@ -423,7 +549,13 @@ __global__ __launch_bounds__(seq_block(NC)) void mf_sgd_seq_ex_kernel(MfExArgs a
   {
     const double* src = reinterpret_cast<const double*>(a.ex + a.rec_lo);
     double* dst = reinterpret_cast<double*>(exs);
-    for (int i = threadIdx.x; i < n_rec * int(sizeof(MfEx) / 8); i += kSeqBlock) dst[i] = src[i];
+    // (a record is three doubles, the third its label / propensity: where that comes from the
+    // model's vector, it is fetched first -- two dependent loads -- and the copy leaves it alone)
+    static_assert(sizeof(MfEx) == 24 && offsetof(MfEx, ry) == 16, "MfEx layout");
+    if (!Ry::kInRecord)
+      for (int r = threadIdx.x; r < n_rec; r += kSeqBlock) dst[3 * r + 2] = ry_of(a.rec_lo + r, 0.0);
+    for (int i = threadIdx.x; i < n_rec * 3; i += kSeqBlock)
+      if (Ry::kInRecord || i % 3 != 2) dst[i] = src[i];
   }
   for (int i = threadIdx.x; i < a.n_cached * cw; i += kSeqBlock) {
     const int c = i / cw, f = i % cw;
@@ -471,13 +603,32 @@ __global__ __launch_bounds__(seq_block(NC)) void mf_sgd_seq_ex_kernel(MfExArgs a
   }
 }
 
-// the sequential kernel with its dynamic-LDS limit raised where the item cache needs it
+template <int LPR, int VEC, int NC>
+__global__ __launch_bounds__(seq_block(NC)) void mf_sgd_seq_ex_kernel(MfExArgs a) {
+  mf_seq_ex_body<LPR, VEC, NC>(a, RyOfRecord{});
+}
+
+// the chain of every model, ONE sequential workgroup each: blockIdx.x is the model
+template <int LPR, int VEC, int NC>
+__global__ __launch_bounds__(seq_block(NC)) void mf_sgd_seq_many_kernel(MfManyArgs m) {
+  const rfm_mf_model mod = m.models[blockIdx.x];
+  mf_seq_ex_body<LPR, VEC, NC>(mf_model_args(m, mod), RyOfModel{mod.ry, m.ex_rows});
+}
+
+// the sequential kernels with their dynamic-LDS limit raised where the item cache needs it
 template <int L, int Vv, int N>
 static void launch_seq_ex(rfm_ctx* ctx, const MfExArgs& a, int threads, size_t lds) {
   const auto kern = &mf_sgd_seq_ex_kernel<L, Vv, N>;
   static LdsLimits allowed;
   allow_dynamic_lds(ctx, reinterpret_cast<const void*>(kern), lds, allowed);
   hipLaunchKernelGGL(kern, dim3(1), dim3(threads), lds, ctx->stream, a);
+}
+template <int L, int Vv, int N>
+static void launch_seq_many(rfm_ctx* ctx, const MfManyArgs& m, int n_models, int threads, size_t lds) {
+  const auto kern = &mf_sgd_seq_many_kernel<L, Vv, N>;
+  static LdsLimits allowed;
+  allow_dynamic_lds(ctx, reinterpret_cast<const void*>(kern), lds, allowed);
+  hipLaunchKernelGGL(kern, dim3(n_models), dim3(threads), lds, ctx->stream, m);
 }
 
 // the model's fields of a kernel argument block (MfPredArgs, MfSgdArgs, MfExArgs)
@@ -536,6 +687,52 @@ static int32_t mf_predict(rfm_ctx* ctx, const int32_t* d_users, const int32_t* d
     if (want_loss)
       hipLaunchKernelGGL(mf_loss_finish_kernel, dim3(1), dim3(kMfBlock), 0, ctx->stream,
                          a.loss_partial, grid, n_rows, d_out_loss);
+    RFM_HIP_CHECK(hipGetLastError());
+  });
+}
+
+// rfm_mf_predict_many and, with want_loss, rfm_mf_predict_loss_many: the grid of mf_predict over
+// the rows, times the models
+static int32_t mf_predict_many(rfm_ctx* ctx, const int32_t* d_users, const int32_t* d_items,
+                               const rfm_mf_labels* d_labels, const int32_t* d_row_ids, int64_t n_rows,
+                               const rfm_mf_model* d_models, int32_t n_models, int32_t n_factors,
+                               double eps, double* const* d_out_base, int64_t out_offset,
+                               double* d_out_loss, int64_t loss_stride, bool want_loss) {
+  return guarded([&] {
+    RFM_REQUIRE(ctx, "null ctx");
+    RFM_REQUIRE(n_models >= 1 && n_models <= RFM_MF_MAX_MODELS, "n_models=%d out of range (1..%d)",
+                n_models, RFM_MF_MAX_MODELS);
+    RFM_REQUIRE(n_rows >= (want_loss ? 1 : 0), "n_rows=%lld out of range", (long long)n_rows);
+    const Shape s = shape_for(n_factors);
+    if (n_rows == 0) return;
+    RFM_REQUIRE(d_users && d_items && d_models &&
+                    (want_loss ? d_labels && d_out_loss : d_out_base != nullptr),
+                "null pointer");
+    RFM_REQUIRE(out_offset >= 0 && (!want_loss || loss_stride >= 1), "bad output offsets");
+    MfPredManyArgs a{};
+    a.users = d_users;
+    a.items = d_items;
+    a.row_ids = d_row_ids;
+    a.n_rows = n_rows;
+    a.models = d_models;
+    a.labels = want_loss ? d_labels : nullptr;
+    a.k = n_factors;
+    a.eps = eps;
+    a.out_base = d_out_base;
+    a.out_offset = out_offset;
+    const int grid = capped_grid(ctx, n_rows, kMfBlock / s.lpr, 8, 1);
+    if (want_loss) {
+      ctx->loss_partials.ensure(size_t(n_models) * size_t(ctx->n_cu) * 8 * sizeof(double));
+      a.loss_partial = ctx->loss_partials.as<double>();
+    }
+#define RFM_CALL_MFPM(L, Vv, N)                                                                   \
+  hipLaunchKernelGGL((mf_predict_many_kernel<L, Vv, N>), dim3(grid, n_models), dim3(kMfBlock), 0, \
+                     ctx->stream, a)
+    RFM_FOR_SHAPE(s, RFM_CALL_MFPM);
+#undef RFM_CALL_MFPM
+    if (want_loss)
+      hipLaunchKernelGGL(mf_loss_finish_many_kernel, dim3(n_models), dim3(kMfBlock), 0, ctx->stream,
+                         a.loss_partial, grid, n_rows, d_out_loss, loss_stride);
     RFM_HIP_CHECK(hipGetLastError());
   });
 }
@@ -866,6 +1063,94 @@ int32_t rfm_mf_sgd_levels_ex(rfm_ctx* ctx, const void* d_ex, const int32_t* h_le
 #undef RFM_CALL_SEQ_EX
         });
     RFM_HIP_CHECK(hipGetLastError());
+  });
+}
+
+int32_t rfm_mf_sgd_levels_many(rfm_ctx* ctx, const void* d_ex, const int32_t* d_ex_rows,
+                               const int32_t* h_level_ptr, const int32_t* d_level_ptr,
+                               int32_t n_levels, const int32_t* d_cache_items, int32_t n_cached,
+                               const rfm_mf_model* d_models, int32_t n_models, int32_t n_factors) {
+  return guarded([&] {
+    RFM_REQUIRE(ctx && d_ex && d_ex_rows && h_level_ptr && d_level_ptr && d_models, "null pointer");
+    RFM_REQUIRE(n_models >= 1 && n_models <= RFM_MF_MAX_MODELS, "n_models=%d out of range (1..%d)",
+                n_models, RFM_MF_MAX_MODELS);
+    RFM_REQUIRE(n_levels >= 0 && n_cached >= 0 && (n_cached == 0 || d_cache_items),
+                "bad schedule");
+    const Shape s = shape_for(n_factors);
+    const size_t cache_bytes = size_t(n_cached) * size_t(n_factors + 2) * sizeof(double);
+    RFM_REQUIRE(cache_bytes <= size_t(kSeqMaxCacheBytes),
+                "item cache of %d rows exceeds %d bytes of LDS", n_cached, kSeqMaxCacheBytes);
+    MfManyArgs m{};
+    m.ex = static_cast<const MfEx*>(d_ex);
+    m.ex_rows = d_ex_rows;
+    m.level_ptr = d_level_ptr;
+    m.cache_items = d_cache_items;
+    m.n_cached = n_cached;
+    m.models = d_models;
+    m.k = n_factors;
+    // the launch plan of rfm_mf_sgd_levels_ex, each launch with a model dimension
+    const int seq_threads = seq_block(s.nc);
+    mf_walk_levels(
+        h_level_ptr, n_levels, seq_threads / s.lpr, kSeqMaxLevels, kSeqMaxRecs,
+        [&](int32_t rec_lo, int32_t rec_hi) {
+          m.lo = rec_lo;
+          m.hi = rec_hi;
+          const int grid = capped_grid(ctx, rec_hi - rec_lo, kMfBlock / s.lpr, 8, 0);
+#define RFM_CALL_WIDE_MANY(L, Vv, N)                                                              \
+  hipLaunchKernelGGL((mf_sgd_wide_many_kernel<L, Vv, N>), dim3(grid, n_models), dim3(kMfBlock), 0, \
+                     ctx->stream, m)
+          RFM_FOR_SHAPE(s, RFM_CALL_WIDE_MANY);
+#undef RFM_CALL_WIDE_MANY
+        },
+        [&](int32_t lev_lo, int32_t lev_hi) {
+          m.lo = lev_lo;
+          m.hi = lev_hi;
+          m.rec_lo = h_level_ptr[lev_lo];
+          m.rec_hi = h_level_ptr[lev_hi];
+          const size_t lds = size_t((lev_hi - lev_lo + 2) / 2) * 8 +
+                             size_t(m.rec_hi - m.rec_lo) * sizeof(MfEx) + cache_bytes;
+#define RFM_CALL_SEQ_MANY(L, Vv, N) launch_seq_many<L, Vv, N>(ctx, m, n_models, seq_threads, lds)
+          RFM_FOR_SHAPE(s, RFM_CALL_SEQ_MANY);
+#undef RFM_CALL_SEQ_MANY
+        });
+    RFM_HIP_CHECK(hipGetLastError());
+  });
+}
+
+int32_t rfm_mf_predict_many(rfm_ctx* ctx, const int32_t* d_users, const int32_t* d_items,
+                            const int32_t* d_row_ids, int64_t n_rows, const rfm_mf_model* d_models,
+                            int32_t n_models, int32_t n_factors, double* const* d_out_base,
+                            int64_t out_offset) {
+  return mf_predict_many(ctx, d_users, d_items, nullptr, d_row_ids, n_rows, d_models, n_models,
+                         n_factors, 0.0, d_out_base, out_offset, nullptr, 0, false);
+}
+
+int32_t rfm_mf_predict_loss_many(rfm_ctx* ctx, const int32_t* d_users, const int32_t* d_items,
+                                 const rfm_mf_labels* d_labels, const int32_t* d_row_ids,
+                                 int64_t n_rows, const rfm_mf_model* d_models, int32_t n_models,
+                                 int32_t n_factors, double eps, double* const* d_out_base,
+                                 int64_t out_offset, double* d_out_loss, int64_t loss_stride) {
+  return mf_predict_many(ctx, d_users, d_items, d_labels, d_row_ids, n_rows, d_models, n_models,
+                         n_factors, eps, d_out_base, out_offset, d_out_loss, loss_stride, true);
+}
+
+int32_t rfm_mf_many_geometry(const rfm_ctx* ctx, int32_t n_models, int32_t n_factors, int64_t n_recs,
+                             int32_t* h_out7) {
+  return guarded([&] {
+    RFM_REQUIRE(h_out7, "null pointer");
+    RFM_REQUIRE(n_models >= 1 && n_models <= RFM_MF_MAX_MODELS, "n_models=%d out of range (1..%d)",
+                n_models, RFM_MF_MAX_MODELS);
+    RFM_REQUIRE(n_recs >= 0 && n_recs < (int64_t(1) << 31), "n_recs=%lld out of range", (long long)n_recs);
+    const Shape s = shape_for(n_factors);
+    const rfm_ctx assumed{};  // (the CU count of an MI355X)
+    const rfm_ctx* c = ctx ? ctx : &assumed;
+    h_out7[0] = seq_block(s.nc);
+    h_out7[1] = s.lpr;
+    h_out7[2] = n_models;
+    h_out7[3] = capped_grid(c, n_recs, kMfBlock / s.lpr, 8, 0);
+    h_out7[4] = n_models;
+    h_out7[5] = capped_grid(c, n_recs, kMfBlock / s.lpr, 8, 1);
+    h_out7[6] = n_models;
   });
 }
 

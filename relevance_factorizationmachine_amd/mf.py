@@ -5,7 +5,8 @@ The reference updates a batch strictly example by example
 (``src/mf.py:97-108``).  That order is kept exactly: the host derives, per
 batch, the level schedule (``rfm_mf_schedule``) under which every example runs
 after the latest earlier example sharing its user or item, and the device
-executes the levels in order (``csrc/rfm_mf.hip``).
+executes the levels in order (``csrc/rfm_mf.hip``).  ``fit_many`` runs several models that
+share a training log and batch size on one such schedule at once, one chain each.
 """
 from __future__ import annotations
 
@@ -18,7 +19,7 @@ from . import _lib, fold
 from .base import LOSS_EPS, PointwiseBaseRecommender
 from .evaluate import EvalLoop, FitHook, device_frame
 from .optimizer import DeviceSGD
-from .runtime import BatchIdStream, Runtime, mf_cache_capacity, mf_schedule_ex
+from .runtime import BatchIdStream, Runtime, mf_cache_capacity, mf_schedule_ex, mf_schedule_rows
 
 
 class _SchedulePipe:
@@ -28,11 +29,13 @@ class _SchedulePipe:
     buffers; the consumer enqueues one asynchronous copy per iteration into the matching
     device slot and launches.  A host slot is handed back to the producer only after the copy
     out of it has completed (an event), a device slot is reused ``DEPTH`` iterations later on
-    the same stream, i.e. after the kernels that read it."""
+    the same stream, i.e. after the kernels that read it.  ``with_rows``: the slot also carries
+    the training-log row of every record (``rfm_mf_schedule_rows``, a schedule several models
+    share)."""
 
     DEPTH = 8
 
-    def __init__(self, rt: Runtime, batch_size: int, cache_cap: int):
+    def __init__(self, rt: Runtime, batch_size: int, cache_cap: int, with_rows: bool = False):
         import queue
 
         import torch
@@ -41,7 +44,9 @@ class _SchedulePipe:
         self.ex_bytes = 24 * batch_size
         self.lptr_off = (self.ex_bytes + 15) // 16 * 16
         self.cache_off = (self.lptr_off + 4 * (batch_size + 1) + 15) // 16 * 16
-        self.total = self.cache_off + 4 * max(cache_cap, 1)
+        self.rows_off = (self.cache_off + 4 * max(cache_cap, 1) + 15) // 16 * 16
+        self.total = self.rows_off + (4 * batch_size if with_rows else 0)
+        self.with_rows = with_rows
         self.host = [torch.empty(self.total, dtype=torch.uint8, pin_memory=True) for _ in range(self.DEPTH)]
         self.dev = [rt.empty((self.total,), torch.uint8) for _ in range(self.DEPTH)]
         self.free: "queue.Queue" = queue.Queue()
@@ -51,8 +56,9 @@ class _SchedulePipe:
         self.torch = torch
 
     def produce(self, epochs, schedule_fn) -> None:
-        """Runs in the producer thread: ``schedule_fn(rows) -> (ex, level_ptr, cache_items)``
-        for every ``(epoch, rows, ids_ptr)`` of ``epochs``."""
+        """Runs in the producer thread: ``schedule_fn(rows) -> (ex, level_ptr, cache_items)`` (with
+        rows: ``(ex, ex_rows, level_ptr, cache_items)``) for every ``(epoch, rows, ids_ptr)`` of
+        ``epochs``."""
         try:
             for epoch, rows, ids_ptr in epochs:
                 slot, ev = self.free.get()
@@ -60,8 +66,10 @@ class _SchedulePipe:
                     return
                 if ev is not None:
                     ev.synchronize()  # the copy out of this host slot has completed
-                ex, level_ptr, cache_items = schedule_fn(rows)
+                ex, *ex_rows, level_ptr, cache_items = schedule_fn(rows)
                 h = self.host[slot].numpy()
+                if self.with_rows:
+                    h[self.rows_off: self.rows_off + 4 * len(ex_rows[0])] = ex_rows[0].view(np.uint8)
                 h[: self.ex_bytes] = ex.view(np.uint8)
                 h[self.lptr_off: self.lptr_off + 4 * len(level_ptr)] = level_ptr.view(np.uint8)
                 h[self.cache_off: self.cache_off + 4 * len(cache_items)] = cache_items.view(np.uint8)
@@ -78,8 +86,8 @@ class _SchedulePipe:
 
     def take(self):
         """Next iteration: enqueues the copy and returns ``(epoch, ids_ptr, device ex ptr, HOST
-        level_ptr ptr, device level_ptr ptr, n_levels, device cache ptr, n_cached, done)``;
-        call ``done()`` after the launches that read the slot have been enqueued."""
+        level_ptr ptr, device level_ptr ptr, n_levels, device cache ptr, n_cached, device ex_rows
+        ptr, done)``; call ``done()`` after the launches that read the slot have been enqueued."""
         item = self.ready.get()
         if item is None:
             return None
@@ -95,10 +103,30 @@ class _SchedulePipe:
             self.free.put((slot, ev))
 
         return (epoch, ids_ptr, base, hbase + self.lptr_off, base + self.lptr_off, n_levels,
-                base + self.cache_off, n_cached, done)
+                base + self.cache_off, n_cached, base + self.rows_off, done)
 
     def stop(self) -> None:
         self.free.put((None, None))
+
+    def run(self, epochs, schedule_fn, step) -> None:
+        """The exact-mode loop of ``fit()`` and ``fit_many()``: the level schedules of the coming
+        batches are derived and staged by a host thread while the GPU runs the batch before (the
+        GPU never waits for them); ``step(*take())`` enqueues one iteration."""
+        import threading
+
+        worker = threading.Thread(target=self.produce, args=(epochs, schedule_fn), name="rfm-mf-schedule",
+                                  daemon=True)
+        worker.start()
+        try:
+            while True:
+                got = self.take()
+                if got is None:
+                    break
+                step(*got)
+        finally:
+            self.stop()
+            self.rt.sync()
+            worker.join(timeout=5.0)
 
 
 class DevicePairs:
@@ -263,34 +291,21 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
                     float(self.reg)))
                 after_sgd(epoch, ids_ptr)
         else:
-            # exact mode: the level schedules of the coming batches are derived and staged by
-            # a host thread while the GPU runs the batch before (the GPU never waits for them)
-            import threading
-
+            # exact mode (_SchedulePipe.run)
             pipe = _SchedulePipe(rt, self.batch_size, cache_cap)
 
             def schedule(rows):
                 return mf_schedule_ex(tr.h_users[rows], tr.h_items[rows], h_y[rows], h_p[rows],
                                       self.n_users, self.n_items, cache_cap)
 
-            worker = threading.Thread(target=pipe.produce, args=(self._epochs(id_stream), schedule),
-                                      name="rfm-mf-schedule", daemon=True)
-            worker.start()
-            try:
-                while True:
-                    got = pipe.take()
-                    if got is None:
-                        break
-                    epoch, ids_ptr, d_ex, h_lptr, d_lptr, n_levels, d_cache, n_cached, done = got
-                    _lib.check(rt.lib.rfm_mf_sgd_levels_ex(
-                        rt.ctx, d_ex, h_lptr, d_lptr, n_levels, d_cache, n_cached, *params, b,
-                        self.n_factors, float(self.lr), float(self.reg)))
-                    done()
-                    after_sgd(epoch, ids_ptr)
-            finally:
-                pipe.stop()
-                rt.sync()
-                worker.join(timeout=5.0)
+            def step(epoch, ids_ptr, d_ex, h_lptr, d_lptr, n_levels, d_cache, n_cached, _d_rows, done):
+                _lib.check(rt.lib.rfm_mf_sgd_levels_ex(
+                    rt.ctx, d_ex, h_lptr, d_lptr, n_levels, d_cache, n_cached, *params, b,
+                    self.n_factors, float(self.lr), float(self.reg)))
+                done()
+                after_sgd(epoch, ids_ptr)
+
+            pipe.run(self._epochs(id_stream), schedule, step)
         rt.sync()
         self._keep_ids = []
         hook.finish()
@@ -415,3 +430,193 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
         from . import recommend as rec
 
         return rec.rank_catalogue(*rec.operands(self, new_users=new_users), depth, users, exclude)
+
+
+# ---------------------------------------------------------------------------
+# several models on one training log
+# ---------------------------------------------------------------------------
+_SHARED_FIELDS = ("n_users", "n_items", "n_factors", "batch_size", "n_epochs")
+
+
+def _one_per_model(split, n: int, name: str) -> list:
+    if isinstance(split, dict):
+        return [split] * n
+    split = list(split)
+    if len(split) != n:
+        raise ValueError(f"fit_many: {name} must be one dict or one per model ({len(split)} for {n} models)")
+    return split
+
+
+def _same_features(splits: list, name: str) -> None:
+    first = np.asarray(splits[0]["features"])
+    for s in splits[1:]:
+        if s is not splits[0] and not np.array_equal(first, np.asarray(s["features"])):
+            raise ValueError(f"fit_many: the models' {name} features differ (one schedule serves one log)")
+
+
+def _device_table(rt: Runtime, structs):
+    """A ctypes array of structs (or of pointers) as bytes on the device."""
+    return rt.upload(np.frombuffer(bytes(structs), dtype=np.uint8).copy())
+
+
+def fit_many(models, train, val) -> list:
+    """``model.fit(train, val)`` of every model of ``models`` at once, one chain each:
+    ``[(train_loss, val_loss), ...]`` in model order, and every model left exactly as its own
+    ``fit()`` leaves it (``b``, ``P``, ``Q``, ``b_u``, ``b_i``, ``val_metrics`` and the evaluator
+    counters), bit for bit.
+
+    ``train`` / ``val``: one dict shared by all, or a list with one per model.  The models must
+    agree in ``n_users``, ``n_items``, ``n_factors``, ``batch_size``, ``n_epochs`` and in the
+    ``features`` of both splits (and of their evaluators): they then draw the same batch ids in
+    every iteration (``resample(..., random_state=epoch)``, ``src/mf.py:88-95``) and share the level
+    schedule, which is derived and uploaded once per iteration (``rfm_mf_schedule_rows``,
+    ``rfm_mf_sgd_levels_many``).  They may differ in ``seed``, ``alpha``, ``lr``, ``reg``,
+    ``estimator``, labels, propensities and evaluator instance.  Exact mode only; an evaluator must
+    be one the device computes (``evaluate.recognise``) -- anything else is a ``ValueError``."""
+    from .evaluate import CatalogueValEvaluator, recognise
+
+    models = list(models)
+    n = len(models)
+    if n == 0:
+        return []
+    if n > _lib.MF_MAX_MODELS:
+        raise ValueError(f"fit_many: {n} models, at most {_lib.MF_MAX_MODELS} in one call")
+    if any(not isinstance(m, LogisticMatrixFactorization) for m in models):
+        raise TypeError("fit_many takes LogisticMatrixFactorization models")
+    if len({id(m) for m in models}) != n:
+        raise ValueError("fit_many: a model is listed twice")
+    trains, vals = _one_per_model(train, n, "train"), _one_per_model(val, n, "val")
+    m0 = models[0]
+    for name in _SHARED_FIELDS:
+        if any(getattr(m, name) != getattr(m0, name) for m in models):
+            raise ValueError(f"fit_many: the models differ in {name}")
+    if any(m.hogwild for m in models):
+        raise ValueError("fit_many: hogwild = True has no order to share; use fit()")
+    _same_features(trains, "train")
+    _same_features(vals, "val")
+    with_ev = [m.evaluator is not None for m in models]
+    if any(with_ev):
+        if not all(with_ev):
+            raise ValueError("fit_many: evaluator on some models only; give every model one or use fit()")
+        ev_X = np.asarray(m0.evaluator.features[m0.model_name])
+        for m in models:
+            ev = m.evaluator
+            if isinstance(ev, CatalogueValEvaluator):
+                raise ValueError("fit_many: a CatalogueValEvaluator evaluator is not served; use fit()")
+            if not m.device_evaluator:
+                raise ValueError("fit_many: device_evaluator = False (a host callback per iteration); use fit()")
+            got = recognise(ev, m.estimator)
+            X = np.asarray(ev.features[m.model_name])
+            if got is None or got[0].shape[0] != X.shape[0]:
+                raise ValueError("fit_many: an evaluator that is a host callback is not served; use fit()")
+            if ev is not m0.evaluator and not np.array_equal(ev_X, X):
+                raise ValueError("fit_many: the models' evaluator features differ")
+    for m, t in zip(models, trains):
+        m.b = np.mean(t["labels"])  # global bias: mean of the training labels (src/mf.py:84)
+    if m0.n_epochs <= 0:
+        return [([], []) for _ in models]
+    n_rows = int(np.asarray(trains[0]["features"]).shape[0])
+    id_stream = BatchIdStream(m0._rt, n_rows, m0.batch_size, m0.n_epochs)
+    try:
+        return _fit_many(models, trains, vals, id_stream)
+    finally:
+        id_stream.close()
+
+
+def _fit_many(models: list, trains: list, vals: list, id_stream: BatchIdStream) -> list:
+    import torch
+
+    m0, n = models[0], len(models)
+    rt, B, kf, n_epochs = m0._rt, m0.batch_size, m0.n_factors, m0.n_epochs
+    m0._keep_ids = []
+    tr = DevicePairs(rt, trains[0]["features"])
+    va = DevicePairs(rt, vals[0]["features"])
+    m0._check_ids(tr)
+    m0._check_ids(va)
+
+    # label and propensity vectors, each distinct pair uploaded once; label / propensity over the
+    # training log divided once per distinct pair, on the host as rfm_mf_schedule_ex divides it
+    keep, vectors, ratios = [], {}, {}
+
+    def vector(a):
+        if id(a) not in vectors:
+            keep.append(a)
+            vectors[id(a)] = rt.upload(np.asarray(a), dtype=np.float64)
+        return vectors[id(a)]
+
+    def ratio(y, p):
+        key = (id(y), id(p))
+        if key not in ratios:
+            keep.extend((y, p))
+            ratios[key] = rt.upload(np.ascontiguousarray(y, dtype=np.float64) / np.ascontiguousarray(p, dtype=np.float64))
+        return ratios[key]
+
+    model_rows, tr_labels, va_labels = [], [], []
+    for m, t, v in zip(models, trains, vals):
+        ry = ratio(t["labels"], t["pscores"])
+        model_rows.append(_lib.MfModel(m.P.dev.data_ptr(), m.Q.dev.data_ptr(), m.b_u.dev.data_ptr(),
+                                       m.b_i.dev.data_ptr(), ry.data_ptr(), float(m.b), float(m.lr), float(m.reg)))
+        tr_labels.append(_lib.MfLabels(vector(t["labels"]).data_ptr(), vector(t["pscores"]).data_ptr()))
+        va_labels.append(_lib.MfLabels(vector(v["labels"]).data_ptr(), vector(v["pscores"]).data_ptr()))
+    # the device tables are built here, once: no launch of the fit rewrites them
+    d_models = _device_table(rt, (_lib.MfModel * n)(*model_rows))
+    d_tr_labels = _device_table(rt, (_lib.MfLabels * n)(*tr_labels))
+    d_va_labels = _device_table(rt, (_lib.MfLabels * n)(*va_labels))
+    tl = rt.empty((n, n_epochs), torch.float64)
+    vl = rt.empty((n, n_epochs), torch.float64)
+    if va.n == 0:  # the reference's mean over no rows is nan (src/base.py:61)
+        vl.fill_(float("nan"))
+    cache_cap = mf_cache_capacity(kf)
+
+    def make_loop(m):
+        def make(evaluator):
+            ev_X = evaluator.features[m.model_name]
+            frame = device_frame(rt, evaluator, m.estimator, int(np.asarray(ev_X).shape[0]))
+            return EvalLoop(rt, frame, evaluator, m.estimator, n_epochs)
+        return make
+
+    hooks = [FitHook(m, n_epochs, m.predict, make_loop(m)) for m in models]
+    loops = [h.loop for h in hooks if h.loop is not None]
+    d_slots = ev_pairs = None
+    if loops:
+        if len(loops) != n or len({(lp.chunk, int(lp.scores.shape[1])) for lp in loops}) != 1:
+            raise ValueError("fit_many: the models' evaluator frames differ in shape; use fit()")
+        ev_pairs = DevicePairs(rt, m0.evaluator.features[m0.model_name])
+        m0._check_ids(ev_pairs)
+        d_slots = _device_table(rt, (_lib.C.c_void_p * n)(*(lp.scores.data_ptr() for lp in loops)))
+        slot_stride = int(loops[0].scores.shape[1])
+
+    def schedule(rows):
+        return mf_schedule_rows(tr.h_users[rows], tr.h_items[rows], rows, m0.n_users, m0.n_items, cache_cap)
+
+    lib, ctx = rt.lib, rt.ctx
+    models_ptr = d_models.data_ptr()
+
+    def step(epoch, ids_ptr, d_ex, h_lptr, d_lptr, n_levels, d_cache, n_cached, d_rows, done):
+        _lib.check(lib.rfm_mf_sgd_levels_many(ctx, d_ex, d_rows, h_lptr, d_lptr, n_levels, d_cache, n_cached,
+                                              models_ptr, n, kf))
+        done()
+        # train loss on the same batch with the updated parameters (src/mf.py:110-116)
+        _lib.check(lib.rfm_mf_predict_loss_many(
+            ctx, tr.users.data_ptr(), tr.items.data_ptr(), d_tr_labels.data_ptr(), ids_ptr, B, models_ptr, n, kf,
+            LOSS_EPS, None, 0, tl.data_ptr() + epoch * 8, n_epochs))
+        if va.n > 0:
+            _lib.check(lib.rfm_mf_predict_loss_many(
+                ctx, va.users.data_ptr(), va.items.data_ptr(), d_va_labels.data_ptr(), None, va.n, models_ptr, n,
+                kf, LOSS_EPS, None, 0, vl.data_ptr() + epoch * 8, n_epochs))
+        if loops:
+            _lib.check(lib.rfm_mf_predict_many(
+                ctx, ev_pairs.users.data_ptr(), ev_pairs.items.data_ptr(), None, ev_pairs.n, models_ptr, n, kf,
+                d_slots.data_ptr(), (epoch % loops[0].chunk) * slot_stride))
+            for lp in loops:
+                lp.measure(epoch)
+        for h in hooks:
+            h.ran(epoch, 1)
+
+    _SchedulePipe(rt, B, cache_cap, with_rows=True).run(m0._epochs(id_stream), schedule, step)
+    rt.sync()
+    m0._keep_ids = []
+    for h in hooks:
+        h.finish()
+    tl, vl = tl.cpu().numpy(), vl.cpu().numpy()
+    return [(tl[j].tolist(), vl[j].tolist()) for j in range(n)]

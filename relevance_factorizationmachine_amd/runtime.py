@@ -588,3 +588,38 @@ def mf_schedule_ex(users: np.ndarray, items: np.ndarray, y: np.ndarray, pscore: 
                                       ex.ctypes.data, level_ptr.ctypes.data, C.byref(n_levels),
                                       cache_items.ctypes.data, C.byref(n_cached)))
     return ex, level_ptr[: n_levels.value + 1].copy(), cache_items[: n_cached.value].copy()
+
+
+def mf_schedule_rows(users: np.ndarray, items: np.ndarray, rows: np.ndarray, n_users: int, n_items: int,
+                     cache_cap: int):
+    """``mf_schedule_ex`` for a schedule that several models share (``rfm_mf_schedule_rows``):
+    ``(ex[B] with every ry NaN, ex_rows int32[B], level_ptr int32[L+1], cache_items int32[n_cached])``;
+    ``rows`` is the training-log row of each batch position, ``ex_rows`` that of each record."""
+    lib = _lib.load()
+    users = np.ascontiguousarray(users, dtype=np.int32)
+    items = np.ascontiguousarray(items, dtype=np.int32)
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    b = users.shape[0]
+    if rows.shape != (b,):
+        raise ValueError("rows must name one training-log row per batch position")
+    ex = np.empty(b, dtype=MF_EX_DTYPE)
+    ex_rows = np.empty(b, dtype=np.int32)
+    level_ptr = np.empty(b + 1, dtype=np.int32)
+    cache_items = np.empty(max(cache_cap, 1), dtype=np.int32)
+    n_levels, n_cached = C.c_int32(0), C.c_int32(0)
+    _lib.check(lib.rfm_mf_schedule_rows(users.ctypes.data, items.ctypes.data, rows.ctypes.data, b, n_users,
+                                        n_items, cache_cap, ex.ctypes.data, ex_rows.ctypes.data,
+                                        level_ptr.ctypes.data, C.byref(n_levels), cache_items.ctypes.data,
+                                        C.byref(n_cached)))
+    return ex, ex_rows, level_ptr[: n_levels.value + 1].copy(), cache_items[: n_cached.value].copy()
+
+
+def mf_many_geometry(rt: Optional["Runtime"], n_models: int, n_factors: int, n_recs: int) -> dict:
+    """Launch shapes of the many-model MF calls (``rfm_mf_many_geometry``); ``rt`` None: a device of
+    256 CUs."""
+    out = (C.c_int32 * 7)()
+    _lib.check(_lib.load().rfm_mf_many_geometry(rt.ctx if rt is not None else None, int(n_models), int(n_factors),
+                                                int(n_recs), out))
+    keys = ("seq_threads", "lanes_per_row", "seq_grid", "wide_grid_x", "wide_grid_y", "predict_grid_x",
+            "predict_grid_y")
+    return dict(zip(keys, (int(v) for v in out)))
