@@ -620,6 +620,13 @@ int32_t rfm_fm_fold_in(rfm_ctx* ctx, const int64_t* d_row_ptr, const int32_t* d_
  * each per grid-stride turn).  ctx == NULL: the grid on a device of 256 CUs (an MI355X). */
 int32_t rfm_fm_fold_geometry(const rfm_ctx* ctx, int64_t n_new, int32_t n_factors, int32_t* h_out5);
 
+/* ---- fold-in: the examples grouped on the device -----------------------------------
+ * rfm_fold_group, rfm_fold_group_workspace and rfm_fold_group_geometry: d_row_ptr, d_ids, d_ry and
+ * d_order of the two fold-in entries above from a log in device memory.  Semantics and declarations
+ * in rfm_fold_group.h (a part of this ABI in a file of its own, with a ctypes table of its own:
+ * _lib.FOLD_GROUP_SIGNATURES). */
+#include "rfm_fold_group.h"
+
 /* ---- MF across GPUs: user-range partition ------------------
  * NOT the reference's semantics (its batch is strictly sequential, src/mf.py:97-108;
  * exact mode = one GPU or independent replicas).  Throughput mode: rank r runs the exact

@@ -17,10 +17,10 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 # RFM_LIB_PATH: load another build of the same ABI (timing experiments under profiles/)
 LIB_PATH = os.environ.get("RFM_LIB_PATH") or os.path.join(PKG_DIR, "librfm_hip.so")
-SOURCES = ["rfm_capi.hip", "rfm_fm.hip", "rfm_fm_plan.hip", "rfm_mf.hip", "rfm_fm_fold.hip", "rfm_eval.hip", "rfm_csr.hip", "rfm_sample.hip", "rfm_pairs.hip", "rfm_host.cpp", "rfm_comm.cpp"]
+SOURCES = ["rfm_capi.hip", "rfm_fm.hip", "rfm_fm_plan.hip", "rfm_mf.hip", "rfm_fm_fold.hip", "rfm_fold_group.hip", "rfm_eval.hip", "rfm_csr.hip", "rfm_sample.hip", "rfm_pairs.hip", "rfm_host.cpp", "rfm_comm.cpp"]
 # every header under csrc/ (a change of any of them rebuilds every object) + the C ABI
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp"))) + [
-    os.path.join(os.path.dirname(PKG_DIR), "include", h) for h in ("rfm_hip.h", "rfm_mf_many.h")]
+    os.path.join(os.path.dirname(PKG_DIR), "include", h) for h in ("rfm_hip.h", "rfm_mf_many.h", "rfm_fold_group.h")]
 
 RFM_OK, RFM_ERR_BAD_ARG, RFM_ERR_HIP, RFM_ERR_NO_DEVICE, RFM_ERR_INTERNAL = range(5)
 MF_MAX_MODELS = 1024  # RFM_MF_MAX_MODELS of include/rfm_mf_many.h
@@ -210,6 +210,14 @@ MF_MANY_SIGNATURES = {
     "rfm_mf_many_geometry": [_vp, _i32, _i32, _i64, _vp],
 }
 
+# fold-in examples grouped on the device, the part of the ABI that include/rfm_fold_group.h declares
+# (tests/test_fold_group_host.py compares the two, argument by argument)
+FOLD_GROUP_SIGNATURES = {
+    "rfm_fold_group": [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
+    "rfm_fold_group_workspace": [_i64, _i64, C.POINTER(_i64)],
+    "rfm_fold_group_geometry": [_vp, _i64, _i64, _vp],
+}
+
 # ``rfm_transport`` of include/rfm_hip.h: the collectives of rfm_fm_fit_dp as caller functions
 TRANSPORT_ALL_GATHER = C.CFUNCTYPE(_i32, _vp, _vp, _vp, _i64)
 TRANSPORT_ALL_REDUCE = C.CFUNCTYPE(_i32, _vp, _vp, _i64)
@@ -276,7 +284,7 @@ def load():
         lib = C.CDLL(path)
     except OSError as exc:
         raise RfmError(f"cannot load {path}: {exc}") from exc
-    for name, argtypes in {**SIGNATURES, **MF_MANY_SIGNATURES}.items():
+    for name, argtypes in {**SIGNATURES, **MF_MANY_SIGNATURES, **FOLD_GROUP_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError = header/library mismatch
         fn.argtypes = argtypes
         fn.restype = _i32

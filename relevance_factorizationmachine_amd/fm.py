@@ -395,7 +395,8 @@ class FactorizationMachines(PointwiseBaseRecommender):
         return out.cpu().numpy()
 
     # -------------------------------------------------------------- fold-in
-    def _fold_in(self, side: int, sides, new_rows, data: dict, n_passes: int, init, lr, ops) -> FoldedColumns:
+    def _fold_in(self, side: int, sides, new_rows, data: dict, n_passes: int, init, lr, ops, group=None,
+                 check=True) -> FoldedColumns:
         """The id columns of new rows of ``side`` (0: users, 1: items) trained against the fixed
         other side (``rfm_fm_fold_in``): every check on the host first, then the
         side sums of ``new_rows`` and the fold launch enqueued on the runtime's stream, no host wait."""
@@ -405,7 +406,7 @@ class FactorizationMachines(PointwiseBaseRecommender):
         kf, kp = int(self.n_factors), rec.pad4(self.n_factors)
         X = fold_rows(sides, new_rows, side, self.n_features)
         n_new, n_fixed = int(X.shape[0]), (n_items, n_users)[side]
-        row_ptr, ids, ry, order = fold.fold_examples(data, n_new, n_fixed, side, n_passes)
+        examples = fold.grouped_examples(self._rt, data, n_new, n_fixed, side, n_passes, group, check)
         lr = float(self.lr if lr is None else lr)
         start = fold.initial_state(init, n_new, kf, ("V", "w"))
         if ops is not None and (tuple(ops.A.shape) != (n_users, kp) or tuple(ops.B.shape) != (n_items, kp)):
@@ -425,14 +426,15 @@ class FactorizationMachines(PointwiseBaseRecommender):
                 ops = rec.operands(self, sides)
             F, fL = ((ops.B, ops.LI), (ops.A, ops.LU))[side]
             g, l = rec.side_sums(rt, DeviceCSR(rt, X), self.w.dev, self.V.dev, self.n_features, kf)
-            dev = fold.upload_examples(rt, row_ptr, ids, ry, order)
+            dev = examples()
             _lib.check(rt.lib.rfm_fm_fold_in(
                 rt.ctx, *(d.data_ptr() for d in dev), n_new, g.data_ptr(), l.data_ptr(), F.data_ptr(), fL.data_ptr(),
                 n_fixed, self.w0.dev.data_ptr(), kf, lr, int(n_passes), w_new.data_ptr(), V_new.data_ptr(),
                 A_new.data_ptr(), L_new.data_ptr()))
         return FoldedColumns(("user", "item")[side], w_new, V_new, A_new, L_new, rt)
 
-    def fold_in_users(self, sides, new_rows, data: dict, n_passes: int, init=None, lr=None, ops=None) -> FoldedColumns:
+    def fold_in_users(self, sides, new_rows, data: dict, n_passes: int, init=None, lr=None, ops=None, group=None,
+                      check=True) -> FoldedColumns:
         """Id columns for users who arrived after the fit: each new user's one-hot
         id column -- its weight and factor row -- is learned from the user's interactions by the
         reference's batch-sum step (``src/fm.py:80-88``) with the trained model held fixed.
@@ -443,13 +445,16 @@ class FactorizationMachines(PointwiseBaseRecommender):
         column, ``labels``, ``pscores``.  One pass is one full-batch step over a user's examples;
         ``lr``: the model's unless given; ``init``: ``(V [n_new, k], w [n_new])`` to start from
         (default zeros); ``ops``: ``recommend.operands(self, sides)`` to reuse.  The model is not
-        written; serve the result through ``new_users=`` or ``append_columns`` it."""
-        return self._fold_in(0, sides, new_rows, data, n_passes, init, lr, ops)
+        written; serve the result through ``new_users=`` or ``append_columns`` it.  ``group``, ``check``:
+        where the examples are grouped by user and whether the device's id check is waited for, as
+        ``LogisticMatrixFactorization.fold_in_users`` takes them."""
+        return self._fold_in(0, sides, new_rows, data, n_passes, init, lr, ops, group, check)
 
-    def fold_in_items(self, sides, new_rows, data: dict, n_passes: int, init=None, lr=None, ops=None) -> FoldedColumns:
+    def fold_in_items(self, sides, new_rows, data: dict, n_passes: int, init=None, lr=None, ops=None, group=None,
+                      check=True) -> FoldedColumns:
         """``fold_in_users`` with the sides exchanged: ``new_rows`` holds new items' feature entries,
         the item column of ``features`` new-item indices and the user column user rows of ``sides``."""
-        return self._fold_in(1, sides, new_rows, data, n_passes, init, lr, ops)
+        return self._fold_in(1, sides, new_rows, data, n_passes, init, lr, ops, group, check)
 
     def append_columns(self, folded: FoldedColumns) -> np.ndarray:
         """Grows ``w``, ``V`` and ``n_features`` by folded id columns, at the end; returns their

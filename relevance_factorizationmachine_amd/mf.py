@@ -336,7 +336,7 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
         return out.cpu().numpy()
 
     # -------------------------------------------------------------- fold-in
-    def _fold_in(self, side: int, data: dict, n_new: int, n_passes: int, init) -> FoldedRows:
+    def _fold_in(self, side: int, data: dict, n_new: int, n_passes: int, init, group=None, check=True) -> FoldedRows:
         """New rows of ``side`` (0: users, 1: items) trained against the fixed other side
         (``rfm_mf_fold_in``): enqueued on the runtime's stream, no host wait."""
         import torch
@@ -346,7 +346,7 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
             # the reference's global bias exists only after fit() (src/mf.py:84)
             raise AttributeError("'LogisticMatrixFactorization' object has no attribute 'b'")
         F, fb, n_fixed = ((self.Q, self.b_i, self.n_items), (self.P, self.b_u, self.n_users))[side]
-        row_ptr, ids, ry, order = fold.fold_examples(data, n_new, n_fixed, side, n_passes)
+        examples = fold.grouped_examples(rt, data, n_new, n_fixed, side, n_passes, group, check)
         n_new, kf = int(n_new), int(self.n_factors)
         start = fold.initial_state(init, n_new, kf, ("rows", "bias"))
         if start is None:
@@ -355,26 +355,32 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
         else:
             rows, bias = rt.upload(start[0]), rt.upload(start[1])
         if n_new and int(n_passes):
-            dev = fold.upload_examples(rt, row_ptr, ids, ry, order)
+            dev = examples()
             _lib.check(rt.lib.rfm_mf_fold_in(
                 rt.ctx, *(d.data_ptr() for d in dev), n_new, F.dev.data_ptr(), fb.dev.data_ptr(), n_fixed,
                 float(self.b), kf, float(self.lr), float(self.reg), int(n_passes), rows.data_ptr(),
                 bias.data_ptr()))
         return FoldedRows(("user", "item")[side], rows, bias, rt)
 
-    def fold_in_users(self, data: dict, n_new: int, n_passes: int, init=None) -> FoldedRows:
+    def fold_in_users(self, data: dict, n_new: int, n_passes: int, init=None, group=None, check=True) -> FoldedRows:
         """Rows and biases for ``n_new`` users who arrived after the fit, by the reference's own
         per-example update (``src/mf.py:99-108``) with ``Q, b_i`` held fixed.  ``data`` as ``fit()``
         takes it: the user column of ``features`` holds new-user indices 0..n_new-1, the item column
         known item ids; a user's examples are taken in input order, ``n_passes`` times.  ``init``:
         ``(rows [n_new, k], bias [n_new])`` to start from (default zeros).  The model is not
-        written; serve the result through ``new_users=`` or ``append_users`` it."""
-        return self._fold_in(0, data, n_new, n_passes, init)
+        written; serve the result through ``new_users=`` or ``append_users`` it.
+        ``group``: where the examples are grouped by user -- "host" (NumPy, then
+        uploaded), "device" (``rfm_fold_group``; the pieces of ``data`` may be tensors on the device,
+        host pieces are uploaded as they are), None: "device" if ``data["features"]`` is a device
+        tensor, else "host"; the result has the same bits either way.  ``check`` (device grouping
+        only): True waits once for the device's id check and raises the host path's ``IndexError``;
+        False waits for nothing, and an example with an id out of range is left out."""
+        return self._fold_in(0, data, n_new, n_passes, init, group, check)
 
-    def fold_in_items(self, data: dict, n_new: int, n_passes: int, init=None) -> FoldedRows:
+    def fold_in_items(self, data: dict, n_new: int, n_passes: int, init=None, group=None, check=True) -> FoldedRows:
         """``fold_in_users`` with the sides exchanged: the item column of ``features`` holds new-item
         indices, the user column known user ids, and ``P, b_u`` are held fixed."""
-        return self._fold_in(1, data, n_new, n_passes, init)
+        return self._fold_in(1, data, n_new, n_passes, init, group, check)
 
     def _append(self, folded: FoldedRows, side: str, M: DeviceSGD, bias: DeviceSGD) -> np.ndarray:
         if not isinstance(folded, FoldedRows) or folded.side != side:
