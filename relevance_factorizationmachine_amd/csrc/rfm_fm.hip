@@ -9,10 +9,11 @@
 //                          the row's sparse-class entries and adds the hot entries'
 //                          err_t x_tj [q_t, 1, x_tj] into the workgroup's LDS sums.
 //   2. fm_consume_kernel   one task (a fixed number of 64-slot bitmap words) per lane group:
-//                          lists the marked slots, accumulates err_t x_tj [Q[t,:], 1, x_tj]
-//                          IN SLOT ORDER, updates the columns inside the task in place and
-//                          combines columns that run over several tasks of the workgroup in
-//                          LDS; trailing workgroups reduce the hot columns' slabs and w0.
+//                          lists the marked slots; the workgroup's marks are dealt evenly to
+//                          its groups, each accumulates err_t x_tj [Q[t,:], 1, x_tj] of its
+//                          part IN SLOT ORDER, updates the columns inside the part in place
+//                          and combines columns that run over several parts of the workgroup
+//                          in LDS; trailing workgroups reduce the hot columns' slabs and w0.
 //  (3. fm_finalize_kernel  only for columns longer than a whole workgroup's tasks.)
 // The only global float atomics are the no-return f64 adds to w[col] and w0 by the value's only
 // writer of the step.  Sparse-class sums have a fixed order (bitwise reproducible);
@@ -442,6 +443,7 @@ void enqueue_step(rfm_ctx* ctx, rfm_fm_plan* plan, const int32_t* d_row_ids, int
   c.c = col;
   c.tasks = plan->tasks.as<TaskRec>();
   c.task_words = plan->task_words;
+  c.pool = consume_pools(plan->task_words, plan->max_batch, plan->n_rows) ? 1 : 0;
   c.slot_bits = bits;
   c.slot_bits_other = bits_other;
   c.slot_mark = plan->slot_t.as<SlotMark>();

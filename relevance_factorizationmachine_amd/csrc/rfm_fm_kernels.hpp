@@ -1044,6 +1044,7 @@ struct ConsArgs {
   ColArgs c;
   const TaskRec* tasks;  // [nb_tasks * tasks per workgroup]
   int32_t task_words;    // 64-slot words of the slot bitmap per task
+  int32_t pool;          // single-chunk forms: deal a workgroup's marks evenly (consume_pools)
   unsigned long long* slot_bits;  // one bit per slot: set by the forward, cleared here
   unsigned long long* slot_bits_other;  // CH form: the bitmap of the step before, cleared here
   const SlotMark* slot_mark;      // {batch position, residual} of a marked slot's row
@@ -1061,6 +1062,15 @@ struct ConsArgs {
   int32_t n_chunks;           // CH form: chunks of 64 lanes x VEC factors (fm_chunks)
   int32_t xcd_chunks;         // CH form: 1 = chunks dealt to XCDs (1-D grid), 0 = blockIdx.y
 };
+
+// Whether the gradient launch of a plan deals a workgroup's marks evenly to its groups: where a
+// task expects more marks per max_batch step than one batch of the chain (kConsBatch entries).
+// A plan cuts its tasks for kTaskMarks = 8 expected marks; it stays below that only where
+// task_words is capped by the lanes of a group -- small batches, 2 marks at B = 2 000 of 10^6 rows.
+constexpr int kConsBatch = 4;
+inline bool consume_pools(int task_words, int64_t max_batch, int64_t n_rows) {
+  return int64_t(task_words) * 64 * max_batch > int64_t(kConsBatch) * n_rows;
+}
 
 // chunks of 64 lanes x vec factors that cover a row of k factors
 inline int fm_chunks(int k, int vec) { return ((k + vec - 1) / vec + 63) / 64; }
@@ -1211,12 +1221,14 @@ struct WinShape {
 };
 
 // LDS of a workgroup of fm_consume_kernel: per group the list of marked slots and their parked
-// records, then the groups' head rows; or (hot-column / w0 workgroups) reduction scratch and totals
+// records, then the groups' head rows, then how many slots each group listed (one int each); or
+// (hot-column / w0 workgroups) reduction scratch and totals
 constexpr int kConsHotBytes = (kBlock + 1024 + 2) * int(sizeof(double));
 template <int LPR>
 constexpr size_t consume_lds_bytes_of(int k) {
   constexpr size_t gpb = kBlock / LPR;
-  const size_t tasks = gpb * WinShape<LPR>::kGroupBytes + gpb * size_t(k + 3) * sizeof(double);
+  const size_t tasks = gpb * WinShape<LPR>::kGroupBytes + gpb * size_t(k + 3) * sizeof(double) +
+                       (gpb * sizeof(int32_t) + 7) / 8 * 8;
   return tasks > size_t(kConsHotBytes) ? tasks : size_t(kConsHotBytes);
 }
 inline size_t consume_lds_bytes(int lpr, int k) {
@@ -1280,7 +1292,9 @@ __device__ inline void consume_w0(const ConsArgs& a, double* lds) {
 // its own and updates the column.  Only a column longer than a whole workgroup's tasks
 // leaves partial rows in memory (one per workgroup) for fm_finalize_kernel.  The work of a
 // launch follows the batch (marked slots): an untouched task reads its bitmap words and
-// waits at the barrier.
+// waits at the barrier.  (Single-chunk forms, plans whose tasks expect more than one batch of
+// the chain: the chain runs over an even share of the workgroup's listed slots instead of the
+// group's own list -- see "dealt evenly" in the kernel.)
 // (The lane groups of a wave run in lock step: ballots and shuffles are wave-wide.)
 // A lane holds VEC factors of a row: one chunk of LPR x VEC factors covers it, or -- CH, factor
 // counts of more than one chunk per lane -- the chunks of a row are dealt to DIFFERENT workgroups
@@ -1363,8 +1377,11 @@ __global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
   double* heads = reinterpret_cast<double*>(reinterpret_cast<char*>(lds_raw) + GPB * kGroupBytes);
   double* head = heads + gb * (k + 3);  // the group's head row; [k+2] flags
 
-  const bool head_open = tk.flags & 1;  // first_col continues from the previous task
-  const bool tail_open = tk.flags & 2;  // last_col continues into the next task
+  // the columns at the edges of what this group sums: of its task (from the plan), or of its part
+  // of the workgroup's pooled marks (from the marks themselves, below)
+  bool head_open = tk.flags & 1;  // first_col continues from the previous task / part
+  bool tail_open = tk.flags & 2;  // last_col continues into the next task / part
+  int32_t first_col = tk.first_col, last_col = tk.last_col;
   ColAcc<VEC> acc;
   acc.clear();
   Pack<VEC> vold;       // V row of the column being accumulated
@@ -1375,7 +1392,7 @@ __global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
   // a finished column: into the head row (continues from the previous task), or updated in
   // place; the last column of a tail-open task stays in `acc` for the combine below
   const auto finish = [&]() {
-    if (head_open && cur == tk.first_col) {
+    if (head_open && cur == first_col) {
       acc.store_row(head, f, k, l == 0);
       head_done = true;
     } else {
@@ -1383,22 +1400,24 @@ __global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
     }
   };
 
-  // the chain over the group's list of `fill` marked slots
-  const auto run_list = [&]() {
-    // records and marks of the listed slots, parked in LDS by list position
+  // the chain over `fill` marked slots; slot_of(e) = the e-th of them (slot0 where e >= fill),
+  // planes = an upper bound of every group's fill (uniform in the workgroup)
+  const auto run_list = [&](auto slot_of, int planes) {
+    // records and marks of the slots, parked in LDS by position
     SlotRec sr[PLANES];
     SlotMark mk[PLANES];
 #pragma unroll
     for (int pl = 0; pl < PLANES; ++pl) {
-      const int e = pl * LPR + l;
-      const int32_t s = e < fill ? list[e] : slot0;
-      mk[pl] = a.slot_mark[s];
-      sr[pl] = a.slots[s];
+      if (pl * LPR < planes) {
+        const int32_t s = slot_of(pl * LPR + l);
+        mk[pl] = a.slot_mark[s];
+        sr[pl] = a.slots[s];
+      }
     }
 #pragma unroll
     for (int pl = 0; pl < PLANES; ++pl) {
       const int e = pl * LPR + l;
-      if (e < fill) {
+      if (pl * LPR < planes && e < fill) {
         const double coef = mk[pl].err * sr[pl].x;
         wrec[e] = WinRec{mk[pl].t, sr[pl].col, coef, coef * sr[pl].x};
       }
@@ -1445,41 +1464,115 @@ __global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
     fill = 0;
   };
 
+  const auto own_slot = [&](int e) -> int32_t { return e < fill ? list[e] : slot0; };
+  // ---- the workgroup's marks, dealt evenly to its groups ------------------------------------
+  // What a task gets is a draw around what the plan expects, and the workgroup waits for its
+  // longest chain.  So the chain does not run over a group's own list: every group lists its
+  // task, the lists laid end to end are the workgroup's T marked slots in slot order, and group g
+  // runs the chain over the positions [g * per, (g + 1) * per) of that pool, per = ceil(T / GPB)
+  // -- its PART.  Which columns come into a part and go on behind it is read off the marks
+  // (the columns of the positions before and behind the part), not off the plan.  A workgroup in
+  // which a task has more marks than a list holds runs the tasks as they are instead.  So does
+  // every workgroup of a plan whose tasks expect no more than one batch of the chain (a.pool = 0:
+  // small batches, where a task's chain is one batch whatever it gets and the exchange below
+  // would only stand in front of the first load).
+  bool pooled = false;
+  int32_t next_col = -2;  // pooled: column of the position behind the part (-2: there is none)
+  if constexpr (!CH) if (a.pool) {
+    bool over = false;  // the task has more marks than the list holds (uniform in the group)
 #pragma unroll
-  for (int u = 0; u < TRIPS; ++u) {
-    unsigned long long word = wd[u];
-    const int32_t s0 = slot0 + (u * LPR + l) * 64;  // first slot of this lane's word
-    // move the trip's marked slots into the list in lane (= slot) order, as many as the list
-    // has room for; when a group's list is full and it has marks left, every group of the
-    // wave runs the chain on what it has listed so far
-    while (__ballot(word != 0ull)) {
+    for (int u = 0; u < TRIPS; ++u) {
+      // the task's marked slots into the list in lane (= slot) order, as far as the list has room
+      unsigned long long word = wd[u];
+      const int32_t s0 = slot0 + (u * LPR + l) * 64;
       const int cnt = __popcll(word);
-      const int before = group_scan<LPR>(cnt, l) - cnt;  // marks of the group's earlier lanes
-      const int take = min(cnt, max(WIN - fill - before, 0));
-      int pos = fill + before;
+      const int upto = group_scan<LPR>(cnt, l);
+      const int take = min(cnt, max(WIN - fill - (upto - cnt), 0));
+      int pos = fill + upto - cnt;
       for (int i = 0; i < take; ++i) {
         list[pos++] = s0 + (__ffsll((long long)word) - 1);
         word &= word - 1ull;
       }
-      int added = take;
+      fill += __shfl(upto, LPR - 1, LPR);
+      over |= fill > WIN;
+    }
+    int32_t* fills = reinterpret_cast<int32_t*>(heads + GPB * (k + 3));
+    if (l == 0) fills[gb] = over ? WIN + 1 : fill;
+    __syncthreads();
+    // lane j < GPB of every wave: the fill of group j and the fills before it
+    const int gl = lane % GPB;
+    const int mine = fills[gl];
+    const int incl = group_scan<GPB>(mine, gl);
+    const int excl = incl - mine;
+    if (__ballot(mine > WIN) == 0ull) {  // (the same in every wave of the workgroup)
+      pooled = true;
+      const int T = __builtin_amdgcn_readlane(incl, GPB - 1);
+      const int per = (T + GPB - 1) / GPB;
+      const int p0 = gb * per;
+      const int n = max(min(per, T - p0), 0);  // empty parts come last
+      // the slot at pooled position p (slot0 unless ok): the list it lies in is the last one
+      // that starts at or before p, found by bisection of the prefix sums
+      const auto pooled_slot = [&](int p, bool ok) -> int32_t {
+        const int pc = max(min(p, T - 1), 0);
+        int o = 0;
 #pragma unroll
-      for (int o = 1; o < LPR; o <<= 1) added += __shfl_xor(added, o, LPR);
-      fill += added;
-      if (__ballot(word != 0ull)) run_list();
+        for (int st = GPB / 2; st > 0; st >>= 1) o += __shfl(excl, o + st) <= pc ? st : 0;
+        const int i = pc - __shfl(excl, o);  // < the fill of group o (0 where T = 0)
+        const int32_t* lo = reinterpret_cast<const int32_t*>(
+            reinterpret_cast<const char*>(lds_raw) + o * kGroupBytes + WIN * sizeof(WinRec));
+        const int32_t s = lo[i];
+        return ok ? s : slot0;
+      };
+      const bool has_prev = n > 0 && gb > 0, has_next = p0 + n < T && n > 0;
+      const int32_t sp = pooled_slot(p0 - 1, has_prev), sn = pooled_slot(p0 + n, has_next);
+      const int32_t cp = a.slots[sp].col, cn = a.slots[sn].col;
+      head_open = has_prev;
+      first_col = has_prev ? cp : -1;
+      if (has_next) next_col = cn;
+      fill = n;
+      if (T > 0) run_list([&](int e) -> int32_t { return pooled_slot(p0 + e, e < fill); }, per);
+      last_col = cur;
+      tail_open = next_col == cur;
     }
   }
-  if (__ballot(fill > 0)) run_list();
+  if (!pooled) {
+    if constexpr (!CH) fill = 0;  // (an overflowing workgroup lists again from the start)
+#pragma unroll
+    for (int u = 0; u < TRIPS; ++u) {
+      unsigned long long word = wd[u];
+      const int32_t s0 = slot0 + (u * LPR + l) * 64;  // first slot of this lane's word
+      // move the trip's marked slots into the list in lane (= slot) order, as many as the list
+      // has room for; when a group's list is full and it has marks left, every group of the
+      // wave runs the chain on what it has listed so far
+      while (__ballot(word != 0ull)) {
+        const int cnt = __popcll(word);
+        const int before = group_scan<LPR>(cnt, l) - cnt;  // marks of the group's earlier lanes
+        const int take = min(cnt, max(WIN - fill - before, 0));
+        int pos = fill + before;
+        for (int i = 0; i < take; ++i) {
+          list[pos++] = s0 + (__ffsll((long long)word) - 1);
+          word &= word - 1ull;
+        }
+        int added = take;
+#pragma unroll
+        for (int o = 1; o < LPR; o <<= 1) added += __shfl_xor(added, o, LPR);
+        fill += added;
+        if (__ballot(word != 0ull)) run_list(own_slot, WIN);
+      }
+    }
+    if (__ballot(fill > 0)) run_list(own_slot, WIN);
+  }
 
-  // ---- columns that run over several tasks of this workgroup -----------------------------
+  // ---- columns that run over several tasks / parts of this workgroup ----------------------
   // the last column of a tail-open task is still in `acc` (if it got any entry here); a
   // column that both comes in and goes on (the task lies inside it) counts as a head row
-  const bool through = head_open && tail_open && tk.first_col == tk.last_col;
-  // this group owns the combine of tk.last_col: the column starts (or, for a piece of a very
+  const bool through = head_open && tail_open && first_col == last_col;
+  // this group owns the combine of last_col: the column starts (or, for a piece of a very
   // long column, this workgroup's share of it starts) in this task
   const bool own = (tail_open && !through) || tk.part >= 0;
   bool own_acc = false;  // ... and holds entries of it in `acc`
   if (cur >= 0) {
-    if (own && cur == tk.last_col) {
+    if (own && cur == last_col) {
       own_acc = true;
     } else {
       finish();
@@ -1490,8 +1583,9 @@ __global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
   __syncthreads();
   if (own) {
     if (!own_acc) {
+      // (pooled: only the first part of a piece without marks, which needs no row of V)
       acc.clear();
-      vold = load_v_row<VEC>(c.V, tk.last_col, k, f);
+      if (!pooled) vold = load_v_row<VEC>(c.V, last_col, k, f);
     }
     bool any = own_acc;
     for (int g2 = gb + 1; g2 < GPB; ++g2) {
@@ -1509,7 +1603,7 @@ __global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
       acc.store_row(row, f, k, scalars);
       if (scalars) row[k + 2] = any ? c.stamp : 0.0;
     } else if (any) {
-      apply_column(c, tk.last_col, acc, vold, f, scalars);
+      apply_column(c, last_col, acc, vold, f, scalars);
     }
   }
 }
