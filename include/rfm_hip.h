@@ -884,6 +884,18 @@ int32_t rfm_pair_order(rfm_ctx* ctx, const double* d_A, const double* d_LU, int6
                        const int64_t* d_excl_indptr, const int32_t* d_excl_items, int64_t depth,
                        void* d_workspace, int64_t workspace_bytes, int32_t* d_out_items,
                        double* d_out_scores, int32_t* d_out_n_ranked);
+/* The launches the rfm_pair_* entries make for these sizes (host only, no context; nothing is
+ * launched; computed by the functions the launches are sized by).  rfm_pair_geometry, n_sel_users
+ * >= 1: h_out8[0]=kpad, [1]=chunks of 32 factors a tile goes through, [2]=factors per MFMA k-slot
+ * in the last chunk, (kpad - 32 ([1] - 1)) / 4 in 1..8, [3]=user tiles, [4]=item tiles (of 64),
+ * and for the entries whose workgroups walk a split of the item tiles (rfm_pair_topk,
+ * rfm_pair_ranks): [5]=splits, [6]=tiles per split, [7]=tiles of the last split.
+ * rfm_pair_order_geometry: h_out4[0]=entries of the ranking kernel's list in LDS (a power of two,
+ * 256..4096), [1]=items of a pass over the row, [2]=the staged count above which a flush (sort and
+ * merge of the staging area) precedes a pass, [0] - [1]; the remainder is flushed after the last
+ * pass, [3]=pages (launches of the ranking kernel per block of users). */
+int32_t rfm_pair_geometry(int64_t n_sel_users, int64_t n_items, int32_t n_factors, int64_t* h_out8);
+int32_t rfm_pair_order_geometry(int64_t n_items, int64_t depth, int64_t* h_out4);
 
 #ifdef __cplusplus
 }

@@ -197,6 +197,8 @@ SIGNATURES = {
     "rfm_rank_metrics": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
     "rfm_pair_order_workspace": [_i64, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64)],
     "rfm_pair_order": _PAIR + [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
+    "rfm_pair_geometry": [_i64, _i64, _i32, C.POINTER(_i64)],
+    "rfm_pair_order_geometry": [_i64, _i64, C.POINTER(_i64)],
 }
 
 # several MF models on one schedule, the part of the ABI that include/rfm_mf_many.h declares

@@ -1186,6 +1186,45 @@ int32_t rfm_pair_order_workspace(int64_t n_sel_users, int64_t n_items, int64_t d
   });
 }
 
+int32_t rfm_pair_geometry(int64_t n_sel_users, int64_t n_items, int32_t n_factors, int64_t* h_out8) {
+  return guarded([&] {
+    RFM_REQUIRE(h_out8, "null pointer");
+    RFM_REQUIRE(n_factors >= 1 && n_factors <= RFM_MAX_FACTORS, "n_factors=%d unsupported (1..%d)",
+                n_factors, RFM_MAX_FACTORS);
+    RFM_REQUIRE(n_sel_users >= 1 && n_sel_users <= kMaxSel && n_items >= 1, "no selected user or no items");
+    const int64_t kpad = pad4(n_factors);
+    const int64_t chunks = (kpad + kChunk - 1) / kChunk;               // trips of the tile's k0 loop
+    const int64_t k0 = (chunks - 1) * kChunk;                          // the last of them
+    const int64_t item_tiles = (n_items + kTile - 1) / kTile;          // the tile's n_item_tiles
+    const Split sp = topk_split(n_sel_users, n_items);
+    h_out8[0] = kpad;
+    h_out8[1] = chunks;
+    h_out8[2] = std::min<int64_t>(kChunk, kpad - k0) >> 2;             // the tile's q at k0
+    h_out8[3] = (n_sel_users + kTile - 1) / kTile;                     // grid y of every pair launch
+    h_out8[4] = item_tiles;
+    h_out8[5] = sp.n_splits;
+    h_out8[6] = sp.tiles_per_split;
+    // the tile's t_last - t_first of the last workgroup along x
+    h_out8[7] = std::min<int64_t>(int64_t(sp.n_splits) * sp.tiles_per_split, item_tiles) -
+                int64_t(sp.n_splits - 1) * sp.tiles_per_split;
+  });
+}
+
+int32_t rfm_pair_order_geometry(int64_t n_items, int64_t depth, int64_t* h_out4) {
+  return guarded([&] {
+    RFM_REQUIRE(h_out4, "null pointer");
+    RFM_REQUIRE(depth >= 1, "depth=%lld: the ranking depth must be at least 1", (long long)depth);
+    RFM_REQUIRE(n_items >= 1 && n_items < (int64_t(1) << 31) - kTile, "n_items=%lld: none, or too many for int32 item ids",
+                (long long)n_items);
+    const int64_t n_ranks = std::min(depth, n_items);  // as rfm_pair_order
+    const int P = order_list_len(n_ranks);
+    h_out4[0] = P;
+    h_out4[1] = order_pass(P);
+    h_out4[2] = P - order_pass(P);           // a pass is preceded by a flush when more than this is staged
+    h_out4[3] = (n_ranks + P - 1) / P;       // launches of the ranking kernel per block of users
+  });
+}
+
 int32_t rfm_pair_order(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t n_users,
                        const int32_t* d_user_ids, int64_t n_sel_users, const double* d_B,
                        const double* d_LI, int64_t n_items, int32_t n_factors, const double* d_c,
