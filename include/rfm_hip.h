@@ -473,6 +473,12 @@ int32_t rfm_fm_fit_dp_eval(rfm_ctx* ctx, rfm_fm_plan* plan, const rfm_transport*
                            int32_t max_local_segments, int32_t n_segments, double* d_full_out,
                            double* d_dcg_out);
 
+/* ---- FM: the update rule of a plan's steps -------------------------------------------
+ * rfm_fm_plan_set_optimizer and rfm_fm_plan_optimizer: semantics and declarations in rfm_fm_opt.h
+ * (a part of this ABI in a file of its own, with a ctypes table of its own:
+ * _lib.FM_OPT_SIGNATURES). */
+#include "rfm_fm_opt.h"
+
 /* ---- MF ------------------------------------------------------------------
  * Replaces LogisticMatrixFactorization.predict/_predict_pair
  * (src/mf.py:136-170): out[t] = sigmoid(clip(P_u . Q_i + b_u + b_i + b)). */

@@ -11,11 +11,12 @@ raises if the HIP extension or the device is missing.
 from .base import PointwiseBaseRecommender
 from .fm import FactorizationMachines
 from .mf import LogisticMatrixFactorization
-from .optimizer import DeviceSGD
+from .optimizer import DeviceAdaGrad, DeviceSGD
 
 __all__ = [
     "PointwiseBaseRecommender",
     "FactorizationMachines",
     "LogisticMatrixFactorization",
     "DeviceSGD",
+    "DeviceAdaGrad",
 ]

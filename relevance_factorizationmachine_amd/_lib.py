@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("RFM_LIB_PATH") or os.path.join(PKG_DIR, "librfm_hip.s
 SOURCES = ["rfm_capi.hip", "rfm_fm.hip", "rfm_fm_plan.hip", "rfm_mf.hip", "rfm_fm_fold.hip", "rfm_fold_group.hip", "rfm_eval.hip", "rfm_csr.hip", "rfm_sample.hip", "rfm_pairs.hip", "rfm_host.cpp", "rfm_comm.cpp"]
 # every header under csrc/ (a change of any of them rebuilds every object) + the C ABI
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp"))) + [
-    os.path.join(os.path.dirname(PKG_DIR), "include", h) for h in ("rfm_hip.h", "rfm_mf_many.h", "rfm_fold_group.h")]
+    os.path.join(os.path.dirname(PKG_DIR), "include", h) for h in ("rfm_hip.h", "rfm_mf_many.h", "rfm_fold_group.h", "rfm_fm_opt.h")]
 
 RFM_OK, RFM_ERR_BAD_ARG, RFM_ERR_HIP, RFM_ERR_NO_DEVICE, RFM_ERR_INTERNAL = range(5)
 MF_MAX_MODELS = 1024  # RFM_MF_MAX_MODELS of include/rfm_mf_many.h
@@ -220,6 +220,14 @@ FOLD_GROUP_SIGNATURES = {
     "rfm_fold_group_geometry": [_vp, _i64, _i64, _vp],
 }
 
+# the update rule of an FM plan's steps, the part of the ABI that include/rfm_fm_opt.h declares
+# (tests/test_adagrad_host.py compares the two, argument by argument)
+FM_OPT_SGD, FM_OPT_ADAGRAD = 0, 1  # RFM_FM_OPT_* of include/rfm_fm_opt.h
+FM_OPT_SIGNATURES = {
+    "rfm_fm_plan_set_optimizer": [_vp, _i32, _vp, _vp, _vp, _f64],
+    "rfm_fm_plan_optimizer": [_vp, _vp],
+}
+
 # ``rfm_transport`` of include/rfm_hip.h: the collectives of rfm_fm_fit_dp as caller functions
 TRANSPORT_ALL_GATHER = C.CFUNCTYPE(_i32, _vp, _vp, _vp, _i64)
 TRANSPORT_ALL_REDUCE = C.CFUNCTYPE(_i32, _vp, _vp, _i64)
@@ -286,7 +294,7 @@ def load():
         lib = C.CDLL(path)
     except OSError as exc:
         raise RfmError(f"cannot load {path}: {exc}") from exc
-    for name, argtypes in {**SIGNATURES, **MF_MANY_SIGNATURES, **FOLD_GROUP_SIGNATURES}.items():
+    for name, argtypes in {**SIGNATURES, **MF_MANY_SIGNATURES, **FOLD_GROUP_SIGNATURES, **FM_OPT_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError = header/library mismatch
         fn.argtypes = argtypes
         fn.restype = _i32

@@ -355,7 +355,8 @@ int launch_step_forward(rfm_ctx* ctx, FwdArgs f, const XtraRows* xtra) {
 }
 
 // the step's consume launch (fm_consume_kernel): the slot-ordered sums and the updates
-void launch_consume(rfm_ctx* ctx, ConsArgs c, const Shape& s) {
+// (ada: the plan's AdaGrad operands, null for the SGD instantiations)
+void launch_consume(rfm_ctx* ctx, ConsArgs c, const Shape& s, const AdaGradRule* ada) {
   const int grid = c.nb_tasks + c.n_hot + 1;  // tasks, then the hot columns, then w0
   const size_t lds = consume_lds_bytes(s.lpr, c.c.k);
   if (s.nc > 1) {
@@ -366,10 +367,27 @@ void launch_consume(rfm_ctx* ctx, ConsArgs c, const Shape& s) {
     c.xcd_chunks = n_chunks <= 8 ? 1 : 0;
     const int per_chunk = 8 / n_chunks;  // (the fewest XCDs a chunk gets)
     const dim3 g2 = c.xcd_chunks ? dim3(8 * ((grid + per_chunk - 1) / per_chunk)) : dim3(grid, n_chunks);
-    if (s.vec == 2)
+    if (ada) {
+      ConsArgsOpt co{};
+      static_cast<ConsArgs&>(co) = c;
+      co.o = *ada;
+      if (s.vec == 2)
+        hipLaunchKernelGGL((fm_consume_kernel<64, 2, true, AdaGradRule>), g2, dim3(kBlock), lds, ctx->stream, co);
+      else
+        hipLaunchKernelGGL((fm_consume_kernel<64, 1, true, AdaGradRule>), g2, dim3(kBlock), lds, ctx->stream, co);
+    } else if (s.vec == 2)
       hipLaunchKernelGGL((fm_consume_kernel<64, 2, true>), g2, dim3(kBlock), lds, ctx->stream, c);
     else
       hipLaunchKernelGGL((fm_consume_kernel<64, 1, true>), g2, dim3(kBlock), lds, ctx->stream, c);
+  } else if (ada) {
+    ConsArgsOpt co{};
+    static_cast<ConsArgs&>(co) = c;
+    co.o = *ada;
+#define RFM_CALL_CONS_ADA(L, Vv, N)                                                                      \
+  hipLaunchKernelGGL((fm_consume_kernel<L, Vv, false, AdaGradRule>), dim3(grid), dim3(kBlock), lds, \
+                     ctx->stream, co)
+    RFM_FOR_SINGLE_CHUNK_SHAPE(s, RFM_CALL_CONS_ADA);
+#undef RFM_CALL_CONS_ADA
   } else {
 #define RFM_CALL_CONS(L, Vv, N) \
   hipLaunchKernelGGL((fm_consume_kernel<L, Vv>), dim3(grid), dim3(kBlock), lds, ctx->stream, c)
@@ -380,16 +398,33 @@ void launch_consume(rfm_ctx* ctx, ConsArgs c, const Shape& s) {
 }
 
 // the finalize launch of the columns cut into several tasks
-void launch_finalize(rfm_ctx* ctx, const FinArgs& fa, const Shape& s) {
+void launch_finalize(rfm_ctx* ctx, const FinArgs& fa, const Shape& s, const AdaGradRule* ada) {
   const int gpb = kBlock / s.lpr;
   const int nb_short = (fa.n_split_short + gpb - 1) / gpb;
   const int grid = nb_short + fa.n_split_long;
   if (s.nc > 1) {
     const dim3 g2(grid, fm_chunks(fa.c.k, s.vec));
-    if (s.vec == 2)
+    if (ada) {
+      FinArgsOpt fo{};
+      static_cast<FinArgs&>(fo) = fa;
+      fo.o = *ada;
+      if (s.vec == 2)
+        hipLaunchKernelGGL((fm_finalize_chunk_kernel<2, AdaGradRule>), g2, dim3(kBlock), 0, ctx->stream, fo, nb_short);
+      else
+        hipLaunchKernelGGL((fm_finalize_chunk_kernel<1, AdaGradRule>), g2, dim3(kBlock), 0, ctx->stream, fo, nb_short);
+    } else if (s.vec == 2)
       hipLaunchKernelGGL(fm_finalize_chunk_kernel<2>, g2, dim3(kBlock), 0, ctx->stream, fa, nb_short);
     else
       hipLaunchKernelGGL(fm_finalize_chunk_kernel<1>, g2, dim3(kBlock), 0, ctx->stream, fa, nb_short);
+  } else if (ada) {
+    FinArgsOpt fo{};
+    static_cast<FinArgs&>(fo) = fa;
+    fo.o = *ada;
+#define RFM_CALL_FIN_ADA(L, Vv, N)                                                                    \
+  hipLaunchKernelGGL((fm_finalize_kernel<L, Vv, AdaGradRule>), dim3(grid), dim3(kBlock), 0, ctx->stream, \
+                     fo, nb_short)
+    RFM_FOR_SINGLE_CHUNK_SHAPE(s, RFM_CALL_FIN_ADA);
+#undef RFM_CALL_FIN_ADA
   } else {
 #define RFM_CALL_FIN(L, Vv, N)                                                              \
   hipLaunchKernelGGL((fm_finalize_kernel<L, Vv>), dim3(grid), dim3(kBlock), 0, ctx->stream, \
@@ -428,6 +463,16 @@ void enqueue_step(rfm_ctx* ctx, rfm_fm_plan* plan, const int32_t* d_row_ids, int
     const size_t bytes = (size_t(plan->n_features) * (k + 1) + 1) * sizeof(double);
     RFM_HIP_CHECK(hipMemsetAsync(d_grad, 0, bytes, ctx->stream));
   }
+  // the rule of the plan (rfm_fm_plan_set_optimizer); gradient mode forms g alone, under any rule
+  AdaGradRule ada_rule{};
+  const AdaGradRule* ada = nullptr;
+  if (!d_grad && plan->opt_kind == RFM_FM_OPT_ADAGRAD) {
+    ada_rule.acc_V = plan->opt_acc_V;
+    ada_rule.acc_w = plan->opt_acc_w;
+    ada_rule.acc_w0 = plan->opt_acc_w0;
+    ada_rule.eps = plan->opt_eps;
+    ada = &ada_rule;
+  }
   ColArgs col{};  // what both launches need to finish a column
   col.V = d_V;
   col.w = d_w;
@@ -456,7 +501,7 @@ void enqueue_step(rfm_ctx* ctx, rfm_fm_plan* plan, const int32_t* d_row_ids, int
   c.hot_slab = plan->hot_slab.as<double>();
   c.n_slabs = n_slabs;
   c.err_partial = plan->err_partial.as<double>();
-  launch_consume(ctx, c, s);
+  launch_consume(ctx, c, s, ada);
   ctx->prof_mark();
   // columns cut into several tasks (none on most plans): their partial rows
   if (plan->n_split_short + plan->n_split_long > 0) {
@@ -465,7 +510,7 @@ void enqueue_step(rfm_ctx* ctx, rfm_fm_plan* plan, const int32_t* d_row_ids, int
     fa.split = plan->split.as<SplitCol>();
     fa.n_split_short = plan->n_split_short;
     fa.n_split_long = plan->n_split_long;
-    launch_finalize(ctx, fa, s);
+    launch_finalize(ctx, fa, s, ada);
   }
   ctx->prof_mark();
 }

@@ -378,6 +378,9 @@ void fit_dp(rfm_ctx* ctx, rfm_fm_plan* plan, const rfm_transport* transport, int
   RFM_REQUIRE(ctx && plan && d_w0 && d_w && d_V, "null pointer");
   RFM_REQUIRE(exchange == 0 || exchange == 1, "exchange=%d (0 dense, 1 touched rows)", exchange);
   RFM_REQUIRE(n_iters >= 0 && global_batch >= 1 && n_val >= 0, "bad shape");
+  RFM_REQUIRE(plan->opt_kind == RFM_FM_OPT_SGD,
+              "the data-parallel fit applies summed gradients with the SGD rule; the plan's rule is kind %d",
+              plan->opt_kind);
   if (n_iters == 0) return;
   RFM_REQUIRE(d_ids, "null row ids");
   DpExchange ex = dp_exchange(ctx, transport);

@@ -1155,6 +1155,37 @@ __device__ inline double updated_factor(double vold, double m, double d, double 
   return grad ? g : fma(lr, -g, vold);
 }
 
+// THE OPTIMISER of the update sites (apply_scalar, apply_column, apply_column_block and the long
+// columns of fm_finalize_chunk_kernel), a type parameter of launches 2 and 3.  SgdRule: theta -=
+// lr * g as spelled above, the form every site had before there was a choice; its instantiations
+// take the branches they always took.  AdaGradRule: every element of w0, w and V has an
+// accumulator G of its own (same shape, float64) and, with g the element's gradient exactly as
+// gradient mode writes it (so -s for a scalar, updated_factor(..., grad = true, ...) for a factor),
+//   G_new = G + g * g             (the product rounded, then the sum)
+//   theta_new = theta - (lr * g) / (sqrt(G_new) + eps)
+// in IEEE basic operations.  g = 0 changes neither, so a hot column without an entry in the batch
+// keeps its bits although it is visited; an untouched column of the sparse class is not visited.
+// Gradient mode never runs under AdaGradRule (enqueue_step).
+struct SgdRule {
+  static constexpr bool kAda = false;
+};
+struct AdaGradRule {
+  static constexpr bool kAda = true;
+  double* acc_V;   // [n][k]
+  double* acc_w;   // [n]
+  double* acc_w0;  // [1]
+  double eps;
+};
+
+// one element under AdaGradRule; *G: its accumulator as it was read, then as it is to be written
+__device__ inline double adagrad_element(double theta, double g, double lr, double eps, double* G) {
+#pragma clang fp contract(off)
+  const double gg = g * g;
+  const double gn = *G + gg;
+  *G = gn;
+  return theta - (lr * g) / (sqrt(gn) + eps);
+}
+
 // *p += x by its only writer of the step.  As `*p += x` the wavefront stands still for the load of *p
 // (nothing else waits for it) -- once per finished column in the gradient launch, eight times per task
 // where columns are short, and one dependent level in the finalize; the no-return atomic add gives the
@@ -1162,52 +1193,97 @@ __device__ inline double updated_factor(double vold, double m, double d, double 
 __device__ inline void add_by_only_writer(double* p, double x) { unsafeAtomicAdd(p, x); }
 
 // ... and a scalar parameter from the sum s of its residual terms, by one thread: *p += lr * s in
-// place, or grad[n*k + at] = -s
-__device__ inline void apply_scalar(const ColArgs& c, double* p, int64_t at, double s) {
-  if (c.grad)
-    c.grad[c.n * c.k + at] = -s;
-  else
-    add_by_only_writer(p, c.lr * s);
+// place, or grad[n*k + at] = -s.  (AdaGradRule, G = the element's accumulator: its step is no sum,
+// so the element's only writer reads, computes and writes both.)
+template <class O>
+__device__ inline void apply_scalar(const ColArgs& c, const O& o, double* p, double* G, int64_t at,
+                                    double s) {
+  if constexpr (O::kAda) {
+    double gacc = *G;
+    *p = adagrad_element(*p, -s, c.lr, o.eps, &gacc);
+    *G = gacc;
+  } else {
+    if (c.grad)
+      c.grad[c.n * c.k + at] = -s;
+    else
+      add_by_only_writer(p, c.lr * s);
+  }
 }
 
 // w[col] so, with the column's mark in touched-row mode (the row is valid for this step)
-__device__ inline void apply_w(const ColArgs& c, int32_t col, double gw) {
-  apply_scalar(c, c.w + col, col, gw);
-  if (c.grad && c.touch) c.touch[col] = c.touch_id;
+template <class O>
+__device__ inline void apply_w(const ColArgs& c, const O& o, int32_t col, double gw) {
+  if constexpr (O::kAda) {
+    apply_scalar(c, o, c.w + col, o.acc_w + col, col, gw);
+  } else {
+    apply_scalar(c, o, c.w + col, nullptr, col, gw);
+    if (c.grad && c.touch) c.touch[col] = c.touch_id;
+  }
+}
+
+// the lane's factors of a column's accumulator row, requested where its row of V is
+template <int VEC, class O>
+__device__ inline void load_acc_row(const O& o, Pack<VEC>& p, int32_t col, int k, int f) {
+  if constexpr (O::kAda) p.load(o.acc_V + int64_t(col) * k + (f < k ? f : 0));
 }
 
 // V[col,:] and w[col] from the sums of one column in a lane group: update in place, or write the
-// gradient row (grad mode).  vold = the lane's factors f.. of the row as they were read before;
+// gradient row (grad mode).  vold = the lane's factors f.. of the row as they were read before
+// (gold: of its accumulator row, AdaGradRule only);
 // `scalars`: this lane writes w / touch (lane 0 of the group that has the row's first chunk).
-template <int VEC>
-__device__ inline void apply_column(const ColArgs& c, int32_t col, const ColAcc<VEC>& acc,
-                                    const Pack<VEC>& vold, int f, bool scalars) {
-  if (f < c.k) {
-    Pack<VEC> out;
+template <int VEC, class O>
+__device__ inline void apply_column(const ColArgs& c, const O& o, int32_t col, const ColAcc<VEC>& acc,
+                                    const Pack<VEC>& vold, const Pack<VEC>& gold, int f, bool scalars) {
+  if constexpr (O::kAda) {
+    if (f < c.k) {
+      Pack<VEC> out, gout;
 #pragma unroll
-    for (int v = 0; v < VEC; ++v)
-      out.v[v] = updated_factor(vold.v[v], acc.m[v], acc.d, c.lr, c.grad != nullptr, v == 0);
-    out.store((c.grad ? c.grad : c.V) + int64_t(col) * c.k + f);
+      for (int v = 0; v < VEC; ++v) {
+        gout.v[v] = gold.v[v];
+        const double g = updated_factor(vold.v[v], acc.m[v], acc.d, c.lr, true, v == 0);
+        out.v[v] = adagrad_element(vold.v[v], g, c.lr, o.eps, &gout.v[v]);
+      }
+      out.store(c.V + int64_t(col) * c.k + f);
+      gout.store(o.acc_V + int64_t(col) * c.k + f);
+    }
+    if (scalars) apply_w(c, o, col, acc.gw);
+  } else {
+    if (f < c.k) {
+      Pack<VEC> out;
+#pragma unroll
+      for (int v = 0; v < VEC; ++v)
+        out.v[v] = updated_factor(vold.v[v], acc.m[v], acc.d, c.lr, c.grad != nullptr, v == 0);
+      out.store((c.grad ? c.grad : c.V) + int64_t(col) * c.k + f);
+    }
+    if (scalars) apply_w(c, o, col, acc.gw);
   }
-  if (scalars) apply_w(c, col, acc.gw);
 }
 
 // The same from a whole workgroup, sums in LDS: tot[0..k) = M, tot[k] = sum coef,
 // tot[k+1] = sum coef*x.
 // (vpre: the row as the caller read it before the sums were formed -- threadIdx.x + j * kBlock
-// -- so that the load is in flight beside the sums' own loads; null: read here)
+// -- so that the load is in flight beside the sums' own loads; null: read here.  gpre: the
+// accumulator row so, with vpre)
 constexpr int kRowPre = (RFM_MAX_FACTORS + kBlock - 1) / kBlock;
-__device__ inline void apply_column_block(const ColArgs& c, int32_t col, const double* tot,
-                                          const double* vpre = nullptr) {
+template <class O>
+__device__ inline void apply_column_block(const ColArgs& c, const O& o, int32_t col, const double* tot,
+                                          const double* vpre = nullptr, const double* gpre = nullptr) {
   const int k = c.k;
   const double gw = tot[k], d = tot[k + 1];
   int j = 0;
   for (int f = threadIdx.x; f < k; f += kBlock, ++j) {
     const int64_t at = int64_t(col) * k + f;
     const double vold = vpre ? vpre[j] : c.V[at];
-    (c.grad ? c.grad : c.V)[at] = updated_factor(vold, tot[f], d, c.lr, c.grad != nullptr, false);
+    if constexpr (O::kAda) {
+      double gacc = vpre ? gpre[j] : o.acc_V[at];
+      const double g = updated_factor(vold, tot[f], d, c.lr, true, false);
+      c.V[at] = adagrad_element(vold, g, c.lr, o.eps, &gacc);
+      o.acc_V[at] = gacc;
+    } else {
+      (c.grad ? c.grad : c.V)[at] = updated_factor(vold, tot[f], d, c.lr, c.grad != nullptr, false);
+    }
   }
-  if (threadIdx.x == 0) apply_w(c, col, gw);
+  if (threadIdx.x == 0) apply_w(c, o, col, gw);
 }
 
 // slots a lane group handles per pass over a 64-slot word of the bitmap: PLANES pieces of
@@ -1252,9 +1328,25 @@ __device__ inline int group_scan(int v, int l) {
   return v;
 }
 
+// the arguments of launches 2 and 3 under a rule: SgdRule's are ConsArgs / FinArgs themselves
+struct ConsArgsOpt : ConsArgs {
+  AdaGradRule o;
+};
+template <class O>
+struct ConsArgsOf {
+  using type = ConsArgs;
+};
+template <>
+struct ConsArgsOf<AdaGradRule> {
+  using type = ConsArgsOpt;
+};
+__device__ inline SgdRule rule_of(const ConsArgs&) { return SgdRule{}; }
+__device__ inline const AdaGradRule& rule_of(const ConsArgsOpt& a) { return a.o; }
+
 // A hot column, by one workgroup: the forward workgroups' slabs, in block order; the column's row
 // of V is requested first, so that it arrives with the slabs and not after them.
-__device__ inline void consume_hot_column(const ConsArgs& a, int hb, double* lds) {
+template <class O>
+__device__ inline void consume_hot_column(const ConsArgs& a, const O& o, int hb, double* lds) {
   const int k = a.c.k;
   const int32_t col = a.hot_cols[hb];
   double vpre[kRowPre];
@@ -1263,18 +1355,35 @@ __device__ inline void consume_hot_column(const ConsArgs& a, int hb, double* lds
     const int f = int(threadIdx.x) + j * kBlock;
     vpre[j] = a.c.V[int64_t(col) * k + (f < k ? f : 0)];
   }
+  double gpre[kRowPre];
+  if constexpr (O::kAda) {
+#pragma unroll
+    for (int j = 0; j < kRowPre; ++j) {
+      const int f = int(threadIdx.x) + j * kBlock;
+      gpre[j] = o.acc_V[int64_t(col) * k + (f < k ? f : 0)];
+    }
+  }
   double* tot = lds + kBlock;
   ordered_rows_sum<32>(SlabRows{a.hot_slab + int64_t(hb) * a.n_slabs * (k + 2), k + 2}, a.n_slabs,
                        k + 2, lds, tot);
-  apply_column_block(a.c, col, tot, vpre);
+  if constexpr (O::kAda)
+    apply_column_block(a.c, o, col, tot, vpre, gpre);
+  else
+    apply_column_block(a.c, o, col, tot, vpre);
 }
 
 // w0, by one workgroup, from the forward workgroups' residual sums
-__device__ inline void consume_w0(const ConsArgs& a, double* lds) {
+template <class O>
+__device__ inline void consume_w0(const ConsArgs& a, const O& o, double* lds) {
   double acc = 0.0;
   for (int i = threadIdx.x; i < a.n_slabs; i += kBlock) acc += a.err_partial[i];
   const double s = block_sum<kBlock>(acc, lds);
-  if (threadIdx.x == 0) apply_scalar(a.c, a.w0, a.c.n, s);
+  if (threadIdx.x == 0) {
+    if constexpr (O::kAda)
+      apply_scalar(a.c, o, a.w0, o.acc_w0, a.c.n, s);
+    else
+      apply_scalar(a.c, o, a.w0, nullptr, a.c.n, s);
+  }
 }
 
 // One TASK per lane group: `task_words` 64-slot words of the slot view, the same number for
@@ -1307,8 +1416,10 @@ __device__ inline void consume_w0(const ConsArgs& a, double* lds) {
 // cleared while a sibling may still read them: the bitmap is double-buffered by step parity and
 // chunk 0 clears the task's words of the OTHER buffer (the step before, long consumed).
 constexpr int kConsChBatch = 4;  // CH form: entries whose Q and V rows are in flight together
-template <int LPR, int VEC, bool CH = false>
-__global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
+// O: the update rule (SgdRule: the arguments are ConsArgs; AdaGradRule: ConsArgsOpt).
+template <int LPR, int VEC, bool CH = false, class O = SgdRule>
+__global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(typename ConsArgsOf<O>::type a) {
+  const O& o = rule_of(a);
   constexpr int GPB = kBlock / LPR;  // tasks of a workgroup
   constexpr int PLANES = WinShape<LPR>::PLANES;
   constexpr int WIN = WinShape<LPR>::WIN;  // marked slots a group lists before it runs the chain
@@ -1341,9 +1452,9 @@ __global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
     if (CH && chunk != 0) return;
     const int hb = bx - a.nb_tasks;
     if (hb < a.n_hot)
-      consume_hot_column(a, hb, lds_raw);
+      consume_hot_column(a, o, hb, lds_raw);
     else
-      consume_w0(a, lds_raw);
+      consume_w0(a, o, lds_raw);
     return;
   }
   const int lane = threadIdx.x % kWave;
@@ -1388,6 +1499,7 @@ __global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
   int32_t cur = -1;     // that column (uniform in the lane group)
   int fill = 0;         // marked slots listed and not yet consumed (uniform in the lane group)
   bool head_done = false;
+  Pack<VEC> gold;       // AdaGradRule: the accumulator row of the column being accumulated (with vold)
 
   // a finished column: into the head row (continues from the previous task), or updated in
   // place; the last column of a tail-open task stays in `acc` for the combine below
@@ -1396,7 +1508,7 @@ __global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
       acc.store_row(head, f, k, l == 0);
       head_done = true;
     } else {
-      apply_column(c, cur, acc, vold, f, scalars);
+      apply_column(c, o, cur, acc, vold, gold, f, scalars);
     }
   };
 
@@ -1427,7 +1539,7 @@ __global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
     while (__ballot(at < fill)) {
       const int nb = max(min(BATCH, fill - at), 0);
       WinRec rec[BATCH];
-      Pack<VEC> qq[BATCH], vv[BATCH];
+      Pack<VEC> qq[BATCH], vv[BATCH], ga[BATCH];
 #pragma unroll
       for (int u = 0; u < BATCH; ++u) {
         rec[u] = wrec[u < nb ? at + u : 0];
@@ -1440,8 +1552,10 @@ __global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
         // items in a small batch) costs one round trip, not one per column
         qq[u].load(a.Q + int64_t(rec[u].t) * k + (f < k ? f : 0));
         // (an entry of the column the one before it belongs to needs no V row)
-        if (rec[u].col != (u == 0 ? cur : rec[u > 0 ? u - 1 : 0].col))
+        if (rec[u].col != (u == 0 ? cur : rec[u > 0 ? u - 1 : 0].col)) {
           vv[u] = load_v_row<VEC>(c.V, rec[u].col, k, f);
+          load_acc_row(o, ga[u], rec[u].col, k, f);
+        }
       }
 #pragma unroll
       for (int u = 0; u < BATCH; ++u) {
@@ -1451,6 +1565,7 @@ __global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
             acc.clear();
             cur = rec[u].col;
             vold = vv[u];
+            if constexpr (O::kAda) gold = ga[u];
           }
           const double coef = rec[u].coef, cx = rec[u].cx;
 #pragma unroll
@@ -1585,7 +1700,10 @@ __global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
     if (!own_acc) {
       // (pooled: only the first part of a piece without marks, which needs no row of V)
       acc.clear();
-      if (!pooled) vold = load_v_row<VEC>(c.V, last_col, k, f);
+      if (!pooled) {
+        vold = load_v_row<VEC>(c.V, last_col, k, f);
+        load_acc_row(o, gold, last_col, k, f);
+      }
     }
     bool any = own_acc;
     for (int g2 = gb + 1; g2 < GPB; ++g2) {
@@ -1603,7 +1721,7 @@ __global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ConsArgs a) {
       acc.store_row(row, f, k, scalars);
       if (scalars) row[k + 2] = any ? c.stamp : 0.0;
     } else if (any) {
-      apply_column(c, last_col, acc, vold, f, scalars);
+      apply_column(c, o, last_col, acc, vold, gold, f, scalars);
     }
   }
 }
@@ -1621,8 +1739,22 @@ struct FinArgs {
 // The short split columns, one per lane group (workgroup b takes kBlock / LPR of them), the
 // factors fb + lane * VEC on of each: the column's partial rows CB to a round of loads, read
 // unconditionally -- a stale row is masked by its stamp -- and added in row order.
-template <int LPR, int VEC, int CB>
-__device__ inline void finalize_short_columns(const FinArgs& a, int b, int fb) {
+struct FinArgsOpt : FinArgs {
+  AdaGradRule o;
+};
+template <class O>
+struct FinArgsOf {
+  using type = FinArgs;
+};
+template <>
+struct FinArgsOf<AdaGradRule> {
+  using type = FinArgsOpt;
+};
+__device__ inline SgdRule rule_of(const FinArgs&) { return SgdRule{}; }
+__device__ inline const AdaGradRule& rule_of(const FinArgsOpt& a) { return a.o; }
+
+template <int LPR, int VEC, int CB, class O>
+__device__ inline void finalize_short_columns(const FinArgs& a, const O& o, int b, int fb) {
   constexpr int GPB = kBlock / LPR;
   const ColArgs& c = a.c;
   const int k = c.k;
@@ -1635,6 +1767,8 @@ __device__ inline void finalize_short_columns(const FinArgs& a, int b, int fb) {
   ColAcc<VEC> acc;
   acc.clear();
   const Pack<VEC> vold = load_v_row<VEC>(c.V, cc.col, k, f);
+  Pack<VEC> gold;
+  load_acc_row(o, gold, cc.col, k, f);
   bool any = false;
   for (int i = 0; i < cc.part_count; i += CB) {
     ColAcc<VEC> part[CB];
@@ -1652,20 +1786,21 @@ __device__ inline void finalize_short_columns(const FinArgs& a, int b, int fb) {
       acc.add_if(ok, part[u]);
     }
   }
-  if (any) apply_column(c, cc.col, acc, vold, f, l == 0 && fb == 0);
+  if (any) apply_column(c, o, cc.col, acc, vold, gold, f, l == 0 && fb == 0);
 }
 
 // blocks [0, nb_short): short split columns, one per lane group; then one block per long
 // split column.  Launched only when the plan has split columns.
-template <int LPR, int VEC>
-__global__ __launch_bounds__(kBlock) void fm_finalize_kernel(FinArgs a, int nb_short) {
+template <int LPR, int VEC, class O = SgdRule>
+__global__ __launch_bounds__(kBlock) void fm_finalize_kernel(typename FinArgsOf<O>::type a, int nb_short) {
+  const O& o = rule_of(a);
   __shared__ double scratch[kBlock];
   __shared__ double tot[1024 + 2];
   __shared__ int touched;
   const ColArgs& c = a.c;
   const int k = c.k;
   const int b = blockIdx.x;
-  if (b < nb_short) return finalize_short_columns<LPR, VEC, 4>(a, b, 0);
+  if (b < nb_short) return finalize_short_columns<LPR, VEC, 4>(a, o, b, 0);
   const SplitCol cc = a.split[a.n_split_short + (b - nb_short)];
   // is any partial row of this step's?  (an untouched column is left alone)
   if (threadIdx.x == 0) touched = 0;
@@ -1675,7 +1810,7 @@ __global__ __launch_bounds__(kBlock) void fm_finalize_kernel(FinArgs a, int nb_s
   __syncthreads();
   if (!touched) return;
   ordered_rows_sum<8>(PartRows{c.parts, cc.part_begin, k, c.stamp}, cc.part_count, k + 2, scratch, tot);
-  apply_column_block(c, cc.col, tot);
+  apply_column_block(c, o, cc.col, tot);
 }
 
 // The same for factor counts of several chunks per lane, one chunk of 64 x VEC factors per
@@ -1684,8 +1819,10 @@ __global__ __launch_bounds__(kBlock) void fm_finalize_kernel(FinArgs a, int nb_s
 // factor of the chunk with 32 rows in flight; stamps ride with the rows and the column's row of
 // V is requested before the sums, so a workgroup's chain is two dependent levels instead of
 // eight (k = 400, B = 2 000: 8.1 -> 6.8 us per launch, profiles/r3j vs r3q).
-template <int VEC>
-__global__ __launch_bounds__(kBlock) void fm_finalize_chunk_kernel(FinArgs a, int nb_short) {
+template <int VEC, class O = SgdRule>
+__global__ __launch_bounds__(kBlock) void fm_finalize_chunk_kernel(typename FinArgsOf<O>::type a,
+                                                                  int nb_short) {
+  const O& o = rule_of(a);
   constexpr int CW = kWave * VEC;
   __shared__ double tot[CW + 2];
   const ColArgs& c = a.c;
@@ -1708,6 +1845,8 @@ __global__ __launch_bounds__(kBlock) void fm_finalize_chunk_kernel(FinArgs a, in
     acc.clear();
     Pack<VEC> vold;
     vold.load(c.V + int64_t(cc.col) * k + fc);
+    Pack<VEC> gold;
+    load_acc_row(o, gold, cc.col, k, f);
     bool any = false;
     for (int i = 0; i < cc.part_count; i += CB) {
       Pack<VEC> mm[CB];
@@ -1730,7 +1869,7 @@ __global__ __launch_bounds__(kBlock) void fm_finalize_chunk_kernel(FinArgs a, in
         acc.d += ok ? dd[u] : 0.0;
       }
     }
-    if (any) apply_column(c, cc.col, acc, vold, f, l == 0 && fb == 0);
+    if (any) apply_column(c, o, cc.col, acc, vold, gold, f, l == 0 && fb == 0);
     return;
   }
   const SplitCol cc = a.split[a.n_split_short + (b - nb_short)];
@@ -1739,6 +1878,8 @@ __global__ __launch_bounds__(kBlock) void fm_finalize_chunk_kernel(FinArgs a, in
   const bool live = j < fcnt + 2;
   const int cidx = j < fcnt ? fb + j : k + (j - fcnt);
   const double vold = c.V[int64_t(cc.col) * k + (j < fcnt ? fb + j : 0)];
+  double gold = 0.0;
+  if constexpr (O::kAda) gold = o.acc_V[int64_t(cc.col) * k + (j < fcnt ? fb + j : 0)];
   double acc = 0.0;
   bool any = false;
   constexpr int U = 32;
@@ -1763,13 +1904,19 @@ __global__ __launch_bounds__(kBlock) void fm_finalize_chunk_kernel(FinArgs a, in
   const double gw = tot[fcnt], d = tot[fcnt + 1];
   if (j < fcnt) {
     const int64_t at = int64_t(cc.col) * k + fb + j;
-    if (c.grad)
+    if constexpr (O::kAda) {
+      const double g = updated_factor(vold, acc, d, c.lr, true, false);
+      c.V[at] = adagrad_element(vold, g, c.lr, o.eps, &gold);
+      o.acc_V[at] = gold;
+    } else if (c.grad)
       c.grad[at] = updated_factor(vold, acc, d, c.lr, true, false);
     else
       c.V[at] = updated_factor(vold, acc, d, c.lr, false, false);
   }
   if (j == 0 && fb == 0) {
-    if (c.grad) {
+    if constexpr (O::kAda) {
+      apply_w(c, o, cc.col, gw);
+    } else if (c.grad) {
       c.grad[c.n * k + cc.col] = -gw;
       if (c.touch) c.touch[cc.col] = c.touch_id;
     } else {

@@ -17,6 +17,10 @@ struct rfm_fm_plan {
   int32_t hot_rounds = 1;  // rounds of a lane group's entries that cover the longest row
   bool hot_fixed = false;  // hot-class sums in a fixed order (hot_min_count = -2)
   int64_t step = 0;  // stamps the partial rows of a step
+  // the update rule of the plan's steps (rfm_fm_plan_set_optimizer); the accumulators are the caller's
+  int32_t opt_kind = RFM_FM_OPT_SGD;
+  double *opt_acc_w0 = nullptr, *opt_acc_w = nullptr, *opt_acc_V = nullptr;
+  double opt_eps = 0.0;
   int64_t bits_words = 0;  // 64-slot words of ONE slot bitmap (slot_bits holds two)
   int32_t fwd_grid_max = 0;  // forward workgroups of a max_batch step (= hot-sum slabs)
   rfm::DevBuf ell;            // padded row blocks (every row <= lanes-per-group entries), else empty

@@ -593,6 +593,31 @@ int32_t rfm_fm_plan_layout(const rfm_fm_plan* plan, int32_t* h_out4) {
   });
 }
 
+int32_t rfm_fm_plan_set_optimizer(rfm_fm_plan* plan, int32_t kind, double* d_acc_w0, double* d_acc_w,
+                                  double* d_acc_V, double eps) {
+  return guarded([&] {
+    RFM_REQUIRE(plan, "null pointer");
+    RFM_REQUIRE(kind == RFM_FM_OPT_SGD || kind == RFM_FM_OPT_ADAGRAD, "optimizer kind=%d (0 SGD, 1 AdaGrad)", kind);
+    const bool ada = kind == RFM_FM_OPT_ADAGRAD;
+    if (ada) {
+      RFM_REQUIRE(d_acc_w0 && d_acc_w && d_acc_V, "AdaGrad: null accumulator");
+      RFM_REQUIRE(eps > 0.0, "AdaGrad: eps=%g must be > 0", eps);
+    }
+    plan->opt_kind = kind;
+    plan->opt_acc_w0 = ada ? d_acc_w0 : nullptr;
+    plan->opt_acc_w = ada ? d_acc_w : nullptr;
+    plan->opt_acc_V = ada ? d_acc_V : nullptr;
+    plan->opt_eps = ada ? eps : 0.0;
+  });
+}
+
+int32_t rfm_fm_plan_optimizer(const rfm_fm_plan* plan, int32_t* h_out) {
+  return guarded([&] {
+    RFM_REQUIRE(plan && h_out, "null pointer");
+    h_out[0] = plan->opt_kind;
+  });
+}
+
 int32_t rfm_fm_plan_hot_columns(const rfm_fm_plan* plan, int32_t* h_out, int32_t capacity) {
   return guarded([&] {
     RFM_REQUIRE(plan && (h_out || capacity == 0), "null pointer");

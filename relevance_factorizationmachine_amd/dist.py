@@ -822,6 +822,11 @@ def fit_data_parallel(model, train: dict, val: dict, exchange: str = "auto", tra
         # (its users would have to be shared out over the ranks: DESIGN.md 8 N8, not built)
         raise NotImplementedError("fit_data_parallel does not take a CatalogueValEvaluator: the catalogue "
                                   "metrics per iteration are computed by the single-GPU fit() only")
+    if getattr(model, "optimizer", "sgd") != "sgd":
+        # (the ranks' gradients are summed before one rule is applied; AdaGrad there is not built:
+        # DESIGN.md 8 N19)
+        raise ValueError(f"fit_data_parallel applies the SGD rule only, the model's optimizer is "
+                         f"{model.optimizer!r}")
     import torch.distributed as dist
 
     world, rank = dist.get_world_size(), dist.get_rank()

@@ -25,7 +25,7 @@ import numpy as np
 from . import _lib, fold
 from .base import LOSS_EPS, PointwiseBaseRecommender
 from .evaluate import EvalLoop, FitHook, device_frame, runs
-from .optimizer import DeviceSGD
+from .optimizer import DeviceAdaGrad, DeviceSGD
 from .runtime import BatchIdStream, CsrCache, DeviceCSR, Runtime
 
 
@@ -136,6 +136,17 @@ class FmPlan:
         _lib.check(self.rt.lib.rfm_fm_sliced_geometry(self.rt.ctx, self.handle, int(n_rows), int(form_rows),
                                                       out.ctypes.data))
         return dict(zip(("sliced", "workgroups", "rows_per_workgroup", "lds_bytes"), (int(v) for v in out)))
+
+    def set_optimizer(self, kind: int, acc_w0=None, acc_w=None, acc_V=None, eps: float = 0.0) -> None:
+        """The update rule of the plan's steps (``rfm_fm_plan_set_optimizer``): ``_lib.FM_OPT_SGD``, or
+        ``_lib.FM_OPT_ADAGRAD`` with the three accumulators (device tensors the caller keeps alive)."""
+        ptr = [t.data_ptr() if t is not None else None for t in (acc_w0, acc_w, acc_V)]
+        _lib.check(self.rt.lib.rfm_fm_plan_set_optimizer(self.handle, int(kind), *ptr, float(eps)))
+
+    def optimizer(self) -> int:
+        out = np.zeros(1, dtype=np.int32)
+        _lib.check(self.rt.lib.rfm_fm_plan_optimizer(self.handle, out.ctypes.data))
+        return int(out[0])
 
     def close(self) -> None:
         if self.handle is not None:
@@ -281,6 +292,13 @@ class FactorizationMachines(PointwiseBaseRecommender):
     # cores; fit() and dist.fit_data_parallel honour it.  Off by default until it outruns the
     # host threads on a cold fit.
     device_sampler = False
+    # Not constructor arguments: the update rule of fit() -- "sgd" (the reference's, theta -= lr * g)
+    # or "adagrad" (G += g * g; theta -= lr * g / (sqrt(G) + adagrad_eps), accumulators G of the
+    # parameters' shapes that start at adagrad_init and persist across fit() calls: DESIGN §8 N19).
+    # The data-parallel fit and fold-in take the SGD step only.
+    optimizer = "sgd"
+    adagrad_eps = 1e-10
+    adagrad_init = 0.0
 
     def __post_init__(self) -> None:
         # src/fm.py:31-53 -- the reference's NumPy calls, in its draw order
@@ -302,6 +320,22 @@ class FactorizationMachines(PointwiseBaseRecommender):
             self.model_name = "FM"
 
     # ------------------------------------------------------------------ fit
+    def _take_optimizer(self) -> bool:
+        """Checks ``optimizer``; with "adagrad" the three handles become ``DeviceAdaGrad`` on the
+        same device tensors (once: the accumulators persist).  True for AdaGrad."""
+        if self.optimizer not in ("sgd", "adagrad"):
+            raise ValueError(f"optimizer must be 'sgd' or 'adagrad', got {self.optimizer!r}")
+        if self.optimizer == "sgd":
+            return False
+        if not float(self.adagrad_eps) > 0.0:
+            raise ValueError(f"adagrad_eps={self.adagrad_eps!r} must be > 0")
+        for name in ("w0", "w", "V"):
+            h = getattr(self, name)
+            if not isinstance(h, DeviceAdaGrad):
+                setattr(self, name, DeviceAdaGrad(self._rt, None, h.lr, self.adagrad_eps, self.adagrad_init,
+                                                  dev=h.dev))
+        return True
+
     def fit(self, train: dict, val: dict) -> tuple:
         """src/fm.py:55-112.  One "epoch" is one mini-batch step; returns the
         per-iteration train and validation IPS log-loss as two lists."""
@@ -310,6 +344,7 @@ class FactorizationMachines(PointwiseBaseRecommender):
         n_rows = X.shape[0]
         if X.shape[1] != self.n_features:
             raise ValueError(f"train features have {X.shape[1]} columns, model has {self.n_features}")
+        self._take_optimizer()
         if self.n_epochs <= 0:
             return [], []
         # batch selection: resample(..., random_state=epoch) (src/fm.py:72-79), sampled chunk by
@@ -349,6 +384,9 @@ class FactorizationMachines(PointwiseBaseRecommender):
             return EvalLoop(rt, frame, evaluator, self.estimator, self.n_epochs, log=ev)
 
         try:
+            if self._take_optimizer():
+                # (plans are shared through plan_cache: the rule is set for this fit and taken back below)
+                plan.set_optimizer(_lib.FM_OPT_ADAGRAD, self.w0.acc, self.w.acc, self.V.acc, self.adagrad_eps)
             hook = FitHook(self, self.n_epochs, self.predict, make_loop)
             for first, host_ids, dev_ids in id_stream.chunks():
                 count = dev_ids.shape[0]
@@ -375,6 +413,7 @@ class FactorizationMachines(PointwiseBaseRecommender):
             # (the registration ends with the fit: the plan may outlive this split's device copy)
             for log_slot in (0, 1):
                 rt.lib.rfm_fm_plan_register_log(rt.ctx, plan.handle, log_slot, None, None, None, 0)
+            rt.lib.rfm_fm_plan_set_optimizer(plan.handle, _lib.FM_OPT_SGD, None, None, None, 0.0)
             st.release()
         return st.losses()
 
@@ -437,7 +476,9 @@ class FactorizationMachines(PointwiseBaseRecommender):
                       check=True) -> FoldedColumns:
         """Id columns for users who arrived after the fit: each new user's one-hot
         id column -- its weight and factor row -- is learned from the user's interactions by the
-        reference's batch-sum step (``src/fm.py:80-88``) with the trained model held fixed.
+        reference's batch-sum step (``src/fm.py:80-88``) with the trained model held fixed.  That is
+        the SGD step whatever ``optimizer`` the model was fitted with: a new column has no history
+        of gradients, and ``append_columns`` starts its accumulators at ``adagrad_init``.
         ``sides``: the catalogue the model serves; ``new_rows``: CSR ``[n_new, n_features]`` of the
         new users' FEATURE entries (a column stored on the item side is a ``ValueError``); ``data``
         as ``fit()`` of the MF model takes it: ``features`` ``(N, 2)`` of ``[user, item]`` with
@@ -457,7 +498,8 @@ class FactorizationMachines(PointwiseBaseRecommender):
         return self._fold_in(1, sides, new_rows, data, n_passes, init, lr, ops, group, check)
 
     def append_columns(self, folded: FoldedColumns) -> np.ndarray:
-        """Grows ``w``, ``V`` and ``n_features`` by folded id columns, at the end; returns their
+        """Grows ``w``, ``V`` and ``n_features`` by folded id columns, at the end (and, under
+        ``optimizer = "adagrad"``, their accumulators by rows of ``adagrad_init``); returns their
         column ids.  Rows that store those columns (entry 1 next to the row's feature entries) are
         then scored by ``predict``, served by the catalogue methods on a ``Sides`` of the grown
         width and trained by a further ``fit``; where a loader's id segment sits is the loader's
