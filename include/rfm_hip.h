@@ -558,6 +558,11 @@ int32_t rfm_mf_sgd_levels_ex(rfm_ctx* ctx, const void* d_ex, const int32_t* h_le
  * its own, with a ctypes table of its own: _lib.MF_MANY_SIGNATURES). */
 #include "rfm_mf_many.h"
 
+/* ---- MF: the optimiser seam ---------------------------------------------------------
+ * rfm_mf_sgd_levels_opt and rfm_mf_opt_geometry: semantics and declarations in rfm_mf_opt.h (a
+ * part of this ABI in a file of its own, with a ctypes table of its own: _lib.MF_OPT_SIGNATURES). */
+#include "rfm_mf_opt.h"
+
 /* ---- MF fold-in: new rows of one side against the fixed other side ----------------
  * The per-example update of src/mf.py:99-108 with _update_P / _update_b_u (src/mf.py:172-216)
  * restricted to ONE side: new row r has factors x_r = d_rows[r][0..k) and bias c_r = d_bias[r]

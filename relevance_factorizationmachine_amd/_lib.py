@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("RFM_LIB_PATH") or os.path.join(PKG_DIR, "librfm_hip.s
 SOURCES = ["rfm_capi.hip", "rfm_fm.hip", "rfm_fm_plan.hip", "rfm_mf.hip", "rfm_fm_fold.hip", "rfm_fold_group.hip", "rfm_eval.hip", "rfm_csr.hip", "rfm_sample.hip", "rfm_pairs.hip", "rfm_host.cpp", "rfm_comm.cpp"]
 # every header under csrc/ (a change of any of them rebuilds every object) + the C ABI
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp"))) + [
-    os.path.join(os.path.dirname(PKG_DIR), "include", h) for h in ("rfm_hip.h", "rfm_mf_many.h", "rfm_fold_group.h", "rfm_fm_opt.h")]
+    os.path.join(os.path.dirname(PKG_DIR), "include", h) for h in ("rfm_hip.h", "rfm_mf_many.h", "rfm_fold_group.h", "rfm_fm_opt.h", "rfm_mf_opt.h")]
 
 RFM_OK, RFM_ERR_BAD_ARG, RFM_ERR_HIP, RFM_ERR_NO_DEVICE, RFM_ERR_INTERNAL = range(5)
 MF_MAX_MODELS = 1024  # RFM_MF_MAX_MODELS of include/rfm_mf_many.h
@@ -228,6 +228,14 @@ FM_OPT_SIGNATURES = {
     "rfm_fm_plan_optimizer": [_vp, _vp],
 }
 
+# the update rule of the exact MF batch step, the part of the ABI that include/rfm_mf_opt.h declares
+# (tests/test_mf_adagrad_host.py compares the two, argument by argument)
+MF_OPT_SGD, MF_OPT_ADAGRAD = FM_OPT_SGD, FM_OPT_ADAGRAD  # RFM_MF_OPT_* of include/rfm_mf_opt.h
+MF_OPT_SIGNATURES = {
+    "rfm_mf_sgd_levels_opt": SIGNATURES["rfm_mf_sgd_levels_ex"] + [_i32, _vp, _vp, _vp, _vp, _f64],
+    "rfm_mf_opt_geometry": [_vp, _i32, _i32, _vp],
+}
+
 # ``rfm_transport`` of include/rfm_hip.h: the collectives of rfm_fm_fit_dp as caller functions
 TRANSPORT_ALL_GATHER = C.CFUNCTYPE(_i32, _vp, _vp, _vp, _i64)
 TRANSPORT_ALL_REDUCE = C.CFUNCTYPE(_i32, _vp, _vp, _i64)
@@ -294,7 +302,8 @@ def load():
         lib = C.CDLL(path)
     except OSError as exc:
         raise RfmError(f"cannot load {path}: {exc}") from exc
-    for name, argtypes in {**SIGNATURES, **MF_MANY_SIGNATURES, **FOLD_GROUP_SIGNATURES, **FM_OPT_SIGNATURES}.items():
+    for name, argtypes in {**SIGNATURES, **MF_MANY_SIGNATURES, **FOLD_GROUP_SIGNATURES, **FM_OPT_SIGNATURES,
+                           **MF_OPT_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError = header/library mismatch
         fn.argtypes = argtypes
         fn.restype = _i32

@@ -190,12 +190,52 @@ __global__ __launch_bounds__(kMfBlock) void mf_loss_finish_many_kernel(const dou
                       out + int64_t(blockIdx.x) * out_stride);
 }
 
+// THE UPDATE RULE of the record form's kernels (mf_update and the bodies that call it), a type
+// parameter O.  MfSgdRule: theta -= lr * g, the text every site had before there was a choice; its
+// instantiations are that code.  MfAdaGradRule (rfm_mf_sgd_levels_opt, include/rfm_mf_opt.h): every
+// element of P, Q, b_u, b_i has an accumulator G of its own (same shapes, float64) and, with g the
+// element's gradient as the SGD text forms it,
+//   G_new = G + g * g             (the product rounded, then the sum)
+//   theta_new = theta - (lr * g) / (sqrt(G_new) + eps)
+// in IEEE basic operations, the four updates of an example in the reference's order.
+struct MfSgdRule {
+  static constexpr bool kAda = false;
+};
+struct MfAdaGradRule {
+  static constexpr bool kAda = true;
+  double* acc_P;   // [n_users][k]
+  double* acc_Q;   // [n_items][k]
+  double* acc_bu;  // [n_users]
+  double* acc_bi;  // [n_items]
+  double eps;
+};
+
+// the accumulators of one example's two rows and two biases in registers (nothing under MfSgdRule)
+template <int VEC, int NC, bool ADA>
+struct MfAccRegs {};
+template <int VEC, int NC>
+struct MfAccRegs<VEC, NC, true> {
+  Pack<VEC> gp[NC], gq[NC];
+  double gbu, gbi;
+};
+
+// one element under MfAdaGradRule; *G: its accumulator as it was read, then as it is to be written
+__device__ inline double mf_adagrad_element(double theta, double g, double lr, double eps, double* G) {
+#pragma clang fp contract(off)
+  const double gg = g * g;
+  const double gn = *G + gg;
+  *G = gn;
+  return theta - (lr * g) / (sqrt(gn) + eps);
+}
+
 // the arithmetic of one example on rows already in registers (src/mf.py:99-108,
-// 172-216): returns the residual, rows and biases are updated in place
-template <int LPR, int VEC, int NC>
+// 172-216): returns the residual, rows and biases are updated in place (acc: their accumulators,
+// MfAdaGradRule only, needed after the residual)
+template <int LPR, int VEC, int NC, class O = MfSgdRule>
 __device__ inline void mf_update(Pack<VEC> (&pp)[NC], Pack<VEC> (&pq)[NC], double& bu,
                                  double& bi, double ry, double b, double lr, double reg, int k,
-                                 int l) {
+                                 int l, const O& o = O{},
+                                 MfAccRegs<VEC, NC, O::kAda>* acc = nullptr) {
   double dot = 0.0;
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
@@ -207,19 +247,41 @@ __device__ inline void mf_update(Pack<VEC> (&pp)[NC], Pack<VEC> (&pq)[NC], doubl
   }
   dot = group_sum<LPR>(dot);
   const double err = ry - sigmoid_clipped(dot + bu + bi + b);
+  if constexpr (O::kAda) {
+    // (the four updates are independent but for the item row reading the new user row: the user's
+    // two first, then the item's two, gives the bits of the reference's order)
 #pragma unroll
-  for (int c = 0; c < NC; ++c) {
+    for (int c = 0; c < NC; ++c) {
 #pragma unroll
-    for (int v = 0; v < VEC; ++v) {
-      const double p_new = pp[c].v[v] - lr * (-err * pq[c].v[v] + reg * pp[c].v[v]);
-      // the item row sees the user row this example has just updated (src/mf.py:193)
-      const double q_new = pq[c].v[v] - lr * (-err * p_new + reg * pq[c].v[v]);
-      pp[c].v[v] = p_new;
-      pq[c].v[v] = q_new;
+      for (int v = 0; v < VEC; ++v)
+        pp[c].v[v] = mf_adagrad_element(pp[c].v[v], -err * pq[c].v[v] + reg * pp[c].v[v], lr, o.eps,
+                                        &acc->gp[c].v[v]);
     }
+    bu = mf_adagrad_element(bu, -err + reg * bu, lr, o.eps, &acc->gbu);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+#pragma unroll
+      for (int v = 0; v < VEC; ++v)
+        // the item row sees the user row this example has just updated (src/mf.py:193)
+        pq[c].v[v] = mf_adagrad_element(pq[c].v[v], -err * pp[c].v[v] + reg * pq[c].v[v], lr, o.eps,
+                                        &acc->gq[c].v[v]);
+    }
+    bi = mf_adagrad_element(bi, -err + reg * bi, lr, o.eps, &acc->gbi);
+  } else {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) {
+        const double p_new = pp[c].v[v] - lr * (-err * pq[c].v[v] + reg * pp[c].v[v]);
+        // the item row sees the user row this example has just updated (src/mf.py:193)
+        const double q_new = pq[c].v[v] - lr * (-err * p_new + reg * pq[c].v[v]);
+        pp[c].v[v] = p_new;
+        pq[c].v[v] = q_new;
+      }
+    }
+    bu = bu - lr * (-err + reg * bu);
+    bi = bi - lr * (-err + reg * bi);
   }
-  bu = bu - lr * (-err + reg * bu);
-  bi = bi - lr * (-err + reg * bi);
 }
 
 template <int LPR, int VEC, int NC>
@@ -228,6 +290,20 @@ __device__ inline void mf_load_row(Pack<VEC> (&dst)[NC], const double* row, int 
   for (int c = 0; c < NC; ++c) {
     const int f = (c * LPR + l) * VEC;
     dst[c].load(row + (f < k ? f : 0));
+  }
+}
+
+// an accumulator row (memory or LDS): a chunk past k is not read -- its lanes compute on zeros and
+// store nothing -- so every chunk's address is the row's plus a constant and none is kept in
+// registers of its own (mf_load_row's clamped addresses are: two registers a chunk and row)
+template <int LPR, int VEC, int NC>
+__device__ inline void mf_load_acc_row(Pack<VEC> (&dst)[NC], const double* row, int k, int l) {
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const int f = (c * LPR + l) * VEC;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) dst[c].v[v] = 0.0;
+    if (f < k) dst[c].load(row + f);
   }
 }
 
@@ -329,6 +405,21 @@ struct MfExArgs {
   double lr, reg;
 };
 
+// the argument block of a kernel under a rule: MfSgdRule's is MfExArgs itself
+struct MfExArgsOpt : MfExArgs {
+  MfAdaGradRule o;
+};
+template <class O>
+struct MfExArgsOf {
+  using type = MfExArgs;
+};
+template <>
+struct MfExArgsOf<MfAdaGradRule> {
+  using type = MfExArgsOpt;
+};
+__device__ inline MfSgdRule rule_of(const MfExArgs&) { return MfSgdRule{}; }
+__device__ inline const MfAdaGradRule& rule_of(const MfExArgsOpt& a) { return a.o; }
+
 // where a record's label / propensity comes from: the record itself (one model), or the model's
 // own vector over the training log through the record's row (several models on one schedule)
 struct RyOfRecord {
@@ -344,8 +435,8 @@ struct RyOfModel {
 
 // one level, many workgroups (examples of a level touch disjoint rows); blockIdx.x / gridDim.x
 // walk the level
-template <int LPR, int VEC, int NC, class Ry>
-__device__ __forceinline__ void mf_wide_ex_body(const MfExArgs& a, Ry ry_of) {
+template <int LPR, int VEC, int NC, class Ry, class O = MfSgdRule>
+__device__ __forceinline__ void mf_wide_ex_body(const MfExArgs& a, Ry ry_of, const O& o = O{}) {
   constexpr int GPB = kMfBlock / LPR;
   const int l = threadIdx.x % LPR;
   const int g = threadIdx.x / LPR;
@@ -357,7 +448,23 @@ __device__ __forceinline__ void mf_wide_ex_body(const MfExArgs& a, Ry ry_of) {
     mf_load_row<LPR, VEC, NC>(pp, a.P + int64_t(e.u) * k, k, l);
     mf_load_row<LPR, VEC, NC>(pq, a.Q + int64_t(e.i) * k, k, l);
     double bu = a.bu[e.u], bi = a.bi[e.i];
-    mf_update<LPR, VEC, NC>(pp, pq, bu, bi, ry_of(int32_t(idx), e.ry), a.b, a.lr, a.reg, k, l);
+    if constexpr (O::kAda) {
+      // the two accumulator rows and the two bias accumulators beside the parameter rows
+      MfAccRegs<VEC, NC, true> acc;
+      mf_load_acc_row<LPR, VEC, NC>(acc.gp, o.acc_P + int64_t(e.u) * k, k, l);
+      mf_load_acc_row<LPR, VEC, NC>(acc.gq, o.acc_Q + int64_t(e.i) * k, k, l);
+      acc.gbu = o.acc_bu[e.u];
+      acc.gbi = o.acc_bi[e.i];
+      mf_update<LPR, VEC, NC, O>(pp, pq, bu, bi, ry_of(int32_t(idx), e.ry), a.b, a.lr, a.reg, k, l, o, &acc);
+      mf_store_row<LPR, VEC, NC>(acc.gp, o.acc_P + int64_t(e.u) * k, k, l);
+      mf_store_row<LPR, VEC, NC>(acc.gq, o.acc_Q + int64_t(e.i) * k, k, l);
+      if (l == 0) {
+        o.acc_bu[e.u] = acc.gbu;
+        o.acc_bi[e.i] = acc.gbi;
+      }
+    } else {
+      mf_update<LPR, VEC, NC>(pp, pq, bu, bi, ry_of(int32_t(idx), e.ry), a.b, a.lr, a.reg, k, l);
+    }
     mf_store_row<LPR, VEC, NC>(pp, a.P + int64_t(e.u) * k, k, l);
     mf_store_row<LPR, VEC, NC>(pq, a.Q + int64_t(e.i) * k, k, l);
     if (l == 0) {
@@ -367,9 +474,9 @@ __device__ __forceinline__ void mf_wide_ex_body(const MfExArgs& a, Ry ry_of) {
   }
 }
 
-template <int LPR, int VEC, int NC>
-__global__ __launch_bounds__(kMfBlock) void mf_sgd_wide_ex_kernel(MfExArgs a) {
-  mf_wide_ex_body<LPR, VEC, NC>(a, RyOfRecord{});
+template <int LPR, int VEC, int NC, class O = MfSgdRule>
+__global__ __launch_bounds__(kMfBlock) void mf_sgd_wide_ex_kernel(typename MfExArgsOf<O>::type a) {
+  mf_wide_ex_body<LPR, VEC, NC, RyOfRecord, O>(a, RyOfRecord{}, rule_of(a));
 }
 
 // Several models on one schedule (rfm_mf_sgd_levels_many): the records, level pointers and cached
@@ -451,9 +558,16 @@ struct MfSlot {
 struct MfSeqLds {
   const int32_t* lptr;  // [n_lev + 1], relative to the chunk's first record
   const MfEx* exs;      // [n_rec]
-  double* qcache;       // [n_cached][k+2]: item row, item bias, pad
+  double* qcache;       // [n_cached][k+2]: item row, item bias, pad (MfAdaGradRule: [n_cached][2][k+2],
+                        // the same of the item's accumulators behind it)
   int32_t n_lev;
 };
+
+// doubles of one cached item in LDS under rule O
+template <class O>
+__device__ __forceinline__ int mf_cache_width(int k) {
+  return O::kAda ? 2 * (k + 2) : k + 2;
+}
 
 // what lane group g runs at chunk level t, and its rows if they may be read now: the
 // user row is final when its previous writer lies more than `ahead` levels back
@@ -484,9 +598,13 @@ __device__ __forceinline__ void mf_slot_fetch(const MfExArgs& a, const MfSeqLds&
   }
 }
 
-template <int LPR, int VEC, int NC>
+// (MfAdaGradRule: the accumulators are not in the ring.  They are requested here, behind whatever
+// parameter rows are still to be read, and are needed only after the residual, so their latency
+// lies beside the dot product, the lane-group sum and the sigmoid; an accumulator row has the
+// writer of its parameter row, so it is final here as that row is.)
+template <int LPR, int VEC, int NC, class O = MfSgdRule>
 __device__ __forceinline__ void mf_slot_run(const MfExArgs& a, const MfSeqLds& m, int l,
-                                            MfSlot<VEC, NC>& s) {
+                                            MfSlot<VEC, NC>& s, const O& o = O{}) {
   if (!s.has) return;
   const int k = a.k;
   const MfEx e = s.e;
@@ -498,7 +616,7 @@ __device__ __forceinline__ void mf_slot_run(const MfExArgs& a, const MfSeqLds& m
     mf_load_row<LPR, VEC, NC>(s.pq, a.Q + int64_t(e.i) * k, k, l);
     s.bi = a.bi[e.i];
   }
-  double* crow = m.qcache + (e.cslot >= 0 ? e.cslot : 0) * (k + 2);
+  double* crow = m.qcache + (e.cslot >= 0 ? e.cslot : 0) * mf_cache_width<O>(k);
   if (e.cslot >= 0) {
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
@@ -507,7 +625,35 @@ __device__ __forceinline__ void mf_slot_run(const MfExArgs& a, const MfSeqLds& m
     }
     s.bi = crow[k];
   }
-  mf_update<LPR, VEC, NC>(s.pp, s.pq, s.bu, s.bi, e.ry, a.b, a.lr, a.reg, k, l);
+  if constexpr (O::kAda) {
+    MfAccRegs<VEC, NC, true> acc;
+    double* grow = crow + (k + 2);  // a cached item's accumulators
+    mf_load_acc_row<LPR, VEC, NC>(acc.gp, o.acc_P + int64_t(e.u) * k, k, l);
+    acc.gbu = o.acc_bu[e.u];
+    if (e.cslot >= 0) {
+      mf_load_acc_row<LPR, VEC, NC>(acc.gq, grow, k, l);
+      acc.gbi = grow[k];
+    } else {
+      mf_load_acc_row<LPR, VEC, NC>(acc.gq, o.acc_Q + int64_t(e.i) * k, k, l);
+      acc.gbi = o.acc_bi[e.i];
+    }
+    mf_update<LPR, VEC, NC, O>(s.pp, s.pq, s.bu, s.bi, e.ry, a.b, a.lr, a.reg, k, l, o, &acc);
+    mf_store_row<LPR, VEC, NC>(acc.gp, o.acc_P + int64_t(e.u) * k, k, l);
+    if (l == 0) o.acc_bu[e.u] = acc.gbu;
+    if (e.cslot >= 0) {
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        const int f = (c * LPR + l) * VEC;
+        if (f < k) acc.gq[c].store(grow + f);
+      }
+      if (l == 0) grow[k] = acc.gbi;
+    } else {
+      mf_store_row<LPR, VEC, NC>(acc.gq, o.acc_Q + int64_t(e.i) * k, k, l);
+      if (l == 0) o.acc_bi[e.i] = acc.gbi;
+    }
+  } else {
+    mf_update<LPR, VEC, NC>(s.pp, s.pq, s.bu, s.bi, e.ry, a.b, a.lr, a.reg, k, l);
+  }
   mf_store_row<LPR, VEC, NC>(s.pp, a.P + int64_t(e.u) * k, k, l);
   if (l == 0) a.bu[e.u] = s.bu;
   if (e.cslot >= 0) {
@@ -530,16 +676,33 @@ __device__ __forceinline__ void mf_slot_run(const MfExArgs& a, const MfSeqLds& m
 // groups then, and more than four chunks run without the ring)
 constexpr int seq_block(int nc) { return nc > 1 ? 512 : kSeqBlock; }
 
-template <int LPR, int VEC, int NC, class Ry>
-__device__ __forceinline__ void mf_seq_ex_body(const MfExArgs& a, Ry ry_of) {
+// Slots of the read-ahead ring under MfAdaGradRule, by shape class.  The accumulators of the running
+// example (as many registers as its two rows and biases) and the root and quotient come on top of
+// the ring, and no instantiation may spill (profiles/n23/register_counts.txt): at one chunk of two
+// factors per lane the 1024-thread workgroup has 128 registers a lane and MfSgdRule's ring of four
+// takes 116 of them, so two slots; at four chunks three slots.
+constexpr int mf_ada_ring(int vec, int nc) {
+  return nc > 4 ? 0 : nc == 4 ? 3 : (vec == 2 && nc == 1) ? 2 : kMfAhead;
+}
+// Threads of the sequential workgroup under a rule.  The level limit (seq_block(nc) / LPR examples)
+// is the schedule's and does not depend on the rule; at sixteen chunks a lane the four rows of an
+// AdaGrad example and the residual's constants do not fit the 256 registers of a 512-thread
+// workgroup, so that class runs 256 threads and a lane group takes its level in two passes.
+template <class O>
+constexpr int mf_seq_threads(int nc) {
+  return O::kAda && nc > 8 ? 256 : seq_block(nc);
+}
+
+template <int LPR, int VEC, int NC, class Ry, class O = MfSgdRule>
+__device__ __forceinline__ void mf_seq_ex_body(const MfExArgs& a, Ry ry_of, const O& o = O{}) {
   extern __shared__ double seq_lds[];
-  constexpr int kSeqBlock = seq_block(NC);  // (shadows the one-chunk constant inside this kernel)
+  constexpr int kSeqBlock = mf_seq_threads<O>(NC);  // (shadows the one-chunk constant inside this kernel)
   // rows wider than four chunks per lane leave no registers for a ring of them
   constexpr bool PF = NC <= 4;
   const int l = threadIdx.x % LPR;
   const int g = threadIdx.x / LPR;
   const int k = a.k;
-  const int cw = k + 2;
+  const int cw = mf_cache_width<O>(k);
   const int n_lev = a.hi - a.lo;
   const int n_rec = a.rec_hi - a.rec_lo;
   int32_t* lptr = reinterpret_cast<int32_t*>(seq_lds);
@@ -560,52 +723,101 @@ __device__ __forceinline__ void mf_seq_ex_body(const MfExArgs& a, Ry ry_of) {
   for (int i = threadIdx.x; i < a.n_cached * cw; i += kSeqBlock) {
     const int c = i / cw, f = i % cw;
     const int32_t item = a.cache_items[c];
-    qcache[i] = f < k ? a.Q[int64_t(item) * k + f] : (f == k ? a.bi[item] : 0.0);
+    if constexpr (O::kAda) {
+      // the item's row, bias and pad, then the same of its accumulators
+      const int h = f / (k + 2), ff = f % (k + 2);
+      const double* rows = h ? o.acc_Q : a.Q;
+      const double* bias = h ? o.acc_bi : a.bi;
+      qcache[i] = ff < k ? rows[int64_t(item) * k + ff] : (ff == k ? bias[item] : 0.0);
+    } else {
+      qcache[i] = f < k ? a.Q[int64_t(item) * k + f] : (f == k ? a.bi[item] : 0.0);
+    }
   }
   __syncthreads();
   const MfSeqLds m{lptr, exs, qcache, n_lev};
 
   MfSlot<VEC, NC> s0, s1, s2, s3;
-  // every level before lo has run, so the first level's rows are final; a row of one
-  // of the next levels is final if its previous writer lies before this launch
-  mf_slot_fetch<LPR, VEC, NC, PF>(a, m, 0, g, l, 0, s0);
-  mf_slot_fetch<LPR, VEC, NC, PF>(a, m, 1, g, l, 1, s1);
-  mf_slot_fetch<LPR, VEC, NC, PF>(a, m, 2, g, l, 2, s2);
-  mf_slot_fetch<LPR, VEC, NC, PF>(a, m, 3, g, l, 3, s3);
-  for (int t = 0; t < n_lev; t += kMfAhead) {
-    // the rows of level t+4 are read while level t is still running: final if the
-    // previous writer lies before level t, i.e. more than four levels back
-    mf_slot_run<LPR, VEC, NC>(a, m, l, s0);
-    mf_slot_fetch<LPR, VEC, NC, PF>(a, m, t + 4, g, l, kMfAhead, s0);
-    __syncthreads();
-    if (t + 1 >= n_lev) break;
-    mf_slot_run<LPR, VEC, NC>(a, m, l, s1);
-    mf_slot_fetch<LPR, VEC, NC, PF>(a, m, t + 5, g, l, kMfAhead, s1);
-    __syncthreads();
-    if (t + 2 >= n_lev) break;
-    mf_slot_run<LPR, VEC, NC>(a, m, l, s2);
-    mf_slot_fetch<LPR, VEC, NC, PF>(a, m, t + 6, g, l, kMfAhead, s2);
-    __syncthreads();
-    if (t + 3 >= n_lev) break;
-    mf_slot_run<LPR, VEC, NC>(a, m, l, s3);
-    mf_slot_fetch<LPR, VEC, NC, PF>(a, m, t + 7, g, l, kMfAhead, s3);
-    __syncthreads();
+  if constexpr (O::kAda) {
+    // the same walk with a ring of as many slots as the class's registers hold beside the
+    // accumulators (mf_ada_ring): the rows of level t + D are read while level t is still running,
+    // final if the previous writer lies more than D levels back; D = 0 reads every row where it is used
+    constexpr int D = mf_ada_ring(VEC, NC);
+    if constexpr (D > 0) {
+      MfSlot<VEC, NC> s[D];
+#pragma unroll
+      for (int d = 0; d < D; ++d) mf_slot_fetch<LPR, VEC, NC, true>(a, m, d, g, l, d, s[d]);
+      for (int t = 0; t < n_lev; t += D) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+          if (t + d >= n_lev) break;
+          mf_slot_run<LPR, VEC, NC, O>(a, m, l, s[d], o);
+          mf_slot_fetch<LPR, VEC, NC, true>(a, m, t + d + D, g, l, D, s[d]);
+          __syncthreads();
+        }
+      }
+    } else {
+      // (a level holds up to seq_block(NC) / LPR examples whatever the workgroup's size)
+      MfSlot<VEC, NC> s;
+      for (int t = 0; t < n_lev; ++t) {
+        for (int gg = g; gg < seq_block(NC) / LPR; gg += kSeqBlock / LPR) {
+          mf_slot_fetch<LPR, VEC, NC, false>(a, m, t, gg, l, 0, s);
+          mf_slot_run<LPR, VEC, NC, O>(a, m, l, s, o);
+        }
+        __syncthreads();
+      }
+    }
+  } else {
+    // every level before lo has run, so the first level's rows are final; a row of one
+    // of the next levels is final if its previous writer lies before this launch
+    mf_slot_fetch<LPR, VEC, NC, PF>(a, m, 0, g, l, 0, s0);
+    mf_slot_fetch<LPR, VEC, NC, PF>(a, m, 1, g, l, 1, s1);
+    mf_slot_fetch<LPR, VEC, NC, PF>(a, m, 2, g, l, 2, s2);
+    mf_slot_fetch<LPR, VEC, NC, PF>(a, m, 3, g, l, 3, s3);
+    for (int t = 0; t < n_lev; t += kMfAhead) {
+      // the rows of level t+4 are read while level t is still running: final if the
+      // previous writer lies before level t, i.e. more than four levels back
+      mf_slot_run<LPR, VEC, NC, O>(a, m, l, s0, o);
+      mf_slot_fetch<LPR, VEC, NC, PF>(a, m, t + 4, g, l, kMfAhead, s0);
+      __syncthreads();
+      if (t + 1 >= n_lev) break;
+      mf_slot_run<LPR, VEC, NC, O>(a, m, l, s1, o);
+      mf_slot_fetch<LPR, VEC, NC, PF>(a, m, t + 5, g, l, kMfAhead, s1);
+      __syncthreads();
+      if (t + 2 >= n_lev) break;
+      mf_slot_run<LPR, VEC, NC, O>(a, m, l, s2, o);
+      mf_slot_fetch<LPR, VEC, NC, PF>(a, m, t + 6, g, l, kMfAhead, s2);
+      __syncthreads();
+      if (t + 3 >= n_lev) break;
+      mf_slot_run<LPR, VEC, NC, O>(a, m, l, s3, o);
+      mf_slot_fetch<LPR, VEC, NC, PF>(a, m, t + 7, g, l, kMfAhead, s3);
+      __syncthreads();
+    }
   }
   __syncthreads();
   // write the cached item rows back
   for (int i = threadIdx.x; i < a.n_cached * cw; i += kSeqBlock) {
     const int c = i / cw, f = i % cw;
     const int32_t item = a.cache_items[c];
-    if (f < k)
-      a.Q[int64_t(item) * k + f] = qcache[i];
-    else if (f == k)
-      a.bi[item] = qcache[i];
+    if constexpr (O::kAda) {
+      const int h = f / (k + 2), ff = f % (k + 2);
+      double* rows = h ? o.acc_Q : a.Q;
+      double* bias = h ? o.acc_bi : a.bi;
+      if (ff < k)
+        rows[int64_t(item) * k + ff] = qcache[i];
+      else if (ff == k)
+        bias[item] = qcache[i];
+    } else {
+      if (f < k)
+        a.Q[int64_t(item) * k + f] = qcache[i];
+      else if (f == k)
+        a.bi[item] = qcache[i];
+    }
   }
 }
 
-template <int LPR, int VEC, int NC>
-__global__ __launch_bounds__(seq_block(NC)) void mf_sgd_seq_ex_kernel(MfExArgs a) {
-  mf_seq_ex_body<LPR, VEC, NC>(a, RyOfRecord{});
+template <int LPR, int VEC, int NC, class O = MfSgdRule>
+__global__ __launch_bounds__(mf_seq_threads<O>(NC)) void mf_sgd_seq_ex_kernel(typename MfExArgsOf<O>::type a) {
+  mf_seq_ex_body<LPR, VEC, NC, RyOfRecord, O>(a, RyOfRecord{}, rule_of(a));
 }
 
 // the chain of every model, ONE sequential workgroup each: blockIdx.x is the model
@@ -616,9 +828,9 @@ __global__ __launch_bounds__(seq_block(NC)) void mf_sgd_seq_many_kernel(MfManyAr
 }
 
 // the sequential kernels with their dynamic-LDS limit raised where the item cache needs it
-template <int L, int Vv, int N>
-static void launch_seq_ex(rfm_ctx* ctx, const MfExArgs& a, int threads, size_t lds) {
-  const auto kern = &mf_sgd_seq_ex_kernel<L, Vv, N>;
+template <int L, int Vv, int N, class O = MfSgdRule>
+static void launch_seq_ex(rfm_ctx* ctx, const typename MfExArgsOf<O>::type& a, int threads, size_t lds) {
+  const auto kern = &mf_sgd_seq_ex_kernel<L, Vv, N, O>;
   static LdsLimits allowed;
   allow_dynamic_lds(ctx, reinterpret_cast<const void*>(kern), lds, allowed);
   hipLaunchKernelGGL(kern, dim3(1), dim3(threads), lds, ctx->stream, a);
@@ -1017,21 +1229,28 @@ int32_t rfm_mf_cache_capacity(int32_t n_factors, int32_t* h_out) {
   });
 }
 
-int32_t rfm_mf_sgd_levels_ex(rfm_ctx* ctx, const void* d_ex, const int32_t* h_level_ptr,
-                             const int32_t* d_level_ptr, int32_t n_levels,
-                             const int32_t* d_cache_items, int32_t n_cached, double* d_P,
-                             double* d_Q, double* d_bu, double* d_bi, double b,
-                             int32_t n_factors, double lr, double reg) {
+}  // extern "C"
+
+// rfm_mf_sgd_levels_ex (MfSgdRule) and rfm_mf_sgd_levels_opt under either rule: one schedule, one
+// launch plan; an item cached under MfAdaGradRule takes twice the LDS (its accumulators)
+template <class O>
+static int32_t mf_levels_ex(rfm_ctx* ctx, const void* d_ex, const int32_t* h_level_ptr,
+                            const int32_t* d_level_ptr, int32_t n_levels,
+                            const int32_t* d_cache_items, int32_t n_cached, double* d_P,
+                            double* d_Q, double* d_bu, double* d_bi, double b,
+                            int32_t n_factors, double lr, double reg, const O& o) {
   return guarded([&] {
     RFM_REQUIRE(ctx && d_ex && h_level_ptr && d_level_ptr, "null pointer");
     RFM_REQUIRE(n_levels >= 0 && n_cached >= 0 && (n_cached == 0 || d_cache_items),
                 "bad schedule");
     const Shape s = shape_for(n_factors);
-    const size_t cache_bytes = size_t(n_cached) * size_t(n_factors + 2) * sizeof(double);
-    RFM_REQUIRE(cache_bytes <= size_t(kSeqMaxCacheBytes),
+    const size_t row_bytes = size_t(n_cached) * size_t(n_factors + 2) * sizeof(double);
+    RFM_REQUIRE(row_bytes <= size_t(kSeqMaxCacheBytes),
                 "item cache of %d rows exceeds %d bytes of LDS", n_cached, kSeqMaxCacheBytes);
-    MfExArgs a{};
+    const size_t cache_bytes = row_bytes * (O::kAda ? 2 : 1);
+    typename MfExArgsOf<O>::type a{};
     set_model(a, d_P, d_Q, d_bu, d_bi, b, n_factors, lr, reg);
+    if constexpr (O::kAda) a.o = o;
     a.ex = static_cast<const MfEx*>(d_ex);
     a.level_ptr = d_level_ptr;
     a.cache_items = d_cache_items;
@@ -1046,7 +1265,7 @@ int32_t rfm_mf_sgd_levels_ex(rfm_ctx* ctx, const void* d_ex, const int32_t* h_le
           a.hi = rec_hi;
           const int grid = capped_grid(ctx, rec_hi - rec_lo, kMfBlock / s.lpr, 8, 0);
 #define RFM_CALL_WIDE_EX(L, Vv, N)                                                            \
-  hipLaunchKernelGGL((mf_sgd_wide_ex_kernel<L, Vv, N>), dim3(grid), dim3(kMfBlock), 0,        \
+  hipLaunchKernelGGL((mf_sgd_wide_ex_kernel<L, Vv, N, O>), dim3(grid), dim3(kMfBlock), 0,     \
                      ctx->stream, a)
           RFM_FOR_SHAPE(s, RFM_CALL_WIDE_EX);
 #undef RFM_CALL_WIDE_EX
@@ -1058,11 +1277,60 @@ int32_t rfm_mf_sgd_levels_ex(rfm_ctx* ctx, const void* d_ex, const int32_t* h_le
           a.rec_hi = h_level_ptr[lev_hi];
           const size_t lds = size_t((lev_hi - lev_lo + 2) / 2) * 8 +
                              size_t(a.rec_hi - a.rec_lo) * sizeof(MfEx) + cache_bytes;
-#define RFM_CALL_SEQ_EX(L, Vv, N) launch_seq_ex<L, Vv, N>(ctx, a, seq_threads, lds)
+#define RFM_CALL_SEQ_EX(L, Vv, N) launch_seq_ex<L, Vv, N, O>(ctx, a, mf_seq_threads<O>(N), lds)
           RFM_FOR_SHAPE(s, RFM_CALL_SEQ_EX);
 #undef RFM_CALL_SEQ_EX
         });
     RFM_HIP_CHECK(hipGetLastError());
+  });
+}
+
+extern "C" {
+
+int32_t rfm_mf_sgd_levels_ex(rfm_ctx* ctx, const void* d_ex, const int32_t* h_level_ptr,
+                             const int32_t* d_level_ptr, int32_t n_levels,
+                             const int32_t* d_cache_items, int32_t n_cached, double* d_P,
+                             double* d_Q, double* d_bu, double* d_bi, double b,
+                             int32_t n_factors, double lr, double reg) {
+  return mf_levels_ex(ctx, d_ex, h_level_ptr, d_level_ptr, n_levels, d_cache_items, n_cached, d_P, d_Q,
+                      d_bu, d_bi, b, n_factors, lr, reg, MfSgdRule{});
+}
+
+int32_t rfm_mf_sgd_levels_opt(rfm_ctx* ctx, const void* d_ex, const int32_t* h_level_ptr,
+                              const int32_t* d_level_ptr, int32_t n_levels,
+                              const int32_t* d_cache_items, int32_t n_cached, double* d_P,
+                              double* d_Q, double* d_bu, double* d_bi, double b,
+                              int32_t n_factors, double lr, double reg, int32_t kind,
+                              double* d_acc_P, double* d_acc_Q, double* d_acc_bu, double* d_acc_bi,
+                              double eps) {
+  if (kind == RFM_MF_OPT_SGD)
+    return rfm_mf_sgd_levels_ex(ctx, d_ex, h_level_ptr, d_level_ptr, n_levels, d_cache_items, n_cached,
+                                d_P, d_Q, d_bu, d_bi, b, n_factors, lr, reg);
+  const int32_t rc = guarded([&] {
+    RFM_REQUIRE(kind == RFM_MF_OPT_ADAGRAD, "optimizer kind %d is neither SGD nor AdaGrad", kind);
+    RFM_REQUIRE(d_acc_P && d_acc_Q && d_acc_bu && d_acc_bi, "AdaGrad with a null accumulator");
+    RFM_REQUIRE(eps > 0.0, "AdaGrad eps must be > 0");  // (false for a NaN)
+  });
+  if (rc != RFM_OK) return rc;
+  return mf_levels_ex(ctx, d_ex, h_level_ptr, d_level_ptr, n_levels, d_cache_items, n_cached, d_P, d_Q,
+                      d_bu, d_bi, b, n_factors, lr, reg,
+                      MfAdaGradRule{d_acc_P, d_acc_Q, d_acc_bu, d_acc_bi, eps});
+}
+
+int32_t rfm_mf_opt_geometry(const rfm_ctx*, int32_t kind, int32_t n_factors, int32_t* h_out7) {
+  return guarded([&] {
+    RFM_REQUIRE(h_out7, "null pointer");
+    RFM_REQUIRE(kind == RFM_MF_OPT_SGD || kind == RFM_MF_OPT_ADAGRAD,
+                "optimizer kind %d is neither SGD nor AdaGrad", kind);
+    const Shape s = shape_for(n_factors);
+    const bool ada = kind == RFM_MF_OPT_ADAGRAD;
+    h_out7[0] = s.lpr;
+    h_out7[1] = s.vec;
+    h_out7[2] = s.nc;
+    h_out7[3] = ada ? mf_seq_threads<MfAdaGradRule>(s.nc) : seq_block(s.nc);
+    h_out7[4] = 0;  // the accumulators are read where they are used, in every class
+    h_out7[5] = (n_factors + 2) * int32_t(sizeof(double)) * (ada ? 2 : 1);
+    h_out7[6] = ada ? mf_ada_ring(s.vec, s.nc) : (s.nc <= 4 ? kMfAhead : 0);
   });
 }
 

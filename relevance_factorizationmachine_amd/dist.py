@@ -380,6 +380,11 @@ def hip_mf_partition_worker(rt, model, train: dict, world: int, rank: int, all_r
     from .mf import DevicePairs
     from .runtime import mf_cache_capacity, mf_schedule_ex, sample_batches
 
+    if getattr(model, "optimizer", "sgd") != "sgd":
+        # (the replicas' changes of Q / b_i are added up: a sum of steps, not of gradients; AdaGrad
+        # there is not built: DESIGN.md 8 N20)
+        raise ValueError(f"the user-partitioned MF fit applies the SGD rule only, the model's optimizer is "
+                         f"{model.optimizer!r}")
     tr = DevicePairs(rt, train["features"])
     h_y = np.ascontiguousarray(train["labels"], dtype=np.float64)
     h_p = np.ascontiguousarray(train["pscores"], dtype=np.float64)

@@ -18,7 +18,7 @@ import numpy as np
 from . import _lib, fold
 from .base import LOSS_EPS, PointwiseBaseRecommender
 from .evaluate import EvalLoop, FitHook, device_frame
-from .optimizer import DeviceSGD
+from .optimizer import DeviceAdaGrad, DeviceSGD
 from .runtime import BatchIdStream, Runtime, mf_cache_capacity, mf_schedule_ex, mf_schedule_rows
 
 
@@ -184,6 +184,14 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
     # Not a constructor argument: a ValEvaluator-like ``evaluator`` (see evaluate.py) is
     # computed on the device; False keeps the host callback for every evaluator.
     device_evaluator = True
+    # Not constructor arguments: the update rule of fit() -- "sgd" (the reference's, theta -= lr * g)
+    # or "adagrad" (G += g * g; theta -= lr * g / (sqrt(G) + adagrad_eps) for each of an example's four
+    # updates in the reference's order, accumulators G of the parameters' shapes that start at
+    # adagrad_init and persist across fit() calls: DESIGN §8 N20).  Exact mode only; fit_many, the
+    # user-partitioned fit and fold-in take the SGD step only.
+    optimizer = "sgd"
+    adagrad_eps = 1e-10
+    adagrad_init = 0.0
 
     def __post_init__(self) -> None:
         # src/mf.py:34-66 -- the reference's NumPy calls, in its draw order
@@ -213,9 +221,28 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
             raise IndexError("item id out of range")
 
     # ------------------------------------------------------------------ fit
+    def _take_optimizer(self) -> bool:
+        """Checks ``optimizer``; with "adagrad" the four handles become ``DeviceAdaGrad`` on the
+        same device tensors (once: the accumulators persist).  True for AdaGrad."""
+        if self.optimizer not in ("sgd", "adagrad"):
+            raise ValueError(f"optimizer must be 'sgd' or 'adagrad', got {self.optimizer!r}")
+        if self.optimizer == "sgd":
+            return False
+        if not float(self.adagrad_eps) > 0.0:
+            raise ValueError(f"adagrad_eps={self.adagrad_eps!r} must be > 0")
+        if self.hogwild:
+            raise ValueError("optimizer = 'adagrad' runs in exact mode only (hogwild = True has no order)")
+        for name in ("P", "Q", "b_u", "b_i"):
+            h = getattr(self, name)
+            if not isinstance(h, DeviceAdaGrad):
+                setattr(self, name, DeviceAdaGrad(self._rt, None, h.lr, self.adagrad_eps, self.adagrad_init,
+                                                  dev=h.dev))
+        return True
+
     def fit(self, train: dict, val: dict) -> tuple:
         """src/mf.py:68-134."""
         rt = self._rt
+        self._take_optimizer()
         # global bias: mean of the training labels (src/mf.py:84)
         self.b = np.mean(train["labels"])
         n_rows = int(np.asarray(train["features"]).shape[0])
@@ -248,6 +275,7 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
         params = (self.P.dev.data_ptr(), self.Q.dev.data_ptr(), self.b_u.dev.data_ptr(),
                   self.b_i.dev.data_ptr())
         b = float(self.b)
+        adagrad = self._take_optimizer()
         h_y = np.ascontiguousarray(train["labels"], dtype=np.float64)
         h_p = np.ascontiguousarray(train["pscores"], dtype=np.float64)
         # item rows the sequential kernel may keep in LDS (rows + bias, 32 KiB)
@@ -304,6 +332,18 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
                     self.n_factors, float(self.lr), float(self.reg)))
                 done()
                 after_sgd(epoch, ids_ptr)
+
+            if adagrad:
+                # the same schedule under the other rule (rfm_mf_sgd_levels_opt)
+                accs = tuple(h.acc.data_ptr() for h in (self.P, self.Q, self.b_u, self.b_i))
+
+                def step(epoch, ids_ptr, d_ex, h_lptr, d_lptr, n_levels, d_cache, n_cached, _d_rows, done):  # noqa: F811
+                    _lib.check(rt.lib.rfm_mf_sgd_levels_opt(
+                        rt.ctx, d_ex, h_lptr, d_lptr, n_levels, d_cache, n_cached, *params, b,
+                        self.n_factors, float(self.lr), float(self.reg), _lib.MF_OPT_ADAGRAD, *accs,
+                        float(self.adagrad_eps)))
+                    done()
+                    after_sgd(epoch, ids_ptr)
 
             pipe.run(self._epochs(id_stream), schedule, step)
         rt.sync()
@@ -368,7 +408,9 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
         takes it: the user column of ``features`` holds new-user indices 0..n_new-1, the item column
         known item ids; a user's examples are taken in input order, ``n_passes`` times.  ``init``:
         ``(rows [n_new, k], bias [n_new])`` to start from (default zeros).  The model is not
-        written; serve the result through ``new_users=`` or ``append_users`` it.
+        written; serve the result through ``new_users=`` or ``append_users`` it.  That is the SGD
+        step whatever ``optimizer`` the model was fitted with: a new row has no history of gradients,
+        and ``append_users`` starts its accumulators at ``adagrad_init``.
         ``group``: where the examples are grouped by user -- "host" (NumPy, then
         uploaded), "device" (``rfm_fold_group``; the pieces of ``data`` may be tensors on the device,
         host pieces are uploaded as they are), None: "device" if ``data["features"]`` is a device
@@ -393,13 +435,15 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
         return np.arange(first, first + len(folded))
 
     def append_users(self, folded: FoldedRows) -> np.ndarray:
-        """Grows ``P, b_u`` and ``n_users`` by folded user rows; returns their user ids."""
+        """Grows ``P, b_u`` and ``n_users`` by folded user rows (and, under ``optimizer = "adagrad"``,
+        their accumulators by ``adagrad_init``); returns their user ids."""
         ids = self._append(folded, "user", self.P, self.b_u)
         self.n_users += len(folded)
         return ids
 
     def append_items(self, folded: FoldedRows) -> np.ndarray:
-        """Grows ``Q, b_i`` and ``n_items`` by folded item rows; returns their item ids."""
+        """Grows ``Q, b_i`` and ``n_items`` by folded item rows (and, under ``optimizer = "adagrad"``,
+        their accumulators by ``adagrad_init``); returns their item ids."""
         ids = self._append(folded, "item", self.Q, self.b_i)
         self.n_items += len(folded)
         return ids
@@ -477,7 +521,7 @@ def fit_many(models, train, val) -> list:
     every iteration (``resample(..., random_state=epoch)``, ``src/mf.py:88-95``) and share the level
     schedule, which is derived and uploaded once per iteration (``rfm_mf_schedule_rows``,
     ``rfm_mf_sgd_levels_many``).  They may differ in ``seed``, ``alpha``, ``lr``, ``reg``,
-    ``estimator``, labels, propensities and evaluator instance.  Exact mode only; an evaluator must
+    ``estimator``, labels, propensities and evaluator instance.  Exact mode and the SGD rule only; an evaluator must
     be one the device computes (``evaluate.recognise``) -- anything else is a ``ValueError``."""
     from .evaluate import CatalogueValEvaluator, recognise
 
@@ -498,6 +542,9 @@ def fit_many(models, train, val) -> list:
             raise ValueError(f"fit_many: the models differ in {name}")
     if any(m.hogwild for m in models):
         raise ValueError("fit_many: hogwild = True has no order to share; use fit()")
+    if any(m.optimizer != "sgd" for m in models):
+        # (rfm_mf_model is a fixed ABI struct without accumulators: DESIGN.md 8 N20)
+        raise ValueError("fit_many applies the SGD rule only; fit() a model whose optimizer is 'adagrad'")
     _same_features(trains, "train")
     _same_features(vals, "val")
     with_ev = [m.evaluator is not None for m in models]

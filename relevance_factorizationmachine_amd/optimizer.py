@@ -7,8 +7,9 @@ moves them to the host when a caller asks.  ``update`` is kept for API
 compatibility (the training path never calls it).
 
 ``DeviceAdaGrad`` is the same handle with a second update rule: the subclass of the reference's
-``BaseOptimizer`` that keeps an accumulator per element (DESIGN.md 8 N19).  The FM fit runs it
-inside the gradient launch (``FactorizationMachines.optimizer = "adagrad"``)."""
+``BaseOptimizer`` that keeps an accumulator per element (DESIGN.md 8 N19, N20).  The FM fit runs it
+inside the gradient launch (``FactorizationMachines.optimizer = "adagrad"``), the exact MF fit inside
+the level kernels (``LogisticMatrixFactorization.optimizer = "adagrad"``)."""
 from __future__ import annotations
 
 import numpy as np
