@@ -473,11 +473,38 @@ int32_t rfm_fm_fit_dp_eval(rfm_ctx* ctx, rfm_fm_plan* plan, const rfm_transport*
                            int32_t max_local_segments, int32_t n_segments, double* d_full_out,
                            double* d_dcg_out);
 
-/* ---- FM: the update rule of a plan's steps -------------------------------------------
- * rfm_fm_plan_set_optimizer and rfm_fm_plan_optimizer: semantics and declarations in rfm_fm_opt.h
- * (a part of this ABI in a file of its own, with a ctypes table of its own:
- * _lib.FM_OPT_SIGNATURES). */
-#include "rfm_fm_opt.h"
+/* kinds of rfm_fm_plan_set_optimizer */
+#define RFM_FM_OPT_SGD 0
+#define RFM_FM_OPT_ADAGRAD 1
+
+/* ---- FM: the optimiser seam ---------------------------------------------------------
+ * The reference builds w0, w and V as SGD(params, lr) objects behind BaseOptimizer.update(grad,
+ * index) (utils/optimizer.py, src/fm.py:48-50); another rule there is another subclass.  Here the
+ * rule is fused into the gradient launch, so it is a property of the plan whose steps run it.
+ *
+ * kind = RFM_FM_OPT_SGD (a new plan's rule): theta -= lr * g.  The accumulator arguments and eps
+ * are ignored and nothing is kept of them.
+ *
+ * kind = RFM_FM_OPT_ADAGRAD: every element of w0, w and V has an accumulator G of its own in
+ * d_acc_w0[1], d_acc_w[n_features], d_acc_V[n_features][n_factors] (float64, the caller's device
+ * memory, read and written by every step, kept alive by the caller while the rule is set).  With g
+ * the element's batch-SUM gradient, bit for bit what rfm_fm_grad writes for it,
+ *   G_new     = G + g * g                            (the product rounded, then the sum)
+ *   theta_new = theta - (lr * g) / (sqrt(G_new) + eps)
+ * in IEEE basic operations, all three gradients from the residual before the update
+ * (src/fm.py:80-88).  g = 0 is a no-op, so which columns a step visits cannot be seen in the
+ * result; a column no batch row holds keeps the bits of its parameters and accumulators.
+ *
+ * The rule is taken by rfm_fm_step, rfm_fm_train, rfm_fm_train_part and rfm_fm_train_eval.
+ * rfm_fm_grad and rfm_fm_grad_rows form g alone under any rule.  rfm_fm_fit_dp and
+ * rfm_fm_fit_dp_eval apply gradients that were summed over ranks with the SGD rule and return
+ * RFM_ERR_BAD_ARG on a plan whose rule is another.
+ * RFM_ERR_BAD_ARG: a kind outside the two, AdaGrad with a null accumulator or eps <= 0 (or NaN);
+ * the plan's rule is then unchanged. */
+int32_t rfm_fm_plan_set_optimizer(rfm_fm_plan* plan, int32_t kind, double* d_acc_w0, double* d_acc_w,
+                                  double* d_acc_V, double eps);
+/* h_out[0] = the plan's kind */
+int32_t rfm_fm_plan_optimizer(const rfm_fm_plan* plan, int32_t* h_out);
 
 /* ---- MF ------------------------------------------------------------------
  * Replaces LogisticMatrixFactorization.predict/_predict_pair
@@ -552,16 +579,119 @@ int32_t rfm_mf_sgd_levels_ex(rfm_ctx* ctx, const void* d_ex, const int32_t* h_le
                              double* d_Q, double* d_bu, double* d_bi, double b,
                              int32_t n_factors, double lr, double reg);
 
+/* models of one rfm_mf_sgd_levels_many / rfm_mf_predict_many call */
+#define RFM_MF_MAX_MODELS 1024
+
 /* ---- MF: several models on one schedule --------------------------------------------
- * rfm_mf_schedule_rows, rfm_mf_sgd_levels_many, rfm_mf_predict_many, rfm_mf_predict_loss_many and
- * rfm_mf_many_geometry: semantics and declarations in rfm_mf_many.h (a part of this ABI in a file of
- * its own, with a ctypes table of its own: _lib.MF_MANY_SIGNATURES). */
-#include "rfm_mf_many.h"
+ * Models that are fitted on the same (user, item) log with the same batch_size draw the same
+ * batch ids in every iteration (resample(..., random_state=epoch), src/mf.py:88-95, does not
+ * depend on the model) and so share the level schedule; they differ in their parameters, lr,
+ * reg, b and in label / propensity.  The schedule is derived once and the device runs it for
+ * every model: one sequential workgroup per model, wide levels on a grid with a model
+ * dimension.  Each model's result has the bits of its own rfm_mf_sgd_levels_ex.
+ *
+ * rfm_mf_schedule_rows is rfm_mf_schedule_ex for such a shared schedule: h_rows[batch] (the
+ * training-log row of each batch position) in place of h_y / h_pscore; the same records, level
+ * pointers, cached items and counts, every record's label / propensity a quiet NaN, and
+ * h_ex_rows[batch] = the training-log row of each record, in level order. */
+int32_t rfm_mf_schedule_rows(const int32_t* h_users, const int32_t* h_items, const int32_t* h_rows,
+                             int64_t batch, int32_t n_users, int32_t n_items, int32_t cache_cap,
+                             void* h_ex, int32_t* h_ex_rows, int32_t* h_level_ptr,
+                             int32_t* h_n_levels, int32_t* h_cache_items, int32_t* h_n_cached);
+
+/* One model of a many-model call, in device memory.  A table of these is built once per fit: no
+ * launch rewrites it, and what changes per iteration travels by value. */
+typedef struct rfm_mf_model {      /* 64 bytes */
+  double *P, *Q, *bu, *bi;
+  const double* ry;                /* [rows of the training log] label / propensity, divided on the host */
+  double b, lr, reg;
+} rfm_mf_model;
+/* Labels and propensities of a scored log, per model (rfm_mf_predict_loss_many divides on the
+ * device, as rfm_mf_predict_loss does). */
+typedef struct rfm_mf_labels {     /* 16 bytes */
+  const double *y, *pscore;
+} rfm_mf_labels;
+
+/* Replaces the inner loop src/mf.py:97-108 with _update_P/_Q/_b_u/_b_i (src/mf.py:172-216) of
+ * n_models fits at once: rfm_mf_sgd_levels_ex on the records of rfm_mf_schedule_rows for every
+ * model of d_models[n_models], model m reading label / propensity d_models[m].ry[d_ex_rows[rec]].
+ * The launches are those of rfm_mf_sgd_levels_ex for the same level pointers; a run of small
+ * levels is one launch of n_models sequential workgroups, a wide level one launch whose grid has
+ * the model as its second dimension.  The models' arrays must not overlap.
+ * 1 <= n_models <= RFM_MF_MAX_MODELS. */
+int32_t rfm_mf_sgd_levels_many(rfm_ctx* ctx, const void* d_ex, const int32_t* d_ex_rows,
+                               const int32_t* h_level_ptr, const int32_t* d_level_ptr,
+                               int32_t n_levels, const int32_t* d_cache_items, int32_t n_cached,
+                               const rfm_mf_model* d_models, int32_t n_models, int32_t n_factors);
+/* Replaces LogisticMatrixFactorization.predict (src/mf.py:136-170) and the loss of
+ * src/base.py:37-61 for n_models models on one log: rfm_mf_predict / rfm_mf_predict_loss with a
+ * model dimension.  The rows are walked by the grid of the single-model call and the partial sums
+ * are added in its order, so each model's scores and loss have the bits of its own call.  Model
+ * m's scores go to d_out_base[m] + out_offset (d_out_base: a device table of n_models pointers,
+ * built once; NULL in rfm_mf_predict_loss_many: no scores), its loss to
+ * d_out_loss[m * loss_stride]; d_labels[m] names its labels and propensities of the scored log. */
+int32_t rfm_mf_predict_many(rfm_ctx* ctx, const int32_t* d_users, const int32_t* d_items,
+                            const int32_t* d_row_ids, int64_t n_rows, const rfm_mf_model* d_models,
+                            int32_t n_models, int32_t n_factors, double* const* d_out_base,
+                            int64_t out_offset);
+int32_t rfm_mf_predict_loss_many(rfm_ctx* ctx, const int32_t* d_users, const int32_t* d_items,
+                                 const rfm_mf_labels* d_labels, const int32_t* d_row_ids,
+                                 int64_t n_rows, const rfm_mf_model* d_models, int32_t n_models,
+                                 int32_t n_factors, double eps, double* const* d_out_base,
+                                 int64_t out_offset, double* d_out_loss, int64_t loss_stride);
+/* The launch shapes of the three calls above (host only, nothing is launched): h_out7[0]=threads
+ * of the sequential workgroup, [1]=lanes per row, [2]=sequential workgroups (one per model),
+ * [3], [4]=grid x and y of a wide level of n_recs records, [5], [6]=grid x and y of a prediction
+ * over n_recs rows.  ctx == NULL: the grids on a device of 256 CUs (an MI355X). */
+int32_t rfm_mf_many_geometry(const rfm_ctx* ctx, int32_t n_models, int32_t n_factors, int64_t n_recs,
+                             int32_t* h_out7);
+
+/* kinds of rfm_mf_sgd_levels_opt: the numbering of RFM_FM_OPT_* */
+#define RFM_MF_OPT_SGD RFM_FM_OPT_SGD
+#define RFM_MF_OPT_ADAGRAD RFM_FM_OPT_ADAGRAD
 
 /* ---- MF: the optimiser seam ---------------------------------------------------------
- * rfm_mf_sgd_levels_opt and rfm_mf_opt_geometry: semantics and declarations in rfm_mf_opt.h (a
- * part of this ABI in a file of its own, with a ctypes table of its own: _lib.MF_OPT_SIGNATURES). */
-#include "rfm_mf_opt.h"
+ * The reference builds P, Q, b_u and b_i as SGD(params, lr) objects behind
+ * BaseOptimizer.update(grad, index) (utils/optimizer.py, src/mf.py:45-62); another rule there is
+ * another subclass.  Here the rule is fused into the level kernels, so it is an argument of the
+ * call that runs a batch.
+ *
+ * rfm_mf_sgd_levels_opt is rfm_mf_sgd_levels_ex (same records, level pointers, cached items and
+ * rfm_mf_cache_capacity, same launches for the same level pointers) under the rule `kind`.
+ *
+ * kind = RFM_MF_OPT_SGD: exactly the launches and the bits of rfm_mf_sgd_levels_ex; the
+ * accumulator arguments and eps are never read.
+ *
+ * kind = RFM_MF_OPT_ADAGRAD: every element of P, Q, b_u, b_i has an accumulator G of its own in
+ * d_acc_P[n_users][n_factors], d_acc_Q[n_items][n_factors], d_acc_bu[n_users], d_acc_bi[n_items]
+ * (float64, the caller's device memory, in / out).  Examples run in the strict batch order of the
+ * level schedule.  For one example (u, i), err is formed once, before any of its updates, and then
+ *   g = -err Q_i + reg P_u;       G_P[u] += g g;  P_u -= (lr g) / (sqrt(G_P[u]) + eps)
+ *   g = -err P_u(new) + reg Q_i;  G_Q[i], Q_i likewise (the item row sees the updated user row)
+ *   g = -err + reg b_u[u];        G_bu[u], b_u[u] likewise
+ *   g = -err + reg b_i[i];        G_bi[i], b_i[i] likewise
+ * element by element, G + g g as the product rounded, then the sum; root and quotient correctly
+ * rounded.  A user or item outside the batch keeps the bits of its parameters and accumulators.
+ * A cached item keeps its accumulator row and bias accumulator in LDS beside its parameter row
+ * (twice the LDS per cached item); both are written back at the end of a launch.
+ *
+ * RFM_ERR_BAD_ARG: a kind outside the two, AdaGrad with a null accumulator or eps <= 0 (or NaN),
+ * and whatever rfm_mf_sgd_levels_ex rejects; nothing is launched then. */
+int32_t rfm_mf_sgd_levels_opt(rfm_ctx* ctx, const void* d_ex, const int32_t* h_level_ptr,
+                              const int32_t* d_level_ptr, int32_t n_levels,
+                              const int32_t* d_cache_items, int32_t n_cached, double* d_P,
+                              double* d_Q, double* d_bu, double* d_bi, double b,
+                              int32_t n_factors, double lr, double reg, int32_t kind,
+                              double* d_acc_P, double* d_acc_Q, double* d_acc_bu, double* d_acc_bi,
+                              double eps);
+
+/* Host-only: what rfm_mf_sgd_levels_opt launches for `kind` and `n_factors` (ctx may be NULL).
+ * h_out7 = {lanes per row, factors per lane and chunk, chunks per lane, threads of the sequential
+ * workgroup, levels ahead of their use at which the accumulators are read (0: where they are
+ * used), LDS bytes per cached item, levels ahead at which the parameter rows are read (the slots
+ * of the read-ahead ring; 0: where they are used)}.  The largest level the sequential workgroup
+ * takes does not depend on the kind. */
+int32_t rfm_mf_opt_geometry(const rfm_ctx* ctx, int32_t kind, int32_t n_factors, int32_t* h_out7);
 
 /* ---- MF fold-in: new rows of one side against the fixed other side ----------------
  * The per-example update of src/mf.py:99-108 with _update_P / _update_b_u (src/mf.py:172-216)
@@ -631,12 +761,46 @@ int32_t rfm_fm_fold_in(rfm_ctx* ctx, const int64_t* d_row_ptr, const int32_t* d_
  * each per grid-stride turn).  ctx == NULL: the grid on a device of 256 CUs (an MI355X). */
 int32_t rfm_fm_fold_geometry(const rfm_ctx* ctx, int64_t n_new, int32_t n_factors, int32_t* h_out5);
 
-/* ---- fold-in: the examples grouped on the device -----------------------------------
- * rfm_fold_group, rfm_fold_group_workspace and rfm_fold_group_geometry: d_row_ptr, d_ids, d_ry and
- * d_order of the two fold-in entries above from a log in device memory.  Semantics and declarations
- * in rfm_fold_group.h (a part of this ABI in a file of its own, with a ctypes table of its own:
- * _lib.FOLD_GROUP_SIGNATURES). */
-#include "rfm_fold_group.h"
+/* ---- fold-in: the examples of a log in device memory, grouped by new row -----------
+ * What fold.fold_examples does on the host, for a log that already lies in HBM: the n examples
+ * (new-row id, other id, label, propensity) grouped by new row with a stable sort (a row's examples
+ * keep their input order), label / propensity as an IEEE double quotient, and the new rows by
+ * descending example count, ties in row order.  Everything is enqueued on the context's stream and
+ * nothing waits for the device; rfm_mf_fold_in / rfm_fm_fold_in may be enqueued right behind.
+ *
+ * d_new, d_other: the FIRST element of each id column; consecutive examples lie id_stride elements
+ * apart (2 for the columns of an (N, 2) array, 1 for separate arrays); id_bytes: 4 (int32) or 8
+ * (int64).  d_labels, d_pscores: float64 [n].  Inputs are never written.
+ *
+ * Outputs, as the two fold-in entries take them: d_row_ptr int64 [n_new + 1]; d_ids int32 [n] (the
+ * other column in grouped order); d_ry float64 [n]; d_order int32 [n_new]; d_status int32 [4]:
+ * [0] = examples whose new-row id lies outside 0..n_new-1, [1] = examples whose other id lies outside
+ * 0..n_fixed-1, [2] = the index of the first example counted in either, -1 if there is none,
+ * [3] = 0 (spare).  Such an example is left out of every output: d_row_ptr[n_new] is the number of
+ * examples kept, and only that many elements of d_ids / d_ry are written -- a fold launch behind this
+ * call stays in bounds whatever the log holds.
+ *
+ * n_new == 0: the status and d_row_ptr[0] are zeroed, nothing else happens.  n == 0: d_row_ptr is
+ * zeroed and d_order is 0..n_new-1 (the stable order of equal counts), one launch.
+ * d_workspace: rfm_fold_group_workspace(n, n_new) bytes, 16-byte aligned, the caller's until the
+ * stream has passed this call.  n, n_new < 2^31; anything else is RFM_ERR_BAD_ARG. */
+int32_t rfm_fold_group(rfm_ctx* ctx, const void* d_new, const void* d_other, int64_t id_stride,
+                       int32_t id_bytes, const double* d_labels, const double* d_pscores, int64_t n,
+                       int64_t n_new, int64_t n_fixed, void* d_workspace, int64_t workspace_bytes,
+                       int64_t* d_row_ptr, int32_t* d_ids, double* d_ry, int32_t* d_order,
+                       int32_t* d_status);
+/* Bytes of workspace of rfm_fold_group for n examples and n_new rows (host only). */
+int32_t rfm_fold_group_workspace(int64_t n, int64_t n_new, int64_t* h_bytes);
+/* The launch shape of one grouping of n keys into n_bins bins (host only, nothing is launched);
+ * rfm_fold_group makes two: (n, n_new) for the examples and (n_new, n + 1) for the row order.
+ * h_out8[0] = the longest bin that is ordered in LDS (the cap; a longer bin is rebuilt by a walk over
+ * all keys), [1] = lanes per workgroup of the per-bin launches, [2] = workgroups of the per-bin launch
+ * (a wavefront per bin and turn), [3] = the longest bin a wavefront orders (longer ones up to the cap
+ * take a workgroup), [4] = workgroups of that workgroup-per-bin launch (0: not launched, no bin can be
+ * that long), [5] = workgroups of the walk (0: not launched), [6] = lanes per workgroup of the walk,
+ * [7] = workgroups of the per-key launches (count, place, gather).  ctx == NULL: the grids on a device
+ * of 256 CUs (an MI355X). */
+int32_t rfm_fold_group_geometry(const rfm_ctx* ctx, int64_t n, int64_t n_bins, int32_t* h_out8);
 
 /* ---- MF across GPUs: user-range partition ------------------
  * NOT the reference's semantics (its batch is strictly sequential, src/mf.py:97-108;

@@ -42,7 +42,7 @@ ids = rt.upload(sample_batches(X.shape[0], B, 0, K + 5))
 plan = FmPlan(rt, csr, train["labels"], train["pscores"], k, B, 0)
 if rule == "adagrad":
     acc = [torch.zeros_like(t.dev) for t in (m.w0, m.w, m.V)]
-    plan.set_optimizer(_lib.FM_OPT_ADAGRAD, *acc, 1e-10)
+    plan.set_optimizer(_lib.OPT_ADAGRAD, *acc, 1e-10)
 args = (csr.indptr.data_ptr(), csr.indices.data_ptr(), csr.values.data_ptr(), y.data_ptr(), p.data_ptr())
 par = (m.w0.dev.data_ptr(), m.w.dev.data_ptr(), m.V.dev.data_ptr())
 def run(first, count):

@@ -20,10 +20,11 @@ LIB_PATH = os.environ.get("RFM_LIB_PATH") or os.path.join(PKG_DIR, "librfm_hip.s
 SOURCES = ["rfm_capi.hip", "rfm_fm.hip", "rfm_fm_plan.hip", "rfm_mf.hip", "rfm_fm_fold.hip", "rfm_fold_group.hip", "rfm_eval.hip", "rfm_csr.hip", "rfm_sample.hip", "rfm_pairs.hip", "rfm_host.cpp", "rfm_comm.cpp"]
 # every header under csrc/ (a change of any of them rebuilds every object) + the C ABI
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp"))) + [
-    os.path.join(os.path.dirname(PKG_DIR), "include", h) for h in ("rfm_hip.h", "rfm_mf_many.h", "rfm_fold_group.h", "rfm_fm_opt.h", "rfm_mf_opt.h")]
+    os.path.join(os.path.dirname(PKG_DIR), "include", "rfm_hip.h")]
 
 RFM_OK, RFM_ERR_BAD_ARG, RFM_ERR_HIP, RFM_ERR_NO_DEVICE, RFM_ERR_INTERNAL = range(5)
-MF_MAX_MODELS = 1024  # RFM_MF_MAX_MODELS of include/rfm_mf_many.h
+MF_MAX_MODELS = 1024  # RFM_MF_MAX_MODELS
+OPT_SGD, OPT_ADAGRAD = 0, 1  # the kinds of both optimiser seams: the update rule of a plan's steps or an MF batch
 
 
 class RfmError(RuntimeError):
@@ -111,6 +112,9 @@ _FIT_DP = [_vp, _vp, _vp, _i32, _vp, _i64, _i64] + _TRAIN_TAIL
 # every rfm_pair_* entry (recommend.Operands.pair_args): ctx, A, LU, n_users, user ids, n_sel, B,
 # LI, n_items, n_factors, c
 _PAIR = [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp]
+# rfm_mf_sgd_levels_ex, and what rfm_mf_sgd_levels_opt begins with: ctx, records, level pointers (host, device),
+# n_levels, cached items, n_cached, P, Q, bu, bi, b, n_factors, lr, reg
+_MF_LEVELS_EX = [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _f64, _i32, _f64, _f64]
 
 # name -> argtypes; every function returns int32.  Mirrors include/rfm_hip.h
 # (tests/test_host_abi.py compares the two, argument by argument).
@@ -171,8 +175,7 @@ SIGNATURES = {
     "rfm_mf_cache_capacity": [_i32, C.POINTER(_i32)],
     "rfm_mf_schedule_ex": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, C.POINTER(_i32), _vp,
                            C.POINTER(_i32)],
-    "rfm_mf_sgd_levels_ex": [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _f64, _i32, _f64,
-                             _f64],
+    "rfm_mf_sgd_levels_ex": _MF_LEVELS_EX,
     "rfm_mf_fold_in": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _f64, _i32, _f64, _f64, _i32, _vp, _vp],
     "rfm_mf_fold_geometry": [_vp, _i64, _i32, _vp],
     "rfm_fm_fold_in": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _f64, _i32, _vp, _vp, _vp,
@@ -199,40 +202,21 @@ SIGNATURES = {
     "rfm_pair_order": _PAIR + [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
     "rfm_pair_geometry": [_i64, _i64, _i32, C.POINTER(_i64)],
     "rfm_pair_order_geometry": [_i64, _i64, C.POINTER(_i64)],
-}
-
-# several MF models on one schedule, the part of the ABI that include/rfm_mf_many.h declares
-# (tests/test_mf_many_host.py compares the two, argument by argument)
-MF_MANY_SIGNATURES = {
+    # several MF models on one schedule
     "rfm_mf_schedule_rows": [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, C.POINTER(_i32), _vp,
                              C.POINTER(_i32)],
     "rfm_mf_sgd_levels_many": [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32],
     "rfm_mf_predict_many": [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _i64],
     "rfm_mf_predict_loss_many": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _f64, _vp, _i64, _vp, _i64],
     "rfm_mf_many_geometry": [_vp, _i32, _i32, _i64, _vp],
-}
-
-# fold-in examples grouped on the device, the part of the ABI that include/rfm_fold_group.h declares
-# (tests/test_fold_group_host.py compares the two, argument by argument)
-FOLD_GROUP_SIGNATURES = {
+    # fold-in examples grouped on the device
     "rfm_fold_group": [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
     "rfm_fold_group_workspace": [_i64, _i64, C.POINTER(_i64)],
     "rfm_fold_group_geometry": [_vp, _i64, _i64, _vp],
-}
-
-# the update rule of an FM plan's steps, the part of the ABI that include/rfm_fm_opt.h declares
-# (tests/test_adagrad_host.py compares the two, argument by argument)
-FM_OPT_SGD, FM_OPT_ADAGRAD = 0, 1  # RFM_FM_OPT_* of include/rfm_fm_opt.h
-FM_OPT_SIGNATURES = {
+    # the update rule of an FM plan's steps, and of the exact MF batch step
     "rfm_fm_plan_set_optimizer": [_vp, _i32, _vp, _vp, _vp, _f64],
     "rfm_fm_plan_optimizer": [_vp, _vp],
-}
-
-# the update rule of the exact MF batch step, the part of the ABI that include/rfm_mf_opt.h declares
-# (tests/test_mf_adagrad_host.py compares the two, argument by argument)
-MF_OPT_SGD, MF_OPT_ADAGRAD = FM_OPT_SGD, FM_OPT_ADAGRAD  # RFM_MF_OPT_* of include/rfm_mf_opt.h
-MF_OPT_SIGNATURES = {
-    "rfm_mf_sgd_levels_opt": SIGNATURES["rfm_mf_sgd_levels_ex"] + [_i32, _vp, _vp, _vp, _vp, _f64],
+    "rfm_mf_sgd_levels_opt": _MF_LEVELS_EX + [_i32, _vp, _vp, _vp, _vp, _f64],
     "rfm_mf_opt_geometry": [_vp, _i32, _i32, _vp],
 }
 
@@ -302,8 +286,7 @@ def load():
         lib = C.CDLL(path)
     except OSError as exc:
         raise RfmError(f"cannot load {path}: {exc}") from exc
-    for name, argtypes in {**SIGNATURES, **MF_MANY_SIGNATURES, **FOLD_GROUP_SIGNATURES, **FM_OPT_SIGNATURES,
-                           **MF_OPT_SIGNATURES}.items():
+    for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError = header/library mismatch
         fn.argtypes = argtypes
         fn.restype = _i32

@@ -354,9 +354,10 @@ int launch_step_forward(rfm_ctx* ctx, FwdArgs f, const XtraRows* xtra) {
   return geom.grid;
 }
 
-// the step's consume launch (fm_consume_kernel): the slot-ordered sums and the updates
-// (ada: the plan's AdaGrad operands, null for the SGD instantiations)
-void launch_consume(rfm_ctx* ctx, ConsArgs c, const Shape& s, const AdaGradRule* ada) {
+// the step's consume launch (fm_consume_kernel): the slot-ordered sums and the updates under
+// the rule o
+template <class O>
+void launch_consume(rfm_ctx* ctx, ConsArgs c, const Shape& s, const O& o) {
   const int grid = c.nb_tasks + c.n_hot + 1;  // tasks, then the hot columns, then w0
   const size_t lds = consume_lds_bytes(s.lpr, c.c.k);
   if (s.nc > 1) {
@@ -367,30 +368,15 @@ void launch_consume(rfm_ctx* ctx, ConsArgs c, const Shape& s, const AdaGradRule*
     c.xcd_chunks = n_chunks <= 8 ? 1 : 0;
     const int per_chunk = 8 / n_chunks;  // (the fewest XCDs a chunk gets)
     const dim3 g2 = c.xcd_chunks ? dim3(8 * ((grid + per_chunk - 1) / per_chunk)) : dim3(grid, n_chunks);
-    if (ada) {
-      ConsArgsOpt co{};
-      static_cast<ConsArgs&>(co) = c;
-      co.o = *ada;
-      if (s.vec == 2)
-        hipLaunchKernelGGL((fm_consume_kernel<64, 2, true, AdaGradRule>), g2, dim3(kBlock), lds, ctx->stream, co);
-      else
-        hipLaunchKernelGGL((fm_consume_kernel<64, 1, true, AdaGradRule>), g2, dim3(kBlock), lds, ctx->stream, co);
-    } else if (s.vec == 2)
-      hipLaunchKernelGGL((fm_consume_kernel<64, 2, true>), g2, dim3(kBlock), lds, ctx->stream, c);
+    const auto a = args_under(c, o);
+    if (s.vec == 2)
+      hipLaunchKernelGGL((fm_consume_kernel<64, 2, true, O>), g2, dim3(kBlock), lds, ctx->stream, a);
     else
-      hipLaunchKernelGGL((fm_consume_kernel<64, 1, true>), g2, dim3(kBlock), lds, ctx->stream, c);
-  } else if (ada) {
-    ConsArgsOpt co{};
-    static_cast<ConsArgs&>(co) = c;
-    co.o = *ada;
-#define RFM_CALL_CONS_ADA(L, Vv, N)                                                                      \
-  hipLaunchKernelGGL((fm_consume_kernel<L, Vv, false, AdaGradRule>), dim3(grid), dim3(kBlock), lds, \
-                     ctx->stream, co)
-    RFM_FOR_SINGLE_CHUNK_SHAPE(s, RFM_CALL_CONS_ADA);
-#undef RFM_CALL_CONS_ADA
+      hipLaunchKernelGGL((fm_consume_kernel<64, 1, true, O>), g2, dim3(kBlock), lds, ctx->stream, a);
   } else {
+    const auto a = args_under(c, o);
 #define RFM_CALL_CONS(L, Vv, N) \
-  hipLaunchKernelGGL((fm_consume_kernel<L, Vv>), dim3(grid), dim3(kBlock), lds, ctx->stream, c)
+  hipLaunchKernelGGL((fm_consume_kernel<L, Vv, false, O>), dim3(grid), dim3(kBlock), lds, ctx->stream, a)
     RFM_FOR_SINGLE_CHUNK_SHAPE(s, RFM_CALL_CONS);
 #undef RFM_CALL_CONS
   }
@@ -398,41 +384,42 @@ void launch_consume(rfm_ctx* ctx, ConsArgs c, const Shape& s, const AdaGradRule*
 }
 
 // the finalize launch of the columns cut into several tasks
-void launch_finalize(rfm_ctx* ctx, const FinArgs& fa, const Shape& s, const AdaGradRule* ada) {
+template <class O>
+void launch_finalize(rfm_ctx* ctx, const FinArgs& fa, const Shape& s, const O& o) {
   const int gpb = kBlock / s.lpr;
   const int nb_short = (fa.n_split_short + gpb - 1) / gpb;
   const int grid = nb_short + fa.n_split_long;
+  const auto a = args_under(fa, o);
   if (s.nc > 1) {
     const dim3 g2(grid, fm_chunks(fa.c.k, s.vec));
-    if (ada) {
-      FinArgsOpt fo{};
-      static_cast<FinArgs&>(fo) = fa;
-      fo.o = *ada;
-      if (s.vec == 2)
-        hipLaunchKernelGGL((fm_finalize_chunk_kernel<2, AdaGradRule>), g2, dim3(kBlock), 0, ctx->stream, fo, nb_short);
-      else
-        hipLaunchKernelGGL((fm_finalize_chunk_kernel<1, AdaGradRule>), g2, dim3(kBlock), 0, ctx->stream, fo, nb_short);
-    } else if (s.vec == 2)
-      hipLaunchKernelGGL(fm_finalize_chunk_kernel<2>, g2, dim3(kBlock), 0, ctx->stream, fa, nb_short);
+    if (s.vec == 2)
+      hipLaunchKernelGGL((fm_finalize_chunk_kernel<2, O>), g2, dim3(kBlock), 0, ctx->stream, a, nb_short);
     else
-      hipLaunchKernelGGL(fm_finalize_chunk_kernel<1>, g2, dim3(kBlock), 0, ctx->stream, fa, nb_short);
-  } else if (ada) {
-    FinArgsOpt fo{};
-    static_cast<FinArgs&>(fo) = fa;
-    fo.o = *ada;
-#define RFM_CALL_FIN_ADA(L, Vv, N)                                                                    \
-  hipLaunchKernelGGL((fm_finalize_kernel<L, Vv, AdaGradRule>), dim3(grid), dim3(kBlock), 0, ctx->stream, \
-                     fo, nb_short)
-    RFM_FOR_SINGLE_CHUNK_SHAPE(s, RFM_CALL_FIN_ADA);
-#undef RFM_CALL_FIN_ADA
+      hipLaunchKernelGGL((fm_finalize_chunk_kernel<1, O>), g2, dim3(kBlock), 0, ctx->stream, a, nb_short);
   } else {
-#define RFM_CALL_FIN(L, Vv, N)                                                              \
-  hipLaunchKernelGGL((fm_finalize_kernel<L, Vv>), dim3(grid), dim3(kBlock), 0, ctx->stream, \
-                     fa, nb_short)
+#define RFM_CALL_FIN(L, Vv, N) \
+  hipLaunchKernelGGL((fm_finalize_kernel<L, Vv, O>), dim3(grid), dim3(kBlock), 0, ctx->stream, a, nb_short)
     RFM_FOR_SINGLE_CHUNK_SHAPE(s, RFM_CALL_FIN);
 #undef RFM_CALL_FIN
   }
   RFM_HIP_CHECK(hipGetLastError());
+}
+
+// launches 2 and 3 of a step under the rule o: the consume launch, then the partial rows of the
+// columns cut into several tasks (none on most plans)
+template <class O>
+void launch_updates(rfm_ctx* ctx, const rfm_fm_plan* plan, const ConsArgs& c, const Shape& s, const O& o) {
+  launch_consume(ctx, c, s, o);
+  ctx->prof_mark();
+  if (plan->n_split_short + plan->n_split_long > 0) {
+    FinArgs fa{};
+    fa.c = c.c;
+    fa.split = plan->split.as<SplitCol>();
+    fa.n_split_short = plan->n_split_short;
+    fa.n_split_long = plan->n_split_long;
+    launch_finalize(ctx, fa, s, o);
+  }
+  ctx->prof_mark();
 }
 
 // the launches of one step; grad == nullptr -> update in place
@@ -463,16 +450,6 @@ void enqueue_step(rfm_ctx* ctx, rfm_fm_plan* plan, const int32_t* d_row_ids, int
     const size_t bytes = (size_t(plan->n_features) * (k + 1) + 1) * sizeof(double);
     RFM_HIP_CHECK(hipMemsetAsync(d_grad, 0, bytes, ctx->stream));
   }
-  // the rule of the plan (rfm_fm_plan_set_optimizer); gradient mode forms g alone, under any rule
-  AdaGradRule ada_rule{};
-  const AdaGradRule* ada = nullptr;
-  if (!d_grad && plan->opt_kind == RFM_FM_OPT_ADAGRAD) {
-    ada_rule.acc_V = plan->opt_acc_V;
-    ada_rule.acc_w = plan->opt_acc_w;
-    ada_rule.acc_w0 = plan->opt_acc_w0;
-    ada_rule.eps = plan->opt_eps;
-    ada = &ada_rule;
-  }
   ColArgs col{};  // what both launches need to finish a column
   col.V = d_V;
   col.w = d_w;
@@ -501,18 +478,11 @@ void enqueue_step(rfm_ctx* ctx, rfm_fm_plan* plan, const int32_t* d_row_ids, int
   c.hot_slab = plan->hot_slab.as<double>();
   c.n_slabs = n_slabs;
   c.err_partial = plan->err_partial.as<double>();
-  launch_consume(ctx, c, s, ada);
-  ctx->prof_mark();
-  // columns cut into several tasks (none on most plans): their partial rows
-  if (plan->n_split_short + plan->n_split_long > 0) {
-    FinArgs fa{};
-    fa.c = col;
-    fa.split = plan->split.as<SplitCol>();
-    fa.n_split_short = plan->n_split_short;
-    fa.n_split_long = plan->n_split_long;
-    launch_finalize(ctx, fa, s, ada);
-  }
-  ctx->prof_mark();
+  // the rule of the plan (rfm_fm_plan_set_optimizer); gradient mode forms g alone, under any rule
+  if (!d_grad && plan->opt_kind == RFM_FM_OPT_ADAGRAD)
+    launch_updates(ctx, plan, c, s, AdaGradRule{plan->opt_acc_V, plan->opt_acc_w, plan->opt_acc_w0, plan->opt_eps});
+  else
+    launch_updates(ctx, plan, c, s, SgdRule{});
 }
 
 FwdArgs forward_args(const int64_t* d_indptr, const int32_t* d_indices, const double* d_values,

@@ -11,6 +11,7 @@
 
 #include "rfm_device_utils.hpp"
 #include "rfm_fm_records.h"
+#include "rfm_rule.hpp"
 
 namespace rfm {
 
@@ -1156,19 +1157,14 @@ __device__ inline double updated_factor(double vold, double m, double d, double 
 }
 
 // THE OPTIMISER of the update sites (apply_scalar, apply_column, apply_column_block and the long
-// columns of fm_finalize_chunk_kernel), a type parameter of launches 2 and 3.  SgdRule: theta -=
-// lr * g as spelled above, the form every site had before there was a choice; its instantiations
-// take the branches they always took.  AdaGradRule: every element of w0, w and V has an
-// accumulator G of its own (same shape, float64) and, with g the element's gradient exactly as
-// gradient mode writes it (so -s for a scalar, updated_factor(..., grad = true, ...) for a factor),
-//   G_new = G + g * g             (the product rounded, then the sum)
-//   theta_new = theta - (lr * g) / (sqrt(G_new) + eps)
-// in IEEE basic operations.  g = 0 changes neither, so a hot column without an entry in the batch
+// columns of fm_finalize_chunk_kernel), a type parameter of launches 2 and 3.  SgdRule
+// (rfm_rule.hpp): theta -= lr * g as spelled above, the form every site had before there was a
+// choice; its instantiations take the branches they always took.  AdaGradRule: every element of
+// w0, w and V has an accumulator G of its own and takes adagrad_element's step, with g the
+// element's gradient exactly as gradient mode writes it (so -s for a scalar, updated_factor(...,
+// grad = true, ...) for a factor).  g = 0 changes neither, so a hot column without an entry in the batch
 // keeps its bits although it is visited; an untouched column of the sparse class is not visited.
 // Gradient mode never runs under AdaGradRule (enqueue_step).
-struct SgdRule {
-  static constexpr bool kAda = false;
-};
 struct AdaGradRule {
   static constexpr bool kAda = true;
   double* acc_V;   // [n][k]
@@ -1176,15 +1172,6 @@ struct AdaGradRule {
   double* acc_w0;  // [1]
   double eps;
 };
-
-// one element under AdaGradRule; *G: its accumulator as it was read, then as it is to be written
-__device__ inline double adagrad_element(double theta, double g, double lr, double eps, double* G) {
-#pragma clang fp contract(off)
-  const double gg = g * g;
-  const double gn = *G + gg;
-  *G = gn;
-  return theta - (lr * g) / (sqrt(gn) + eps);
-}
 
 // *p += x by its only writer of the step.  As `*p += x` the wavefront stands still for the load of *p
 // (nothing else waits for it) -- once per finished column in the gradient launch, eight times per task
@@ -1328,21 +1315,6 @@ __device__ inline int group_scan(int v, int l) {
   return v;
 }
 
-// the arguments of launches 2 and 3 under a rule: SgdRule's are ConsArgs / FinArgs themselves
-struct ConsArgsOpt : ConsArgs {
-  AdaGradRule o;
-};
-template <class O>
-struct ConsArgsOf {
-  using type = ConsArgs;
-};
-template <>
-struct ConsArgsOf<AdaGradRule> {
-  using type = ConsArgsOpt;
-};
-__device__ inline SgdRule rule_of(const ConsArgs&) { return SgdRule{}; }
-__device__ inline const AdaGradRule& rule_of(const ConsArgsOpt& a) { return a.o; }
-
 // A hot column, by one workgroup: the forward workgroups' slabs, in block order; the column's row
 // of V is requested first, so that it arrives with the slabs and not after them.
 template <class O>
@@ -1416,9 +1388,9 @@ __device__ inline void consume_w0(const ConsArgs& a, const O& o, double* lds) {
 // cleared while a sibling may still read them: the bitmap is double-buffered by step parity and
 // chunk 0 clears the task's words of the OTHER buffer (the step before, long consumed).
 constexpr int kConsChBatch = 4;  // CH form: entries whose Q and V rows are in flight together
-// O: the update rule (SgdRule: the arguments are ConsArgs; AdaGradRule: ConsArgsOpt).
+// O: the update rule (SgdRule: the arguments are ConsArgs; AdaGradRule: ConsArgs with the rule behind).
 template <int LPR, int VEC, bool CH = false, class O = SgdRule>
-__global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(typename ConsArgsOf<O>::type a) {
+__global__ __launch_bounds__(kBlock, 1) void fm_consume_kernel(ArgsUnder<ConsArgs, O> a) {
   const O& o = rule_of(a);
   constexpr int GPB = kBlock / LPR;  // tasks of a workgroup
   constexpr int PLANES = WinShape<LPR>::PLANES;
@@ -1739,20 +1711,6 @@ struct FinArgs {
 // The short split columns, one per lane group (workgroup b takes kBlock / LPR of them), the
 // factors fb + lane * VEC on of each: the column's partial rows CB to a round of loads, read
 // unconditionally -- a stale row is masked by its stamp -- and added in row order.
-struct FinArgsOpt : FinArgs {
-  AdaGradRule o;
-};
-template <class O>
-struct FinArgsOf {
-  using type = FinArgs;
-};
-template <>
-struct FinArgsOf<AdaGradRule> {
-  using type = FinArgsOpt;
-};
-__device__ inline SgdRule rule_of(const FinArgs&) { return SgdRule{}; }
-__device__ inline const AdaGradRule& rule_of(const FinArgsOpt& a) { return a.o; }
-
 template <int LPR, int VEC, int CB, class O>
 __device__ inline void finalize_short_columns(const FinArgs& a, const O& o, int b, int fb) {
   constexpr int GPB = kBlock / LPR;
@@ -1792,7 +1750,7 @@ __device__ inline void finalize_short_columns(const FinArgs& a, const O& o, int 
 // blocks [0, nb_short): short split columns, one per lane group; then one block per long
 // split column.  Launched only when the plan has split columns.
 template <int LPR, int VEC, class O = SgdRule>
-__global__ __launch_bounds__(kBlock) void fm_finalize_kernel(typename FinArgsOf<O>::type a, int nb_short) {
+__global__ __launch_bounds__(kBlock) void fm_finalize_kernel(ArgsUnder<FinArgs, O> a, int nb_short) {
   const O& o = rule_of(a);
   __shared__ double scratch[kBlock];
   __shared__ double tot[1024 + 2];
@@ -1820,7 +1778,7 @@ __global__ __launch_bounds__(kBlock) void fm_finalize_kernel(typename FinArgsOf<
 // V is requested before the sums, so a workgroup's chain is two dependent levels instead of
 // eight (k = 400, B = 2 000: 8.1 -> 6.8 us per launch, profiles/r3j vs r3q).
 template <int VEC, class O = SgdRule>
-__global__ __launch_bounds__(kBlock) void fm_finalize_chunk_kernel(typename FinArgsOf<O>::type a,
+__global__ __launch_bounds__(kBlock) void fm_finalize_chunk_kernel(ArgsUnder<FinArgs, O> a,
                                                                   int nb_short) {
   const O& o = rule_of(a);
   constexpr int CW = kWave * VEC;

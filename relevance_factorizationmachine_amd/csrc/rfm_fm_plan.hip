@@ -26,6 +26,7 @@
 
 #include "rfm_fm_plan.h"
 #include "rfm_fm_records.h"
+#include "rfm_rule.hpp"
 
 namespace rfm {
 namespace {
@@ -597,12 +598,7 @@ int32_t rfm_fm_plan_set_optimizer(rfm_fm_plan* plan, int32_t kind, double* d_acc
                                   double* d_acc_V, double eps) {
   return guarded([&] {
     RFM_REQUIRE(plan, "null pointer");
-    RFM_REQUIRE(kind == RFM_FM_OPT_SGD || kind == RFM_FM_OPT_ADAGRAD, "optimizer kind=%d (0 SGD, 1 AdaGrad)", kind);
-    const bool ada = kind == RFM_FM_OPT_ADAGRAD;
-    if (ada) {
-      RFM_REQUIRE(d_acc_w0 && d_acc_w && d_acc_V, "AdaGrad: null accumulator");
-      RFM_REQUIRE(eps > 0.0, "AdaGrad: eps=%g must be > 0", eps);
-    }
+    const bool ada = require_rule(kind, d_acc_w0 && d_acc_w && d_acc_V, eps);
     plan->opt_kind = kind;
     plan->opt_acc_w0 = ada ? d_acc_w0 : nullptr;
     plan->opt_acc_w = ada ? d_acc_w : nullptr;

@@ -36,6 +36,7 @@
 #include "rfm_common.h"
 #include "rfm_device_utils.hpp"
 #include "rfm_fold.hpp"
+#include "rfm_rule.hpp"
 
 namespace rfm {
 
@@ -191,16 +192,11 @@ __global__ __launch_bounds__(kMfBlock) void mf_loss_finish_many_kernel(const dou
 }
 
 // THE UPDATE RULE of the record form's kernels (mf_update and the bodies that call it), a type
-// parameter O.  MfSgdRule: theta -= lr * g, the text every site had before there was a choice; its
-// instantiations are that code.  MfAdaGradRule (rfm_mf_sgd_levels_opt, include/rfm_mf_opt.h): every
-// element of P, Q, b_u, b_i has an accumulator G of its own (same shapes, float64) and, with g the
-// element's gradient as the SGD text forms it,
-//   G_new = G + g * g             (the product rounded, then the sum)
-//   theta_new = theta - (lr * g) / (sqrt(G_new) + eps)
-// in IEEE basic operations, the four updates of an example in the reference's order.
-struct MfSgdRule {
-  static constexpr bool kAda = false;
-};
+// parameter O.  SgdRule (rfm_rule.hpp): theta -= lr * g, the text every site had before there was
+// a choice; its instantiations are that code.  MfAdaGradRule (rfm_mf_sgd_levels_opt): every element
+// of P, Q, b_u, b_i has an accumulator G of its own and takes adagrad_element's step, with g the
+// element's gradient as the SGD text forms it, the four updates of an example in the reference's
+// order.
 struct MfAdaGradRule {
   static constexpr bool kAda = true;
   double* acc_P;   // [n_users][k]
@@ -210,7 +206,7 @@ struct MfAdaGradRule {
   double eps;
 };
 
-// the accumulators of one example's two rows and two biases in registers (nothing under MfSgdRule)
+// the accumulators of one example's two rows and two biases in registers (nothing under SgdRule)
 template <int VEC, int NC, bool ADA>
 struct MfAccRegs {};
 template <int VEC, int NC>
@@ -219,19 +215,10 @@ struct MfAccRegs<VEC, NC, true> {
   double gbu, gbi;
 };
 
-// one element under MfAdaGradRule; *G: its accumulator as it was read, then as it is to be written
-__device__ inline double mf_adagrad_element(double theta, double g, double lr, double eps, double* G) {
-#pragma clang fp contract(off)
-  const double gg = g * g;
-  const double gn = *G + gg;
-  *G = gn;
-  return theta - (lr * g) / (sqrt(gn) + eps);
-}
-
 // the arithmetic of one example on rows already in registers (src/mf.py:99-108,
 // 172-216): returns the residual, rows and biases are updated in place (acc: their accumulators,
 // MfAdaGradRule only, needed after the residual)
-template <int LPR, int VEC, int NC, class O = MfSgdRule>
+template <int LPR, int VEC, int NC, class O = SgdRule>
 __device__ inline void mf_update(Pack<VEC> (&pp)[NC], Pack<VEC> (&pq)[NC], double& bu,
                                  double& bi, double ry, double b, double lr, double reg, int k,
                                  int l, const O& o = O{},
@@ -254,19 +241,19 @@ __device__ inline void mf_update(Pack<VEC> (&pp)[NC], Pack<VEC> (&pq)[NC], doubl
     for (int c = 0; c < NC; ++c) {
 #pragma unroll
       for (int v = 0; v < VEC; ++v)
-        pp[c].v[v] = mf_adagrad_element(pp[c].v[v], -err * pq[c].v[v] + reg * pp[c].v[v], lr, o.eps,
+        pp[c].v[v] = adagrad_element(pp[c].v[v], -err * pq[c].v[v] + reg * pp[c].v[v], lr, o.eps,
                                         &acc->gp[c].v[v]);
     }
-    bu = mf_adagrad_element(bu, -err + reg * bu, lr, o.eps, &acc->gbu);
+    bu = adagrad_element(bu, -err + reg * bu, lr, o.eps, &acc->gbu);
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
 #pragma unroll
       for (int v = 0; v < VEC; ++v)
         // the item row sees the user row this example has just updated (src/mf.py:193)
-        pq[c].v[v] = mf_adagrad_element(pq[c].v[v], -err * pp[c].v[v] + reg * pq[c].v[v], lr, o.eps,
+        pq[c].v[v] = adagrad_element(pq[c].v[v], -err * pp[c].v[v] + reg * pq[c].v[v], lr, o.eps,
                                         &acc->gq[c].v[v]);
     }
-    bi = mf_adagrad_element(bi, -err + reg * bi, lr, o.eps, &acc->gbi);
+    bi = adagrad_element(bi, -err + reg * bi, lr, o.eps, &acc->gbi);
   } else {
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
@@ -405,21 +392,6 @@ struct MfExArgs {
   double lr, reg;
 };
 
-// the argument block of a kernel under a rule: MfSgdRule's is MfExArgs itself
-struct MfExArgsOpt : MfExArgs {
-  MfAdaGradRule o;
-};
-template <class O>
-struct MfExArgsOf {
-  using type = MfExArgs;
-};
-template <>
-struct MfExArgsOf<MfAdaGradRule> {
-  using type = MfExArgsOpt;
-};
-__device__ inline MfSgdRule rule_of(const MfExArgs&) { return MfSgdRule{}; }
-__device__ inline const MfAdaGradRule& rule_of(const MfExArgsOpt& a) { return a.o; }
-
 // where a record's label / propensity comes from: the record itself (one model), or the model's
 // own vector over the training log through the record's row (several models on one schedule)
 struct RyOfRecord {
@@ -435,7 +407,7 @@ struct RyOfModel {
 
 // one level, many workgroups (examples of a level touch disjoint rows); blockIdx.x / gridDim.x
 // walk the level
-template <int LPR, int VEC, int NC, class Ry, class O = MfSgdRule>
+template <int LPR, int VEC, int NC, class Ry, class O = SgdRule>
 __device__ __forceinline__ void mf_wide_ex_body(const MfExArgs& a, Ry ry_of, const O& o = O{}) {
   constexpr int GPB = kMfBlock / LPR;
   const int l = threadIdx.x % LPR;
@@ -474,8 +446,8 @@ __device__ __forceinline__ void mf_wide_ex_body(const MfExArgs& a, Ry ry_of, con
   }
 }
 
-template <int LPR, int VEC, int NC, class O = MfSgdRule>
-__global__ __launch_bounds__(kMfBlock) void mf_sgd_wide_ex_kernel(typename MfExArgsOf<O>::type a) {
+template <int LPR, int VEC, int NC, class O = SgdRule>
+__global__ __launch_bounds__(kMfBlock) void mf_sgd_wide_ex_kernel(ArgsUnder<MfExArgs, O> a) {
   mf_wide_ex_body<LPR, VEC, NC, RyOfRecord, O>(a, RyOfRecord{}, rule_of(a));
 }
 
@@ -602,7 +574,7 @@ __device__ __forceinline__ void mf_slot_fetch(const MfExArgs& a, const MfSeqLds&
 // parameter rows are still to be read, and are needed only after the residual, so their latency
 // lies beside the dot product, the lane-group sum and the sigmoid; an accumulator row has the
 // writer of its parameter row, so it is final here as that row is.)
-template <int LPR, int VEC, int NC, class O = MfSgdRule>
+template <int LPR, int VEC, int NC, class O = SgdRule>
 __device__ __forceinline__ void mf_slot_run(const MfExArgs& a, const MfSeqLds& m, int l,
                                             MfSlot<VEC, NC>& s, const O& o = O{}) {
   if (!s.has) return;
@@ -679,7 +651,7 @@ constexpr int seq_block(int nc) { return nc > 1 ? 512 : kSeqBlock; }
 // Slots of the read-ahead ring under MfAdaGradRule, by shape class.  The accumulators of the running
 // example (as many registers as its two rows and biases) and the root and quotient come on top of
 // the ring, and no instantiation may spill (profiles/n23/register_counts.txt): at one chunk of two
-// factors per lane the 1024-thread workgroup has 128 registers a lane and MfSgdRule's ring of four
+// factors per lane the 1024-thread workgroup has 128 registers a lane and SgdRule's ring of four
 // takes 116 of them, so two slots; at four chunks three slots.
 constexpr int mf_ada_ring(int vec, int nc) {
   return nc > 4 ? 0 : nc == 4 ? 3 : (vec == 2 && nc == 1) ? 2 : kMfAhead;
@@ -693,7 +665,7 @@ constexpr int mf_seq_threads(int nc) {
   return O::kAda && nc > 8 ? 256 : seq_block(nc);
 }
 
-template <int LPR, int VEC, int NC, class Ry, class O = MfSgdRule>
+template <int LPR, int VEC, int NC, class Ry, class O = SgdRule>
 __device__ __forceinline__ void mf_seq_ex_body(const MfExArgs& a, Ry ry_of, const O& o = O{}) {
   extern __shared__ double seq_lds[];
   constexpr int kSeqBlock = mf_seq_threads<O>(NC);  // (shadows the one-chunk constant inside this kernel)
@@ -815,8 +787,8 @@ __device__ __forceinline__ void mf_seq_ex_body(const MfExArgs& a, Ry ry_of, cons
   }
 }
 
-template <int LPR, int VEC, int NC, class O = MfSgdRule>
-__global__ __launch_bounds__(mf_seq_threads<O>(NC)) void mf_sgd_seq_ex_kernel(typename MfExArgsOf<O>::type a) {
+template <int LPR, int VEC, int NC, class O = SgdRule>
+__global__ __launch_bounds__(mf_seq_threads<O>(NC)) void mf_sgd_seq_ex_kernel(ArgsUnder<MfExArgs, O> a) {
   mf_seq_ex_body<LPR, VEC, NC, RyOfRecord, O>(a, RyOfRecord{}, rule_of(a));
 }
 
@@ -828,8 +800,8 @@ __global__ __launch_bounds__(seq_block(NC)) void mf_sgd_seq_many_kernel(MfManyAr
 }
 
 // the sequential kernels with their dynamic-LDS limit raised where the item cache needs it
-template <int L, int Vv, int N, class O = MfSgdRule>
-static void launch_seq_ex(rfm_ctx* ctx, const typename MfExArgsOf<O>::type& a, int threads, size_t lds) {
+template <int L, int Vv, int N, class O = SgdRule>
+static void launch_seq_ex(rfm_ctx* ctx, const ArgsUnder<MfExArgs, O>& a, int threads, size_t lds) {
   const auto kern = &mf_sgd_seq_ex_kernel<L, Vv, N, O>;
   static LdsLimits allowed;
   allow_dynamic_lds(ctx, reinterpret_cast<const void*>(kern), lds, allowed);
@@ -1231,7 +1203,7 @@ int32_t rfm_mf_cache_capacity(int32_t n_factors, int32_t* h_out) {
 
 }  // extern "C"
 
-// rfm_mf_sgd_levels_ex (MfSgdRule) and rfm_mf_sgd_levels_opt under either rule: one schedule, one
+// rfm_mf_sgd_levels_ex (SgdRule) and rfm_mf_sgd_levels_opt under either rule: one schedule, one
 // launch plan; an item cached under MfAdaGradRule takes twice the LDS (its accumulators)
 template <class O>
 static int32_t mf_levels_ex(rfm_ctx* ctx, const void* d_ex, const int32_t* h_level_ptr,
@@ -1248,9 +1220,8 @@ static int32_t mf_levels_ex(rfm_ctx* ctx, const void* d_ex, const int32_t* h_lev
     RFM_REQUIRE(row_bytes <= size_t(kSeqMaxCacheBytes),
                 "item cache of %d rows exceeds %d bytes of LDS", n_cached, kSeqMaxCacheBytes);
     const size_t cache_bytes = row_bytes * (O::kAda ? 2 : 1);
-    typename MfExArgsOf<O>::type a{};
+    auto a = args_under(MfExArgs{}, o);
     set_model(a, d_P, d_Q, d_bu, d_bi, b, n_factors, lr, reg);
-    if constexpr (O::kAda) a.o = o;
     a.ex = static_cast<const MfEx*>(d_ex);
     a.level_ptr = d_level_ptr;
     a.cache_items = d_cache_items;
@@ -1293,7 +1264,7 @@ int32_t rfm_mf_sgd_levels_ex(rfm_ctx* ctx, const void* d_ex, const int32_t* h_le
                              double* d_Q, double* d_bu, double* d_bi, double b,
                              int32_t n_factors, double lr, double reg) {
   return mf_levels_ex(ctx, d_ex, h_level_ptr, d_level_ptr, n_levels, d_cache_items, n_cached, d_P, d_Q,
-                      d_bu, d_bi, b, n_factors, lr, reg, MfSgdRule{});
+                      d_bu, d_bi, b, n_factors, lr, reg, SgdRule{});
 }
 
 int32_t rfm_mf_sgd_levels_opt(rfm_ctx* ctx, const void* d_ex, const int32_t* h_level_ptr,
@@ -1303,15 +1274,12 @@ int32_t rfm_mf_sgd_levels_opt(rfm_ctx* ctx, const void* d_ex, const int32_t* h_l
                               int32_t n_factors, double lr, double reg, int32_t kind,
                               double* d_acc_P, double* d_acc_Q, double* d_acc_bu, double* d_acc_bi,
                               double eps) {
-  if (kind == RFM_MF_OPT_SGD)
+  bool ada = false;
+  const int32_t rc = guarded([&] { ada = require_rule(kind, d_acc_P && d_acc_Q && d_acc_bu && d_acc_bi, eps); });
+  if (rc != RFM_OK) return rc;
+  if (!ada)
     return rfm_mf_sgd_levels_ex(ctx, d_ex, h_level_ptr, d_level_ptr, n_levels, d_cache_items, n_cached,
                                 d_P, d_Q, d_bu, d_bi, b, n_factors, lr, reg);
-  const int32_t rc = guarded([&] {
-    RFM_REQUIRE(kind == RFM_MF_OPT_ADAGRAD, "optimizer kind %d is neither SGD nor AdaGrad", kind);
-    RFM_REQUIRE(d_acc_P && d_acc_Q && d_acc_bu && d_acc_bi, "AdaGrad with a null accumulator");
-    RFM_REQUIRE(eps > 0.0, "AdaGrad eps must be > 0");  // (false for a NaN)
-  });
-  if (rc != RFM_OK) return rc;
   return mf_levels_ex(ctx, d_ex, h_level_ptr, d_level_ptr, n_levels, d_cache_items, n_cached, d_P, d_Q,
                       d_bu, d_bi, b, n_factors, lr, reg,
                       MfAdaGradRule{d_acc_P, d_acc_Q, d_acc_bu, d_acc_bi, eps});

@@ -25,7 +25,7 @@ import numpy as np
 from . import _lib, fold
 from .base import LOSS_EPS, PointwiseBaseRecommender
 from .evaluate import EvalLoop, FitHook, device_frame, runs
-from .optimizer import DeviceAdaGrad, DeviceSGD
+from .optimizer import DeviceSGD, take_optimizer
 from .runtime import BatchIdStream, CsrCache, DeviceCSR, Runtime
 
 
@@ -138,8 +138,8 @@ class FmPlan:
         return dict(zip(("sliced", "workgroups", "rows_per_workgroup", "lds_bytes"), (int(v) for v in out)))
 
     def set_optimizer(self, kind: int, acc_w0=None, acc_w=None, acc_V=None, eps: float = 0.0) -> None:
-        """The update rule of the plan's steps (``rfm_fm_plan_set_optimizer``): ``_lib.FM_OPT_SGD``, or
-        ``_lib.FM_OPT_ADAGRAD`` with the three accumulators (device tensors the caller keeps alive)."""
+        """The update rule of the plan's steps (``rfm_fm_plan_set_optimizer``): ``_lib.OPT_SGD``, or
+        ``_lib.OPT_ADAGRAD`` with the three accumulators (device tensors the caller keeps alive)."""
         ptr = [t.data_ptr() if t is not None else None for t in (acc_w0, acc_w, acc_V)]
         _lib.check(self.rt.lib.rfm_fm_plan_set_optimizer(self.handle, int(kind), *ptr, float(eps)))
 
@@ -320,22 +320,6 @@ class FactorizationMachines(PointwiseBaseRecommender):
             self.model_name = "FM"
 
     # ------------------------------------------------------------------ fit
-    def _take_optimizer(self) -> bool:
-        """Checks ``optimizer``; with "adagrad" the three handles become ``DeviceAdaGrad`` on the
-        same device tensors (once: the accumulators persist).  True for AdaGrad."""
-        if self.optimizer not in ("sgd", "adagrad"):
-            raise ValueError(f"optimizer must be 'sgd' or 'adagrad', got {self.optimizer!r}")
-        if self.optimizer == "sgd":
-            return False
-        if not float(self.adagrad_eps) > 0.0:
-            raise ValueError(f"adagrad_eps={self.adagrad_eps!r} must be > 0")
-        for name in ("w0", "w", "V"):
-            h = getattr(self, name)
-            if not isinstance(h, DeviceAdaGrad):
-                setattr(self, name, DeviceAdaGrad(self._rt, None, h.lr, self.adagrad_eps, self.adagrad_init,
-                                                  dev=h.dev))
-        return True
-
     def fit(self, train: dict, val: dict) -> tuple:
         """src/fm.py:55-112.  One "epoch" is one mini-batch step; returns the
         per-iteration train and validation IPS log-loss as two lists."""
@@ -344,7 +328,7 @@ class FactorizationMachines(PointwiseBaseRecommender):
         n_rows = X.shape[0]
         if X.shape[1] != self.n_features:
             raise ValueError(f"train features have {X.shape[1]} columns, model has {self.n_features}")
-        self._take_optimizer()
+        take_optimizer(self, ("w0", "w", "V"))
         if self.n_epochs <= 0:
             return [], []
         # batch selection: resample(..., random_state=epoch) (src/fm.py:72-79), sampled chunk by
@@ -384,9 +368,9 @@ class FactorizationMachines(PointwiseBaseRecommender):
             return EvalLoop(rt, frame, evaluator, self.estimator, self.n_epochs, log=ev)
 
         try:
-            if self._take_optimizer():
+            if take_optimizer(self, ("w0", "w", "V")):
                 # (plans are shared through plan_cache: the rule is set for this fit and taken back below)
-                plan.set_optimizer(_lib.FM_OPT_ADAGRAD, self.w0.acc, self.w.acc, self.V.acc, self.adagrad_eps)
+                plan.set_optimizer(_lib.OPT_ADAGRAD, self.w0.acc, self.w.acc, self.V.acc, self.adagrad_eps)
             hook = FitHook(self, self.n_epochs, self.predict, make_loop)
             for first, host_ids, dev_ids in id_stream.chunks():
                 count = dev_ids.shape[0]
@@ -413,7 +397,7 @@ class FactorizationMachines(PointwiseBaseRecommender):
             # (the registration ends with the fit: the plan may outlive this split's device copy)
             for log_slot in (0, 1):
                 rt.lib.rfm_fm_plan_register_log(rt.ctx, plan.handle, log_slot, None, None, None, 0)
-            rt.lib.rfm_fm_plan_set_optimizer(plan.handle, _lib.FM_OPT_SGD, None, None, None, 0.0)
+            rt.lib.rfm_fm_plan_set_optimizer(plan.handle, _lib.OPT_SGD, None, None, None, 0.0)
             st.release()
         return st.losses()
 

@@ -18,7 +18,7 @@ import numpy as np
 from . import _lib, fold
 from .base import LOSS_EPS, PointwiseBaseRecommender
 from .evaluate import EvalLoop, FitHook, device_frame
-from .optimizer import DeviceAdaGrad, DeviceSGD
+from .optimizer import DeviceSGD, take_optimizer
 from .runtime import BatchIdStream, Runtime, mf_cache_capacity, mf_schedule_ex, mf_schedule_rows
 
 
@@ -221,28 +221,10 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
             raise IndexError("item id out of range")
 
     # ------------------------------------------------------------------ fit
-    def _take_optimizer(self) -> bool:
-        """Checks ``optimizer``; with "adagrad" the four handles become ``DeviceAdaGrad`` on the
-        same device tensors (once: the accumulators persist).  True for AdaGrad."""
-        if self.optimizer not in ("sgd", "adagrad"):
-            raise ValueError(f"optimizer must be 'sgd' or 'adagrad', got {self.optimizer!r}")
-        if self.optimizer == "sgd":
-            return False
-        if not float(self.adagrad_eps) > 0.0:
-            raise ValueError(f"adagrad_eps={self.adagrad_eps!r} must be > 0")
-        if self.hogwild:
-            raise ValueError("optimizer = 'adagrad' runs in exact mode only (hogwild = True has no order)")
-        for name in ("P", "Q", "b_u", "b_i"):
-            h = getattr(self, name)
-            if not isinstance(h, DeviceAdaGrad):
-                setattr(self, name, DeviceAdaGrad(self._rt, None, h.lr, self.adagrad_eps, self.adagrad_init,
-                                                  dev=h.dev))
-        return True
-
     def fit(self, train: dict, val: dict) -> tuple:
         """src/mf.py:68-134."""
         rt = self._rt
-        self._take_optimizer()
+        take_optimizer(self, ("P", "Q", "b_u", "b_i"), inexact=self.hogwild)
         # global bias: mean of the training labels (src/mf.py:84)
         self.b = np.mean(train["labels"])
         n_rows = int(np.asarray(train["features"]).shape[0])
@@ -275,7 +257,7 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
         params = (self.P.dev.data_ptr(), self.Q.dev.data_ptr(), self.b_u.dev.data_ptr(),
                   self.b_i.dev.data_ptr())
         b = float(self.b)
-        adagrad = self._take_optimizer()
+        adagrad = take_optimizer(self, ("P", "Q", "b_u", "b_i"), inexact=self.hogwild)
         h_y = np.ascontiguousarray(train["labels"], dtype=np.float64)
         h_p = np.ascontiguousarray(train["pscores"], dtype=np.float64)
         # item rows the sequential kernel may keep in LDS (rows + bias, 32 KiB)
@@ -326,24 +308,19 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
                 return mf_schedule_ex(tr.h_users[rows], tr.h_items[rows], h_y[rows], h_p[rows],
                                       self.n_users, self.n_items, cache_cap)
 
+            # the SGD fit runs rfm_mf_sgd_levels_ex; the other rule is the same schedule through
+            # rfm_mf_sgd_levels_opt, whose arguments end with kind, accumulators and eps
+            levels, rule = rt.lib.rfm_mf_sgd_levels_ex, ()
+            if adagrad:
+                levels = rt.lib.rfm_mf_sgd_levels_opt
+                rule = (_lib.OPT_ADAGRAD, *(h.acc.data_ptr() for h in (self.P, self.Q, self.b_u, self.b_i)),
+                        float(self.adagrad_eps))
+
             def step(epoch, ids_ptr, d_ex, h_lptr, d_lptr, n_levels, d_cache, n_cached, _d_rows, done):
-                _lib.check(rt.lib.rfm_mf_sgd_levels_ex(
-                    rt.ctx, d_ex, h_lptr, d_lptr, n_levels, d_cache, n_cached, *params, b,
-                    self.n_factors, float(self.lr), float(self.reg)))
+                _lib.check(levels(rt.ctx, d_ex, h_lptr, d_lptr, n_levels, d_cache, n_cached, *params, b,
+                                  self.n_factors, float(self.lr), float(self.reg), *rule))
                 done()
                 after_sgd(epoch, ids_ptr)
-
-            if adagrad:
-                # the same schedule under the other rule (rfm_mf_sgd_levels_opt)
-                accs = tuple(h.acc.data_ptr() for h in (self.P, self.Q, self.b_u, self.b_i))
-
-                def step(epoch, ids_ptr, d_ex, h_lptr, d_lptr, n_levels, d_cache, n_cached, _d_rows, done):  # noqa: F811
-                    _lib.check(rt.lib.rfm_mf_sgd_levels_opt(
-                        rt.ctx, d_ex, h_lptr, d_lptr, n_levels, d_cache, n_cached, *params, b,
-                        self.n_factors, float(self.lr), float(self.reg), _lib.MF_OPT_ADAGRAD, *accs,
-                        float(self.adagrad_eps)))
-                    done()
-                    after_sgd(epoch, ids_ptr)
 
             pipe.run(self._epochs(id_stream), schedule, step)
         rt.sync()

@@ -54,7 +54,7 @@ class DeviceSGD:
 def adagrad_update(params: np.ndarray, acc: np.ndarray, grad, lr: float, eps: float, index=None) -> None:
     """The AdaGrad rule on host arrays, in place: ``G += g * g`` (the product rounded, then the sum),
     ``theta -= (lr * g) / (sqrt(G) + eps)`` -- NumPy float64 states the operations the kernels run
-    (``include/rfm_fm_opt.h``)."""
+    (``include/rfm_hip.h``, "the optimiser seam")."""
     g = np.asarray(grad, dtype=np.float64)
     if index is None:
         acc += g * g
@@ -96,3 +96,23 @@ class DeviceAdaGrad(DeviceSGD):
         grown = torch.full((int(dev_rows.shape[0]),) + tuple(self.acc.shape[1:]), self.init, dtype=torch.float64,
                            device=self.acc.device)
         self.acc = torch.cat([self.acc, grown], dim=0).contiguous()
+
+
+def take_optimizer(model, names, inexact: bool = False) -> bool:
+    """Checks ``model.optimizer``; with "adagrad" the handles ``names`` of the model become
+    ``DeviceAdaGrad`` on the same device tensors (once: the accumulators persist).  ``inexact``: the
+    model is in a mode without a batch order (MF's ``hogwild``), which only the SGD rule runs in.
+    True for AdaGrad."""
+    if model.optimizer not in ("sgd", "adagrad"):
+        raise ValueError(f"optimizer must be 'sgd' or 'adagrad', got {model.optimizer!r}")
+    if model.optimizer == "sgd":
+        return False
+    if not float(model.adagrad_eps) > 0.0:
+        raise ValueError(f"adagrad_eps={model.adagrad_eps!r} must be > 0")
+    if inexact:
+        raise ValueError("optimizer = 'adagrad' runs in exact mode only (hogwild = True has no order)")
+    for name in names:
+        h = getattr(model, name)
+        if not isinstance(h, DeviceAdaGrad):
+            setattr(model, name, DeviceAdaGrad(model._rt, None, h.lr, model.adagrad_eps, model.adagrad_init, dev=h.dev))
+    return True

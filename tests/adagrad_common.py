@@ -1,5 +1,5 @@
 """Shared by the tests of the FM fit's AdaGrad rule (test_adagrad_host.py, test_gpu_adagrad.py): the
-rule in NumPy float64 and in long double, the intervals a device value has to lie in, the case lists
+rule in NumPy float64 and in long double (optimizer_common.py), the intervals a device value has to lie in, the case lists
 of the GPU tests with their oracle (no GPU needed to build them, so the host test can check the
 condition below on every one), a float64 restatement of the fit, and thin wrappers of the raw ABI.
 Importing this module touches neither the GPU nor the package under test.
@@ -39,31 +39,22 @@ import numpy as np
 from scipy.sparse import csr_matrix
 
 import grad_forms_common as gf
+from optimizer_common import ADAGRAD, LD, SGD, log_digest, rule_f64, rule_ld  # noqa: F401 (the tests' names for them)
 from oracle import cpu_ref
 
-LD = np.longdouble
 LR = 2.0 ** -3
 EPS = 1e-10
 EMPTY_ROWS = (5, 700, 1499)
 SHARD = np.array([11, 5, 1200, 42, 977], dtype=np.int32)  # row 5 is empty
 K_SHORT_SPLIT = 8
-SGD, ADAGRAD = 0, 1
 
 
 # --------------------------------------------------------------------------
 # the rule
 # --------------------------------------------------------------------------
-def rule_f64(theta, G, g, lr, eps):
-    """(theta_new, G_new) in NumPy float64: the operations the kernels run, one rounding each."""
-    theta, G, g = (np.asarray(a, dtype=np.float64) for a in (theta, G, g))
-    gg = g * g
-    Gn = G + gg
-    return theta - (lr * g) / (np.sqrt(Gn) + eps), Gn
-
-
 def step_ld(g, G, lr, eps):
-    g, G = np.asarray(g).astype(LD), np.asarray(G).astype(LD)
-    return LD(lr) * g / (np.sqrt(G + g * g) + LD(eps))
+    """step(g) in long double: what the shared rule takes off theta."""
+    return -rule_ld(0.0, G, g, lr, eps)[0]
 
 
 def intervals(theta, G, g, S, lr, eps, rows):
@@ -231,24 +222,6 @@ def fit_f64(train, val, n_epochs, n_factors, lr, eps, init, batch_size, seed, or
 def coat_split(est):
     from relevance_factorizationmachine_amd import synth
     return synth.make_log(synth.SHAPES["coat"], "FM", est, seed=0)
-
-
-def log_digest(train, val):
-    """The input digest the golden generators store (tests/golden/make_golden.py log_digest)."""
-    import hashlib
-
-    def digest(*arrays):
-        h = hashlib.sha256()
-        for a in arrays:
-            h.update(np.ascontiguousarray(a).tobytes())
-        return h.hexdigest()
-
-    parts = []
-    for d in (train, val):
-        f = d["features"]
-        parts.append(digest(f.indptr.astype(np.int64), f.indices.astype(np.int64), f.data))
-        parts.append(digest(d["labels"], d["pscores"]))
-    return "|".join(parts)
 
 
 # --------------------------------------------------------------------------

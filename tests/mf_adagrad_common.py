@@ -6,8 +6,9 @@ arrays between sentinels.  The cases, builders, distances of parameters and the 
 ``DeviceParams`` wrappers are those of mf_step_common.py.  Importing this module touches neither the
 GPU nor the library under test.
 
-The rule (include/rfm_mf_opt.h).  Every element of P, Q, b_u, b_i has an accumulator G.  For one
-example (u, i), err is formed once and then, in the reference's order,
+The rule (include/rfm_hip.h, "MF: the optimiser seam"; one array's update: optimizer_common.py).
+Every element of P, Q, b_u, b_i has an accumulator G.  For one example (u, i), err is formed once
+and then, in the reference's order,
     g = -err Q_i + reg P_u;       G_P[u] += g g;  P_u -= (lr g) / (sqrt(G_P[u]) + eps)
     g = -err P_u(new) + reg Q_i;  G_Q[i], Q_i likewise
     g = -err + reg b_u[u];        G_bu[u], b_u[u] likewise
@@ -42,6 +43,7 @@ import numpy as np
 
 import mf_step_common as ms
 from mf_step_common import B0, LD, LR, REG
+from optimizer_common import ADAGRAD, SGD, log_digest, rule_f64, rule_ld  # noqa: F401 (the tests' names for them)
 
 EPS = 1e-10
 ACC_KINDS = ("zero", "uniform")
@@ -70,11 +72,6 @@ def acc_init(case, kind):
 # --------------------------------------------------------------------------
 # the oracle: long double, example by example
 # --------------------------------------------------------------------------
-def _rule_ld(theta, G, g, lr, eps):
-    Gn = G + g * g
-    return theta - (lr * g) / (np.sqrt(Gn) + eps), Gn
-
-
 def mf_adagrad_batch_ld(pairs, ry, params, accs, b, lr, reg, eps, form=None):
     """One batch under the rule in np.longdouble; returns the eight arrays (P, Q, b_u, b_i and their
     accumulators).  ``form`` as in ``ms.mf_sgd_batch_ld``: "loop" walks the batch example by example,
@@ -90,19 +87,19 @@ def mf_adagrad_batch_ld(pairs, ry, params, accs, b, lr, reg, eps, form=None):
         assert ms.is_disjoint(pairs)
         u, i = pairs[:, 0], pairs[:, 1]
         err = ry - ms._sigmoid_ld((P[u] * Q[i]).sum(axis=1) + bu[u] + bi[i] + b)
-        P[u], GP[u] = _rule_ld(P[u], GP[u], -err[:, None] * Q[i] + reg * P[u], lr, eps)
-        Q[i], GQ[i] = _rule_ld(Q[i], GQ[i], -err[:, None] * P[u] + reg * Q[i], lr, eps)
-        bu[u], Gbu[u] = _rule_ld(bu[u], Gbu[u], -err + reg * bu[u], lr, eps)
-        bi[i], Gbi[i] = _rule_ld(bi[i], Gbi[i], -err + reg * bi[i], lr, eps)
+        P[u], GP[u] = rule_ld(P[u], GP[u], -err[:, None] * Q[i] + reg * P[u], lr, eps)
+        Q[i], GQ[i] = rule_ld(Q[i], GQ[i], -err[:, None] * P[u] + reg * Q[i], lr, eps)
+        bu[u], Gbu[u] = rule_ld(bu[u], Gbu[u], -err + reg * bu[u], lr, eps)
+        bi[i], Gbi[i] = rule_ld(bi[i], Gbi[i], -err + reg * bi[i], lr, eps)
         return P, Q, bu, bi, GP, GQ, Gbu, Gbi
     assert form == "loop"
     for (u, i), r in zip(pairs, ry):
         err = r - ms._sigmoid_ld((P[u] * Q[i]).sum() + bu[u] + bi[i] + b)
-        P[u], GP[u] = _rule_ld(P[u], GP[u], -err * Q[i] + reg * P[u], lr, eps)
+        P[u], GP[u] = rule_ld(P[u], GP[u], -err * Q[i] + reg * P[u], lr, eps)
         # the item row sees the user row this example has just updated
-        Q[i], GQ[i] = _rule_ld(Q[i], GQ[i], -err * P[u] + reg * Q[i], lr, eps)
-        bu[u], Gbu[u] = _rule_ld(bu[u], Gbu[u], -err + reg * bu[u], lr, eps)
-        bi[i], Gbi[i] = _rule_ld(bi[i], Gbi[i], -err + reg * bi[i], lr, eps)
+        Q[i], GQ[i] = rule_ld(Q[i], GQ[i], -err * P[u] + reg * Q[i], lr, eps)
+        bu[u], Gbu[u] = rule_ld(bu[u], Gbu[u], -err + reg * bu[u], lr, eps)
+        bi[i], Gbi[i] = rule_ld(bi[i], Gbi[i], -err + reg * bi[i], lr, eps)
     return P, Q, bu, bi, GP, GQ, Gbu, Gbi
 
 
@@ -113,18 +110,18 @@ MUTATIONS = ("old_G", "eps_in_root", "stale_user_row", "row_acc")
 
 
 def _rule_f64(theta, G, g, lr, eps, mutation=None):
-    """One array's update in float64: returns (theta_new, G_new)."""
+    """One array's update in float64, the shared rule or a wrong one: returns (theta_new, G_new)."""
     if mutation == "row_acc" and np.ndim(g) >= 1 and np.ndim(G) == np.ndim(g):
         # one accumulator per row instead of per element: kept in the row's first element, read by all
         Gn = np.array(G, dtype=np.float64)
         Gn[..., :] = G[..., :1] + (g * g).sum(axis=-1, keepdims=True)
         return theta - (lr * g) / (np.sqrt(Gn) + eps), Gn
-    Gn = G + g * g
+    new, Gn = rule_f64(theta, G, g, lr, eps)
     if mutation == "old_G":
         return theta - (lr * g) / (np.sqrt(G) + eps), Gn
     if mutation == "eps_in_root":
         return theta - (lr * g) / np.sqrt(Gn + eps), Gn
-    return theta - (lr * g) / (np.sqrt(Gn) + eps), Gn
+    return new, Gn
 
 
 def mf_adagrad_batch_f64(pairs, ry, params, accs, b, lr, reg, eps, mutation=None, dot=ms._dot_reversed):
@@ -180,20 +177,6 @@ def assert_all_within(got8, want8, start8, pairs, what, lr=LR):
     return tuple(worst)
 
 
-def log_digest(train, val):
-    """The input digest the golden generators store for an MF log (tests/golden/make_golden.py
-    log_digest on dense ``features``)."""
-    import hashlib
-
-    def digest(*arrays):
-        h = hashlib.sha256()
-        for a in arrays:
-            h.update(np.ascontiguousarray(a).tobytes())
-        return h.hexdigest()
-
-    return "|".join(part for d in (train, val) for part in (digest(d["features"]), digest(d["labels"], d["pscores"])))
-
-
 # --------------------------------------------------------------------------
 # oracles and floors of the cases
 # --------------------------------------------------------------------------
@@ -225,7 +208,6 @@ def floor_of(case, kind):
 # --------------------------------------------------------------------------
 # the raw ABI call, all eight device arrays between sentinels
 # --------------------------------------------------------------------------
-SGD, ADAGRAD = 0, 1   # RFM_MF_OPT_* of include/rfm_mf_opt.h
 GEOMETRY = ("lanes_per_row", "factors_per_chunk", "chunks_per_lane", "seq_threads", "acc_ahead",
             "lds_bytes_per_cached_item", "row_ahead")
 

@@ -3,7 +3,7 @@ mf_adagrad_common.py against a float64 loop on ``optimizer.adagrad_update`` (the
 ``DeviceAdaGrad``), that loop against the golden the reference produced with an AdaGrad subclass of
 its BaseOptimizer (tests/golden/make_golden_mf_adagrad.py), the tolerance floors and the condition
 that keeps them from hiding a failure, four wrong rules caught on the affected elements and only
-there, include/rfm_mf_opt.h against ``_lib.MF_OPT_SIGNATURES``, and the argument checks that need no
+there, the kinds of the header against the Python pair, and the argument checks that need no
 device."""
 import numpy as np
 import pytest
@@ -156,53 +156,22 @@ def test_mutation_one_accumulator_per_row_is_caught():
 
 
 # --------------------------------------------------------------------------
-# the ABI table, the geometry query and the argument checks that need no device
+# the kinds of the ABI, the geometry query and the argument checks that need no device
 # --------------------------------------------------------------------------
-def test_optimizer_header_table_and_library_agree():
-    """include/rfm_mf_opt.h against ``_lib.MF_OPT_SIGNATURES`` argument by argument (the rule of
-    test_host_abi.py: a parameter with a ``*`` is a pointer, the scalars are themselves), the library
-    exports every entry, rfm_hip.h includes the header and the tables do not overlap."""
-    import ctypes as C
+def test_optimizer_kinds_and_entry_extend_the_existing_ones():
+    """``RFM_MF_OPT_*`` of include/rfm_hip.h are defined as ``RFM_FM_OPT_*``, the Python pair, and the entry is
+    rfm_mf_sgd_levels_ex's arguments, unmoved, then kind, four accumulators, eps (the declarations:
+    test_host_abi.py)."""
     import os
     import re
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    assert '#include "rfm_mf_opt.h"' in open(os.path.join(root, "include", "rfm_hip.h")).read()
-    header = open(os.path.join(root, "include", "rfm_mf_opt.h")).read()
-    assert any(h.endswith("rfm_mf_opt.h") for h in _lib.HEADERS)
+    header = open(os.path.join(root, "include", "rfm_hip.h")).read()
     defines = dict(re.findall(r"#define (RFM_MF_OPT_\w+) (\w+)", header))
     assert defines == {"RFM_MF_OPT_SGD": "RFM_FM_OPT_SGD", "RFM_MF_OPT_ADAGRAD": "RFM_FM_OPT_ADAGRAD"}
-    assert (_lib.MF_OPT_SGD, _lib.MF_OPT_ADAGRAD) == (_lib.FM_OPT_SGD, _lib.FM_OPT_ADAGRAD) == (ma.SGD, ma.ADAGRAD)
-    header = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
-    scalars = {"int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double}
-
-    def header_kind(param):
-        if "*" in param:
-            return "pointer"
-        kinds = [name for name in scalars if re.search(r"\b%s\b" % name, param)]
-        assert len(kinds) == 1, f"cannot classify parameter {param!r}"
-        return kinds[0]
-
-    def table_kind(ctype):
-        for name, scalar in scalars.items():
-            if ctype is scalar:
-                return name
-        assert ctype is C.c_void_p or issubclass(ctype, C._Pointer), ctype
-        return "pointer"
-
-    declared = re.findall(r"^int32_t\s+(rfm_\w+)\s*\(([^)]*)\)\s*;", header, flags=re.M)
-    assert sorted(n for n, _ in declared) == sorted(_lib.MF_OPT_SIGNATURES) and len(declared) == 2
-    others = {**_lib.SIGNATURES, **_lib.MF_MANY_SIGNATURES, **_lib.FOLD_GROUP_SIGNATURES, **_lib.FM_OPT_SIGNATURES}
-    assert not set(_lib.MF_OPT_SIGNATURES) & set(others)
-    lib = _lib.load()
-    for name, params in declared:
-        assert hasattr(lib, name), f"{name} declared in rfm_mf_opt.h but not exported"
-        want = [header_kind(p.strip()) for p in params.split(",")]
-        got = [table_kind(t) for t in _lib.MF_OPT_SIGNATURES[name]]
-        assert want == got, (name, want, got)
-    # the entry is rfm_mf_sgd_levels_ex's arguments, unmoved, then kind, four accumulators, eps
+    assert (_lib.OPT_SGD, _lib.OPT_ADAGRAD) == (ma.SGD, ma.ADAGRAD)
     ex = _lib.SIGNATURES["rfm_mf_sgd_levels_ex"]
-    assert _lib.MF_OPT_SIGNATURES["rfm_mf_sgd_levels_opt"][: len(ex)] == ex
+    assert _lib.SIGNATURES["rfm_mf_sgd_levels_opt"][: len(ex)] == ex and len(ex) == 15
 
 
 @pytest.mark.parametrize("k", ms.SHAPE_KS)
@@ -244,21 +213,25 @@ def test_bad_arguments_that_need_no_device():
 
 
 def test_python_checks_that_need_no_launch():
-    """The attribute's checks come before any launch (``_take_optimizer``)."""
+    """The attribute's checks come before any launch (``optimizer.take_optimizer``, as ``fit`` calls it)."""
     from relevance_factorizationmachine_amd.mf import LogisticMatrixFactorization as MF
+    from relevance_factorizationmachine_amd.optimizer import take_optimizer
+
+    def take(model):
+        return take_optimizer(model, ("P", "Q", "b_u", "b_i"), inexact=model.hogwild)
 
     class Probe:
         optimizer, adagrad_eps, adagrad_init, hogwild = "sgd", 1e-10, 0.0, False
 
     assert (MF.optimizer, MF.adagrad_eps, MF.adagrad_init) == ("sgd", 1e-10, 0.0)
     probe = Probe()
-    assert MF._take_optimizer(probe) is False
+    assert take(probe) is False
     probe.optimizer = "adam"
     with pytest.raises(ValueError, match="optimizer must be"):
-        MF._take_optimizer(probe)
+        take(probe)
     probe.optimizer, probe.adagrad_eps = "adagrad", 0.0
     with pytest.raises(ValueError, match="adagrad_eps"):
-        MF._take_optimizer(probe)
+        take(probe)
     probe.adagrad_eps, probe.hogwild = 1e-10, True
     with pytest.raises(ValueError, match="exact mode only"):
-        MF._take_optimizer(probe)
+        take(probe)
