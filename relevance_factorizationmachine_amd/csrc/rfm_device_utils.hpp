@@ -31,6 +31,9 @@ __device__ inline double group_sum(double v) {
   return v;
 }
 
+// the value of the lane 8 places away in its row of 16 lanes (DPP row_ror:8)
+__device__ inline double dpp_across_8(double v) { return dpp_move<0x128>(v); }
+
 __device__ inline double sigmoid_clipped(double z) {
   // np.clip keeps a NaN logit NaN (src/base.py:65); fmin/fmax alone would turn it into -700
   z = z != z ? z : fmin(fmax(z, -kLogitClip), kLogitClip);

@@ -134,6 +134,17 @@ void launch_forward(rfm_ctx* ctx, FwdArgs a, FwdGeom geom) {
   const Shape s = shape_for(a.k);
   const bool recs = a.ent != nullptr || a.ell != nullptr;  // the plan's records
   const bool fixed = recs && a.hot_fixed && a.n_hot > 0;
+  // the step's forward on padded row blocks, many-rows shape, arrival-order hot sums, k = 20 .. 32
+  // in fours: 8 lanes x 4 factors per row, one row per lane group (the plan and the launch geometry
+  // are those of 16 lanes)
+  if (geom.block == kBigBlock && a.ell && !fixed && forward_lanes8(a.k) && a.out_Q && a.slot_mark &&
+      !a.loss_partial && a.n_rows_x == 0 && a.ell_stride == int64_t(16 * sizeof(Entry))) {
+    const size_t lds8 = forward_lanes8_lds_bytes(geom.block, a.n_hot, a.k);
+    RFM_REQUIRE(lds8 <= (160u << 10), "forward kernel: %zu bytes of LDS", lds8);
+    launch_forward_as<8, 2, 2, kBigBlock, 1, true, true, false>(ctx, a, geom, lds8);
+    RFM_HIP_CHECK(hipGetLastError());
+    return;
+  }
   const size_t lds =
       forward_lds_bytes(geom.block, s.lpr, s.vec, s.nc,
                         geom.block == kBigBlock ? (recs ? rows_in_flight(s.nc) : rows_in_flight_plain(s.nc)) : 1,

@@ -71,6 +71,9 @@ constexpr bool hot_fixed_order(int lpr, int nc, int block, int rows) {
 // hot columns' err * x * q are summed on the matrix core, see the kernel's hot pass
 constexpr int kTileRanks = 16;  // 16 or 32: tiles of 16 ranks (32 measured no faster: DESIGN.md section 7)
 constexpr bool hot_tile(int lpr, int vec, int nc) { return lpr == 16 && vec == 2 && nc == 1; }
+// The step's forward at 8 lanes x 2 chunks x 2 factors per row (fm_forward_lanes8): k = 20, 24, 28, 32
+// on padded row blocks, many-rows shape, arrival-order hot sums.  The plan stays that of 16 lanes per row.
+constexpr bool forward_lanes8(int k) { return k > 16 && k <= 32 && k % 4 == 0; }
 constexpr int kHotUnroll = 2;  // rows of a fixed-order hot sum whose LDS reads are in flight together
 constexpr int kHotPosPad = 4;  // bytes between the position rows of two columns (bank spread)
 // LDS bytes of the forward kernel (what a launch asks for)
@@ -92,6 +95,12 @@ inline size_t forward_lds_bytes(int block, int lpr, int vec, int nc, int rows, i
     bytes += (size_t(n_hot) * (rt + kHotPosPad) + 7) / 8 * 8;            // entry positions
   }
   return bytes;
+}
+// ... of the 8-lane shape: what the 16-lane many-rows shape asks for on the same plan.  Its row
+// buffers (16 entries a lane group, groups one record apart) reach 1 KiB back into `red`, which
+// nothing uses before the trips are over.
+inline size_t forward_lanes8_lds_bytes(int block, int n_hot, int k) {
+  return forward_lds_bytes(block, 16, 2, 1, kFwdRows, n_hot, k, false);
 }
 
 // ---------------------------------------------------------------------------
@@ -164,6 +173,292 @@ struct HotEnt {
 };
 static_assert(sizeof(HotEnt) == sizeof(Entry), "HotEnt replaces an Entry in place");
 
+// The step's forward at 8 lanes x 4 factors per row and ONE row per lane group (forward_lanes8;
+// fm_forward_kernel<8, 2, 2, kBigBlock, 1, true, true>): the many-rows shape on padded row blocks
+// with arrival-order hot sums, with fewer of the instructions of a row that do not depend on the
+// factor -- addresses, parked-entry reads, scores, marks, walk bookkeeping serve 8 rows per
+// wavefront instruction and are issued once, not once per row in flight.  Lane L of a group holds
+// the factor pairs 2L, 2L + 1 and 16 + 2L, 16 + 2L + 1 -- lanes L and 8 + L of the 16-lane map, two
+// chunks of 8 lanes x 2 factors -- so that each of its two 16-byte loads of a row of V is, over
+// the group, one whole 128-byte line (four adjacent factors per lane touch every line twice, half
+// of it each time: measured 1.2 us SLOWER than the 16-lane map).  It holds
+// entries 2L, 2L + 1 of the row's block of 16.  Lane groups 2G and 2G + 1 -- one 16-lane slice --
+// take the rows G and GPB / 2 + G of the trip, the two rows of group G of the 16-lane map.
+//
+// Every row comes out with the bits of the 16-lane map: a factor's sum runs over the entries in
+// their order; a lane's two squared-sum partials go through group_sum<8> apart (stages l ^ 1,
+// l ^ 2 and the half mirror of the 16-lane tree) and are added last (its row mirror); a lane's
+// two linear terms are added first (stage l ^ 1), then group_sum<8> makes the other three stages;
+// the slice's two residuals enter the workgroup's sum in the 16-lane map's thread and order.  The
+// fused multiply-adds are spelled out where the 16-lane map's are contracted.
+// LDS: as forward_lanes8_lds_bytes says -- red | row buffers [GPB][16 + 1] Entry, ending where the
+// 16-lane shape's end | hot sums [H][k+2] | coefficient strips [GPB][kTileRanks].
+template <int BLOCK>
+__device__ inline void fm_forward_lanes8(const FwdArgs& a) {
+  constexpr int LPR = 8, VEC = 4, EPR = 16;  // lanes, factors of a lane, entries of a row block
+  constexpr int GPB = BLOCK / LPR, GPW = kWave / LPR;
+  static_assert(kTileRanks == 16 && EPR == 2 * LPR, "one tile of 16 ranks; two entries per lane");
+  static_assert(GPB * (EPR + 1) <= BLOCK * kFwdRows + BLOCK / 16 + BLOCK / 16, "row buffers reach at most 1 KiB into red");
+  extern __shared__ double dyn_lds[];
+  const int tid = threadIdx.x;
+  const int l = tid % LPR;
+  const int g = tid / LPR;
+  const int k = a.k;
+  const int hot_w = k + 2;
+  const int H = a.n_hot;
+  const unsigned bx = blockIdx.x, gx = gridDim.x;
+  double* red = dyn_lds;
+  double* hot = dyn_lds + BLOCK + 2 * (BLOCK * kFwdRows + BLOCK / 16);
+  Entry* ebuf = reinterpret_cast<Entry*>(hot) - (GPB - g) * (EPR + 1);
+  const int rt = (g & 1) * (GPB / 2) + (g >> 1);  // the group's row of a trip
+  const double w0 = a.w0[0];
+  const int64_t last_row = a.n_rows - 1;
+  double err_acc = 0.0;
+  // the lane's two pairs of factors; a pair past k reads offset 0 and is masked
+  const int f0 = 2 * l, f1 = 16 + 2 * l;
+  const bool fok[2] = {true, f1 < k};  // (k > 16: the first pair is always there)
+  const int fo[2] = {fok[0] ? f0 : 0, fok[1] ? f1 : 0};
+
+  if (H > 0) {
+    for (int i = tid; i < H * hot_w; i += BLOCK) hot[i] = 0.0;
+    __syncthreads();
+  }
+  for (int64_t base = int64_t(bx) * GPB; base < a.n_rows; base += int64_t(gx) * GPB) {
+    const int64_t t = base + rt;
+    const bool valid = t <= last_row;
+    int32_t r = int32_t(valid ? t : last_row);
+    if (a.row_ids) r = a.row_ids[r];
+    // the workgroup's next trip: its row id now and (under the hot pass) a touch of its row block
+    const int64_t nbase = base + int64_t(gx) * GPB;
+    const bool warm = a.row_ids && nbase < a.n_rows;
+    int32_t nxt = 0;
+    if (warm) nxt = a.row_ids[nbase + rt <= last_row ? nbase + rt : last_row];
+    Entry e[2];
+#pragma unroll
+    for (int n = 0; n < 2; ++n) e[n] = reinterpret_cast<const Entry*>(a.ell + int64_t(r) * a.ell_stride)[2 * l + n];
+    const double2 yp = a.ell_yp[r];
+    // the row's length: its entries that are not padding (they come first)
+    int len = 0;
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+      const unsigned long long live = __ballot(e[n].slot != kNilSlot);
+      len += __popc(unsigned(live >> ((g % GPW) * LPR)) & ((1u << LPR) - 1u));
+    }
+    if (!valid) len = 0;
+    double lin = 0.0;
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+      if (2 * l + n >= len) {  // padding: the row's own last entry again, with x = 0
+        e[n].slot = 0;
+        e[n].x = 0.0;
+      }
+      const double term = __builtin_fma(a.w[e[n].col], e[n].x, 0.0);
+      lin = n == 0 ? term : lin + term;
+      ebuf[2 * l + n] = e[n];
+    }
+
+    double q[VEC], s2[2];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) q[v] = 0.0;
+    s2[0] = s2[1] = 0.0;
+#pragma unroll(kBigUnroll)
+    for (int j = 0; j < len; ++j) {
+      const Entry ej = ebuf[j];  // same address in the lane group: broadcast
+      const double* vrow = a.V + int64_t(ej.col) * k;
+      Pack<2> pv[2];
+#pragma unroll
+      for (int n = 0; n < 2; ++n) pv[n].load(vrow + fo[n]);
+#pragma unroll
+      for (int n = 0; n < 2; ++n) {
+        // (a pair past k re-reads the head of a row of V the row holds anyway, times zero)
+        const double xm = fok[n] ? ej.x : 0.0;
+#pragma unroll
+        for (int v = 0; v < 2; ++v) {
+          const double vx = pv[n].v[v] * xm;
+          q[2 * n + v] = __builtin_fma(pv[n].v[v], xm, q[2 * n + v]);
+          s2[n] = __builtin_fma(vx, vx, s2[n]);
+        }
+      }
+    }
+
+    // (the labels are in registers on every path from here, see fm_forward_kernel)
+    asm volatile("" ::"v"(yp.x), "v"(yp.y));
+    if (len == 0) {  // an empty row scores sigmoid(w0) whatever its padding holds
+      s2[0] = s2[1] = 0.0;
+      lin = 0.0;
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) q[v] = 0.0;
+    }
+    double half[2];
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+      half[n] = __builtin_fma(q[2 * n + 1], q[2 * n + 1], __builtin_fma(q[2 * n], q[2 * n], -s2[n]));
+    const double pair = group_sum<LPR>(half[0]) + group_sum<LPR>(half[1]);
+    const double linsum = group_sum<LPR>(lin);
+    const double pred = sigmoid_clipped(w0 + linsum + 0.5 * pair);
+    const double err = valid ? yp.x / yp.y - pred : 0.0;
+    if (valid) {
+      if (a.out_Q) {  // (Q belongs to a plan: max_batch * k fits 31 bits)
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+          if (fok[n]) {
+            Pack<2> pq;
+            pq.v[0] = q[2 * n];
+            pq.v[1] = q[2 * n + 1];
+            pq.store_through(a.out_Q + (uint32_t(t) * uint32_t(k) + uint32_t(fo[n])));
+          }
+        }
+      }
+      if (l == 0) {
+        if (a.out_pred) a.out_pred[t] = pred;
+        if (a.out_err) a.out_err[t] = err;
+      }
+    }
+    {
+      // the slice's two residuals by its first lane, in the order of the 16-lane map's thread
+      const double second = dpp_across_8(err);
+      if (tid % 16 == 0) {
+        err_acc += err;
+        err_acc += second;
+      }
+    }
+
+    int32_t touched = 0;
+    if (warm)  // lane l touches the 32 bytes of its own entries
+      touched = *reinterpret_cast<const int32_t*>(a.ell + int64_t(nxt) * a.ell_stride + 32 * l);
+    if (a.slot_mark || H > 0) {
+      // after the residual is known: marks of the sparse-class entries, and the hot entries'
+      // err * x * [q, 1, x] into the workgroup's LDS sums (see fm_forward_kernel's hot tile)
+      Entry em[2];
+#pragma unroll
+      for (int n = 0; n < 2; ++n) em[n] = ebuf[2 * l + n];
+      if (a.slot_mark) {
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+          if (2 * l + n < len && em[n].slot >= 0) {
+            Pack<2> pm;
+            pm.v[0] = __hiloint2double(0, int32_t(t));
+            pm.v[1] = err;
+            pm.store_through(reinterpret_cast<double*>(a.slot_mark + em[n].slot));
+            atomicOr(a.slot_bits + (em[n].slot >> 6), 1ull << (em[n].slot & 63));
+          }
+        }
+      }
+      if (H > 0) {  // (uniform: the matrix core ignores the execution mask)
+        typedef double tile_acc __attribute__((ext_vector_type(4)));
+        int tid_here = tid;  // (the pass's lane constants are not hoisted over the gathers)
+        asm volatile("" : "+v"(tid_here));
+        const int lh = tid_here % LPR, gh = tid_here / LPR, gw = gh % GPW;
+        const int l16 = tid_here % 16, slice = (tid_here % kWave) / 16;
+        const bool upper = (tid_here & LPR) != 0;  // the second row of its 16-lane slice
+        HotEnt* const hbuf = reinterpret_cast<HotEnt*>(ebuf);
+        double* const strip = hot + H * hot_w;  // [GPB][kTileRanks], behind the hot sums
+        // a row that is not valid, or whose residual is not finite, gives zeros to the tile and
+        // keeps all its hot entries on the walk (containment of a non-finite row of V)
+        const bool rowok = valid && __builtin_isfinite(err);
+        double* const st = strip + gh * kTileRanks;
+        Pack<2> zero;
+        zero.v[0] = zero.v[1] = 0.0;
+        zero.store(st + 2 * lh);
+        bool won[2];
+        unsigned long long walked[2];
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+          const bool live = 2 * l + n < len && em[n].slot < 0;
+          const int h = -1 - em[n].slot;
+          const bool tile_e = live && rowok && h < kTileRanks;
+          won[n] = live && !tile_e;
+          walked[n] = __ballot(won[n]);
+          const double coef = err * em[n].x;
+          if (live) {  // the [k] / [k+1] sums by the entry's own lane, tile entry or not
+            double* const hsum = hot + (-em[n].slot * hot_w - 2);
+            unsafeAtomicAdd(hsum, coef);
+            unsafeAtomicAdd(hsum + 1, coef * em[n].x);
+          }
+          if (tile_e) st[h] = coef;  // (after the zeros: same wavefront, program order)
+        }
+        // the entries the wave walks: the largest count of a row of its groups (scalar)
+        int wcnt = 0;
+#pragma unroll
+        for (int gq = 0; gq < GPW; ++gq)
+          wcnt = max(wcnt, __popc(unsigned(walked[0] >> (gq * LPR)) & ((1u << LPR) - 1u)) +
+                               __popc(unsigned(walked[1] >> (gq * LPR)) & ((1u << LPR) - 1u)));
+        const int rot = (gw * wcnt) / GPW;  // (the groups of a wave start at different entries)
+        {
+          // walked entries first -- the lanes' first entries, then their second ones -- and the
+          // others behind them as fillers
+          const unsigned b0 = unsigned(walked[0] >> (gw * LPR)) & ((1u << LPR) - 1u);
+          const unsigned b1 = unsigned(walked[1] >> (gw * LPR)) & ((1u << LPR) - 1u);
+          const unsigned lower = (1u << lh) - 1u;
+          const int n0 = __popc(b0), nw = n0 + __popc(b1);
+#pragma unroll
+          for (int n = 0; n < 2; ++n) {
+            const int below = n == 0 ? __popc(b0 & lower) : n0 + __popc(b1 & lower);
+            const int p = won[n] ? below : nw + n * LPR + lh - below;
+            const int at = p - rot < 0 ? p - rot + wcnt : p - rot;
+            if (p < wcnt)
+              hbuf[at] = HotEnt{won[n] ? (-1 - em[n].slot) * hot_w : -1, 0, err * em[n].x};
+          }
+        }
+        // G[rank][factor] += C[rank][row] * Q[row][factor] on the matrix core.  A K index is one
+        // row: the first rows of the wave's four slices in one product, the second rows in the
+        // next.  Column j < 8 of a product is factor 16 vp + 2 j, column 8 + j factor 16 vp + 2 j + 1
+        // (vp: the factor pair of a lane), so a lane of the row's own group gives one of its
+        // factors as it stands and its neighbour 8 lanes away passes on the other.
+        const double c0 = strip[(gh & ~1) * kTileRanks + l16];
+        const double c1 = strip[(gh | 1) * kTileRanks + l16];
+#pragma unroll
+        for (int vp = 0; vp < VEC / 2; ++vp) {
+          const double even = rowok ? q[2 * vp] : 0.0, odd = rowok ? q[2 * vp + 1] : 0.0;
+          const double odd_across = dpp_across_8(odd), even_across = dpp_across_8(even);
+          const double b0 = upper ? odd_across : even;   // the slice's first row
+          const double b1 = upper ? odd : even_across;   // its second row
+          tile_acc D = tile_acc{0.0, 0.0, 0.0, 0.0};
+          D = __builtin_amdgcn_mfma_f64_16x16x4f64(c0, b0, D, 0, 0, 0);
+          D = __builtin_amdgcn_mfma_f64_16x16x4f64(c1, b1, D, 0, 0, 0);
+          // flush: D register `reg` of a lane is rank (lane >> 4) + 4 reg, column lane & 15
+          const int f = 16 * vp + 2 * (l16 % LPR) + (upper ? 1 : 0);
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg) {
+            const int rank = slice + 4 * reg;
+            if (rank < H && f < k) unsafeAtomicAdd(hot + rank * hot_w + f, D[reg]);
+          }
+        }
+        for (int j = 0; j < wcnt; ++j) {
+          const HotEnt eh = hbuf[j];  // broadcast in the group
+          if (eh.off >= 0) {
+#pragma unroll
+            for (int n = 0; n < 2; ++n) {
+              if (fok[n]) {
+                double* hrow = hot + eh.off + fo[n];
+#pragma unroll
+                for (int v = 0; v < 2; ++v) unsafeAtomicAdd(hrow + v, eh.coef * q[2 * n + v]);
+              }
+            }
+          }
+        }
+      }
+    }
+    if (warm) asm volatile("" ::"v"(touched));  // keep the touch alive
+  }
+
+  if (H > 0) {
+    __syncthreads();
+    // slab layout [H][gridDim.x][k+2], rows of whole 16-byte pairs written through (the gradient
+    // launch reads the slabs next)
+    for (int i = 2 * tid; i < H * hot_w; i += 2 * BLOCK) {
+      const int h = i / hot_w, f = i % hot_w;
+      Pack<2> ps;
+      ps.load(hot + i);
+      ps.store_through(a.hot_slab + (int64_t(h) * gx + bx) * hot_w + f);
+    }
+  }
+  if (a.err_partial) {
+    const double s = block_sum<BLOCK>(err_acc, red);
+    if (tid == 0) a.err_partial[bx] = s;
+  }
+}
+
 // A row is handled by LPR consecutive lanes; lane l holds factors
 // (c*LPR + l)*VEC .. +VEC-1 for c < NC.  k=32 -> LPR=16, VEC=2: one 16-byte
 // load per lane covers a 256-byte row of V, four rows per wave.
@@ -185,10 +480,17 @@ static_assert(sizeof(HotEnt) == sizeof(Entry), "HotEnt replaces an Entry in plac
 // ELL (with REC): the records come as padded row blocks (a.ell).
 // DET (with REC): the hot-class sums in a fixed order (hot_fixed_order) instead of LDS atomics.
 // SEG (without REC, many-rows shape): two logs in one launch, see FwdArgs.
+// <8, 2, 2, kBigBlock, 1, true, true>: the 8-lane form of the step's forward, fm_forward_lanes8 above.
 template <int LPR, int VEC, int NC, int BLOCK, int R, bool REC, bool ELL = false, bool DET = false,
           bool SEG = false, bool XTRA = false>
 __global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? kBigWaves : 1)) void fm_forward_kernel(
     FwdArgs a) {
+  if constexpr (LPR == 8 && NC == 2) {  // the 8-lane shape has a body of its own; nothing below is part of it
+    static_assert(VEC == 2 && BLOCK == kBigBlock && R == 1 && REC && ELL && !DET && !SEG && !XTRA,
+                  "two chunks of 8 lanes: the 8-lane training forward only");
+    fm_forward_lanes8<BLOCK>(a);
+    return;
+  }
   constexpr int GPB = BLOCK / LPR;  // lane groups per block
   // workgroup index and count among the workgroups of its kind (XTRA: the step's, or the ones
   // that only score the extra rows -- a workgroup-uniform switch of what the arguments mean)
