@@ -959,6 +959,7 @@ int32_t rfm_pair_topk(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64
                       const double* d_LI, int64_t n_items, int32_t n_factors, const double* d_c,
                       const int64_t* d_excl_indptr, const int32_t* d_excl_items, int32_t k,
                       void* d_workspace, int32_t* d_out_items, double* d_out_scores);
+#include "rfm_neighbours.h"
 /* Ranks against the whole catalogue: where given (user, item) pairs land in the
  * order rfm_pair_topk ranks by.  The first eleven arguments, the user ids, the exclusion lists and
  * RFM_CHECK_IDS are rfm_pair_topk's.  The CANDIDATES of selected user s are the items whose logit

@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("RFM_LIB_PATH") or os.path.join(PKG_DIR, "librfm_hip.s
 SOURCES = ["rfm_capi.hip", "rfm_fm.hip", "rfm_fm_plan.hip", "rfm_mf.hip", "rfm_fm_fold.hip", "rfm_fold_group.hip", "rfm_eval.hip", "rfm_csr.hip", "rfm_sample.hip", "rfm_pairs.hip", "rfm_host.cpp", "rfm_comm.cpp"]
 # every header under csrc/ (a change of any of them rebuilds every object) + the C ABI
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp"))) + [
-    os.path.join(os.path.dirname(PKG_DIR), "include", "rfm_hip.h")]
+    os.path.join(os.path.dirname(PKG_DIR), "include", h) for h in ("rfm_hip.h", "rfm_neighbours.h")]
 
 RFM_OK, RFM_ERR_BAD_ARG, RFM_ERR_HIP, RFM_ERR_NO_DEVICE, RFM_ERR_INTERNAL = range(5)
 MF_MAX_MODELS = 1024  # RFM_MF_MAX_MODELS
@@ -256,6 +256,14 @@ class CsrSegment(C.Structure):
 _lib = None
 
 
+# nearest neighbours in factor space, the part of the ABI that include/rfm_neighbours.h declares (the table
+# above is pinned, entry for entry, to rfm_hip.h's own text)
+NEIGHBOUR_SIGNATURES = {
+    "rfm_pair_topk_raw": SIGNATURES["rfm_pair_topk"],
+    "rfm_rows_normalise": [_vp, _vp, _i64, _i32, _i64, _vp, _vp],
+}
+
+
 def exported_symbols() -> List[str]:
     return list(SIGNATURES)
 
@@ -286,7 +294,7 @@ def load():
         lib = C.CDLL(path)
     except OSError as exc:
         raise RfmError(f"cannot load {path}: {exc}") from exc
-    for name, argtypes in SIGNATURES.items():
+    for name, argtypes in {**SIGNATURES, **NEIGHBOUR_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError = header/library mismatch
         fn.argtypes = argtypes
         fn.restype = _i32

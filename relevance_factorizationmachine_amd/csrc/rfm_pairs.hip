@@ -21,6 +21,10 @@
 // A user's ranking of the catalogue to any depth is a fifth epilogue, the raw
 // logits of a block of users to a workspace, and a ranking kernel of its own: one workgroup per
 // row, a streaming selection under the same total order with bitonic sorts and merges in LDS.
+//
+// Nearest neighbours in factor space are the top-K launches on one table against
+// itself (or against a table of queries) with the value left as it is: a kernel that divides every
+// row by its norm in a fixed order, and a merge instantiation whose last store skips the sigmoid.
 #include <cmath>
 #include <cstdlib>
 
@@ -98,6 +102,52 @@ __global__ __launch_bounds__(kPairBlock) void side_sums_kernel(
   }
   for (int m = 32; m >= 1; m >>= 1) cross += __shfl_xor(cross, m, 64);
   if (lane == 0) L[r] = lin + 0.5 * cross;
+}
+
+// ---------------------------------------------------------------------------
+// normalised rows: out[r, 0:k] = M[r, 0:k] / ||M[r, 0:k]||_2, zero beyond k,
+// norms[r] = the norm.  One wavefront per row, the rows strided over a capped grid.  The order is
+// fixed (include/rfm_neighbours.h states it): lane l adds the rounded squares of the factors l, l + 64,
+// ... in ascending order, the 64 sums go through the side sums' xor tree, the root and every
+// quotient are IEEE operations.  A norm that is zero, NaN or infinite gives NaN in 0 .. k-1.
+// `wide`: M's rows and out start on 16 bytes, so the second pass moves two factors at a time.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kPairBlock) void rows_normalise_kernel(
+    const double* __restrict__ M, int64_t n_rows, int k, int kpad, int64_t ld, bool wide,
+    double* __restrict__ out, double* __restrict__ norms) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63;
+  const int64_t step = int64_t(gridDim.x) * (kPairBlock / 64);
+  for (int64_t r = int64_t(blockIdx.x) * (kPairBlock / 64) + (threadIdx.x >> 6); r < n_rows; r += step) {
+    const double* __restrict__ row = M + r * ld;
+    double s = 0.0;
+    for (int f = lane; f < k; f += 64) {
+      // (the operators under the pragma above, as rfm_rule.hpp spells a rounded product and sum:
+      // the bodies of __dmul_rn / __dadd_rn are inlined from a header it does not reach, and
+      // their product and sum came out as one v_fmac_f64)
+      const double x = row[f];
+      const double xx = x * x;
+      s = s + xx;
+    }
+    for (int m = 32; m >= 1; m >>= 1) s = s + __shfl_xor(s, m, 64);
+    const double norm = __dsqrt_rn(s);
+    const bool ok = norm > 0.0 && norm < INFINITY;  // (false for a NaN)
+    if (lane == 0) norms[r] = norm;
+    double* __restrict__ o = out + r * int64_t(kpad);
+    if (wide) {
+      for (int f = 2 * lane; f < kpad; f += 128) {  // (kpad is even: f + 1 < kpad)
+        double2 x = make_double2(0.0, 0.0);
+        if (f + 1 < k) x = *reinterpret_cast<const double2*>(row + f);
+        else if (f < k) x.x = row[f];
+        double2 y;
+        y.x = f < k ? (ok ? __ddiv_rn(x.x, norm) : NAN) : 0.0;
+        y.y = f + 1 < k ? (ok ? __ddiv_rn(x.y, norm) : NAN) : 0.0;
+        *reinterpret_cast<double2*>(o + f) = y;
+      }
+    } else {
+      for (int f = lane; f < kpad; f += 64) o[f] = f < k ? (ok ? __ddiv_rn(row[f], norm) : NAN) : 0.0;
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -457,7 +507,9 @@ __global__ __launch_bounds__(kPairBlock) void pair_tile_kernel(PairArgs a) {
 }
 
 // One wavefront per selected user: the splits' partial lists (each sorted) into the final one;
-// scores = sigmoid(logit), an empty slot = item -1 / score NaN.
+// scores = sigmoid(logit), RAW: the logit itself (rfm_pair_topk_raw); an empty slot = item -1 /
+// score NaN.
+template <bool RAW>
 __global__ __launch_bounds__(kPairBlock) void topk_merge_kernel(
     const double* __restrict__ ws_logit, const int32_t* __restrict__ ws_item, int n_splits,
     int64_t n_sel, int K, int32_t* __restrict__ out_items, double* __restrict__ out_scores) {
@@ -478,7 +530,7 @@ __global__ __launch_bounds__(kPairBlock) void topk_merge_kernel(
   }
   if (lane < K) {
     out_items[s * K + lane] = mi;
-    out_scores[s * K + lane] = mi >= 0 ? sigmoid_clipped(ml) : NAN;
+    out_scores[s * K + lane] = mi >= 0 ? (RAW ? ml : sigmoid_clipped(ml)) : NAN;
   }
 }
 
@@ -802,6 +854,36 @@ struct IdCheck {
 LdsLimits g_topk_lds;
 LdsLimits g_order_lds;
 
+// rfm_pair_topk / rfm_pair_topk_raw: the same launches; RAW is the merge's last store alone
+template <bool RAW>
+void pair_topk_run(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t n_users, const int32_t* d_user_ids,
+                   int64_t n_sel_users, const double* d_B, const double* d_LI, int64_t n_items, int32_t n_factors,
+                   const double* d_c, const int64_t* d_excl_indptr, const int32_t* d_excl_items, int32_t k,
+                   void* d_workspace, int32_t* d_out_items, double* d_out_scores) {
+  RFM_REQUIRE(k >= 1 && k <= kMaxTopK, "k=%d outside 1..%d", k, kMaxTopK);
+  PairArgs a = pair_args(ctx, d_A, d_LU, n_users, d_user_ids, n_sel_users, d_B, d_LI, n_items, n_factors, d_c,
+                         d_excl_indptr, d_excl_items);
+  if (n_sel_users == 0) return;
+  RFM_REQUIRE(d_workspace && d_out_items && d_out_scores, "null workspace or output");
+  RFM_HIP_CHECK(hipSetDevice(ctx->device));
+  IdCheck chk(ctx);
+  chk.begin(a);
+  const Split sp = topk_split(n_sel_users, n_items);
+  a.K = k, a.n_splits = sp.n_splits, a.tiles_per_split = sp.tiles_per_split;
+  a.ws_logit = static_cast<double*>(d_workspace);
+  a.ws_item = reinterpret_cast<int32_t*>(a.ws_logit + int64_t(sp.n_splits) * n_sel_users * k);
+  const size_t lds = topk_lds_bytes(k);
+  allow_dynamic_lds(ctx, reinterpret_cast<const void*>(&pair_tile_kernel<kTopK>), lds, g_topk_lds);
+  const dim3 grid((unsigned)sp.n_splits, (unsigned)((n_sel_users + kTile - 1) / kTile));
+  hipLaunchKernelGGL(pair_tile_kernel<kTopK>, grid, dim3(kPairBlock), lds, ctx->stream, a);
+  RFM_HIP_CHECK(hipGetLastError());
+  const int64_t mgrid = (n_sel_users + kPairBlock / 64 - 1) / (kPairBlock / 64);
+  hipLaunchKernelGGL(topk_merge_kernel<RAW>, dim3((unsigned)mgrid), dim3(kPairBlock), 0, ctx->stream,
+                     a.ws_logit, a.ws_item, sp.n_splits, n_sel_users, int(k), d_out_items, d_out_scores);
+  RFM_HIP_CHECK(hipGetLastError());
+  chk.finish();
+}
+
 // rfm_pair_ranks / rfm_pair_ranks_n: `h_n_targets` null = the number of targets is read back from
 // the end of the device indptr (which synchronises); everything after that is the same code
 void pair_ranks_run(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t n_users,
@@ -1065,28 +1147,40 @@ int32_t rfm_pair_topk(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64
                       const int64_t* d_excl_indptr, const int32_t* d_excl_items, int32_t k,
                       void* d_workspace, int32_t* d_out_items, double* d_out_scores) {
   return guarded([&] {
-    RFM_REQUIRE(k >= 1 && k <= kMaxTopK, "k=%d outside 1..%d", k, kMaxTopK);
-    PairArgs a = pair_args(ctx, d_A, d_LU, n_users, d_user_ids, n_sel_users, d_B, d_LI, n_items, n_factors, d_c,
-                           d_excl_indptr, d_excl_items);
-    if (n_sel_users == 0) return;
-    RFM_REQUIRE(d_workspace && d_out_items && d_out_scores, "null workspace or output");
+    pair_topk_run<false>(ctx, d_A, d_LU, n_users, d_user_ids, n_sel_users, d_B, d_LI, n_items, n_factors, d_c,
+                         d_excl_indptr, d_excl_items, k, d_workspace, d_out_items, d_out_scores);
+  });
+}
+
+int32_t rfm_pair_topk_raw(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t n_users,
+                          const int32_t* d_user_ids, int64_t n_sel_users, const double* d_B,
+                          const double* d_LI, int64_t n_items, int32_t n_factors, const double* d_c,
+                          const int64_t* d_excl_indptr, const int32_t* d_excl_items, int32_t k,
+                          void* d_workspace, int32_t* d_out_items, double* d_out_values) {
+  return guarded([&] {
+    pair_topk_run<true>(ctx, d_A, d_LU, n_users, d_user_ids, n_sel_users, d_B, d_LI, n_items, n_factors, d_c,
+                        d_excl_indptr, d_excl_items, k, d_workspace, d_out_items, d_out_values);
+  });
+}
+
+int32_t rfm_rows_normalise(rfm_ctx* ctx, const double* d_M, int64_t n_rows, int32_t n_factors, int64_t ld_in,
+                           double* d_out, double* d_norm) {
+  return guarded([&] {
+    RFM_REQUIRE(ctx && d_M && d_out && d_norm, "null pointer");
+    RFM_REQUIRE(n_factors >= 1 && n_factors <= RFM_MAX_FACTORS, "n_factors=%d unsupported (1..%d)",
+                n_factors, RFM_MAX_FACTORS);
+    RFM_REQUIRE(n_rows >= 0 && n_rows < (int64_t(1) << 40), "n_rows=%lld", (long long)n_rows);
+    RFM_REQUIRE(ld_in >= n_factors && ld_in < (int64_t(1) << 20), "ld_in=%lld for %d factors", (long long)ld_in,
+                n_factors);
+    RFM_REQUIRE(d_out != d_M, "the rows cannot be normalised in place");
+    if (n_rows == 0) return;
     RFM_HIP_CHECK(hipSetDevice(ctx->device));
-    IdCheck chk(ctx);
-    chk.begin(a);
-    const Split sp = topk_split(n_sel_users, n_items);
-    a.K = k, a.n_splits = sp.n_splits, a.tiles_per_split = sp.tiles_per_split;
-    a.ws_logit = static_cast<double*>(d_workspace);
-    a.ws_item = reinterpret_cast<int32_t*>(a.ws_logit + int64_t(sp.n_splits) * n_sel_users * k);
-    const size_t lds = topk_lds_bytes(k);
-    allow_dynamic_lds(ctx, reinterpret_cast<const void*>(&pair_tile_kernel<kTopK>), lds, g_topk_lds);
-    const dim3 grid((unsigned)sp.n_splits, (unsigned)((n_sel_users + kTile - 1) / kTile));
-    hipLaunchKernelGGL(pair_tile_kernel<kTopK>, grid, dim3(kPairBlock), lds, ctx->stream, a);
+    const bool wide = ld_in % 2 == 0 && reinterpret_cast<uintptr_t>(d_M) % 16 == 0 &&
+                      reinterpret_cast<uintptr_t>(d_out) % 16 == 0;
+    hipLaunchKernelGGL(rows_normalise_kernel, dim3(capped_grid(ctx, n_rows, kPairBlock / 64, 8, 1)),
+                       dim3(kPairBlock), 0, ctx->stream, d_M, n_rows, n_factors, int(pad4(n_factors)), ld_in, wide,
+                       d_out, d_norm);
     RFM_HIP_CHECK(hipGetLastError());
-    const int64_t mgrid = (n_sel_users + kPairBlock / 64 - 1) / (kPairBlock / 64);
-    hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)mgrid), dim3(kPairBlock), 0, ctx->stream,
-                       a.ws_logit, a.ws_item, sp.n_splits, n_sel_users, int(k), d_out_items, d_out_scores);
-    RFM_HIP_CHECK(hipGetLastError());
-    chk.finish();
   });
 }
 

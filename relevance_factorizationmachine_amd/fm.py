@@ -537,3 +537,25 @@ class FactorizationMachines(PointwiseBaseRecommender):
         from . import recommend as rec
 
         return rec.rank_catalogue(*rec.operands(self, sides, new_users=new_users), depth, users, exclude)
+
+    # new_items / new_users: the FoldedColumns of the matching fold_in_* are the queries (their served
+    # operand A) against the catalogue's own rows -- ``items`` / ``users`` then index the folded rows
+    def similar_items(self, sides, k: int, items=None, metric="cosine", exclude=None, include_self=False,
+                      new_items=None):
+        """The ``k`` (1..64) items of ``sides`` most like each item: ``(items int32 [n, k], values
+        float64 [n, k])``, the cosine (``metric="dot"``: the dot product) of the item vectors
+        ``b_i = sum_j xi_j V[j,:]``, best first, ties: higher index first, an item never its own
+        neighbour unless ``include_self``; ``exclude``: CSR by item id.  Similarity is in factor
+        space only: ``w0``, ``w`` and the sides' own pair terms play no part.  An item without
+        entries has no direction: it is nobody's neighbour and its list is empty (recommend.neighbours)."""
+        from . import recommend as rec
+
+        return rec.similar(self, "item", k, items, metric, exclude, include_self, new_items, sides)
+
+    def similar_users(self, sides, k: int, users=None, metric="cosine", exclude=None, include_self=False,
+                      new_users=None):
+        """``similar_items`` for the user vectors ``a_u = sum_j xu_j V[j,:]`` of ``sides``, in factor
+        space only."""
+        from . import recommend as rec
+
+        return rec.similar(self, "user", k, users, metric, exclude, include_self, new_users, sides)

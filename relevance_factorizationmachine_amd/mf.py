@@ -458,6 +458,24 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
 
         return rec.rank_catalogue(*rec.operands(self, new_users=new_users), depth, users, exclude)
 
+    # new_items / new_users: the FoldedRows of the matching fold_in_* are the queries against the
+    # model's own rows -- ``items`` / ``users`` then index the folded rows, which have no self
+    def similar_items(self, k: int, items=None, metric="cosine", exclude=None, include_self=False, new_items=None):
+        """The ``k`` (1..64) items most like each item: ``(items int32 [n, k], values float64 [n, k])``,
+        the cosine (``metric="dot"``: the dot product) of rows of ``Q``, best first, ties: higher
+        index first, an item never its own neighbour unless ``include_self``; ``exclude``: CSR by
+        item id.  Similarity is in factor space only: ``b_i`` plays no part (recommend.neighbours)."""
+        from . import recommend as rec
+
+        return rec.similar(self, "item", k, items, metric, exclude, include_self, new_items)
+
+    def similar_users(self, k: int, users=None, metric="cosine", exclude=None, include_self=False, new_users=None):
+        """``similar_items`` for the rows of ``P``: the ``k`` users most like each user, in factor
+        space only (``b_u`` plays no part)."""
+        from . import recommend as rec
+
+        return rec.similar(self, "user", k, users, metric, exclude, include_self, new_users)
+
 
 # ---------------------------------------------------------------------------
 # several models on one training log (DESIGN.md 8 N17)

@@ -18,6 +18,8 @@ would tie.  The returned scores are probabilities, ``sigmoid(logit)``, as ``pred
 given (user, item) pairs in the user's ranking of the whole catalogue, at any depth.
 ``rank_catalogue`` is ``topk`` without the limit of 64: the items at positions
 0 .. depth-1, up to the user's full ordering of the catalogue.
+``neighbours`` asks the tables themselves: the rows of ``B`` (or of ``A``) nearest to
+each other by cosine or dot product, under the same order, with the value itself returned.
 """
 from __future__ import annotations
 
@@ -441,3 +443,152 @@ def rank_catalogue(rt: Runtime, A, LU, B, LI, c, n_factors: int, depth: int, use
                                      workspace_bytes, items.data_ptr(), scores.data_ptr(), n_ranked.data_ptr()))
     rt.sync()
     return items.cpu().numpy(), scores.cpu().numpy(), n_ranked.cpu().numpy()
+
+
+# ---------------------------------------------------------------------------
+# nearest neighbours in factor space
+# ---------------------------------------------------------------------------
+METRICS = ("cosine", "dot")
+
+
+def _table(M, n_factors: int):
+    """``M`` if it is a table of rows of ``n_factors`` factors: float64 ``[n, k]`` or ``[n, kpad]``, contiguous."""
+    torch = __import__("torch")
+    if M.dim() != 2 or M.dtype != torch.float64 or not M.is_contiguous() or M.shape[0] < 1:
+        raise ValueError("a table of rows must be a contiguous float64 matrix with at least one row")
+    if int(M.shape[1]) not in (int(n_factors), pad4(n_factors)):
+        raise ValueError(f"rows of {tuple(M.shape)} for {int(n_factors)} factors")
+    return M
+
+
+def normalised(rt: Runtime, M, n_factors: int):
+    """``(rows [n, kpad], norms [n])`` of a device table ``M`` (``[n, k]`` or ``[n, kpad]``): every row
+    divided by its Euclidean norm over the first ``n_factors`` columns, the padding zero
+    (``rfm_rows_normalise``, whose fixed order include/rfm_neighbours.h states).  A row whose norm is zero,
+    NaN or infinite comes out as NaN."""
+    torch = __import__("torch")
+    M, kf = _table(M, n_factors), int(n_factors)
+    n = int(M.shape[0])
+    out, norms = rt.empty((n, pad4(kf)), torch.float64), rt.empty((n,), torch.float64)
+    _lib.check(rt.lib.rfm_rows_normalise(rt.ctx, M.data_ptr(), n, kf, int(M.shape[1]), out.data_ptr(),
+                                         norms.data_ptr()))
+    return out, norms
+
+
+def _with_self(excl, n: int):
+    """The checked host lists ``excl`` (or None) of ``n`` rows with every row's own id merged in."""
+    own = np.arange(n, dtype=np.int64)
+    if excl is None:
+        return np.arange(n + 1, dtype=np.int64), own.astype(np.int32)
+    indptr, items = excl
+    rows = np.repeat(own, np.diff(indptr))
+    missing = np.ones(n, dtype=bool)
+    missing[rows[items == rows]] = False
+    add = own[missing]
+    rows, items = np.concatenate([rows, add]), np.concatenate([items.astype(np.int64), add])
+    order = np.lexsort((items, rows))
+    indptr = np.concatenate(([0], np.cumsum(np.bincount(rows, minlength=n)))).astype(np.int64)
+    return indptr, items[order].astype(np.int32)
+
+
+def check_neighbours(n_rows: int, k, ids=None, metric="cosine", exclude=None, include_self=False,
+                     n_queries: Optional[int] = None, what: str = "items"):
+    """The checks of ``neighbours`` that need no device -> ``(k, ids int32 or None, host exclusion
+    lists or None)``.  ``n_queries``: the rows of a query table of its own, None = the queries are
+    rows of the table itself, whose own ids are merged into the lists unless ``include_self``."""
+    k = int(k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f"k={k} outside 1..{MAX_K}")
+    if metric not in METRICS:
+        raise ValueError(f"metric {metric!r} is neither 'cosine' nor 'dot'")
+    own = n_queries is None
+    if include_self and not own:
+        raise ValueError("include_self with rows of another table: they are not in the catalogue and have no self")
+    n_q = int(n_rows) if own else int(n_queries)
+    sel = None if ids is None else _id_array(ids, what, n_q).astype(np.int32)
+    excl = _host_exclusions(exclude, n_q, int(n_rows))
+    if own and not include_self:
+        excl = _with_self(excl, int(n_rows))
+    return k, sel, excl
+
+
+def neighbours(rt: Runtime, R, n_factors: int, k: int, ids=None, metric="cosine", exclude=None, include_self=False,
+               queries=None, what: str = "items"):
+    """The ``k`` (1..64) nearest rows of the device table ``R`` for every query:
+    ``(ids int32 [n, k], values float64 [n, k])``, best first under ``topk``'s total order (value
+    descending, then id descending), short lists padded with id -1 / value NaN.  Similarity is in
+    FACTOR SPACE only: biases and linear terms play no part.
+
+    ``queries`` None: the queries are the rows ``ids`` of ``R`` (None = all; any order, repeats
+    allowed), and a query never gets itself unless ``include_self``.  ``queries`` given: another
+    table of the same factor count whose rows (``ids`` index them) are the queries; nothing of
+    ``R`` is their self.  ``metric`` "cosine": both tables go through ``normalised`` (once when they
+    are one buffer), the value is the cosine, and a row without a direction (norm zero, NaN or
+    infinite) is nobody's neighbour and has an empty list; "dot": the rows as they are.
+    ``exclude``: as ``topk`` takes it, by query row id, shape ``(queries, rows of R)``.
+    ``what`` names the ids in an error message ("users" / "items")."""
+    torch = __import__("torch")
+    kf = int(n_factors)
+    R = _table(R, kf)
+    if queries is not None:
+        _table(queries, kf)
+    k, sel, excl = check_neighbours(R.shape[0], k, ids, metric, exclude, include_self,
+                                    None if queries is None else queries.shape[0], what)
+    n_q = int((R if queries is None else queries).shape[0])
+    n_sel = n_q if sel is None else int(sel.shape[0])
+    if n_sel == 0:
+        return np.zeros((0, k), np.int32), np.zeros((0, k), np.float64)
+    if metric == "cosine":
+        rows = lambda M: normalised(rt, M, kf)[0]  # noqa: E731
+    else:
+        rows = lambda M: M if M.shape[1] == pad4(kf) else padded(rt, M, kf)  # noqa: E731
+    B = rows(R)
+    same = queries is None or (queries.data_ptr() == R.data_ptr() and queries.shape == R.shape)
+    A = B if same else rows(queries)
+    zero = torch.zeros((max(n_q, int(R.shape[0])),), dtype=torch.float64, device=rt.torch_device)
+    ops = Operands(rt, A, zero, B, zero, zero, kf)
+    d_ids, d_excl = None if sel is None else rt.upload(sel), _exclusions(rt, excl)
+    ws = rt.empty((topk_workspace_bytes(n_sel, ops.n_items, k),), torch.uint8)
+    out_ids, values = rt.empty((n_sel, k), torch.int32), rt.empty((n_sel, k), torch.float64)
+    _lib.check(rt.lib.rfm_pair_topk_raw(*ops.pair_args(d_ids, n_sel), *excl_args(d_excl), k, ws.data_ptr(),
+                                        out_ids.data_ptr(), values.data_ptr()))
+    rt.sync()
+    return out_ids.cpu().numpy(), values.cpu().numpy()
+
+
+def folded_queries(model, side: str, folded):
+    """The query table of ``new_items`` / ``new_users`` (``side``: "item" / "user") of a similarity
+    call: the folded rows of the model's own ``fold_in_<side>s``.  The other side's rows and the
+    other model class's are a ``TypeError``, another factor count a ``ValueError``, as in ``operands``."""
+    kf = int(model.n_factors)
+    if hasattr(model, "n_features"):
+        if getattr(folded, "side", None) != side or not hasattr(folded, "A"):
+            raise TypeError(f"new_{side}s of an FM model takes the FoldedColumns of its fold_in_{side}s; rows "
+                            "that are served from their features alone go into its recommend.Sides")
+        if tuple(folded.A.shape[1:]) != (pad4(kf),):
+            raise ValueError(f"folded operands of {tuple(folded.A.shape)} for a model of {kf} factors")
+        return folded.A
+    if getattr(folded, "side", None) != side or not hasattr(folded, "rows"):
+        raise TypeError(f"new_{side}s takes the FoldedRows of fold_in_{side}s")
+    if tuple(folded.rows.shape[1:]) != (kf,):
+        raise ValueError(f"folded rows of {tuple(folded.rows.shape)} for a model of {kf} factors")
+    return folded.rows
+
+
+def similar(model, side: str, k: int, ids=None, metric="cosine", exclude=None, include_self=False, new_rows=None,
+            sides=None):
+    """``similar_items`` / ``similar_users`` of both model classes (``side``: "item" / "user"):
+    ``neighbours`` among the rows of Q / P (MF) or among the side sums b_i / a_u of ``sides`` (FM: one
+    side-sum launch, for the side asked for).  ``new_rows``: folded rows of that side as the queries
+    against the model's own rows.  Every argument is checked before the first launch."""
+    item = side == "item"
+    n_rows = catalogue_shape(model, sides)[item]
+    queries = None if new_rows is None else folded_queries(model, side, new_rows)
+    request = (k, ids, metric, exclude, include_self)
+    check_neighbours(n_rows, *request, None if queries is None else int(queries.shape[0]), side + "s")
+    rt, kf = model._rt, int(model.n_factors)
+    if hasattr(model, "n_features"):
+        R, _ = side_sums(rt, sides.device(rt)[item], model.w.dev, model.V.dev, model.n_features, kf)
+    else:
+        R = (model.P, model.Q)[item].dev
+    return neighbours(rt, R, kf, *request, queries, side + "s")
