@@ -342,6 +342,26 @@ int32_t rfm_fm_train_part(rfm_ctx* ctx, rfm_fm_plan* plan, const int64_t* d_indp
  * rfm_fm_forward_loss, the validation-loss forward). */
 int32_t rfm_fm_forward_geometry(const rfm_ctx* ctx, int64_t n_rows, int32_t n_factors, int32_t records,
                                 int32_t* h_out4);
+/* The forward launch of a step of `batch` rows on this plan (rfm_fm_step, the steps of rfm_fm_train),
+ * with n_riding_rows rows of another batch riding in it (0: none); nothing is launched.
+ * h_out8[0]=threads per workgroup, [1]=workgroups that score the batch's rows (riding rows add
+ * theirs), [2]=rows of a workgroup's trip, [3]=lanes per row of the kernel that runs (8 for the
+ * 8-lane kernel of k = 20, 24, 28, 32, where rfm_fm_forward_geometry reports the plan's 16),
+ * [4]=the form, RFM_FWD_*, [5]=1 the 8-lane kernel, [6]=bytes of LDS per workgroup, [7]=1 the
+ * hot-class sums in a fixed order.  Fails where the step would: riding rows on a step of the
+ * many-rows shape or with fixed-order hot sums. */
+enum {
+  RFM_FWD_CSR = 0,         /* the caller's CSR arrays (never a step) */
+  RFM_FWD_CSR_PAIR = 1,    /* ... of two logs in one launch (never a step) */
+  RFM_FWD_RECORDS = 2,     /* the plan's row and entry records */
+  RFM_FWD_BLOCKS = 3,      /* the plan's padded row blocks */
+  RFM_FWD_RECORDS_FIXED = 4, /* records / blocks, hot-class sums in a fixed order */
+  RFM_FWD_BLOCKS_FIXED = 5,
+  RFM_FWD_RECORDS_RIDERS = 6, /* records / blocks, with riding rows */
+  RFM_FWD_BLOCKS_RIDERS = 7
+};
+int32_t rfm_fm_step_form(const rfm_ctx* ctx, const rfm_fm_plan* plan, int64_t batch, int64_t n_riding_rows,
+                         int32_t* h_out8);
 /* The launch of a sliced forward of n_rows rows through this plan (rfm_fm_plan_forward; the loss
  * forwards of rfm_fm_train with n_rows = batch + n_val), form_rows >= 0: the decision between the
  * sliced and the plain form taken for that many rows instead (a shard of a log), -1: for n_rows.

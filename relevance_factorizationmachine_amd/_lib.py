@@ -25,6 +25,8 @@ HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((
 RFM_OK, RFM_ERR_BAD_ARG, RFM_ERR_HIP, RFM_ERR_NO_DEVICE, RFM_ERR_INTERNAL = range(5)
 MF_MAX_MODELS = 1024  # RFM_MF_MAX_MODELS
 OPT_SGD, OPT_ADAGRAD = 0, 1  # the kinds of both optimiser seams: the update rule of a plan's steps or an MF batch
+# RFM_FWD_*: the forms of the FM forward kernel, by value (rfm_fm_step_form)
+FWD_KINDS = ("csr", "csr_pair", "records", "blocks", "records_fixed", "blocks_fixed", "records_riders", "blocks_riders")
 
 
 class RfmError(RuntimeError):
@@ -156,6 +158,7 @@ SIGNATURES = {
     "rfm_fm_train": _TRAIN,
     "rfm_fm_train_part": _TRAIN + [_i64],
     "rfm_fm_forward_geometry": [_vp, _i64, _i32, _i32, _vp],
+    "rfm_fm_step_form": [_vp, _vp, _i64, _i64, _vp],
     "rfm_fm_sliced_geometry": [_vp, _vp, _i64, _i64, _vp],
     "rfm_fm_train_forms": [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
     "rfm_fm_train_eval": _TRAIN + _CSR + [_i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _i64, _i64, _vp],

@@ -38,170 +38,155 @@ static_assert(RFM_MAX_FACTORS <= 1024, "fm_finalize_kernel's LDS totals hold 102
 
 namespace rfm {
 
-// forward launch geometry: 1024-thread workgroups whose lane groups keep several
-// rows in flight once the batch fills the chip with them (one per CU: as few
-// hot-sum slabs as possible), 256-thread / one-row ones otherwise.
-struct FwdGeom {
-  int block, grid;
-};
-constexpr int kSmallBlock = 256;  // threads of the one-row-per-group shape
-
-inline FwdGeom forward_geom(const rfm_ctx* ctx, int64_t n_rows, const Shape& s, bool records) {
+// The one decision of a forward launch (FwdForm).  What the rows and the factor count decide -- a
+// plan-level question -- of `n_rows` rows through the plan's records or the caller's CSR arrays:
+// 1024-thread workgroups whose lane groups keep several rows in flight once the batch fills the
+// chip with them (one per CU: as few hot-sum slabs as possible), 256-thread / one-row ones otherwise ...
+FwdForm forward_form(const rfm_ctx* ctx, int64_t n_rows, int k, bool records) {
   constexpr int per_cu = kBigBlock >= 1024 ? 1 : 2;
-  FwdGeom g;
+  FwdForm f{};
+  f.shape = shape_for(k);
+  f.lanes = f.shape.lpr;
   // (the plain forward -- the caller's CSR arrays: predict, validation loss -- takes the same two
   // shapes with its own number of rows per lane group)
-  const int64_t rows_big = int64_t(kBigBlock / s.lpr) * (records ? rows_in_flight(s.nc) : rows_in_flight_plain(s.nc));
-  const int64_t blocks_big = (n_rows + rows_big - 1) / rows_big;
+  f.kind = records ? FwdKind::kRecords : FwdKind::kCsr;
+  const int64_t rows_big = int64_t(kBigBlock / f.lanes) * forward_rows(kBigBlock, f.shape.nc, f.kind);
   // (measured on config 3: the many-rows shape wins from about a third of a chip of such
   // workgroups: 16 384 rows 26 vs 30 us, 8 192 rows 21 vs 20 us)
-  if (blocks_big * 2 >= int64_t(ctx->n_cu) * per_cu) {
-    g.block = kBigBlock;
-    g.grid = capped_grid(ctx, n_rows, rows_big, per_cu, 1);
+  const bool big = (n_rows + rows_big - 1) / rows_big * 2 >= int64_t(ctx->n_cu) * per_cu;
+  f.block = big ? kBigBlock : kSmallBlock;
+  f.rows = forward_rows(f.block, f.shape.nc, f.kind);
+  f.trip = f.block / f.lanes * f.rows;
+  f.grid = std::min(capped_grid(ctx, n_rows, f.trip, big ? per_cu : 8, 1), kMaxFwdGrid);
+  return f;
+}
+
+// ... and what the arguments add: the kind, the kernel and its LDS
+FwdForm forward_form(const rfm_ctx* ctx, const FwdArgs& a) {
+  const bool recs = a.ent != nullptr || a.ell != nullptr;  // the plan's records
+  FwdForm f = forward_form(ctx, a.n_rows, a.k, recs);
+  const bool big = f.block == kBigBlock, riders = a.n_rows_x > 0;
+  f.fixed = recs && a.hot_fixed && a.n_hot > 0;
+  RFM_REQUIRE(!f.fixed || forward_form_exists(f.shape.lpr, f.shape.nc, f.block, FwdKind::kBlocksFixed),
+              big ? "fixed-order hot sums are not built for this factor count at this batch"
+                  : "fixed-order hot sums are not built for this factor count");
+  RFM_REQUIRE(!riders || (recs && !big && !f.fixed), "this step cannot score extra rows");
+  if (!recs) {
+    f.kind = a.indptr2 ? FwdKind::kCsrPair : FwdKind::kCsr;
+  } else if (a.ell) {
+    // (a plan made for many-rows batches keeps only the padded row blocks: a step of fewer rows
+    // on it reads those too)
+    f.kind = f.fixed ? FwdKind::kBlocksFixed : riders ? FwdKind::kBlocksRiders : FwdKind::kBlocks;
   } else {
-    g.block = kSmallBlock;
-    g.grid = capped_grid(ctx, n_rows, kSmallBlock / s.lpr, 8, 1);
+    RFM_REQUIRE(a.ent && a.rows, "the plan holds no row records");
+    f.kind = f.fixed ? FwdKind::kRecordsFixed : riders ? FwdKind::kRecordsRiders : FwdKind::kRecords;
   }
-  g.grid = std::min(g.grid, 2048);
-  return g;
+  // the step's forward on padded row blocks, many-rows shape, arrival-order hot sums, k = 20 .. 32
+  // in fours: 8 lanes x 4 factors per row, one row per lane group (the plan, the trip and the LDS
+  // are those of 16 lanes)
+  f.lanes8 = big && f.kind == FwdKind::kBlocks && forward_lanes8(a.k) && a.out_Q && a.slot_mark &&
+             !a.loss_partial && a.ell_stride == int64_t(16 * sizeof(Entry));
+  if (f.lanes8) {
+    f.lanes = 8;
+    f.rows = 1;
+  }
+  f.lds = forward_lds_bytes(f, a.n_hot, a.k);
+  return f;
 }
 
 int forward_grid(const rfm_ctx* ctx, int64_t rows, int n_factors) {
-  return forward_geom(ctx, rows, shape_for(n_factors), true).grid;
+  return forward_form(ctx, rows, n_factors, true).grid;
 }
 
 bool forward_many_rows(const rfm_ctx* ctx, int64_t rows, int n_factors) {
-  return forward_geom(ctx, rows, shape_for(n_factors), true).block == kBigBlock;
-}
-
-// one instantiation: raises its dynamic-LDS limit when a launch needs more than the default
-template <int L, int Vv, int N, int BLOCK, int R, bool REC, bool ELL, bool DET, bool SEG = false, bool XTRA = false>
-void launch_forward_as(rfm_ctx* ctx, const FwdArgs& a, const FwdGeom& geom, size_t lds) {
-  const auto kern = &fm_forward_kernel<L, Vv, N, BLOCK, R, REC, ELL, DET, SEG, XTRA>;
-  static LdsLimits allowed;
-  allow_dynamic_lds(ctx, reinterpret_cast<const void*>(kern), lds, allowed);
-  hipLaunchKernelGGL(kern, dim3(geom.grid), dim3(BLOCK), lds, ctx->stream, a);
-}
-
-// the instantiation a launch takes: shape of the workgroups (geom), source of the records,
-// and -- for a plan that asks for them -- fixed-order hot sums
-template <int L, int Vv, int N>
-void launch_forward_shape(rfm_ctx* ctx, const FwdArgs& a, const FwdGeom& geom, size_t lds,
-                          bool recs, bool fixed) {
-  constexpr int R = rows_in_flight(N);
-  if (geom.block == kBigBlock) {
-    if (!recs) return launch_forward_as<L, Vv, N, kBigBlock, rows_in_flight_plain(N), false, false, false>(ctx, a, geom, lds);
-    if constexpr (hot_fixed_order(L, N, kBigBlock, R)) {
-      if (fixed) {
-        if (a.ell) return launch_forward_as<L, Vv, N, kBigBlock, R, true, true, true>(ctx, a, geom, lds);
-        return launch_forward_as<L, Vv, N, kBigBlock, R, true, false, true>(ctx, a, geom, lds);
-      }
-    }
-    RFM_REQUIRE(!fixed, "fixed-order hot sums are not built for this factor count at this batch");
-    if (a.ell) return launch_forward_as<L, Vv, N, kBigBlock, R, true, true, false>(ctx, a, geom, lds);
-    RFM_REQUIRE(a.ent && a.rows, "the plan holds no row records");
-    return launch_forward_as<L, Vv, N, kBigBlock, R, true, false, false>(ctx, a, geom, lds);
-  }
-  if (!recs) return launch_forward_as<L, Vv, N, kSmallBlock, 1, false, false, false>(ctx, a, geom, lds);
-  // (a plan made for many-rows batches keeps only the padded row blocks: a step of fewer rows
-  // on it reads those too)
-  if constexpr (hot_fixed_order(L, N, kSmallBlock, 1)) {
-    if (fixed) {
-      if (a.ell) return launch_forward_as<L, Vv, N, kSmallBlock, 1, true, true, true>(ctx, a, geom, lds);
-      return launch_forward_as<L, Vv, N, kSmallBlock, 1, true, false, true>(ctx, a, geom, lds);
-    }
-  }
-  RFM_REQUIRE(!fixed, "fixed-order hot sums are not built for this factor count");
-  if (a.n_rows_x > 0) {  // (XTRA form: the last workgroups only score another batch's rows)
-    if (a.ell) return launch_forward_as<L, Vv, N, kSmallBlock, 1, true, true, false, false, true>(ctx, a, geom, lds);
-    RFM_REQUIRE(a.ent && a.rows, "the plan holds no row records");
-    return launch_forward_as<L, Vv, N, kSmallBlock, 1, true, false, false, false, true>(ctx, a, geom, lds);
-  }
-  if (a.ell) return launch_forward_as<L, Vv, N, kSmallBlock, 1, true, true, false>(ctx, a, geom, lds);
-  RFM_REQUIRE(a.ent && a.rows, "the plan holds no row records");
-  return launch_forward_as<L, Vv, N, kSmallBlock, 1, true, false, false>(ctx, a, geom, lds);
+  return forward_form(ctx, rows, n_factors, true).block == kBigBlock;
 }
 
 bool forward_fixed_order_ok(const rfm_ctx* ctx, int64_t max_batch, int n_factors) {
-  const Shape s = shape_for(n_factors);
-  if (!hot_fixed_order(s.lpr, s.nc, kSmallBlock, 1)) return false;  // (steps of fewer rows)
-  return !forward_many_rows(ctx, max_batch, n_factors) ||
-         hot_fixed_order(s.lpr, s.nc, kBigBlock, rows_in_flight(s.nc));
+  const FwdForm f = forward_form(ctx, max_batch, n_factors, true);  // (steps of fewer rows: the one-row shape)
+  return forward_form_exists(f.shape.lpr, f.shape.nc, kSmallBlock, FwdKind::kBlocksFixed) &&
+         forward_form_exists(f.shape.lpr, f.shape.nc, f.block, FwdKind::kBlocksFixed);
 }
 
-void launch_forward(rfm_ctx* ctx, FwdArgs a, FwdGeom geom) {
-  if (a.n_rows <= 0) return;
-  const Shape s = shape_for(a.k);
-  const bool recs = a.ent != nullptr || a.ell != nullptr;  // the plan's records
-  const bool fixed = recs && a.hot_fixed && a.n_hot > 0;
-  // the step's forward on padded row blocks, many-rows shape, arrival-order hot sums, k = 20 .. 32
-  // in fours: 8 lanes x 4 factors per row, one row per lane group (the plan and the launch geometry
-  // are those of 16 lanes)
-  if (geom.block == kBigBlock && a.ell && !fixed && forward_lanes8(a.k) && a.out_Q && a.slot_mark &&
-      !a.loss_partial && a.n_rows_x == 0 && a.ell_stride == int64_t(16 * sizeof(Entry))) {
-    const size_t lds8 = forward_lanes8_lds_bytes(geom.block, a.n_hot, a.k);
-    RFM_REQUIRE(lds8 <= (160u << 10), "forward kernel: %zu bytes of LDS", lds8);
-    launch_forward_as<8, 2, 2, kBigBlock, 1, true, true, false>(ctx, a, geom, lds8);
-    RFM_HIP_CHECK(hipGetLastError());
-    return;
+// one kernel: raises its dynamic-LDS limit when a launch needs more than the default
+template <auto KERN>
+void launch_forward_kernel(rfm_ctx* ctx, const FwdArgs& a, const FwdForm& f) {
+  static LdsLimits allowed;
+  allow_dynamic_lds(ctx, reinterpret_cast<const void*>(KERN), f.lds, allowed);
+  hipLaunchKernelGGL(KERN, dim3(f.grid), dim3(f.block), f.lds, ctx->stream, a);
+}
+
+template <int L, int Vv, int N, int BLOCK, FwdKind K>
+void launch_forward_as(rfm_ctx* ctx, const FwdArgs& a, const FwdForm& f) {
+  if constexpr (forward_form_exists(L, N, BLOCK, K))
+    launch_forward_kernel<&fm_forward_kernel<L, Vv, N, BLOCK, K>>(ctx, a, f);
+  else
+    RFM_REQUIRE(false, "forward kernel: form %d is not built at %d threads", int(K), BLOCK);
+}
+
+// the instantiation of a shape and block that f.kind names
+template <int L, int Vv, int N, int BLOCK>
+void launch_forward_kind(rfm_ctx* ctx, const FwdArgs& a, const FwdForm& f) {
+#define RFM_KIND(K) case FwdKind::K: return launch_forward_as<L, Vv, N, BLOCK, FwdKind::K>(ctx, a, f)
+  switch (f.kind) {
+    RFM_KIND(kCsr); RFM_KIND(kCsrPair); RFM_KIND(kRecords); RFM_KIND(kBlocks);
+    RFM_KIND(kRecordsFixed); RFM_KIND(kBlocksFixed); RFM_KIND(kRecordsRiders); RFM_KIND(kBlocksRiders);
   }
-  const size_t lds =
-      forward_lds_bytes(geom.block, s.lpr, s.vec, s.nc,
-                        geom.block == kBigBlock ? (recs ? rows_in_flight(s.nc) : rows_in_flight_plain(s.nc)) : 1,
-                        a.n_hot, a.k, fixed);
-  RFM_REQUIRE(lds <= (160u << 10), "forward kernel: %zu bytes of LDS", lds);
-  RFM_REQUIRE(!fixed || a.hot_rounds >= 1, "hot_rounds unset");
-#define RFM_CALL_FWD(L, Vv, N) launch_forward_shape<L, Vv, N>(ctx, a, geom, lds, recs, fixed)
-  RFM_FOR_SHAPE(s, RFM_CALL_FWD);
+#undef RFM_KIND
+}
+
+// launches what `f` says (forward_form of a; a step with riding rows has added their workgroups)
+void launch_forward(rfm_ctx* ctx, const FwdArgs& a, const FwdForm& f) {
+  if (a.n_rows <= 0) return;
+  RFM_REQUIRE(f.lds <= (160u << 10), "forward kernel: %zu bytes of LDS", f.lds);
+  RFM_REQUIRE(!f.fixed || a.hot_rounds >= 1, "hot_rounds unset");
+#define RFM_CALL_FWD(L, Vv, N)                                                \
+  (f.block == kBigBlock ? launch_forward_kind<L, Vv, N, kBigBlock>(ctx, a, f) \
+                        : launch_forward_kind<L, Vv, N, kSmallBlock>(ctx, a, f))
+  if (f.lanes8)
+    launch_forward_kernel<&fm_forward_lanes8_kernel<kBigBlock>>(ctx, a, f);
+  else
+    RFM_FOR_SHAPE(f.shape, RFM_CALL_FWD);
 #undef RFM_CALL_FWD
   RFM_HIP_CHECK(hipGetLastError());
 }
 
-void launch_forward(rfm_ctx* ctx, FwdArgs a) {
+void launch_forward(rfm_ctx* ctx, const FwdArgs& a) {
   if (a.n_rows <= 0) return;
-  launch_forward(ctx, a, forward_geom(ctx, a.n_rows, shape_for(a.k), a.ent != nullptr || a.ell != nullptr));
-}
-
-// forward with loss: partials in ctx scratch, finished into d_out_loss
-void forward_loss(rfm_ctx* ctx, FwdArgs a, double* d_out_loss) {
-  RFM_REQUIRE(a.n_rows > 0, "loss of zero rows");
-  const FwdGeom geom = forward_geom(ctx, a.n_rows, shape_for(a.k), a.ent != nullptr || a.ell != nullptr);
-  ctx->loss_partials.ensure(size_t(std::max(kMaxFwdGrid, ctx->n_cu * 8)) * sizeof(double));
-  a.loss_partial = ctx->loss_partials.as<double>();
-  launch_forward(ctx, a, geom);
-  hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(kBlock), 0, ctx->stream,
-                     ctx->loss_partials.as<double>(), geom.grid, a.n_rows, d_out_loss);
-  RFM_HIP_CHECK(hipGetLastError());
-}
-
-// The two loss forwards of a fit() iteration in ONE launch (fm_forward_kernel's SEG form): rows
-// a.row_ids[0 .. n_rows_a) of the training log (loss partials -> row_a) and every row of the
-// validation log (-> row_b).  Returns the number of partials per row, or -1 when the rows
-// together do not take the many-rows shape (the caller then launches the two separately).
-int forward_loss_pair_deferred(rfm_ctx* ctx, FwdArgs a, double* row_a, double* row_b) {
-  const Shape s = shape_for(a.k);
-  const FwdGeom geom = forward_geom(ctx, a.n_rows, s, false);
-  if (geom.block != kBigBlock || geom.grid > kMaxFwdGrid) return -1;
-  a.loss_partial = row_a;
-  a.loss_partial2 = row_b;
-  const size_t lds = forward_lds_bytes(geom.block, s.lpr, s.vec, s.nc, rows_in_flight_plain(s.nc), 0, a.k, false);
-#define RFM_CALL_SEG(L, Vv, N) \
-  launch_forward_as<L, Vv, N, kBigBlock, rows_in_flight_plain(N), false, false, false, true>(ctx, a, geom, lds)
-  RFM_FOR_SHAPE(s, RFM_CALL_SEG);
-#undef RFM_CALL_SEG
-  RFM_HIP_CHECK(hipGetLastError());
-  return geom.grid;
+  launch_forward(ctx, a, forward_form(ctx, a));
 }
 
 // forward with loss whose partials go to `partial_row` (kMaxFwdGrid doubles) and are
 // finished later, many launches at once; returns the number of partials written
 int forward_loss_deferred(rfm_ctx* ctx, FwdArgs a, double* partial_row) {
   RFM_REQUIRE(a.n_rows > 0, "loss of zero rows");
-  const FwdGeom geom = forward_geom(ctx, a.n_rows, shape_for(a.k), a.ent != nullptr || a.ell != nullptr);
-  RFM_REQUIRE(geom.grid <= kMaxFwdGrid, "forward grid %d exceeds %d", geom.grid, kMaxFwdGrid);
   a.loss_partial = partial_row;
-  launch_forward(ctx, a, geom);
-  return geom.grid;
+  const FwdForm f = forward_form(ctx, a);
+  RFM_REQUIRE(f.grid <= kMaxFwdGrid, "forward grid %d exceeds %d", f.grid, kMaxFwdGrid);
+  launch_forward(ctx, a, f);
+  return f.grid;
+}
+
+// The two loss forwards of a fit() iteration in ONE launch (FwdKind::kCsrPair): rows a.row_ids[0 .. n_rows_a)
+// of the training log (loss partials -> row_a) and every row of the validation log (-> row_b).  Returns the partials
+// per row, or -1 when the rows together do not take the many-rows shape (the caller launches the two separately).
+int forward_loss_pair_deferred(rfm_ctx* ctx, FwdArgs a, double* row_a, double* row_b) {
+  RFM_REQUIRE(a.indptr2, "merged loss forward: no second log");
+  a.loss_partial = row_a;
+  a.loss_partial2 = row_b;
+  const FwdForm f = forward_form(ctx, a);
+  if (f.block != kBigBlock || f.grid > kMaxFwdGrid) return -1;
+  launch_forward(ctx, a, f);
+  return f.grid;
+}
+
+// forward with loss: partials in ctx scratch, finished into d_out_loss
+void forward_loss(rfm_ctx* ctx, FwdArgs a, double* d_out_loss) {
+  ctx->loss_partials.ensure(size_t(std::max(kMaxFwdGrid, ctx->n_cu * 8)) * sizeof(double));
+  const int parts = forward_loss_deferred(ctx, a, ctx->loss_partials.as<double>());
+  hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(kBlock), 0, ctx->stream,
+                     ctx->loss_partials.as<double>(), parts, a.n_rows, d_out_loss);
+  RFM_HIP_CHECK(hipGetLastError());
 }
 
 // Sliced loss forward (rfm_fm_sliced.hpp) over `rows` rows: workgroups per slice (one
@@ -303,7 +288,7 @@ void validate_ids(rfm_ctx* ctx, rfm_fm_plan* plan, const int32_t* d_ids, int64_t
   RFM_REQUIRE(!flags[1], "a row id occurs twice in one batch: the ids of a step must be distinct");
 }
 
-// rows of the plan's log that a step's forward launch scores on the side (fm_forward_kernel, XTRA)
+// rows of the plan's log that a step's forward launch scores on the side (fm_forward_kernel, the ...Riders kinds)
 struct XtraRows {
   const int32_t* ids;  // rows ids[0 .. n) of the plan's log ...
   int64_t n;
@@ -332,25 +317,38 @@ FwdArgs plan_fwd_args(const rfm_fm_plan* plan, const int32_t* ids, int64_t n, co
   return f;
 }
 
+// ... of a step: it leaves Q rows, marks, hot sums and residual sums (the caller adds the slot bitmap)
+FwdArgs step_fwd_args(const rfm_fm_plan* plan, const int32_t* ids, int64_t n, const double* w0,
+                      const double* w, const double* V) {
+  FwdArgs f = plan_fwd_args(plan, ids, n, w0, w, V);
+  f.out_Q = plan->Q.as<double>();
+  f.slot_mark = plan->slot_t.as<SlotMark>();
+  f.n_hot = plan->n_hot;
+  f.hot_rounds = plan->hot_rounds;
+  f.hot_fixed = plan->hot_fixed ? 1 : 0;
+  f.hot_slab = plan->hot_slab.as<double>();
+  f.err_partial = plan->err_partial.as<double>();
+  return f;
+}
+
 // the step's forward launch: its own workgroups (returned: one hot-sum slab each), then those that
 // score the extra rows riding along
 int launch_step_forward(rfm_ctx* ctx, FwdArgs f, const XtraRows* xtra) {
-  const Shape s = shape_for(f.k);
-  const FwdGeom geom = forward_geom(ctx, f.n_rows, s, true);
-  FwdGeom launch = geom;
   if (xtra && xtra->n > 0) {
-    RFM_REQUIRE(geom.block == kSmallBlock && !(f.hot_fixed && f.n_hot > 0),
-                "this step cannot score extra rows");
-    const FwdGeom gx = forward_geom(ctx, xtra->n, s, true);
-    RFM_REQUIRE(gx.block == kSmallBlock, "extra rows: unexpected geometry");
-    f.grid_main = geom.grid;
-    f.grid_x = gx.grid;
     f.row_ids_x = xtra->ids;
     f.n_rows_x = xtra->n;
     f.out_pred_x = xtra->out_pred;
-    launch.grid = geom.grid + gx.grid;
+  }
+  const FwdForm own = forward_form(ctx, f);  // (fails for riding rows on a step that cannot score them)
+  FwdForm launch = own;
+  if (f.n_rows_x > 0) {
+    const FwdForm gx = forward_form(ctx, xtra->n, f.k, true);
+    RFM_REQUIRE(gx.block == kSmallBlock, "extra rows: unexpected geometry");
+    f.grid_main = own.grid;
+    f.grid_x = gx.grid;
+    launch.grid += gx.grid;
     if (xtra->n_y > 0) {
-      const FwdGeom gy = forward_geom(ctx, xtra->n_y, s, true);
+      const FwdForm gy = forward_form(ctx, xtra->n_y, f.k, true);
       RFM_REQUIRE(gy.block == kSmallBlock && f.ent && f.rows, "extra log: unexpected geometry / plan form");
       f.rows_y = xtra->rows_y;
       f.ent_y = xtra->ent_y;
@@ -362,7 +360,7 @@ int launch_step_forward(rfm_ctx* ctx, FwdArgs f, const XtraRows* xtra) {
   ctx->prof_mark();
   launch_forward(ctx, f, launch);
   ctx->prof_mark();
-  return geom.grid;
+  return own.grid;
 }
 
 // the step's consume launch (fm_consume_kernel): the slot-ordered sums and the updates under
@@ -439,9 +437,7 @@ void enqueue_step(rfm_ctx* ctx, rfm_fm_plan* plan, const int32_t* d_row_ids, int
                   int32_t touch_id = 0, const XtraRows* xtra = nullptr) {
   const int k = plan->k;
   const Shape s = shape_for(k);
-  FwdArgs f = plan_fwd_args(plan, d_row_ids, batch, d_w0, d_w, d_V);
-  f.out_Q = plan->Q.as<double>();
-  f.slot_mark = plan->slot_t.as<SlotMark>();
+  FwdArgs f = step_fwd_args(plan, d_row_ids, batch, d_w0, d_w, d_V);
   // more than one chunk per lane: the slot bitmap alternates between two buffers by step
   // parity (see fm_consume_kernel, CH form)
   const bool chunked = s.nc > 1;
@@ -450,11 +446,6 @@ void enqueue_step(rfm_ctx* ctx, rfm_fm_plan* plan, const int32_t* d_row_ids, int
   unsigned long long* bits_other =
       plan->slot_bits.as<unsigned long long>() + (1 - parity) * plan->bits_words;
   f.slot_bits = bits;
-  f.n_hot = plan->n_hot;
-  f.hot_rounds = plan->hot_rounds;
-  f.hot_fixed = plan->hot_fixed ? 1 : 0;
-  f.hot_slab = plan->hot_slab.as<double>();
-  f.err_partial = plan->err_partial.as<double>();
   const int n_slabs = launch_step_forward(ctx, f, xtra);
 
   if (d_grad && !d_touch) {  // dense gradient: every element is written
@@ -841,9 +832,9 @@ struct FitCall {
 struct LossForms {
   int64_t n_a = 0, n_b = 0;   // rows of an iteration's train / validation loss (0: not asked for)
   SlicedGeom sliced;          // sliced by factors: partial logits, ONE launch per iteration
-  bool merge_call = false;    // both losses in ONE fm_forward_kernel launch (SEG form)
+  bool merge_call = false;    // both losses in ONE fm_forward_kernel launch (FwdKind::kCsrPair)
   bool scores_only = false;   // plain forwards that leave scores; the run's logarithms come later
-  bool ride = false;          // the train rows ride in the next step's forward launch (XTRA form)
+  bool ride = false;          // the train rows ride in the next step's forward launch (the ...Riders kinds)
   bool ride_val = false;      // ... and so do the validation rows
   int zns = 0;                // partial logits per row in plan->sl_z (0: it holds scores)
   int64_t z_per_iter = 0;     // doubles of plan->sl_z per iteration
@@ -869,7 +860,7 @@ LossForms loss_forms(const FitCall& c) {
   // (config 3: 104.7 vs 111.6 us per iteration at B = 65 536).  RFM_MERGE_LOSS=0 / 2: never / always.
   const int merge_mode = env_int("RFM_MERGE_LOSS", 1);
   f.merge_call = !f.sliced.ok && merge_mode != 0 && (merge_mode == 2 || s.nc > 1) && c.out_train_loss &&
-                 c.out_val_loss && forward_geom(ctx, c.batch + c.n_val, s, false).block == kBigBlock;
+                 c.out_val_loss && forward_form(ctx, c.batch + c.n_val, plan->k, false).block == kBigBlock;
   // The plain loss forwards (neither sliced nor merged) leave their rows' SCORES and take no
   // logarithms: the two logs of a row's term are ~200 dependent f64 instructions, and a whole
   // run of iterations' terms are computed by one launch instead (RFM_DEFER_LOSS=0: in the
@@ -881,18 +872,20 @@ LossForms loss_forms(const FitCall& c) {
                   env_int("RFM_DEFER_LOSS", 1) != 0;
   // Small batches: the train-loss forward of iteration it - 1 reads the parameters that step
   // it's forward reads -- it RIDES in that launch (extra workgroups that only score the previous
-  // batch's rows; fm_forward_kernel's XTRA form), and only the last iteration's is a launch of
+  // batch's rows; fm_forward_kernel's ...Riders kinds), and only the last iteration's is a launch of
   // its own.  A run's logarithms then wait for the next step's launch.  The step must take the
   // one-row forward shape and arrival-order hot sums.  (RFM_RIDE_LOSS=0: never.)
-  f.ride = f.scores_only && c.out_train_loss && forward_geom(ctx, c.batch, s, true).block == kSmallBlock &&
+  f.ride = f.scores_only && c.out_train_loss && forward_form(ctx, c.batch, plan->k, true).block == kSmallBlock &&
            !(plan->hot_fixed && plan->n_hot > 0) && env_int("RFM_RIDE_LOSS", 1) != 0;
   // ... and so may the validation rows (the same parameters again), when the caller has registered
-  // the log (rfm_fm_plan_register_log keeps it as records), it takes the one-row shape too, and the
+  // the log (rfm_fm_plan_register_log keeps it as records), it takes the one-row shape too -- as
+  // records in a step's launch and as the caller's arrays in the last iteration's own -- and the
   // plan holds plain records (RFM_RIDE_VAL=0: never)
   const rfm_fm_plan::SlLog& vlog = plan->sl_log[0];
   f.ride_val = f.ride && c.out_val_loss && vlog.records &&
                vlog.holds(c.val_indptr, c.val_indices, c.val_values, c.n_val) && plan->ent.p && !plan->ell.p &&
-               forward_geom(ctx, c.n_val, s, true).block == kSmallBlock && env_int("RFM_RIDE_VAL", 1) != 0;
+               forward_form(ctx, c.n_val, plan->k, true).block == kSmallBlock &&
+               forward_form(ctx, c.n_val, plan->k, false).block == kSmallBlock && env_int("RFM_RIDE_VAL", 1) != 0;
   f.zns = f.sliced.ok ? plan->sl_ns : 0;
   f.z_per_iter = int64_t(std::max(f.zns, 1)) * (f.n_a + f.n_b);
   if (f.deferred()) {
@@ -1084,13 +1077,26 @@ int32_t rfm_fm_forward_geometry(const rfm_ctx* ctx, int64_t n_rows, int32_t n_fa
   return guarded([&] {
     RFM_REQUIRE(ctx && h_out4, "null pointer");
     RFM_REQUIRE(n_rows >= 1 && n_rows < (int64_t(1) << 31), "bad shape");
-    const Shape s = shape_for(n_factors);
-    const FwdGeom g = forward_geom(ctx, n_rows, s, records != 0);
-    const int r = g.block == kBigBlock ? (records ? rows_in_flight(s.nc) : rows_in_flight_plain(s.nc)) : 1;
-    h_out4[0] = g.block;
-    h_out4[1] = g.grid;
-    h_out4[2] = g.block / s.lpr * r;
-    h_out4[3] = s.lpr;
+    const FwdForm f = forward_form(ctx, n_rows, n_factors, records != 0);
+    h_out4[0] = f.block;
+    h_out4[1] = f.grid;
+    h_out4[2] = f.trip;
+    h_out4[3] = f.lanes;
+  });
+}
+
+int32_t rfm_fm_step_form(const rfm_ctx* ctx, const rfm_fm_plan* plan, int64_t batch, int64_t n_riding_rows,
+                         int32_t* h_out8) {
+  return guarded([&] {
+    RFM_REQUIRE(ctx && plan && h_out8, "null pointer");
+    RFM_REQUIRE(batch >= 1 && batch <= plan->max_batch, "batch=%lld outside 1..max_batch=%lld",
+                (long long)batch, (long long)plan->max_batch);
+    RFM_REQUIRE(n_riding_rows >= 0, "negative n_riding_rows");
+    FwdArgs a = step_fwd_args(plan, nullptr, batch, nullptr, nullptr, nullptr);
+    a.n_rows_x = n_riding_rows;
+    const FwdForm f = forward_form(ctx, a);
+    const int32_t out[8] = {f.block, f.grid, f.trip, f.lanes, int32_t(f.kind), f.lanes8, int32_t(f.lds), f.fixed};
+    std::copy(out, out + 8, h_out8);
   });
 }
 
@@ -1132,22 +1138,16 @@ int32_t rfm_fm_train_forms(const rfm_ctx* ctx, const rfm_fm_plan* plan, int64_t 
     c.out_val_loss = want_val ? &wanted : nullptr;
     c.form_iters = call_iters;
     const LossForms f = loss_forms(c);
-    const Shape s = shape_for(plan->k);
     // threads per workgroup of the launch that scores the rows of each loss (fit_loss_forwards,
     // fit_step): the sliced kernel's, the merged launch's, the step's own forward for riding rows
     // (whose last iteration is a launch of its own: loss_forms lets rows ride only where that
-    // launch takes the one-row shape too -- checked here, so that the answer holds for both)
+    // launch takes the one-row shape too, so the answer holds for both)
     const auto block_of = [&](int64_t rows, bool recs, bool rides) {
       if (f.sliced.ok) return kSlBlock;
       if (f.merge_call) return kBigBlock;
       if (rides) return kSmallBlock;
-      return forward_geom(ctx, rows, s, recs).block;
+      return forward_form(ctx, rows, plan->k, recs).block;
     };
-    if (f.ride)
-      RFM_REQUIRE(forward_geom(ctx, batch, s, true).block == kSmallBlock, "riding rows: unexpected geometry");
-    if (f.ride_val)
-      RFM_REQUIRE(forward_geom(ctx, n_val, s, false).block == kSmallBlock,
-                  "riding validation rows: unexpected geometry");
     h_out8[0] = f.sliced.ok ? 1 : 0;
     h_out8[1] = f.merge_call ? 1 : 0;
     h_out8[2] = f.scores_only ? 1 : 0;

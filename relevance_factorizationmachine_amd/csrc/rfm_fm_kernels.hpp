@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "rfm_common.h"
 #include "rfm_device_utils.hpp"
 #include "rfm_fm_records.h"
 #include "rfm_rule.hpp"
@@ -39,6 +40,7 @@ __device__ inline double logloss_term(double y, double p, double pred, double ep
 }
 
 constexpr int kBigBlock = 1024;  // threads of the forward's many-rows-in-flight shape
+constexpr int kSmallBlock = 256;  // threads of the one-row-per-group shape
 // waves per SIMD the big forward shape is compiled for (register budget 512/N)
 constexpr int kBigWaves = 4;
 // rows per lane group of the big forward shape (single-chunk factor counts)
@@ -76,9 +78,78 @@ constexpr bool hot_tile(int lpr, int vec, int nc) { return lpr == 16 && vec == 2
 constexpr bool forward_lanes8(int k) { return k > 16 && k <= 32 && k % 4 == 0; }
 constexpr int kHotUnroll = 2;  // rows of a fixed-order hot sum whose LDS reads are in flight together
 constexpr int kHotPosPad = 4;  // bytes between the position rows of two columns (bank spread)
-// LDS bytes of the forward kernel (what a launch asks for)
-inline size_t forward_lds_bytes(int block, int lpr, int vec, int nc, int rows, int n_hot, int k,
-                                bool fixed_order) {
+
+// The forms of fm_forward_kernel: where a row's entries come from, and what the launch does besides
+// scoring its rows (the values are the C ABI's, rfm_fm_step_form).
+enum class FwdKind : int {
+  // the caller's CSR arrays (predict, validation loss): no Q rows, marks or hot class
+  kCsr = RFM_FWD_CSR,
+  // ... of two logs in one launch (many-rows shape): the train-loss and validation-loss forwards of a
+  // fit() iteration, each part with its own loss partials -- see FwdArgs, n_rows_a
+  kCsrPair = RFM_FWD_CSR_PAIR,
+  // the training plan's records (RowRec / Entry)
+  kRecords = RFM_FWD_RECORDS,
+  // ... in their padded form, one row block Entry[LPR] per row (a.ell)
+  kBlocks = RFM_FWD_BLOCKS,
+  // records / blocks with the hot-class sums in a fixed order (hot_fixed_order) instead of LDS atomics
+  kRecordsFixed = RFM_FWD_RECORDS_FIXED,
+  kBlocksFixed = RFM_FWD_BLOCKS_FIXED,
+  // records / blocks (one-row shape) with riding rows: the last workgroups only score rows of another
+  // batch and of another log -- see FwdArgs, grid_main
+  kRecordsRiders = RFM_FWD_RECORDS_RIDERS,
+  kBlocksRiders = RFM_FWD_BLOCKS_RIDERS,
+};
+constexpr bool fwd_records(FwdKind k) { return k != FwdKind::kCsr && k != FwdKind::kCsrPair; }
+constexpr bool fwd_blocks(FwdKind k) {
+  return k == FwdKind::kBlocks || k == FwdKind::kBlocksFixed || k == FwdKind::kBlocksRiders;
+}
+constexpr bool fwd_fixed(FwdKind k) { return k == FwdKind::kRecordsFixed || k == FwdKind::kBlocksFixed; }
+constexpr bool fwd_riders(FwdKind k) { return k == FwdKind::kRecordsRiders || k == FwdKind::kBlocksRiders; }
+// rows a lane group of fm_forward_kernel keeps in flight
+constexpr int forward_rows(int block, int nc, FwdKind kind) {
+  return block != kBigBlock ? 1 : fwd_records(kind) ? rows_in_flight(nc) : rows_in_flight_plain(nc);
+}
+// the instantiations of fm_forward_kernel that are built
+constexpr bool forward_form_exists(int lpr, int nc, int block, FwdKind kind) {
+  if (block != kBigBlock && block != kSmallBlock) return false;
+  if (kind == FwdKind::kCsrPair) return block == kBigBlock;
+  if (fwd_riders(kind)) return block == kSmallBlock;
+  if (fwd_fixed(kind)) return hot_fixed_order(lpr, nc, block, forward_rows(block, nc, kind));
+  return true;
+}
+// Entries of a row whose V gathers fm_forward_kernel keeps in flight together.  One-row shape at one
+// chunk of factors per lane: kSmallUnroll, it has registers to spare; at two to four chunks
+// kSmallWideUnroll, beyond that 2.  The many-rows shape is at its register budget with two (x the rows
+// of a lane group), except at one chunk on padded row blocks or the caller's CSR arrays with
+// arrival-order hot sums, which hold three.
+constexpr int gather_unroll(int block, int nc, FwdKind kind) {
+  if (block != kBigBlock) return nc == 1 ? kSmallUnroll : nc > 4 ? 2 : kSmallWideUnroll;
+  if (nc == 1 && !fwd_fixed(kind) && (fwd_blocks(kind) || !fwd_records(kind)))
+    return fwd_records(kind) ? kBigUnroll : kPlainUnroll;
+  return 2;
+}
+
+// What a forward launch is (rfm_fm.hip, forward_form): the one answer to "which form does it take".
+struct FwdForm {
+  Shape shape;   // lanes per row, factors per lane and chunks of the plan's map of the factor count
+  int block;     // threads of a workgroup: kBigBlock (many rows in flight) or kSmallBlock (one row)
+  int grid;      // workgroups that score the launch's own rows (riding rows add theirs)
+  int rows;      // rows a lane group keeps in flight
+  int trip;      // rows of a workgroup's trip
+  int lanes;     // lanes per row of the kernel that runs: 8 for fm_forward_lanes8_kernel, else shape.lpr
+  FwdKind kind;
+  bool lanes8;   // fm_forward_lanes8_kernel, not fm_forward_kernel
+  bool fixed;    // fixed-order hot sums
+  size_t lds;    // dynamic LDS bytes (0 until the arguments are known)
+};
+// LDS bytes of the forward kernels (what a launch asks for).  The 8-lane kernel asks for what the
+// 16-lane many-rows shape asks for on the same plan, whose trip it keeps: its row buffers (16 entries
+// a lane group, groups one record apart) reach 1 KiB back into `red`, which nothing uses before the
+// trips are over.
+inline size_t forward_lds_bytes(const FwdForm& f, int n_hot, int k) {
+  const int block = f.block, lpr = f.shape.lpr, vec = f.shape.vec, nc = f.shape.nc;
+  const int rows = f.trip / (block / lpr);
+  const bool fixed_order = f.fixed;
   size_t bytes = size_t(block) * 8 + (size_t(block) * rows + size_t(block / lpr)) * sizeof(Entry) +
                  size_t(n_hot) * size_t(k + 2) * 8;
   // (many-rows shape without a hot class -- the loss forwards: two stages of a trip's
@@ -95,12 +166,6 @@ inline size_t forward_lds_bytes(int block, int lpr, int vec, int nc, int rows, i
     bytes += (size_t(n_hot) * (rt + kHotPosPad) + 7) / 8 * 8;            // entry positions
   }
   return bytes;
-}
-// ... of the 8-lane shape: what the 16-lane many-rows shape asks for on the same plan.  Its row
-// buffers (16 entries a lane group, groups one record apart) reach 1 KiB back into `red`, which
-// nothing uses before the trips are over.
-inline size_t forward_lanes8_lds_bytes(int block, int n_hot, int k) {
-  return forward_lds_bytes(block, 16, 2, 1, kFwdRows, n_hot, k, false);
 }
 
 // ---------------------------------------------------------------------------
@@ -121,7 +186,7 @@ struct FwdArgs {
   const double* pscore;
   const int32_t* row_ids;  // may be null: row t
   int64_t n_rows;
-  // SEG form (loss forwards of fit(), caller's CSR arrays): rows [0, n_rows_a) are rows row_ids[t]
+  // FwdKind::kCsrPair (loss forwards of fit(), caller's CSR arrays): rows [0, n_rows_a) are rows row_ids[t]
   // of the log above, rows [n_rows_a, n_rows) are rows t - n_rows_a of a SECOND log; each part
   // has its own loss partials -- the train-loss and validation-loss forwards in one launch
   int64_t n_rows_a;
@@ -142,12 +207,12 @@ struct FwdArgs {
   unsigned long long* slot_bits;  // ... and set the slot's bit (what fm_consume_kernel scans)
   int32_t n_hot;         // hot columns (training step only)
   int32_t hot_rounds;    // rounds of LPR entries that cover the longest row of the plan
-  int32_t hot_fixed;     // 1: the plan asks for fixed-order hot sums (the DET instantiations)
+  int32_t hot_fixed;     // 1: the plan asks for fixed-order hot sums (the ...Fixed kinds)
   double* hot_slab;      // [n_hot][gridDim.x][k+2]
   double* err_partial;   // nullable: [gridDim.x] per-workgroup sums of the residual (for w0)
   double* loss_partial;  // nullable: [gridDim.x]
   double eps;
-  // XTRA form (with REC, one-row shape): workgroups grid_main .. gridDim.x - 1 only SCORE the rows
+  // The ...Riders kinds (one-row shape): workgroups grid_main .. gridDim.x - 1 only SCORE the rows
   // row_ids_x[0 .. n_rows_x) of the same plan (-> out_pred_x) -- no Q rows, marks, hot sums or
   // residuals: the train-loss forward of the previous batch, which reads the same parameters as
   // this step's forward, rides in its launch (rfm_fm_train)
@@ -174,7 +239,7 @@ struct HotEnt {
 static_assert(sizeof(HotEnt) == sizeof(Entry), "HotEnt replaces an Entry in place");
 
 // The step's forward at 8 lanes x 4 factors per row and ONE row per lane group (forward_lanes8;
-// fm_forward_kernel<8, 2, 2, kBigBlock, 1, true, true>): the many-rows shape on padded row blocks
+// fm_forward_lanes8_kernel): the many-rows shape on padded row blocks
 // with arrival-order hot sums, with fewer of the instructions of a row that do not depend on the
 // factor -- addresses, parked-entry reads, scores, marks, walk bookkeeping serve 8 rows per
 // wavefront instruction and are issued once, not once per row in flight.  Lane L of a group holds
@@ -191,7 +256,7 @@ static_assert(sizeof(HotEnt) == sizeof(Entry), "HotEnt replaces an Entry in plac
 // two linear terms are added first (stage l ^ 1), then group_sum<8> makes the other three stages;
 // the slice's two residuals enter the workgroup's sum in the 16-lane map's thread and order.  The
 // fused multiply-adds are spelled out where the 16-lane map's are contracted.
-// LDS: as forward_lanes8_lds_bytes says -- red | row buffers [GPB][16 + 1] Entry, ending where the
+// LDS: as forward_lds_bytes says -- red | row buffers [GPB][16 + 1] Entry, ending where the
 // 16-lane shape's end | hot sums [H][k+2] | coefficient strips [GPB][kTileRanks].
 template <int BLOCK>
 __device__ inline void fm_forward_lanes8(const FwdArgs& a) {
@@ -459,6 +524,13 @@ __device__ inline void fm_forward_lanes8(const FwdArgs& a) {
   }
 }
 
+// the 8-lane step forward's entry: launched in place of fm_forward_kernel<16, 2, 1, kBigBlock, kBlocks>
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? kBigWaves : 1)) void fm_forward_lanes8_kernel(
+    FwdArgs a) {
+  fm_forward_lanes8<BLOCK>(a);
+}
+
 // A row is handled by LPR consecutive lanes; lane l holds factors
 // (c*LPR + l)*VEC .. +VEC-1 for c < NC.  k=32 -> LPR=16, VEC=2: one 16-byte
 // load per lane covers a 256-byte row of V, four rows per wave.
@@ -472,25 +544,20 @@ __device__ inline void fm_forward_lanes8(const FwdArgs& a) {
 // loads of the R rows and of consecutive entries are issued back to back
 // rather than each waiting for the previous one.
 //
-// REC: read the training plan's records (RowRec / Entry); otherwise the
-// caller's CSR arrays.
+// K: the form, see FwdKind; forward_form_exists says which are built.
 // LDS (dynamic): red[BLOCK] f64 | entry buffer [BLOCK/LPR][R*LPR+1] Entry | hot sums [H][k+2] f64
 //   | hot tile: coefficient strips [R][BLOCK/LPR][kTileRanks] f64 (hot_tile shapes, REC && !DET)
 //   | fixed-order hot sums (DET): Q rows, cell sums, row sets, entry positions
-// ELL (with REC): the records come as padded row blocks (a.ell).
-// DET (with REC): the hot-class sums in a fixed order (hot_fixed_order) instead of LDS atomics.
-// SEG (without REC, many-rows shape): two logs in one launch, see FwdArgs.
-// <8, 2, 2, kBigBlock, 1, true, true>: the 8-lane form of the step's forward, fm_forward_lanes8 above.
-template <int LPR, int VEC, int NC, int BLOCK, int R, bool REC, bool ELL = false, bool DET = false,
-          bool SEG = false, bool XTRA = false>
+template <int LPR, int VEC, int NC, int BLOCK, FwdKind K>
 __global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? kBigWaves : 1)) void fm_forward_kernel(
     FwdArgs a) {
-  if constexpr (LPR == 8 && NC == 2) {  // the 8-lane shape has a body of its own; nothing below is part of it
-    static_assert(VEC == 2 && BLOCK == kBigBlock && R == 1 && REC && ELL && !DET && !SEG && !XTRA,
-                  "two chunks of 8 lanes: the 8-lane training forward only");
-    fm_forward_lanes8<BLOCK>(a);
-    return;
-  }
+  static_assert(forward_form_exists(LPR, NC, BLOCK, K), "this form of the forward is not built");
+  constexpr bool REC = fwd_records(K);            // the plan's records, not the caller's CSR arrays
+  constexpr bool ELL = fwd_blocks(K);             // ... as padded row blocks
+  constexpr bool DET = fwd_fixed(K);              // fixed-order hot sums
+  constexpr bool SEG = K == FwdKind::kCsrPair;    // two logs in one launch
+  constexpr bool XTRA = fwd_riders(K);            // riding rows
+  constexpr int R = forward_rows(BLOCK, NC, K);   // rows a lane group keeps in flight
   constexpr int GPB = BLOCK / LPR;  // lane groups per block
   // workgroup index and count among the workgroups of its kind (XTRA: the step's, or the ones
   // that only score the extra rows -- a workgroup-uniform switch of what the arguments mean)
@@ -711,9 +778,8 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == kBigBlock ? kBigWaves : 1)) void f
         ebuf[i * LPR + l] = e[i];
       }
       const int cnt = (maxlen - pb) < LPR ? (maxlen - pb) : LPR;
-      // entries whose gathers are in flight together: the many-rows shape is at its register
-      // budget with two (x R rows); the one-row shape has registers to spare
-#pragma unroll(BLOCK == kBigBlock || NC > 1 ? (NC == 1 && !DET && (ELL || !REC) ? (REC ? kBigUnroll : kPlainUnroll) : (BLOCK == kBigBlock || NC > 4 ? 2 : kSmallWideUnroll)) : kSmallUnroll)
+      // entries whose gathers are in flight together
+#pragma unroll gather_unroll(BLOCK, NC, K)
       for (int j = 0; j < cnt; ++j) {
         Entry ej[R];
         Pack<VEC> pv[R][NC];

@@ -160,7 +160,7 @@ __global__ __launch_bounds__(kBlock) void sl_translate_kernel(const int64_t* ind
   }
 }
 
-// a log as the records the forward kernel's REC form reads (labels / propensities unused: 0 / 1)
+// a log as the records the forward kernel's record forms (FwdKind::kRecords...) read (labels / propensities unused: 0 / 1)
 __global__ __launch_bounds__(kBlock) void log_records_kernel(const int64_t* indptr, const int32_t* indices,
                                                            const double* values, int64_t n_rows,
                                                            RowRec* rows, Entry* ent) {

@@ -137,6 +137,17 @@ class FmPlan:
                                                       out.ctypes.data))
         return dict(zip(("sliced", "workgroups", "rows_per_workgroup", "lds_bytes"), (int(v) for v in out)))
 
+    def step_form(self, batch: int, n_riding_rows: int = 0) -> dict:
+        """The forward launch of a step of ``batch`` rows on this plan (``rfm_fm_step_form``); ``kind`` is
+        one of ``_lib.FWD_KINDS``."""
+        out = np.zeros(8, dtype=np.int32)
+        _lib.check(self.rt.lib.rfm_fm_step_form(self.rt.ctx, self.handle, int(batch), int(n_riding_rows),
+                                                out.ctypes.data))
+        form = dict(zip(("block", "workgroups", "trip", "lanes", "kind", "lanes8", "lds_bytes", "fixed_order"),
+                        (int(v) for v in out)))
+        form["kind"] = _lib.FWD_KINDS[form["kind"]]
+        return form
+
     def set_optimizer(self, kind: int, acc_w0=None, acc_w=None, acc_V=None, eps: float = 0.0) -> None:
         """The update rule of the plan's steps (``rfm_fm_plan_set_optimizer``): ``_lib.OPT_SGD``, or
         ``_lib.OPT_ADAGRAD`` with the three accumulators (device tensors the caller keeps alive)."""

@@ -70,7 +70,7 @@ def fixed_order(k, hot):
 
 
 def host_sizes(k, n_cu=256, capped=None):
-    """The batch sizes the names stand for on a device of `n_cu` compute units (forward_geom of
+    """The batch sizes the names stand for on a device of `n_cu` compute units (forward_form of
     rfm_fm.hip, restated: the host test needs numbers, the GPU tests ask the library).  `capped`: a
     max_batch below the second trip (k = 400: 3 000)."""
     lpr = lpr_of(k)

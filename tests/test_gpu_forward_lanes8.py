@@ -1,5 +1,8 @@
-"""The step's forward at 8 lanes x 4 factors per row (fm_forward_kernel<8, 2, 2, 1024, 1, ...>: k = 20, 24,
+"""The step's forward at 8 lanes x 4 factors per row (fm_forward_lanes8_kernel<1024>: k = 20, 24,
 28, 32 on padded row blocks, many-rows shape, arrival-order hot sums).  Needs an MI355X: ``pytest -m gpu``.
+Every test asks the library which kernel and form a step on its plan takes (rfm_fm_step_form) and asserts
+it before it compares anything: a launch condition that stopped taking the 8-lane kernel would leave
+every bit below as it is.
 
 What the kernel leaves -- the Q rows, the residuals, the marks -- stays inside the plan: the C ABI shows
 it through the gradient.  The sums of the sparse class run over the marked slots in slot order
@@ -7,9 +10,9 @@ it through the gradient.  The sums of the sparse class run over the marked slots
 functions of those bits alone.  The ORDER-EXACT reference of a row is therefore the 16-lane map
 itself, which this shape has to reproduce bit for bit:
 
-- the same batch on a plan of fixed-order hot sums (hot_min_count -2: fm_forward_kernel<16, 2, 1, 1024, 2,
-  true, true, true>, the 16-lane map at two rows per lane group), and
-- pieces of the batch small enough for the one-row shape on the SAME plan (<16, 2, 1, 256, 1, ...>).
+- the same batch on a plan of fixed-order hot sums (hot_min_count -2: fm_forward_kernel<16, 2, 1, 1024,
+  kBlocksFixed>, the 16-lane map at two rows per lane group), and
+- pieces of the batch small enough for the one-row shape on the SAME plan (<16, 2, 1, 256, kBlocks>).
 
 In the logs of the bit tests every row that is not empty holds a column of its own (below the shared
 columns in even rows: its first entry; above them in odd rows: its last), so G_V and g_w of that
@@ -114,12 +117,20 @@ def _theta(n, k):
     return gf.perturbed_init(500 + k, n, k)
 
 
-def _open(rt, log, k, B, hot_mode, want_hot=None, blocks=True):
+def _open(rt, log, k, B, hot_mode, want_hot=None, blocks=True, lanes8=True):
+    """`lanes8`: a step of B rows on the plan takes the 8-lane kernel (else fm_forward_kernel at the plan's lanes)."""
     dev = gf.DeviceLog(rt, log, k, B, hot_mode)
     try:
         lay = dev.plan.layout()
         assert lay["row_blocks"] == blocks and lay["lanes_per_row"] == gf.CLASS_OF.get(k, (16,))[0], lay
         assert fr.forward_geometry(rt, B, k, True)["block"] == BIG
+        form = dev.plan.step_form(B)
+        assert form["block"] == BIG and form["lanes8"] == int(lanes8), form
+        if lanes8:
+            assert form["lanes"] == 8 and form["kind"] == "blocks" and not form["fixed_order"], form
+        else:
+            assert form["lanes"] == lay["lanes_per_row"], form
+            assert form["fixed_order"] == int(hot_mode == -2) and form["kind"].startswith("blocks" if blocks else "records"), form
         if want_hot is not None:
             np.testing.assert_array_equal(np.sort(dev.plan.hot_columns()), want_hot)
     except BaseException:
@@ -140,7 +151,7 @@ def test_every_row_has_the_bits_of_the_16_lane_map(rt, k, size):
     theta = _theta(log["features"].shape[1], k)
     grads, hots = [], []
     for mode in (hot_min, -2):  # this shape; the 16-lane map at two rows per lane group
-        dev = _open(rt, log, k, B, mode, hot if mode == hot_min else None)
+        dev = _open(rt, log, k, B, mode, hot if mode == hot_min else None, lanes8=mode == hot_min)
         try:
             assert dev.plan.layout()["longest_row"] == 16
             hots.append(dev.plan.hot_columns())
@@ -148,6 +159,8 @@ def test_every_row_has_the_bits_of_the_16_lane_map(rt, k, size):
             if mode == hot_min:  # the one-row shape of the same plan, a piece of the batch at a time
                 piece = _sizes(k)["min"] - 1
                 assert fr.forward_geometry(rt, piece, k, True)["block"] == SMALL
+                form = dev.plan.step_form(piece)
+                assert (form["block"], form["lanes8"], form["lanes"], form["kind"]) == (SMALL, 0, 16, "blocks"), form
                 pieces = [gf.dense_grad(dev, ids[at: at + piece], gf.Params(rt, *theta))[0]
                           for at in range(0, B, piece)][:2]  # (the first two pieces)
         finally:
@@ -259,10 +272,27 @@ def test_plans_outside_the_shape_are_what_they_were(rt, name, k, mode, longest):
     ids = np.random.default_rng(B + k).permutation(B).astype(np.int32)
     oracle = gf.grad_oracle(log, ids, *theta)
     dev = _open(rt, log, k, B, hot_min if mode == 0 else mode, hot if mode == 0 else None,
-                blocks=longest <= gf.CLASS_OF.get(k, (16,))[0])
+                blocks=longest <= gf.CLASS_OF.get(k, (16,))[0], lanes8=False)
     try:
         assert dev.plan.layout()["longest_row"] == longest
         g, _ = gf.dense_grad(dev, ids, gf.Params(rt, *theta))
         gf.check_dense(g, dev, ids, oracle, dev.plan.hot_columns(), name)
+    finally:
+        dev.close()
+
+
+@pytest.mark.parametrize("k", [16, 36])
+def test_the_factor_counts_next_to_the_shape_keep_their_kernel(rt, k):
+    """k = 16 (8 lanes of fm_forward_kernel: the log's rows of 16 entries stay records) and 36 (32 lanes, row
+    blocks), arrival-order hot sums, on the log of the bit tests: no 8-lane kernel (the query alone:
+    nothing is launched)."""
+    B = fr.many_rows_minimum(rt, k, True)
+    log, hot_min, _ = _log(B, True)
+    dev = gf.DeviceLog(rt, log, k, B, hot_min)
+    try:
+        lay, form = dev.plan.layout(), dev.plan.step_form(B)
+        assert lay["row_blocks"] == (k == 36) and form["block"] == BIG and form["lanes8"] == 0, (lay, form)
+        assert form["lanes"] == lay["lanes_per_row"] == (8 if k == 16 else 32), (lay, form)
+        assert form["kind"] == ("blocks" if k == 36 else "records") and not form["fixed_order"], (lay, form)
     finally:
         dev.close()

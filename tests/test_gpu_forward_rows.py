@@ -4,7 +4,7 @@ workgroup shapes, through every way the log is read, in every loss form of rfm_f
 edges of a workgroup's trip.  Needs an MI355X: ``pytest -m gpu``.
 
 Every test asks the library which shape or form a call takes (rfm_fm_forward_geometry,
-rfm_fm_train_forms) and asserts it before it compares anything; sizes -- the smallest row count of
+rfm_fm_train_forms; part D the step's kernel and form, rfm_fm_step_form) and asserts it before it compares anything; sizes -- the smallest row count of
 the many-rows shape, the rows of a trip, of a pass of the grid -- come from those queries, not
 from a CU count written here.  Tolerances (logit, score, loss) are the derived ones of
 forward_rows_common.py.
@@ -308,7 +308,7 @@ def test_train_riding_train_rows_on_a_records_plan(rt, k):
 
 def test_train_riding_train_rows_on_a_row_block_plan(rt):
     """max_batch at the many-rows size, every row within one round of a lane group, the call's batch
-    small: the XTRA form reading padded row blocks."""
+    small: the riders form reading padded row blocks (FwdKind::kBlocksRiders)."""
     k = 32
     g = _geo(k, True)
     tr, va = _train_case(k, g["min"] + 10, 100, max_len=g["lpr"])
@@ -347,7 +347,7 @@ def test_train_130_iterations_cross_the_run_with_riding_rows(rt):
 
 @pytest.mark.parametrize("k,mode", [(130, None), (16, "2")])
 def test_train_merged_launch(rt, monkeypatch, k, mode):
-    """Both losses in one SEG launch of the many-rows shape: batch + validation rows at the
+    """Both losses in one launch of the many-rows shape (FwdKind::kCsrPair): batch + validation rows at the
     many-rows minimum, the batch odd and no multiple of the trip -- the boundary between the two
     logs falls inside a trip and, with two rows in flight, between a lane group's two rows."""
     g = _geo(k, False)
@@ -425,6 +425,16 @@ def test_training_forward_many_rows_through_the_gradient(rt, k, layout, hot):
         want_hot = not chunked and (hot == 0 or (hot == -2 and g["lpr"] >= 16))
         assert (info["hot_columns"] > 0) == want_hot, info
         assert info["hot_columns"] <= dev.n - RARE  # the rare columns stay in the sparse class
+        # the kernel and form of the step's forward (rfm_fm_step_form): the layout's kind, fixed-order
+        # where the plan sums a hot class so; the 8-lane kernel at k = 32 on row blocks otherwise
+        fixed = hot == -2 and want_hot
+        kind = layout + ("_fixed" if fixed else "")
+        lanes8 = k == 32 and layout == "blocks" and not fixed
+        form, small = dev.plan.step_form(len(full)), dev.plan.step_form(len(shard))
+        assert (form["block"], form["kind"], form["fixed_order"], form["lanes8"]) == (BIG, kind, int(fixed), int(lanes8)), form
+        assert form["lanes"] == (8 if lanes8 else g["lpr"]) and form["trip"] == g["T"], form
+        assert form["workgroups"] == info["forward_workgroups"], form
+        assert (small["block"], small["kind"], small["lanes8"], small["lanes"]) == (SMALL, kind, 0, g["lpr"]), small
         gf.check_all_forms(dev, gf.Params(rt, *theta), full, shard, o_full, o_shard, gf.fixed_order(k, hot))
     finally:
         dev.close()

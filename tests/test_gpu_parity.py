@@ -993,7 +993,7 @@ def test_fm_fit_every_chunk_count(rfm, k):
 
 @pytest.mark.parametrize("shape,k,batch", [("kuairec_small", 400, 2000), ("kuairec_small", 16, 2000), ("coat", 300, 500)])
 def test_merged_loss_forward_gives_the_same_losses(rfm, monkeypatch, shape, k, batch):
-    """The train-loss and validation-loss forwards of an iteration as ONE launch (the SEG form of the
+    """The train-loss and validation-loss forwards of an iteration as ONE launch (the FwdKind::kCsrPair form of the
     forward: rows of two logs, two sets of loss partials; default for factor counts of several
     chunks per lane, RFM_MERGE_LOSS=2 forces it, 0 forbids it): same parameters bit for bit, same
     loss curves up to the order of the sums, both against the oracle."""

@@ -42,7 +42,7 @@ def test_every_change_of_shape_class_occurs_around_every_entry(k_class):
 
 def test_shape_classes_are_the_two_forward_shapes():
     """one, group, below (mid) take the one-row shape, min, min+1, trip2 (max) the many-rows shape:
-    on the sizes forward_geom gives a device of 256 compute units."""
+    on the sizes forward_form gives a device of 256 compute units."""
     for name in ph.CASES:
         sizes, _ = _sizes(name)
         m = sizes.get("min", sizes.get("mid", 0) + 1)
