@@ -1,5 +1,5 @@
-"""One real rank of ``rfm_fm_fit_dp`` and W - 1 emulated peers in one process (test_dp_ranks_host.py,
-test_gpu_dp_ranks.py).
+"""One real rank of ``rfm_fm_fit_dp`` / ``rfm_fm_fit_dp_eval`` and W - 1 emulated peers in one process
+(test_dp_ranks_host.py, test_gpu_dp_ranks.py, test_gpu_dp_eval_ranks.py).
 
 ``rfm_transport`` hands the three collectives of the data-parallel fit to the caller, and the
 library's public entry points can compute everything another rank would have sent.  So a world of 8
@@ -13,6 +13,13 @@ the cuts of both all-to-all exchanges, the rank-ordered sum of an owner and the 
 updated value may take.  Importing the module touches neither the GPU nor the package's library;
 test_dp_ranks_host.py holds this half to tests/np_dp_engine.NumpyDpEngine and shows that every check
 rejects its mutation.
+
+With an evaluation description (``EvalArgs``) the call is rfm_fm_fit_dp_eval and the emulation plays
+the peers of its one extra all-gather as well (test_gpu_dp_eval_ranks.py): the reference is the whole
+evaluation log scored by rfm_fm_plan_forward and ranked by rfm_val_dcg on the peers' plan, the rank's
+message must be its groups' rows of that table bit for bit with +0.0 everywhere else, and the peers
+answer with their rows and NaN in every double that belongs to no group.  The host half of that --
+``eval_block``, ``merge_blocks``, ``stable_rule_table`` -- is NumPy as well.
 
 What an updated value may be: with s the float64 sum of a column's records in rank order (plain
 adds, the leader's first), ``fl(theta - fl(lr * s))`` or the correctly rounded ``theta - lr * s`` (a
@@ -205,6 +212,80 @@ def global_oracle(log, ids, w0, w, V):
 
 
 # --------------------------------------------------------------------------
+# host bookkeeping of the evaluator (rfm_fm_fit_dp_eval)
+# --------------------------------------------------------------------------
+class EvalLog:
+    """An evaluation log in frame order with its grouping by user, as rfm_val_dcg takes it: ``order``
+    (grouped position -> frame row, ascending user, frame order inside a user) and ``seg`` (row bounds
+    of the groups in grouped order)."""
+
+    def __init__(self, X, users, labels, pscores):
+        self.X = X.tocsr()
+        self.frame = {"user": np.asarray(users), "label": np.asarray(labels, dtype=np.float64),
+                      "pscore": np.asarray(pscores, dtype=np.float64)}
+        self.n_rows = self.X.shape[0]
+        self.order = np.argsort(self.frame["user"], kind="stable").astype(np.int32)
+        su = self.frame["user"][self.order]
+        self.seg = np.concatenate([[0], np.flatnonzero(su[1:] != su[:-1]) + 1, [self.n_rows]]).astype(np.int32)
+        self.n_seg = len(self.seg) - 1
+
+    def with_ones(self):
+        """The same log with every propensity 1 (what a null d_ev_pscores means)."""
+        return EvalLog(self.X, self.frame["user"], self.frame["label"], np.ones(self.n_rows))
+
+
+def eval_block(table, lo, hi, pad, stride, fill):
+    """What rank with groups lo .. hi - 1 contributes to the evaluator's all-gather for one iteration:
+    ``stride`` doubles, its groups' rows of ``table`` ([vals | counted | order-dependent], n_seg
+    apart) at [u | pad + u | 2 pad + u], ``fill`` everywhere else."""
+    table = np.asarray(table, dtype=np.float64)
+    n_seg, m = table.shape[0] // 3, hi - lo
+    assert table.shape == (3 * n_seg,) and 0 <= lo <= hi <= n_seg and m <= pad and stride >= 3 * pad
+    out = np.full(stride, fill, dtype=np.float64)
+    for part in range(3):
+        out[part * pad: part * pad + m] = table[part * n_seg + lo: part * n_seg + hi]
+    return out
+
+
+def group_owner(group_lo, g):
+    """The rank that owns group g: the LAST rank whose first group is <= g (ranks without groups
+    repeat the start of the next owner)."""
+    return int(np.searchsorted(np.asarray(group_lo)[:-1], g, side="right")) - 1
+
+
+def merge_blocks(blocks, group_lo, pad, n_seg, owner=group_owner, parts=(0, 1, 2), shift=0):
+    """The merge of the gathered blocks ([rank][stride], one iteration) into the table of the whole
+    log, restated in NumPy: group g comes from its owner's block at [u | pad + u | 2 pad + u],
+    u = g - group_lo[owner].  ``owner``, ``parts`` and ``shift`` are there for test_dp_ranks_host.py,
+    which states wrong merges with them (another owner rule, part p read at parts[p] * pad, u + shift)."""
+    out = np.empty(3 * n_seg, dtype=np.float64)
+    for g in range(n_seg):
+        r = owner(group_lo, g)
+        u = g - int(group_lo[r]) + shift
+        for p in range(3):
+            out[p * n_seg + g] = blocks[r][parts[p] * pad + u]
+    return out
+
+
+def check_table(got, want, what):
+    """A merged table against the reference table: every double, bit for bit (a NaN read from a
+    peer's padding differs from any value a table holds)."""
+    assert_bits(got, want, what)
+    assert not np.isnan(np.asarray(got)).any(), f"{what}: a table holds no NaN"
+
+
+def stable_rule_table(frame, scores, k):
+    """Per user (ascending) the value, the counted flag and the order-dependent flag of IPS-DCG@k
+    under the documented tie rule, from NumPy alone (eval_rule_common.py): among equal scores the
+    later row ranks first; rows of different label or propensity that tie inside or across the first
+    k ranks, or a NaN score, make a user order-dependent."""
+    from eval_rule_common import order_dependent_users, stable_rule_dcg
+    scores = np.asarray(scores, dtype=np.float64)
+    vals, counted = stable_rule_dcg(frame, scores, frame["pscore"], k)
+    return vals, counted, order_dependent_users(frame, scores, frame["pscore"], k)
+
+
+# --------------------------------------------------------------------------
 # the device side
 # --------------------------------------------------------------------------
 class GuardedParams:
@@ -248,7 +329,9 @@ class PeerCase:
         self.hot_cols = self.dev.plan.hot_columns()
         assert np.array_equal(self.hot_cols, self.aux.plan.hot_columns())
         assert self.dev.plan.layout() == self.aux.plan.layout()
-        self.fixed = gf.fixed_order(k, hot)
+        # (a factor count gf.CLASS_OF does not list: chunked once its lane units -- two adjacent factors
+        # of an even count -- outnumber a wavefront's 64 lanes)
+        self.fixed = gf.fixed_order(k, hot) if k in gf.CLASS_OF else (hot in (-1, -2) or -(-k // (2 - k % 2)) > 64)
 
     def on_aux(self):
         import torch
@@ -259,6 +342,122 @@ class PeerCase:
         self.aux_rt.sync()
         self.dev.close()
         self.aux.close()
+
+
+class EvalCase:
+    """An evaluation log (EvalLog) whole on the peers' context of a PeerCase, for the reference of
+    rfm_fm_fit_dp_eval: its scores by rfm_fm_plan_forward on the peers' plan and their table by
+    rfm_val_dcg -- the two public entries the evaluator is documented to equal bit for bit; neither
+    runs the shard path, the merge or the means of many tables."""
+
+    def __init__(self, case, elog):
+        from relevance_factorizationmachine_amd.runtime import DeviceCSR
+        assert elog.X.shape[1] == case.n, (elog.X.shape, case.n)
+        self.case, self.log = case, elog
+        with case.on_aux():
+            rt = case.aux_rt
+            self.csr = DeviceCSR(rt, elog.X)
+            self.rows, self.seg = rt.upload(elog.order), rt.upload(elog.seg)
+            self.labels = rt.upload(elog.frame["label"][elog.order])
+            self.pscores = rt.upload(elog.frame["pscore"][elog.order])
+            rt.sync()
+
+    def reference(self, theta, k):
+        """(scores in frame order, table [3 n_seg], out [2]) of the whole log at the replica ``theta``."""
+        import torch
+        from relevance_factorizationmachine_amd import _lib
+        case, log = self.case, self.log
+        with case.on_aux():
+            rt, c = case.aux_rt, self.csr
+            nan = float("nan")
+            w0, w, V = (rt.upload(np.asarray(a, dtype=np.float64)) for a in theta)
+            sc = torch.full((log.n_rows + gf.GUARD,), nan, dtype=torch.float64, device=rt.torch_device)
+            tab = torch.full((3 * log.n_seg + gf.GUARD,), nan, dtype=torch.float64, device=rt.torch_device)
+            out = torch.full((2,), nan, dtype=torch.float64, device=rt.torch_device)
+            _lib.check(rt.lib.rfm_fm_plan_forward(rt.ctx, case.aux.plan.handle, c.indptr.data_ptr(),
+                                                  c.indices.data_ptr(), c.values.data_ptr(), log.n_rows,
+                                                  w0.data_ptr(), w.data_ptr(), V.data_ptr(), sc.data_ptr()))
+            _lib.check(rt.lib.rfm_val_dcg(rt.ctx, sc.data_ptr(), self.seg.data_ptr(), self.rows.data_ptr(),
+                                          self.labels.data_ptr(), self.pscores.data_ptr(), log.n_seg, k,
+                                          tab.data_ptr(), out.data_ptr()))
+            rt.sync()
+            sc, tab, out = sc.cpu().numpy(), tab.cpu().numpy(), out.cpu().numpy()
+        assert np.isnan(sc[log.n_rows:]).all() and np.isnan(tab[3 * log.n_seg:]).all(), "the reference wrote behind its outputs"
+        assert not np.isnan(sc[: log.n_rows]).any() and not np.isnan(tab[: 3 * log.n_seg]).any()
+        return sc[: log.n_rows], tab[: 3 * log.n_seg], out
+
+
+class Slots:
+    """``n`` slots of ``width`` doubles on the device, NaN-filled, with one more slot in front and one
+    behind: ``ptr`` is slot 0, ``host()`` returns [n + 2][width] with slot s at index s + 1."""
+
+    def __init__(self, rt, n, width):
+        import torch
+        self.rt, self.n, self.width = rt, n, width
+        self.t = torch.full(((n + 2) * width,), float("nan"), dtype=torch.float64, device=rt.torch_device)
+        self.ptr = self.t.data_ptr() + width * 8
+
+    def host(self):
+        self.rt.sync()
+        return self.t.cpu().numpy().reshape(self.n + 2, self.width)
+
+
+class EvalArgs:
+    """The evaluation arguments of ONE rfm_fm_fit_dp_eval call of rank ``rank`` of ``world`` on the
+    log of ``whole`` (an EvalCase): the shard's CSR, grouping, labels and propensities as the driver
+    builds them (dist.DpEvalLoop), every output NaN-filled with a slot in front and one behind.
+
+    pad / user_stride: above the smallest legal values when given.  scores_extra: columns of a score
+    slot behind the shard's rows.  permute: the shard's CSR in a shuffled row order with d_rows mapping
+    grouped position to CSR row.  ones: d_ev_pscores NULL (``whole`` then holds all-ones propensities).
+    The fields may be edited before the call (the error cases do)."""
+
+    def __init__(self, rt, whole, world, rank, k, n_iters, pad=None, user_stride=None, scores_extra=0, slot_first=0,
+                 permute=None, ones=False):
+        from relevance_factorizationmachine_amd.dist import group_shard_bounds
+        from relevance_factorizationmachine_amd.runtime import DeviceCSR
+        log = whole.log
+        self.whole, self.world, self.rank, self.k, self.n_iters, self.slot_first = whole, world, rank, k, n_iters, slot_first
+        self.group_lo = np.ascontiguousarray(group_shard_bounds(log.seg, world), dtype=np.int32)
+        self.lo, self.hi = int(self.group_lo[rank]), int(self.group_lo[rank + 1])
+        r0, r1 = int(log.seg[self.lo]), int(log.seg[self.hi])
+        self.n_local, self.n_ev, self.n_ev_total, self.n_seg = self.hi - self.lo, r1 - r0, log.n_rows, log.n_seg
+        self.pad = max(int(np.diff(self.group_lo).max()), 1) if pad is None else pad
+        self.user_stride = 3 * self.pad if user_stride is None else user_stride
+        self.scores_stride = max(self.n_ev + scores_extra, 1)
+        frame_rows = log.order[r0:r1]  # grouped position of the shard -> frame row
+        self.h_rows = None
+        self.csr_frame_rows = frame_rows  # CSR row of the shard -> frame row
+        if permute is not None:
+            self.h_rows = np.random.default_rng(permute).permutation(self.n_ev).astype(np.int32)
+            self.csr_frame_rows = np.empty_like(frame_rows)
+            self.csr_frame_rows[self.h_rows] = frame_rows
+        self.csr = DeviceCSR(rt, log.X[self.csr_frame_rows]) if self.n_ev else None
+        self.rows = None if self.h_rows is None else rt.upload(self.h_rows)
+        self.seg_ptr = rt.upload((log.seg[self.lo: self.hi + 1] - r0).astype(np.int32))
+        self.labels = rt.upload(log.frame["label"][frame_rows] if self.n_ev else np.zeros(1))
+        self.pscores = None if ones else rt.upload(log.frame["pscore"][frame_rows] if self.n_ev else np.ones(1))
+        if ones:
+            assert (log.frame["pscore"] == 1.0).all()
+        n_slots = slot_first + n_iters + 1  # (one free slot behind the call's)
+        self.scores = Slots(rt, n_slots, self.scores_stride)
+        self.scratch = Slots(rt, n_slots, self.user_stride)
+        self.full = Slots(rt, n_iters, max(3 * self.n_seg, 1))
+        self.dcg = Slots(rt, n_iters, 2)
+
+    def tail(self):
+        """The arguments of rfm_fm_fit_dp_eval behind those of rfm_fm_fit_dp, in the header's order."""
+        def p(t):
+            return None if t is None else t.data_ptr()
+        c = self.csr
+        return [p(c and c.indptr), p(c and c.indices), p(c and c.values), self.n_ev, self.n_ev_total, p(self.seg_ptr),
+                p(self.rows), p(self.labels), p(self.pscores), self.n_local, self.k, self.scores.ptr,
+                self.scores_stride, self.scratch.ptr, self.user_stride, self.slot_first, self.group_lo.ctypes.data,
+                self.pad, self.n_seg, self.full.ptr, self.dcg.ptr]
+
+    def outputs_untouched(self):
+        for name in ("scores", "scratch", "full", "dcg"):
+            assert np.isnan(getattr(self, name).host()).all(), f"a refused call wrote to {name}"
 
 
 class EmulatedPeers:
@@ -288,6 +487,9 @@ class EmulatedPeers:
         self.named = []       # rows mode: column -> leader record of every iteration, all owners
         self.expect = []      # dense mode: the replica rfm_fm_apply leaves after every iteration
         self.loss_seen = None
+        self.ev = None        # the EvalArgs of a rfm_fm_fit_dp_eval call (run(ev=...))
+        self.ref = None       # ... its reference per iteration: (scores, table, out) of the whole log
+        self.eval_sent = None  # ... what the rank handed to the evaluator's all-gather
         self.ranges = owner_ranges(self.n, world)
         self.shards = [shard_bounds(self.B, world, s) for s in range(world)]
         self.table = None
@@ -370,6 +572,8 @@ class EmulatedPeers:
     # ---- all_gather: the bounds of every rank, every iteration -----------------
     def _all_gather(self, index, d_send, d_recv, nbytes):
         W, nb = self.W, self.W + 1
+        if self.ev is not None and index == (1 if self.mode == "rows" else 0):
+            return self._eval_gather(d_send, d_recv, nbytes)
         assert self.mode == "rows" and index == 0, "an all-gather nobody expects"
         assert nbytes == self.n_iters * nb * 4, nbytes
         mine = self._d2h(d_send, nbytes, np.int32).reshape(self.n_iters, nb)
@@ -389,6 +593,28 @@ class EmulatedPeers:
             self.tamper(table)
         self.table = table
         self._h2d(d_recv, table)
+
+    # ---- all_gather of the evaluator: every rank's per-user tables of the whole call ----------
+    def _eval_gather(self, d_send, d_recv, nbytes):
+        ea, W, r, n_it = self.ev, self.W, self.r, self.n_iters
+        done = (self.calls["all_to_all"] == 2 * n_it) if self.mode == "rows" else (self.calls["all_reduce_sum"] >= n_it)
+        assert done and len(self.theta) == n_it, "the evaluator's all-gather comes after the last iteration"
+        assert nbytes == n_it * ea.user_stride * 8, nbytes
+        assert d_send == ea.scratch.ptr + ea.slot_first * ea.user_stride * 8, "the send pointer is not the call's first slot"
+        # the replica after every iteration -> the whole log's scores, table and means on the peers' plan
+        self.ref = [ea.whole.reference(theta, ea.k) for theta in self.theta[1:] + [self._live()]]
+        mine = self._d2h(d_send, nbytes, np.float64).reshape(n_it, ea.user_stride).copy()
+        lo, pad, stride = ea.group_lo, ea.pad, ea.user_stride
+        recv = np.empty((W, n_it, stride))
+        for it, (_, table, _) in enumerate(self.ref):
+            assert_bits(mine[it], eval_block(table, lo[r], lo[r + 1], pad, stride, 0.0),
+                        f"the evaluator's message of rank {r}, iteration {it} (its groups' rows of the reference "
+                        "table, +0.0 everywhere else)")
+            for s in range(W):  # a peer's padding is NaN: a merge or a mean that reads it shows
+                recv[s, it] = mine[it] if s == r else eval_block(table, lo[s], lo[s + 1], pad, stride, np.nan)
+            check_table(merge_blocks(recv[:, it], lo, pad, ea.n_seg), table, "the emulation's own merge")
+        self.eval_sent = mine
+        self._h2d(d_recv, recv)
 
     # ---- all_to_all -------------------------------------------------------------
     def _all_to_all(self, index, d_send, soff, sbytes, d_recv, roff, rbytes):
@@ -534,11 +760,13 @@ class EmulatedPeers:
             self.expect.append(tuple(t.cpu().numpy() for t in c))
 
     # ---- the call and what it must leave -------------------------------------------
-    def run(self, val=None, want_losses=False, eps=1e-15):
-        """One rfm_fm_fit_dp.  val: (DeviceCSR, y, p) of the validation log.  Returns the return code
-        (the error text in ``self.message``); an exception of a callback is raised here."""
+    def run(self, val=None, want_losses=False, eps=1e-15, ev=None):
+        """One rfm_fm_fit_dp, or with ``ev`` (an EvalArgs) one rfm_fm_fit_dp_eval.  val: (DeviceCSR, y,
+        p) of the validation log.  Returns the return code (the error text in ``self.message``); an
+        exception of a callback is raised here."""
         import torch
         rt, case = self.case.rt, self.case
+        self.ev = ev
         self.d_ids = rt.upload(self.ids)
         nan = float("nan")
         self.out_train = torch.full((self.n_iters,), nan, dtype=torch.float64, device=rt.torch_device)
@@ -549,11 +777,18 @@ class EmulatedPeers:
             vargs = (csr.indptr.data_ptr(), csr.indices.data_ptr(), csr.values.data_ptr(), vy.data_ptr(),
                      vp.data_ptr(), csr.shape[0])
         self.theta0 = self.params.host()
-        rc = rt.lib.rfm_fm_fit_dp(rt.ctx, case.dev.plan.handle, C.byref(self.struct),
-                                  {"dense": 0, "rows": 1}[self.mode], self.d_ids.data_ptr(), self.B, self.n_iters,
-                                  *self.params.ptrs(), self.lr, *vargs, eps,
-                                  self.out_train.data_ptr() if want_losses else None,
-                                  self.out_val.data_ptr() if want_losses else None)
+        entry = "rfm_fm_fit_dp" if ev is None else "rfm_fm_fit_dp_eval"
+        args = [rt.ctx, case.dev.plan.handle, C.byref(self.struct), {"dense": 0, "rows": 1}[self.mode],
+                self.d_ids.data_ptr(), self.B, self.n_iters, *self.params.ptrs(), self.lr, *vargs, eps,
+                self.out_train.data_ptr() if want_losses else None, self.out_val.data_ptr() if want_losses else None]
+        assert len(args) == len(self._lib.SIGNATURES["rfm_fm_fit_dp"])
+        if ev is not None:
+            args += ev.tail()
+        sig = self._lib.SIGNATURES[entry]
+        assert len(args) == len(sig), (entry, len(args), len(sig))
+        for a, t in zip(args, sig):  # an integer argument is an integer, a pointer an address or NULL
+            assert t is C.c_void_p or isinstance(a, float if t is C.c_double else int), (entry, a, t)
+        rc = getattr(rt.lib, entry)(*args)
         self.message = self._lib.last_error() if rc != 0 else ""
         rt.sync()
         if self.error is not None:
@@ -561,12 +796,53 @@ class EmulatedPeers:
         self.rc = rc
         return rc
 
-    def check_counts(self, losses=False):
+    def check_counts(self, losses=False, evaluator=False):
         if self.mode == "rows":
             want = {"all_gather": 1, "all_to_all": 2 * self.n_iters, "all_reduce_sum": 1 if losses else 0}
         else:
             want = {"all_gather": 0, "all_to_all": 0, "all_reduce_sum": self.n_iters + (1 if losses else 0)}
+        assert evaluator == (self.ev is not None)
+        want["all_gather"] += 1 if evaluator else 0
         assert self.calls == want, (self.calls, want)
+
+    def check_evaluator(self):
+        """After a clean rfm_fm_fit_dp_eval: scores, per-user slots, merged tables and means of every
+        iteration against the reference of the whole log, bit for bit, every double around them still
+        NaN; then the reference tables themselves against the tie rule restated in NumPy (flags exact,
+        values and mean to 1e-12: float64 on both sides, the reference's term order per user, another
+        fixed order over users -- the figure of tests/test_gpu_eval.py)."""
+        ea, n_it = self.ev, self.n_iters
+        assert self.ref is not None and len(self.ref) == n_it and self.eval_sent.shape == (n_it, ea.user_stride)
+        first, n_seg = ea.slot_first + 1, ea.n_seg  # (slot s of a Slots sits at index s + 1)
+        scores, scratch, full, dcg = ea.scores.host(), ea.scratch.host(), ea.full.host(), ea.dcg.host()
+        for it, (ref_scores, table, out) in enumerate(self.ref):
+            what = f"rank {self.r} of {self.W}, iteration {it}"
+            assert_bits(scores[first + it, : ea.n_ev], ref_scores[ea.csr_frame_rows],
+                        f"{what}: the shard's scores against the whole log's")
+            assert np.isnan(scores[first + it, ea.n_ev:]).all(), f"{what}: a score column behind the shard's rows was written"
+            assert_bits(scratch[first + it], self.eval_sent[it], f"{what}: the per-user slot against what was gathered")
+            check_table(full[1 + it, : 3 * n_seg], table, f"{what}: d_full_out against rfm_val_dcg of the whole log")
+            got = dcg[1 + it]
+            assert np.isnan(got[0]) if np.isnan(out[0]) else bits(got[:1])[0] == bits(out[:1])[0], (what, got, out)
+            assert bits(got[1:])[0] == bits(out[1:])[0], (what, got, out)
+            # independent of device code: the tie rule in NumPy on the reference's scores
+            vals, counted, dep = stable_rule_table(ea.whole.log.frame, ref_scores, ea.k)
+            assert np.array_equal(table[n_seg: 2 * n_seg], counted.astype(np.float64)), f"{what}: counted flags"
+            assert np.array_equal(table[2 * n_seg:], dep.astype(np.float64)), f"{what}: order-dependent flags"
+            assert not table[:n_seg][~counted].any(), f"{what}: a user that does not count has a value"
+            np.testing.assert_allclose(table[:n_seg][counted], vals[counted], rtol=1e-12, atol=0, err_msg=what)
+            assert out[1] == dep.sum(), (what, out[1], dep.sum())
+            if counted.any():
+                mean = float(np.mean(vals[counted]))
+                assert abs(out[0] - mean) <= 1e-12 * abs(mean), (what, out[0], mean)
+            else:
+                assert np.isnan(out[0]) and np.isnan(got[0]), (what, out, got)
+        call = np.zeros(scores.shape[0], dtype=bool)
+        call[first: first + n_it] = True
+        assert np.isnan(scores[~call]).all(), "a score slot outside the call was written"
+        assert np.isnan(scratch[~call]).all(), "a per-user slot outside the call was written"
+        assert np.isnan(full[[0, -1]]).all() and np.isnan(full[1:-1, 3 * n_seg:]).all(), "d_full_out: written outside the tables"
+        assert np.isnan(dcg[[0, -1]]).all(), "d_dcg_out: written outside the call's pairs"
 
     def check_replica(self):
         """After a clean call: every transition of the replica, bit for bit.  Rows mode: a row a

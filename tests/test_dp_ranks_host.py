@@ -1,6 +1,8 @@
 """The bookkeeping of the emulated-peer harness (dp_peers_common.py) on the CPU: its expected bounds,
 exchange cuts, rank-ordered sums and rounding candidates against tests/np_dp_engine.NumpyDpEngine at
-2, 8 and 63 ranks, and a mutation that every check of a message must reject.  No GPU."""
+2, 8 and 63 ranks, and a mutation that every check of a message must reject; then the evaluator's
+half: blocks and their merge against random tables cut by dist.group_shard_bounds, and the wrong
+merges that the table comparison of test_gpu_dp_eval_ranks.py must reject.  No GPU."""
 import types
 
 import numpy as np
@@ -242,3 +244,130 @@ def test_rejects_a_minus_one_record_carrying_a_column(recorded):
     block[follower, 0] = np.concatenate(m.peers.segs[0])[follower, 0]
     with pytest.raises(AssertionError, match="column fields"):
         _check_block(m, block)
+
+
+# --------------------------------------------------------------------------
+# the evaluator's tables: blocks, merge, and the mutations the comparison must reject
+# --------------------------------------------------------------------------
+def _random_tables(seed, lens, W, pad_extra=0, stride_extra=0):
+    """A random table [vals | counted | order-dependent] of a log with groups of ``lens`` rows, cut for
+    W ranks by dist.group_shard_bounds, and every rank's block with NaN padding."""
+    from relevance_factorizationmachine_amd.dist import group_shard_bounds
+    rng = np.random.default_rng(seed)
+    n_seg = len(lens)
+    seg = np.concatenate([[0], np.cumsum(lens)])
+    lo = group_shard_bounds(seg, W).astype(np.int32)
+    table = np.concatenate([rng.uniform(0.5, 3.0, n_seg), (rng.random(n_seg) < 0.7).astype(np.float64),
+                            (rng.random(n_seg) < 0.2).astype(np.float64)])
+    pad = max(int(np.diff(lo).max()), 1) + pad_extra
+    stride = 3 * pad + stride_extra
+    blocks = [dp.eval_block(table, lo[r], lo[r + 1], pad, stride, np.nan) for r in range(W)]
+    return types.SimpleNamespace(table=table, lo=lo, pad=pad, stride=stride, blocks=blocks, n_seg=n_seg, W=W)
+
+
+E_FEW = [3, 1, 64, 65, 2]
+
+
+@pytest.mark.parametrize("W", [2, 8, 63])
+@pytest.mark.parametrize("lens", [E_FEW, [2], [1, 129, 1], list(range(1, 41)), [2] * 300 + [129, 1, 65] + [2] * 90],
+                         ids=["few", "one", "long-middle", "ramp", "many"])
+@pytest.mark.parametrize("pad_extra,stride_extra", [(0, 0), (2, 5)])
+def test_merge_of_the_blocks_is_the_table(W, lens, pad_extra, stride_extra):
+    t = _random_tables(7 * W + len(lens), lens, W, pad_extra, stride_extra)
+    assert t.lo[0] == 0 and t.lo[-1] == t.n_seg and (np.diff(t.lo) >= 0).all()
+    if len(lens) < W:
+        assert (np.diff(t.lo) == 0).sum() >= W - len(lens)  # fewer groups than ranks: ranks that own none
+    for r in range(W):  # a block is the rank's rows and nothing else
+        m = t.lo[r + 1] - t.lo[r]
+        assert np.isnan(t.blocks[r]).sum() == t.stride - 3 * m
+    dp.check_table(dp.merge_blocks(t.blocks, t.lo, t.pad, t.n_seg), t.table, "merge")
+    for g in range(t.n_seg):
+        r = dp.group_owner(t.lo, g)
+        assert t.lo[r] <= g < t.lo[r + 1]
+
+
+def test_e_few_bounds():
+    """The two cuts test_gpu_dp_eval_ranks.py relies on."""
+    from relevance_factorizationmachine_amd.dist import group_shard_bounds
+    seg = np.concatenate([[0], np.cumsum(E_FEW)])
+    assert group_shard_bounds(seg, 8).tolist() == [0, 3, 3, 3, 3, 4, 4, 4, 5]
+    lo = group_shard_bounds(seg, 63)
+    assert lo[:3].tolist() == [0, 1, 3] and lo[-1] == 5 and (np.diff(lo) == 0).sum() == 59
+
+
+@pytest.fixture(scope="module")
+def gathered():
+    """E-few at 8 ranks (bounds 0 3 3 3 3 4 4 4 5: repeated starts in front of both later owners); the
+    stride leaves room for a reader whose pad is one too large."""
+    t = _random_tables(11, E_FEW, 8, 0, 4)
+    assert t.lo.tolist() == [0, 3, 3, 3, 3, 4, 4, 4, 5] and t.pad == 3
+    dp.check_table(dp.merge_blocks(t.blocks, t.lo, t.pad, t.n_seg), t.table, "merge")
+    return t
+
+
+def _rejected(t, merged):
+    with pytest.raises(AssertionError):
+        dp.check_table(merged, t.table, "a wrong merge")
+
+
+def test_rejects_two_ranks_blocks_exchanged(gathered):
+    t = gathered
+    blocks = list(t.blocks)
+    blocks[4], blocks[7] = blocks[7], blocks[4]  # both own one group
+    _rejected(t, dp.merge_blocks(blocks, t.lo, t.pad, t.n_seg))
+
+
+@pytest.mark.parametrize("off", [-1, 1])
+def test_rejects_pad_off_by_one_on_the_reading_side(gathered, off):
+    t = gathered
+    _rejected(t, dp.merge_blocks(t.blocks, t.lo, t.pad + off, t.n_seg))
+
+
+def test_rejects_a_block_read_at_u_where_pad_plus_u_is_meant(gathered):
+    t = gathered
+    _rejected(t, dp.merge_blocks(t.blocks, t.lo, t.pad, t.n_seg, parts=(0, 0, 2)))
+    _rejected(t, dp.merge_blocks(t.blocks, t.lo, t.pad, t.n_seg, parts=(0, 1, 1)))
+
+
+def test_rejects_a_padding_nan_read_in_place_of_a_value(gathered):
+    t = gathered
+    merged = dp.merge_blocks(t.blocks, t.lo, t.pad, t.n_seg, shift=1)  # rank 4's one group: u = 1 is padding
+    assert np.isnan(merged[3])
+    _rejected(t, merged)
+    # ... and a NaN alone, in a table that is right everywhere else
+    merged = dp.merge_blocks(t.blocks, t.lo, t.pad, t.n_seg)
+    merged[t.n_seg + 3] = np.nan
+    _rejected(t, merged)
+
+
+def test_rejects_the_first_rank_whose_start_is_not_above_g_as_owner(gathered):
+    """Groups 3 and 4 start at ranks 1 and 5 by that rule (ranks without groups), at ranks 4 and 7 by
+    the right one: only repeated starts separate the two."""
+    t = gathered
+
+    def first_owner(lo, g):
+        prev = [r for r in range(len(lo) - 1) if lo[r] <= g]
+        return min(r for r in prev if lo[r] == max(lo[p] for p in prev))
+
+    assert [first_owner(t.lo, g) for g in range(5)] == [0, 0, 0, 1, 5]
+    assert [dp.group_owner(t.lo, g) for g in range(5)] == [0, 0, 0, 4, 7]
+    _rejected(t, dp.merge_blocks(t.blocks, t.lo, t.pad, t.n_seg, owner=first_owner))
+    # without repeated starts the two rules agree
+    t2 = _random_tables(12, [2] * 16, 8)
+    assert (np.diff(t2.lo) > 0).all()
+    dp.check_table(dp.merge_blocks(t2.blocks, t2.lo, t2.pad, t2.n_seg, owner=first_owner), t2.table, "merge")
+
+
+def test_stable_rule_table_ties_and_nan():
+    """The later row first among equal scores; a tie between rows that differ, inside or across the
+    first k ranks, or a NaN, flags the user; a user without a positive label does not count."""
+    users = np.array([5, 5, 5, 2, 2, 9, 9, 9, 7, 7])
+    frame = {"user": users, "label": np.array([1.0, 0, 0, 1, 0, 0, 0, 0, 0, 1]),
+             "pscore": np.array([0.5, 0.5, 0.25, 1, 1, 1, 1, 1, 0.5, 0.5])}
+    scores = np.array([0.3, 0.3, 0.1, 0.2, 0.9, 0.5, 0.5, 0.5, 0.4, np.nan])
+    vals, counted, dep = dp.stable_rule_table(frame, scores, 1)
+    # users ascending: 2 (distinct scores), 5 (rows 0 and 1 tie across rank 1, labels differ), 7 (NaN), 9 (no label)
+    assert counted.tolist() == [True, True, True, False] and dep.tolist() == [False, True, True, False]
+    assert vals[0] == 0.0 and vals[1] == 0.0 and vals[3] == 0.0  # user 5: the later row (label 0) ranks first
+    vals, counted, dep = dp.stable_rule_table(frame, scores, 2)
+    assert vals[1] == 1.0 / (0.5 * np.log2(2.0)) and vals[0] == 1.0 / np.log2(2.0)

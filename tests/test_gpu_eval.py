@@ -12,6 +12,8 @@ import catalogue_val_common as cv
 import rank_items_common as rk
 import test_gpu_catalogue_val as tcv
 from conftest import load_golden
+from eval_rule_common import order_dependent_users as _order_dependent_users
+from eval_rule_common import stable_rule_dcg as _stable_rule_dcg
 from oracle import cpu_ref
 from relevance_factorizationmachine_amd import synth
 
@@ -26,21 +28,6 @@ TOL = 1e-12
 def ev():
     from relevance_factorizationmachine_amd import evaluate, runtime
     return evaluate, runtime.Runtime.get()
-
-
-def _stable_rule_dcg(frame, scores, pscores, k):
-    """IPS-DCG@k with the documented tie rule (later row first), per user."""
-    vals, ok = [], []
-    for rows in cpu_ref._per_user_slices(frame["user"]):
-        rank = np.argsort(scores[rows], kind="stable")[::-1]
-        ys = frame["label"][rows][rank]
-        if np.sum(ys) == 0:
-            vals.append(0.0)
-            ok.append(False)
-            continue
-        vals.append(cpu_ref.ips_dcg_at_k(ys, k, pscores[rows][rank]))
-        ok.append(True)
-    return np.array(vals), np.array(ok)
 
 
 def test_matches_reference_fixture(ev):
@@ -79,25 +66,6 @@ def test_saturated_ties_follow_the_documented_rule(ev):
     assert order_dependent == _order_dependent_users(frame, g["scores"], g["pscore"], 5).sum() > 0
     # and stays within the spread of tie orders around the reference's value
     assert abs(got - float(g["val_dcg_IPS"])) < 0.05 * float(g["val_dcg_IPS"])
-
-
-def _order_dependent_users(frame, scores, pscores, k):
-    """Users (with a positive label) for whom a score tie between rows of different label or
-    propensity reaches into the first k ranks."""
-    flags = []
-    for rows in cpu_ref._per_user_slices(frame["user"]):
-        if np.sum(frame["label"][rows]) == 0:
-            flags.append(False)
-            continue
-        rank = np.argsort(scores[rows], kind="stable")[::-1]
-        sc, ys, ps = scores[rows][rank], frame["label"][rows][rank], pscores[rows][rank]
-        top = sc[: min(k, len(sc))]
-        flag = bool(np.isnan(sc).any())
-        for v in np.unique(top[~np.isnan(top)]):
-            m = sc == v
-            flag = flag or len(set(zip(ys[m].tolist(), ps[m].tolist()))) > 1
-        flags.append(flag)
-    return np.array(flags)
 
 
 @pytest.mark.parametrize("k", [1, 5, 9])
