@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("RFM_LIB_PATH") or os.path.join(PKG_DIR, "librfm_hip.s
 SOURCES = ["rfm_capi.hip", "rfm_fm.hip", "rfm_fm_plan.hip", "rfm_mf.hip", "rfm_fm_fold.hip", "rfm_fold_group.hip", "rfm_eval.hip", "rfm_csr.hip", "rfm_sample.hip", "rfm_pairs.hip", "rfm_host.cpp", "rfm_comm.cpp"]
 # every header under csrc/ (a change of any of them rebuilds every object) + the C ABI
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp"))) + [
-    os.path.join(os.path.dirname(PKG_DIR), "include", h) for h in ("rfm_hip.h", "rfm_neighbours.h")]
+    os.path.join(os.path.dirname(PKG_DIR), "include", h) for h in ("rfm_hip.h", "rfm_neighbours.h", "rfm_audience.h")]
 
 RFM_OK, RFM_ERR_BAD_ARG, RFM_ERR_HIP, RFM_ERR_NO_DEVICE, RFM_ERR_INTERNAL = range(5)
 MF_MAX_MODELS = 1024  # RFM_MF_MAX_MODELS
@@ -266,6 +266,14 @@ NEIGHBOUR_SIGNATURES = {
     "rfm_rows_normalise": [_vp, _vp, _i64, _i32, _i64, _vp, _vp],
 }
 
+# the item -> users direction, the part that include/rfm_audience.h declares: each entry takes its forward
+# twin's arguments (rfm_pair_topk_by_item: `raw` after k)
+AUDIENCE_SIGNATURES = {
+    "rfm_pair_topk_by_item": _PAIR + [_vp, _vp, _i32, _i32, _vp, _vp, _vp],
+    "rfm_pair_ranks_by_item": SIGNATURES["rfm_pair_ranks_n"],
+    "rfm_pair_order_by_item": SIGNATURES["rfm_pair_order"],
+}
+
 
 def exported_symbols() -> List[str]:
     return list(SIGNATURES)
@@ -297,7 +305,7 @@ def load():
         lib = C.CDLL(path)
     except OSError as exc:
         raise RfmError(f"cannot load {path}: {exc}") from exc
-    for name, argtypes in {**SIGNATURES, **NEIGHBOUR_SIGNATURES}.items():
+    for name, argtypes in {**SIGNATURES, **NEIGHBOUR_SIGNATURES, **AUDIENCE_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError = header/library mismatch
         fn.argtypes = argtypes
         fn.restype = _i32

@@ -25,6 +25,10 @@
 // Nearest neighbours in factor space are the top-K launches on one table against
 // itself (or against a table of queries) with the value left as it is: a kernel that divides every
 // row by its norm in a fixed order, and a merge instantiation whose last store skips the sigmoid.
+//
+// The item -> users direction is a second compile-time form of the tile: its rows
+// are items, its columns users, and the epilogue still adds the user's side term first, so that a
+// pair's logit has the same bytes in both directions.
 #include <cmath>
 #include <cstdlib>
 
@@ -55,6 +59,8 @@ constexpr int kRankAccum = 4096;
 
 // epilogue of the pair tile
 enum PairMode { kScores = 0, kTopK = 1, kTargetLogits = 2, kRankCount = 3, kLogits = 4 };
+// what the tile's rows (the queries) and columns (the candidates) are
+enum PairForm { kByUser = 0, kByItem = 1 };
 
 using f64x4 = __attribute__((__vector_size__(4 * sizeof(double)))) double;
 
@@ -263,7 +269,14 @@ struct PairArgs {
 // its 64 users in LDS lists, written to the workspace at the end.  kTargetLogits stores the logit
 // of every target of its users that lies in the tile.  kRankCount turns excluded items into NaN
 // and adds, per target of a user, the number of the tile's logits that are better than it.
-template <int MODE>
+// FORM kByItem: the host has exchanged the two tables (tile_sides), so "user"
+// below reads "query item" and "item" reads "candidate user": A, LU, user_ids, n_users, the
+// exclusion lists and the targets are by item, B, LI, n_items the users.  The one difference is the
+// order of the two side terms in the epilogue, which stays user first.  The dot product needs no
+// change: every product a * b commutes and the factors are taken in the same order, so the
+// accumulator of (item i, user u) is that of (u, i) in the forward form (test_gpu_audience.py holds
+// the two to the same bytes; the argument alone is not relied on).
+template <int MODE, int FORM = kByUser>
 __global__ __launch_bounds__(kPairBlock) void pair_tile_kernel(PairArgs a) {
   constexpr bool TOPK = MODE == kTopK;
   constexpr bool WALK = MODE != kScores && MODE != kLogits;  // item splits, logits through T
@@ -368,7 +381,10 @@ __global__ __launch_bounds__(kPairBlock) void pair_tile_kernel(PairArgs a) {
           const int il = wn * 32 + y * 16 + (lane & 15);
           const int64_t item = i0 + il;
           const bool in = s < a.n_sel && item < a.n_items;
-          const double logit = in ? ((c + lu) + a.LI[item]) + acc[x][y][reg] : NAN;
+          // ((c + LU[user]) + LI[item]) + acc in either form: by item the row's term is the item's
+          const double logit = !in ? NAN
+                               : FORM == kByItem ? ((c + a.LI[item]) + lu) + acc[x][y][reg]
+                                                 : ((c + lu) + a.LI[item]) + acc[x][y][reg];
           if (WALK) {
             T[ul * kLogitLd + il] = logit;
           } else if (in) {
@@ -808,6 +824,19 @@ PairArgs pair_args(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t 
   return a;
 }
 
+// The one place where the by-item entries differ from their twins on the host: the item table
+// becomes the tile's rows and the user table its columns.  Everything after it -- the checks of
+// pair_args, the splits, the workspaces, the launches -- is the twin's code for the exchanged counts.
+template <int FORM>
+inline void tile_sides(const double*& d_A, const double*& d_LU, int64_t& n_users, const double*& d_B,
+                       const double*& d_LI, int64_t& n_items) {
+  if (FORM == kByItem) {
+    std::swap(d_A, d_B);
+    std::swap(d_LU, d_LI);
+    std::swap(n_users, n_items);
+  }
+}
+
 // flags of a checked call (RFM_CHECK_IDS=1): read back after a synchronisation
 struct IdCheck {
   DevBuf buf;
@@ -851,16 +880,18 @@ struct IdCheck {
   }
 };
 
-LdsLimits g_topk_lds;
+template <int FORM>
+LdsLimits g_topk_lds;  // (per kernel function)
 LdsLimits g_order_lds;
 
 // rfm_pair_topk / rfm_pair_topk_raw: the same launches; RAW is the merge's last store alone
-template <bool RAW>
+template <bool RAW, int FORM = kByUser>
 void pair_topk_run(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t n_users, const int32_t* d_user_ids,
                    int64_t n_sel_users, const double* d_B, const double* d_LI, int64_t n_items, int32_t n_factors,
                    const double* d_c, const int64_t* d_excl_indptr, const int32_t* d_excl_items, int32_t k,
                    void* d_workspace, int32_t* d_out_items, double* d_out_scores) {
   RFM_REQUIRE(k >= 1 && k <= kMaxTopK, "k=%d outside 1..%d", k, kMaxTopK);
+  tile_sides<FORM>(d_A, d_LU, n_users, d_B, d_LI, n_items);
   PairArgs a = pair_args(ctx, d_A, d_LU, n_users, d_user_ids, n_sel_users, d_B, d_LI, n_items, n_factors, d_c,
                          d_excl_indptr, d_excl_items);
   if (n_sel_users == 0) return;
@@ -873,9 +904,9 @@ void pair_topk_run(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t 
   a.ws_logit = static_cast<double*>(d_workspace);
   a.ws_item = reinterpret_cast<int32_t*>(a.ws_logit + int64_t(sp.n_splits) * n_sel_users * k);
   const size_t lds = topk_lds_bytes(k);
-  allow_dynamic_lds(ctx, reinterpret_cast<const void*>(&pair_tile_kernel<kTopK>), lds, g_topk_lds);
+  allow_dynamic_lds(ctx, reinterpret_cast<const void*>(&pair_tile_kernel<kTopK, FORM>), lds, g_topk_lds<FORM>);
   const dim3 grid((unsigned)sp.n_splits, (unsigned)((n_sel_users + kTile - 1) / kTile));
-  hipLaunchKernelGGL(pair_tile_kernel<kTopK>, grid, dim3(kPairBlock), lds, ctx->stream, a);
+  hipLaunchKernelGGL((pair_tile_kernel<kTopK, FORM>), grid, dim3(kPairBlock), lds, ctx->stream, a);
   RFM_HIP_CHECK(hipGetLastError());
   const int64_t mgrid = (n_sel_users + kPairBlock / 64 - 1) / (kPairBlock / 64);
   hipLaunchKernelGGL(topk_merge_kernel<RAW>, dim3((unsigned)mgrid), dim3(kPairBlock), 0, ctx->stream,
@@ -886,12 +917,14 @@ void pair_topk_run(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t 
 
 // rfm_pair_ranks / rfm_pair_ranks_n: `h_n_targets` null = the number of targets is read back from
 // the end of the device indptr (which synchronises); everything after that is the same code
+template <int FORM = kByUser>
 void pair_ranks_run(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t n_users,
                     const int32_t* d_user_ids, int64_t n_sel_users, const double* d_B, const double* d_LI,
                     int64_t n_items, int32_t n_factors, const double* d_c, const int64_t* d_excl_indptr,
                     const int32_t* d_excl_items, const int64_t* d_tgt_indptr, const int32_t* d_tgt_items,
                     const int64_t* h_n_targets, void* d_workspace, int32_t* d_out_ranks, double* d_out_scores,
                     int32_t* d_out_candidates) {
+  tile_sides<FORM>(d_A, d_LU, n_users, d_B, d_LI, n_items);
   PairArgs a = pair_args(ctx, d_A, d_LU, n_users, d_user_ids, n_sel_users, d_B, d_LI, n_items, n_factors, d_c,
                          d_excl_indptr, d_excl_items);
   if (n_sel_users == 0) return;
@@ -924,16 +957,70 @@ void pair_ranks_run(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t
     RFM_HIP_CHECK(hipMemsetAsync(d_workspace, 0xFF, size_t(n_targets) * 8, ctx->stream));
     RFM_HIP_CHECK(hipMemsetAsync(d_out_ranks, 0, size_t(n_targets) * 4, ctx->stream));
     const size_t lds1 = rank_lds_bytes(false);  // (both passes stay under the 64 KiB a launch may ask for as it is)
-    hipLaunchKernelGGL(pair_tile_kernel<kTargetLogits>, grid, dim3(kPairBlock), lds1, ctx->stream, a);
+    hipLaunchKernelGGL((pair_tile_kernel<kTargetLogits, FORM>), grid, dim3(kPairBlock), lds1, ctx->stream, a);
     RFM_HIP_CHECK(hipGetLastError());
   }
   const size_t lds2 = rank_lds_bytes(true);
-  hipLaunchKernelGGL(pair_tile_kernel<kRankCount>, grid, dim3(kPairBlock), lds2, ctx->stream, a);
+  hipLaunchKernelGGL((pair_tile_kernel<kRankCount, FORM>), grid, dim3(kPairBlock), lds2, ctx->stream, a);
   RFM_HIP_CHECK(hipGetLastError());
   if (n_targets > 0) {
     hipLaunchKernelGGL(rank_finish_kernel, dim3(capped_grid(ctx, n_targets, kPairBlock, 16, 1)),
                        dim3(kPairBlock), 0, ctx->stream, a.tgt_logit, n_targets, d_out_ranks, d_out_scores);
     RFM_HIP_CHECK(hipGetLastError());
+  }
+  chk.finish();
+}
+
+// rfm_pair_order / rfm_pair_order_by_item: blocks of users (by item: of items), per block the raw
+// logits of the block and the ranking kernel's pages over them
+template <int FORM = kByUser>
+void pair_order_run(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t n_users,
+                    const int32_t* d_user_ids, int64_t n_sel_users, const double* d_B,
+                    const double* d_LI, int64_t n_items, int32_t n_factors, const double* d_c,
+                    const int64_t* d_excl_indptr, const int32_t* d_excl_items, int64_t depth,
+                    void* d_workspace, int64_t workspace_bytes, int32_t* d_out_items,
+                    double* d_out_scores, int32_t* d_out_n_ranked) {
+  RFM_REQUIRE(depth >= 1, "depth=%lld: the ranking depth must be at least 1", (long long)depth);
+  tile_sides<FORM>(d_A, d_LU, n_users, d_B, d_LI, n_items);
+  PairArgs all = pair_args(ctx, d_A, d_LU, n_users, d_user_ids, n_sel_users, d_B, d_LI, n_items, n_factors, d_c,
+                           d_excl_indptr, d_excl_items);
+  if (n_sel_users == 0) return;
+  RFM_REQUIRE(d_workspace && d_out_items && d_out_scores && d_out_n_ranked, "null workspace or output");
+  const int64_t block_rows = workspace_bytes / order_row_bytes(n_items) / kTile * kTile;
+  RFM_REQUIRE(block_rows >= kTile, "workspace_bytes=%lld is less than one block of %d users (%lld bytes)",
+              (long long)workspace_bytes, kTile, (long long)(kTile * order_row_bytes(n_items)));
+  RFM_HIP_CHECK(hipSetDevice(ctx->device));
+  IdCheck chk(ctx);
+  chk.begin(all);
+  // ranks beyond the catalogue are padding whatever the logits: they take no page of their own
+  const int64_t n_ranks = std::min(depth, n_items);
+  const int P = order_list_len(n_ranks);
+  const size_t lds = size_t(P) * 2 * 12;
+  allow_dynamic_lds(ctx, reinterpret_cast<const void*>(&order_rows_kernel), lds, g_order_lds);
+  double* ws_logits = static_cast<double*>(d_workspace);
+  double* ws_cut_l = ws_logits + block_rows * n_items;
+  int32_t* ws_cut_i = reinterpret_cast<int32_t*>(ws_cut_l + block_rows);
+  for (int64_t first = 0; first < n_sel_users; first += block_rows) {
+    const int64_t rows = std::min(block_rows, n_sel_users - first);
+    PairArgs a = all;  // this block of the selected users
+    a.user_ids = d_user_ids ? d_user_ids + first : nullptr, a.n_sel = rows, a.sel_first = first;
+    a.out = ws_logits;
+    const dim3 grid((unsigned)((n_items + kTile - 1) / kTile), (unsigned)((rows + kTile - 1) / kTile));
+    hipLaunchKernelGGL((pair_tile_kernel<kLogits, FORM>), grid, dim3(kPairBlock), size_t(kOperandDoubles) * 8,
+                       ctx->stream, a);
+    RFM_HIP_CHECK(hipGetLastError());
+    OrderArgs o{};
+    o.logits = ws_logits, o.n_items = n_items, o.user_ids = a.user_ids, o.sel_first = first, o.n_users = n_users;
+    o.excl_indptr = d_excl_indptr, o.excl_items = d_excl_items, o.P = P, o.depth = depth;
+    o.cut_l = ws_cut_l, o.cut_i = ws_cut_i;
+    o.out_items = d_out_items + first * depth, o.out_scores = d_out_scores + first * depth;
+    o.out_n_ranked = d_out_n_ranked + first;
+    for (int64_t col0 = 0; col0 < n_ranks; col0 += P) {  // (more than one page only with P = kOrderMaxP)
+      o.first_page = col0 == 0, o.col0 = col0, o.n_cols = std::min<int64_t>(P, n_ranks - col0);
+      o.fill_to = col0 + o.n_cols < n_ranks ? col0 + o.n_cols : depth;
+      hipLaunchKernelGGL(order_rows_kernel, dim3((unsigned)rows), dim3(kPairBlock), lds, ctx->stream, o);
+      RFM_HIP_CHECK(hipGetLastError());
+    }
   }
   chk.finish();
 }
@@ -1326,48 +1413,48 @@ int32_t rfm_pair_order(rfm_ctx* ctx, const double* d_A, const double* d_LU, int6
                        void* d_workspace, int64_t workspace_bytes, int32_t* d_out_items,
                        double* d_out_scores, int32_t* d_out_n_ranked) {
   return guarded([&] {
-    RFM_REQUIRE(depth >= 1, "depth=%lld: the ranking depth must be at least 1", (long long)depth);
-    PairArgs all = pair_args(ctx, d_A, d_LU, n_users, d_user_ids, n_sel_users, d_B, d_LI, n_items, n_factors, d_c,
-                             d_excl_indptr, d_excl_items);
-    if (n_sel_users == 0) return;
-    RFM_REQUIRE(d_workspace && d_out_items && d_out_scores && d_out_n_ranked, "null workspace or output");
-    const int64_t block_rows = workspace_bytes / order_row_bytes(n_items) / kTile * kTile;
-    RFM_REQUIRE(block_rows >= kTile, "workspace_bytes=%lld is less than one block of %d users (%lld bytes)",
-                (long long)workspace_bytes, kTile, (long long)(kTile * order_row_bytes(n_items)));
-    RFM_HIP_CHECK(hipSetDevice(ctx->device));
-    IdCheck chk(ctx);
-    chk.begin(all);
-    // ranks beyond the catalogue are padding whatever the logits: they take no page of their own
-    const int64_t n_ranks = std::min(depth, n_items);
-    const int P = order_list_len(n_ranks);
-    const size_t lds = size_t(P) * 2 * 12;
-    allow_dynamic_lds(ctx, reinterpret_cast<const void*>(&order_rows_kernel), lds, g_order_lds);
-    double* ws_logits = static_cast<double*>(d_workspace);
-    double* ws_cut_l = ws_logits + block_rows * n_items;
-    int32_t* ws_cut_i = reinterpret_cast<int32_t*>(ws_cut_l + block_rows);
-    for (int64_t first = 0; first < n_sel_users; first += block_rows) {
-      const int64_t rows = std::min(block_rows, n_sel_users - first);
-      PairArgs a = all;  // this block of the selected users
-      a.user_ids = d_user_ids ? d_user_ids + first : nullptr, a.n_sel = rows, a.sel_first = first;
-      a.out = ws_logits;
-      const dim3 grid((unsigned)((n_items + kTile - 1) / kTile), (unsigned)((rows + kTile - 1) / kTile));
-      hipLaunchKernelGGL(pair_tile_kernel<kLogits>, grid, dim3(kPairBlock), size_t(kOperandDoubles) * 8,
-                         ctx->stream, a);
-      RFM_HIP_CHECK(hipGetLastError());
-      OrderArgs o{};
-      o.logits = ws_logits, o.n_items = n_items, o.user_ids = a.user_ids, o.sel_first = first, o.n_users = n_users;
-      o.excl_indptr = d_excl_indptr, o.excl_items = d_excl_items, o.P = P, o.depth = depth;
-      o.cut_l = ws_cut_l, o.cut_i = ws_cut_i;
-      o.out_items = d_out_items + first * depth, o.out_scores = d_out_scores + first * depth;
-      o.out_n_ranked = d_out_n_ranked + first;
-      for (int64_t col0 = 0; col0 < n_ranks; col0 += P) {  // (more than one page only with P = kOrderMaxP)
-        o.first_page = col0 == 0, o.col0 = col0, o.n_cols = std::min<int64_t>(P, n_ranks - col0);
-        o.fill_to = col0 + o.n_cols < n_ranks ? col0 + o.n_cols : depth;
-        hipLaunchKernelGGL(order_rows_kernel, dim3((unsigned)rows), dim3(kPairBlock), lds, ctx->stream, o);
-        RFM_HIP_CHECK(hipGetLastError());
-      }
-    }
-    chk.finish();
+    pair_order_run(ctx, d_A, d_LU, n_users, d_user_ids, n_sel_users, d_B, d_LI, n_items, n_factors, d_c, d_excl_indptr,
+                   d_excl_items, depth, d_workspace, workspace_bytes, d_out_items, d_out_scores, d_out_n_ranked);
+  });
+}
+
+// The item -> users direction (include/rfm_audience.h): the twins' run functions in the by-item form.
+int32_t rfm_pair_topk_by_item(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t n_users,
+                              const int32_t* d_item_ids, int64_t n_sel_items, const double* d_B,
+                              const double* d_LI, int64_t n_items, int32_t n_factors, const double* d_c,
+                              const int64_t* d_excl_indptr, const int32_t* d_excl_users, int32_t k, int32_t raw,
+                              void* d_workspace, int32_t* d_out_users, double* d_out_values) {
+  return guarded([&] {
+    const auto run = raw ? pair_topk_run<true, kByItem> : pair_topk_run<false, kByItem>;
+    run(ctx, d_A, d_LU, n_users, d_item_ids, n_sel_items, d_B, d_LI, n_items, n_factors, d_c, d_excl_indptr,
+        d_excl_users, k, d_workspace, d_out_users, d_out_values);
+  });
+}
+
+int32_t rfm_pair_ranks_by_item(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t n_users,
+                               const int32_t* d_item_ids, int64_t n_sel_items, const double* d_B,
+                               const double* d_LI, int64_t n_items, int32_t n_factors, const double* d_c,
+                               const int64_t* d_excl_indptr, const int32_t* d_excl_users,
+                               const int64_t* d_tgt_indptr, const int32_t* d_tgt_users, int64_t n_targets,
+                               void* d_workspace, int32_t* d_out_ranks, double* d_out_scores,
+                               int32_t* d_out_candidates) {
+  return guarded([&] {
+    pair_ranks_run<kByItem>(ctx, d_A, d_LU, n_users, d_item_ids, n_sel_items, d_B, d_LI, n_items, n_factors, d_c,
+                            d_excl_indptr, d_excl_users, d_tgt_indptr, d_tgt_users, &n_targets, d_workspace,
+                            d_out_ranks, d_out_scores, d_out_candidates);
+  });
+}
+
+int32_t rfm_pair_order_by_item(rfm_ctx* ctx, const double* d_A, const double* d_LU, int64_t n_users,
+                               const int32_t* d_item_ids, int64_t n_sel_items, const double* d_B,
+                               const double* d_LI, int64_t n_items, int32_t n_factors, const double* d_c,
+                               const int64_t* d_excl_indptr, const int32_t* d_excl_users, int64_t depth,
+                               void* d_workspace, int64_t workspace_bytes, int32_t* d_out_users,
+                               double* d_out_scores, int32_t* d_out_n_ranked) {
+  return guarded([&] {
+    pair_order_run<kByItem>(ctx, d_A, d_LU, n_users, d_item_ids, n_sel_items, d_B, d_LI, n_items, n_factors, d_c,
+                            d_excl_indptr, d_excl_users, depth, d_workspace, workspace_bytes, d_out_users,
+                            d_out_scores, d_out_n_ranked);
   });
 }
 

@@ -235,7 +235,9 @@ class FoldedColumns:
     """The id columns of new rows of one side of a trained FM model (``fold_in_users`` /
     ``fold_in_items``): device tensors ``w [n_new]`` and ``V [n_new, k]`` (the new
     columns' weights and factor rows) and the served operands of the grown rows, ``A [n_new, kpad]``
-    and ``L [n_new]`` (``recommend.Operands``); ``side`` "user" or "item"."""
+    and ``L [n_new]`` (``recommend.Operands``); ``side`` "user" or "item".  ``features``: the rows' own
+    feature entries, the canonical host CSR ``[n_new, n_features]`` they were folded with
+    (``recommend.grown_side_sums`` serves folded items from it)."""
 
     side: str
     w: object
@@ -243,6 +245,7 @@ class FoldedColumns:
     A: object
     L: object
     rt: Runtime
+    features: object = None
 
     def __len__(self) -> int:
         return int(self.w.shape[0])
@@ -465,7 +468,7 @@ class FactorizationMachines(PointwiseBaseRecommender):
                 rt.ctx, *(d.data_ptr() for d in dev), n_new, g.data_ptr(), l.data_ptr(), F.data_ptr(), fL.data_ptr(),
                 n_fixed, self.w0.dev.data_ptr(), kf, lr, int(n_passes), w_new.data_ptr(), V_new.data_ptr(),
                 A_new.data_ptr(), L_new.data_ptr()))
-        return FoldedColumns(("user", "item")[side], w_new, V_new, A_new, L_new, rt)
+        return FoldedColumns(("user", "item")[side], w_new, V_new, A_new, L_new, rt, X)
 
     def fold_in_users(self, sides, new_rows, data: dict, n_passes: int, init=None, lr=None, ops=None, group=None,
                       check=True) -> FoldedColumns:
@@ -548,6 +551,37 @@ class FactorizationMachines(PointwiseBaseRecommender):
         from . import recommend as rec
 
         return rec.rank_catalogue(*rec.operands(self, sides, new_users=new_users), depth, users, exclude)
+
+    # the item -> users direction.  new_items: the FoldedColumns of fold_in_items
+    # stand in for the item side -- ``items`` and the item axis of ``exclude`` then index the folded
+    # rows; new_users as above; the model is not touched.  ``exclude`` is recommend()'s, by user id
+    def recommend_users(self, sides, k: int, items=None, exclude=None, new_items=None, new_users=None):
+        """The ``k`` (1..64) best users of ``sides`` per item: ``(users int32 [n, k], scores float64
+        [n, k])``, ranked by logit (ties: higher user index first), scores as ``predict()`` gives
+        them -- the score of (item i, user u) has the bytes ``recommend()`` gives (u, i); short
+        lists are padded with user -1 / score NaN."""
+        from . import recommend as rec
+
+        return rec.topk_users(*rec.operands(self, sides, new_users=new_users, new_items=new_items), k, items, exclude)
+
+    def rank_users(self, sides, items, users, exclude=None, new_items=None, new_users=None):
+        """Where user ``users[n]`` stands among all users of ``sides`` in item ``items[n]``'s ranking:
+        ``(ranks int32 [n], scores float64 [n], candidates int32 [n])`` in input order, ranks
+        0-based under ``recommend_users()``'s order, at any depth (recommend.py)."""
+        from . import recommend as rec
+
+        return rec.rank_users(*rec.operands(self, sides, new_users=new_users, new_items=new_items), items, users,
+                              exclude)
+
+    def rank_audience(self, sides, depth: int, items=None, exclude=None, new_items=None, new_users=None,
+                      workspace_bytes=None):
+        """Every item's ranking of the users of ``sides`` down to ``depth`` (any integer >= 1):
+        ``(users int32 [n, depth], scores float64 [n, depth], n_ranked int32 [n])`` under
+        ``recommend_users()``'s order, short rows padded with user -1 / score NaN (recommend.py)."""
+        from . import recommend as rec
+
+        return rec.rank_audience(*rec.operands(self, sides, new_users=new_users, new_items=new_items), depth, items,
+                                 exclude, workspace_bytes)
 
     # new_items / new_users: the FoldedColumns of the matching fold_in_* are the queries (their served
     # operand A) against the catalogue's own rows -- ``items`` / ``users`` then index the folded rows

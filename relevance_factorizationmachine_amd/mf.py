@@ -458,6 +458,36 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
 
         return rec.rank_catalogue(*rec.operands(self, new_users=new_users), depth, users, exclude)
 
+    # the item -> users direction.  new_items: the FoldedRows of fold_in_items stand
+    # in for Q, b_i -- ``items`` and the item axis of ``exclude`` then index the folded rows; new_users
+    # as above; the model is not touched.  ``exclude`` is the matrix recommend() takes, by user id
+    def recommend_users(self, k: int, items=None, exclude=None, new_items=None, new_users=None):
+        """The ``k`` (1..64) best users per item: ``(users int32 [n, k], scores float64 [n, k])``,
+        ranked by logit (ties: higher user index first), scores ``sigmoid(logit)`` as ``predict()``
+        gives them -- the score of (item i, user u) has the bytes ``recommend()`` gives (u, i);
+        short lists are padded with user -1 / score NaN."""
+        from . import recommend as rec
+
+        return rec.topk_users(*rec.operands(self, new_users=new_users, new_items=new_items), k, items, exclude)
+
+    def rank_users(self, items, users, exclude=None, new_items=None, new_users=None):
+        """Where user ``users[n]`` stands among all users in item ``items[n]``'s ranking:
+        ``(ranks int32 [n], scores float64 [n], candidates int32 [n])`` in input order, ranks
+        0-based under ``recommend_users()``'s order, at any depth (recommend.py)."""
+        from . import recommend as rec
+
+        return rec.rank_users(*rec.operands(self, new_users=new_users, new_items=new_items), items, users, exclude)
+
+    def rank_audience(self, depth: int, items=None, exclude=None, new_items=None, new_users=None,
+                      workspace_bytes=None):
+        """Every item's ranking of all users down to ``depth`` (any integer >= 1): ``(users int32
+        [n, depth], scores float64 [n, depth], n_ranked int32 [n])`` under ``recommend_users()``'s
+        order, short rows padded with user -1 / score NaN (recommend.py)."""
+        from . import recommend as rec
+
+        return rec.rank_audience(*rec.operands(self, new_users=new_users, new_items=new_items), depth, items, exclude,
+                                 workspace_bytes)
+
     # new_items / new_users: the FoldedRows of the matching fold_in_* are the queries against the
     # model's own rows -- ``items`` / ``users`` then index the folded rows, which have no self
     def similar_items(self, k: int, items=None, metric="cosine", exclude=None, include_self=False, new_items=None):

@@ -20,6 +20,9 @@ given (user, item) pairs in the user's ranking of the whole catalogue, at any de
 0 .. depth-1, up to the user's full ordering of the catalogue.
 ``neighbours`` asks the tables themselves: the rows of ``B`` (or of ``A``) nearest to
 each other by cosine or dot product, under the same order, with the value itself returned.
+``topk_users`` / ``rank_users`` / ``rank_audience`` are ``topk`` / ``rank_items`` /
+``rank_catalogue`` for "this item, which users?": the same pair has the same logit, bit for bit, in
+both directions, ties go to the higher USER index, and ``exclude`` stays the matrix by user id.
 """
 from __future__ import annotations
 
@@ -165,7 +168,50 @@ def catalogue_shape(model, sides=None) -> Tuple[int, int]:
     return int(model.n_users), int(model.n_items)
 
 
-def operands(model, sides=None, into: Optional[Operands] = None, new_users=None) -> Operands:
+def grown_side_sums(rt: Runtime, model, folded, S=None, L=None):
+    """``(sums [n_new, kpad], L [n_new])`` of the GROWN rows of an FM model's ``FoldedColumns`` -- each new
+    row's feature entries and then its own id column with entry 1 -- from the side-sum kernel itself:
+    the bits that ``append_columns`` and a ``Sides`` of the grown width (id columns last) give the same
+    rows.  ``folded.A`` holds the same sums, but ``folded.L`` is ``l + omega + g . nu`` as the fold
+    launch forms it, which rounds otherwise than the kernel's ``(lin + omega) + cross / 2``.  Only the
+    columns the rows store are gathered (w, V rows of the model, then the folded ones): the kernel
+    reads nothing else, and a column's number plays no part in the sums."""
+    torch = __import__("torch")
+    import scipy.sparse as sp
+
+    X = folded.features
+    n_new, kf = int(X.shape[0]), int(model.n_factors)
+    cols = np.unique(X.indices)
+    local = sp.csr_matrix((X.data, np.searchsorted(cols, X.indices), X.indptr), shape=(n_new, cols.size))
+    G = sp.hstack([local, sp.identity(n_new, format="csr")]).tocsr()  # (canonical: the id column comes last)
+    at = rt.upload(cols.astype(np.int64)) if cols.size else torch.zeros((0,), dtype=torch.int64, device=rt.torch_device)
+    w = torch.cat([model.w.dev.index_select(0, at), folded.w])
+    V = torch.cat([model.V.dev.index_select(0, at), folded.V])
+    return side_sums(rt, DeviceCSR(rt, G), w, V, int(G.shape[1]), kf, S, L)
+
+
+def _fm_side(rt: Runtime, model, X: DeviceCSR, folded, S, L, grown=False):
+    """One side's ``(sums, L)`` of an FM model: a side-sum launch over ``X``, or the served operands of
+    ``folded`` (``grown``: ``grown_side_sums`` of it, where it carries its rows' feature entries); into
+    ``S, L`` (buffers of an earlier result) if given."""
+    if folded is None:
+        return side_sums(rt, X, model.w.dev, model.V.dev, model.n_features, int(model.n_factors), S, L)
+    if grown and getattr(folded, "features", None) is not None and len(folded):
+        if S is not None and (tuple(S.shape) != tuple(folded.A.shape) or tuple(L.shape) != tuple(folded.L.shape)):
+            raise ValueError(f"folded operands of {tuple(folded.A.shape)} into a buffer of {tuple(S.shape)}")
+        return grown_side_sums(rt, model, folded, S, L)
+    if S is None:
+        return folded.A, folded.L
+    # refreshed in place, as every other buffer of `into`
+    if tuple(S.shape) != tuple(folded.A.shape) or tuple(L.shape) != tuple(folded.L.shape):
+        raise ValueError(f"folded operands of {tuple(folded.A.shape)} into a buffer of {tuple(S.shape)}")
+    if S.data_ptr() != folded.A.data_ptr():
+        S.copy_(folded.A)
+        L.copy_(folded.L)
+    return S, L
+
+
+def operands(model, sides=None, into: Optional[Operands] = None, new_users=None, new_items=None) -> Operands:
     """The ``Operands`` of a model as it stands.  FM (``sides``: its ``Sides``): two side-sum
     launches per call.  MF: ``P, b_u, Q, b_i``, the uploaded ``b``, zero-padded copies of P, Q when
     ``n_factors % 4``.  ``into``: an earlier result for the same shapes, whose buffers are refreshed
@@ -176,40 +222,25 @@ def operands(model, sides=None, into: Optional[Operands] = None, new_users=None)
     N13): the operands' users are then the folded rows, and the model is not touched.  ``new_users``
     (FM): the ``FoldedColumns`` of ``fold_in_users``, whose served operands ``A, L`` stand in for the
     user side sums -- one side-sum launch, for the items; with ``into`` they are
-    copied into its user buffers.  Folded items, and the folded rows of the other model class, are
-    a ``TypeError``."""
+    copied into its user buffers.  ``new_items``: the same for the item side, under
+    the same checks and ``into`` rules -- the ``FoldedRows`` of ``fold_in_items`` stand in for ``Q,
+    b_i``, the ``FoldedColumns`` of an FM model's ``fold_in_items`` for the item side sums; the two
+    may be given together.  The FM item side is served as the rows will be once they are appended:
+    one side-sum launch over the grown rows (``grown_side_sums``), so that ``new_items=`` and
+    ``append_columns`` with a ``Sides`` of the grown width give the same bytes; ``FoldedColumns``
+    built without their rows' feature entries are served through ``A, L``.  Folded rows of the other
+    side, and those of the other model class, are a ``TypeError`` (``folded_queries``)."""
     is_fm = hasattr(model, "n_features")
-    if new_users is not None:
-        if is_fm:
-            # (FoldedColumns carry the served operands A, L; the FoldedRows of an MF model do not)
-            if getattr(new_users, "side", None) != "user" or not hasattr(new_users, "A"):
-                raise TypeError("new_users of an FM model takes the FoldedColumns of its fold_in_users; rows "
-                                "that are served from their features alone go into its recommend.Sides")
-            if tuple(new_users.A.shape[1:]) != (pad4(model.n_factors),):
-                raise ValueError(f"folded operands of {tuple(new_users.A.shape)} for a model of "
-                                 f"{int(model.n_factors)} factors")
-        else:
-            if getattr(new_users, "side", None) != "user" or not hasattr(new_users, "rows"):
-                raise TypeError("new_users takes the FoldedRows of fold_in_users")
-            if tuple(new_users.rows.shape[1:]) != (int(model.n_factors),):
-                raise ValueError(f"folded rows of {tuple(new_users.rows.shape)} for a model of "
-                                 f"{int(model.n_factors)} factors")
+    for side, folded in (("user", new_users), ("item", new_items)):
+        if folded is not None:
+            folded_queries(model, side, folded)
     catalogue_shape(model, sides)
     rt, kf = model._rt, int(model.n_factors)
     _, A, LU, B, LI, c, _ = into or (None,) * 7
     if is_fm:
         XU, XI = sides.device(rt)
-        if new_users is None:
-            A, LU = side_sums(rt, XU, model.w.dev, model.V.dev, model.n_features, kf, A, LU)
-        elif A is None:
-            A, LU = new_users.A, new_users.L
-        else:  # refreshed in place, as every other buffer of `into`
-            if tuple(A.shape) != tuple(new_users.A.shape) or tuple(LU.shape) != tuple(new_users.L.shape):
-                raise ValueError(f"folded operands of {tuple(new_users.A.shape)} into a buffer of {tuple(A.shape)}")
-            if A.data_ptr() != new_users.A.data_ptr():
-                A.copy_(new_users.A)
-                LU.copy_(new_users.L)
-        B, LI = side_sums(rt, XI, model.w.dev, model.V.dev, model.n_features, kf, B, LI)
+        A, LU = _fm_side(rt, model, XU, new_users, A, LU)
+        B, LI = _fm_side(rt, model, XI, new_items, B, LI, grown=True)
         return Operands(rt, A, LU, B, LI, model.w0.dev, kf)
     b = float(model.b)
     if c is None:
@@ -218,8 +249,8 @@ def operands(model, sides=None, into: Optional[Operands] = None, new_users=None)
         c.fill_(b)
     c.holds = b
     user_rows, user_bias = (model.P.dev, model.b_u.dev) if new_users is None else (new_users.rows, new_users.bias)
-    return Operands(rt, padded(rt, user_rows, kf, A), user_bias, padded(rt, model.Q.dev, kf, B),
-                    model.b_i.dev, c, kf)
+    item_rows, item_bias = (model.Q.dev, model.b_i.dev) if new_items is None else (new_items.rows, new_items.bias)
+    return Operands(rt, padded(rt, user_rows, kf, A), user_bias, padded(rt, item_rows, kf, B), item_bias, c, kf)
 
 
 def is_int(v) -> bool:  # an integer argument: a Python or NumPy integer, not a bool
@@ -236,10 +267,11 @@ def _id_array(a, what: str, n: int) -> np.ndarray:
     return a.astype(np.int64)
 
 
-def _users(rt: Runtime, users, n_users: int):
+def _users(rt: Runtime, users, n_users: int, what: str = "users"):
+    """``(device ids or None, n_sel)`` of a selection of query rows (``what``: "users" / "items")."""
     if users is None:
         return None, n_users
-    ids = _id_array(users, "users", n_users).astype(np.int32)
+    ids = _id_array(users, what, n_users).astype(np.int32)
     return rt.upload(ids if ids.size else np.zeros(1, np.int32)), int(ids.shape[0])
 
 
@@ -324,15 +356,16 @@ def users_indptr(users) -> Tuple[np.ndarray, np.ndarray]:
     return sel.astype(np.int32), np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
 
 
-def group_pairs(users, items, n_users: int, n_items: int):
+def group_pairs(users, items, n_users: int, n_items: int, what=("users", "items")):
     """(user, item) pairs in any order, repeats allowed, as ``rfm_pair_ranks`` takes them:
     ``(sel_users int32, tgt_indptr int64, tgt_items int32, order)`` -- the unique users ascending,
     the items of selected user s ascending in ``tgt_items[tgt_indptr[s]:tgt_indptr[s + 1]]``, and
     ``order`` with grouped target t = input pair ``order[t]``.  ``ValueError`` for anything but two
-    equal-length 1-d integer arrays of ids inside their tables."""
-    users, items = _id_array(users, "users", n_users), _id_array(items, "items", n_items)
+    equal-length 1-d integer arrays of ids inside their tables.  ``what``: what the two arrays hold,
+    ``("items", "users")`` for the by-item direction, which groups by item."""
+    users, items = _id_array(users, what[0], n_users), _id_array(items, what[1], n_items)
     if users.shape != items.shape:
-        raise ValueError(f"{users.shape[0]} users for {items.shape[0]} items: the pairs need one of each")
+        raise ValueError(f"{users.shape[0]} {what[0]} for {items.shape[0]} {what[1]}: the pairs need one of each")
     order = np.lexsort((items, users))
     sel, indptr = users_indptr(users)
     return sel, indptr, items[order].astype(np.int32), order
@@ -443,6 +476,114 @@ def rank_catalogue(rt: Runtime, A, LU, B, LI, c, n_factors: int, depth: int, use
                                      workspace_bytes, items.data_ptr(), scores.data_ptr(), n_ranked.data_ptr()))
     rt.sync()
     return items.cpu().numpy(), scores.cpu().numpy(), n_ranked.cpu().numpy()
+
+
+# ---------------------------------------------------------------------------
+# the item -> users direction
+# ---------------------------------------------------------------------------
+def by_item(ops: Operands, entry: str, item_ids, n_sel: int, excl, *tail) -> None:
+    """``rfm_pair_<entry>_by_item`` enqueued on ``ops``: the one place where an ``Operands`` becomes a
+    call of the by-item direction.  The operand arguments are ``pair_args``' as they stand (the ABI
+    exchanges the tables itself and keeps the user's side term first in the sum); ``item_ids``:
+    device item ids, None = every item; ``excl``: device lists BY ITEM (``transposed_exclusions``)."""
+    call = getattr(ops.rt.lib, f"rfm_pair_{entry}_by_item")
+    _lib.check(call(*ops.pair_args(item_ids, n_sel), *excl_args(excl), *tail))
+
+
+def transposed_exclusions(excl, n_items: int):
+    """The checked host lists ``excl`` of ``_host_exclusions`` (by user, items ascending) as the lists
+    by item that the by-item entries take: ``(indptr int64 [n_items + 1], users int32)``, the user
+    ids of an item ascending -- a stable sort by item keeps the users in the order they come in,
+    which is ascending.  None stays None."""
+    if excl is None:
+        return None
+    indptr, items = excl
+    users = np.repeat(np.arange(indptr.shape[0] - 1, dtype=np.int32), np.diff(indptr))
+    t_indptr = np.concatenate(([0], np.cumsum(np.bincount(items, minlength=n_items)))).astype(np.int64)
+    return t_indptr, users[np.argsort(items, kind="stable")]
+
+
+def topk_users(rt: Runtime, A, LU, B, LI, c, n_factors: int, k: int, items=None, exclude=None):
+    """``topk`` in the other direction: ``(users int32 [n_sel, k], scores float64 [n_sel, k])``, the k
+    best users per selected item by logit (ties: higher user index first), scores = sigmoid(logit)
+    with the bytes ``topk`` gives the same pair; fewer than k rankable users pads with user -1 /
+    score NaN.  ``exclude``: what ``topk`` takes, by USER id -- one matrix serves both directions."""
+    torch = __import__("torch")
+    ops = Operands(rt, A, LU, B, LI, c, n_factors)
+    k = int(k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f"k={k} outside 1..{MAX_K}")
+    ids, n_sel = _users(rt, items, ops.n_items, "items")
+    excl = _exclusions(rt, transposed_exclusions(_host_exclusions(exclude, ops.n_users, ops.n_items), ops.n_items))
+    ws = rt.empty((topk_workspace_bytes(n_sel, ops.n_users, k),), torch.uint8)
+    users = rt.empty((n_sel, k), torch.int32)
+    scores = rt.empty((n_sel, k), torch.float64)
+    by_item(ops, "topk", ids, n_sel, excl, k, 0, ws.data_ptr(), users.data_ptr(), scores.data_ptr())
+    rt.sync()
+    return users.cpu().numpy(), scores.cpu().numpy()
+
+
+def rank_users(rt: Runtime, A, LU, B, LI, c, n_factors: int, items, users, exclude=None):
+    """``rank_items`` in the other direction: where user ``users[p]`` stands among all users in item
+    ``items[p]``'s ranking -- ``(ranks int32 [n], scores float64 [n], candidates int32 [n])`` in input
+    order, 0-based, ``candidates[p]`` = the users the item could be shown to (logit not NaN, the
+    pair not in ``exclude``, which is by USER id as everywhere).  ``rank_users`` of ``topk_users``'
+    r-th user is r.  A pair that ``exclude`` lists is a ``ValueError``."""
+    torch = __import__("torch")
+    ops = Operands(rt, A, LU, B, LI, c, n_factors)
+    sel, tgt_indptr, tgt_users, order = group_pairs(items, users, ops.n_items, ops.n_users, ("items", "users"))
+    excl = _host_exclusions(exclude, ops.n_users, ops.n_items)
+    if excl is not None:
+        p = _first_excluded_pair(users, items, excl, ops.n_items)
+        if p is not None:
+            raise ValueError(f"pair {p} (item {int(np.asarray(items)[p])}, user {int(np.asarray(users)[p])}) "
+                             f"is in the user's exclusion list: it has no rank")
+    n = order.shape[0]
+    ranks, scores, cand = np.empty(n, np.int32), np.empty(n, np.float64), np.empty(n, np.int32)
+    n_sel = int(sel.shape[0])
+    if n_sel == 0:
+        return ranks, scores, cand
+    ws = rt.empty((ranks_workspace_bytes(n_sel, ops.n_users, n),), torch.uint8)
+    g_ranks, g_scores = rt.empty((n,), torch.int32), rt.empty((n,), torch.float64)
+    g_cand = rt.empty((n_sel,), torch.int32)
+    d_sel, d_indptr, d_users = rt.upload(sel), rt.upload(tgt_indptr), rt.upload(tgt_users)
+    d_excl = _exclusions(rt, transposed_exclusions(excl, ops.n_items))
+    by_item(ops, "ranks", d_sel, n_sel, d_excl, d_indptr.data_ptr(), d_users.data_ptr(), n, ws.data_ptr(),
+            g_ranks.data_ptr(), g_scores.data_ptr(), g_cand.data_ptr())
+    rt.sync()
+    ranks[order], scores[order] = g_ranks.cpu().numpy(), g_scores.cpu().numpy()
+    cand[order] = np.repeat(g_cand.cpu().numpy(), np.diff(tgt_indptr))
+    return ranks, scores, cand
+
+
+def rank_audience(rt: Runtime, A, LU, B, LI, c, n_factors: int, depth: int, items=None, exclude=None,
+                  workspace_bytes: Optional[int] = None):
+    """``rank_catalogue`` in the other direction: every selected item's ranking of the users down to
+    ``depth`` (any integer >= 1; ``depth >= n_users``: all of them) -- ``(users int32 [n_sel, depth],
+    scores float64 [n_sel, depth], n_ranked int32 [n_sel])``, short rows padded with user -1 / score
+    NaN.  The first ``min(depth, 64)`` columns are ``topk_users``' bytes.  ``workspace_bytes``: as
+    ``rank_catalogue`` takes it, for a block of items' rows of logits over the users."""
+    torch = __import__("torch")
+    ops = Operands(rt, A, LU, B, LI, c, n_factors)
+    depth = _depth(depth)
+    ids, n_sel = _users(rt, items, ops.n_items, "items")
+    excl = _exclusions(rt, transposed_exclusions(_host_exclusions(exclude, ops.n_users, ops.n_items), ops.n_items))
+    if n_sel == 0:
+        return np.zeros((0, depth), np.int32), np.zeros((0, depth), np.float64), np.zeros(0, np.int32)
+    least, preferred = order_workspace_bytes(n_sel, ops.n_users, depth)
+    if workspace_bytes is None:
+        workspace_bytes = max(least, min(preferred, ORDER_WORKSPACE_BYTES))
+    workspace_bytes = int(workspace_bytes)
+    if workspace_bytes < least:
+        raise ValueError(f"workspace_bytes={workspace_bytes} is less than one block of 64 items ({least} bytes)")
+    ws = rt.empty((workspace_bytes,), torch.uint8)
+    users = rt.empty((n_sel, depth), torch.int32)
+    scores = rt.empty((n_sel, depth), torch.float64)
+    n_ranked = rt.empty((n_sel,), torch.int32)
+    by_item(ops, "order", ids, n_sel, excl, depth, ws.data_ptr(), workspace_bytes, users.data_ptr(),
+            scores.data_ptr(), n_ranked.data_ptr())
+    rt.sync()
+    return users.cpu().numpy(), scores.cpu().numpy(), n_ranked.cpu().numpy()
 
 
 # ---------------------------------------------------------------------------
