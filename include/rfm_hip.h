@@ -1093,6 +1093,7 @@ int32_t rfm_pair_order(rfm_ctx* ctx, const double* d_A, const double* d_LU, int6
 int32_t rfm_pair_geometry(int64_t n_sel_users, int64_t n_items, int32_t n_factors, int64_t* h_out8);
 int32_t rfm_pair_order_geometry(int64_t n_items, int64_t depth, int64_t* h_out4);
 #include "rfm_audience.h"
+#include "rfm_diverse.h"
 
 #ifdef __cplusplus
 }

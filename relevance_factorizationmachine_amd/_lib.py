@@ -17,10 +17,10 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 # RFM_LIB_PATH: load another build of the same ABI (timing experiments under profiles/)
 LIB_PATH = os.environ.get("RFM_LIB_PATH") or os.path.join(PKG_DIR, "librfm_hip.so")
-SOURCES = ["rfm_capi.hip", "rfm_fm.hip", "rfm_fm_plan.hip", "rfm_mf.hip", "rfm_fm_fold.hip", "rfm_fold_group.hip", "rfm_eval.hip", "rfm_csr.hip", "rfm_sample.hip", "rfm_pairs.hip", "rfm_host.cpp", "rfm_comm.cpp"]
+SOURCES = ["rfm_capi.hip", "rfm_fm.hip", "rfm_fm_plan.hip", "rfm_mf.hip", "rfm_fm_fold.hip", "rfm_fold_group.hip", "rfm_eval.hip", "rfm_csr.hip", "rfm_sample.hip", "rfm_pairs.hip", "rfm_diverse.hip", "rfm_host.cpp", "rfm_comm.cpp"]
 # every header under csrc/ (a change of any of them rebuilds every object) + the C ABI
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp"))) + [
-    os.path.join(os.path.dirname(PKG_DIR), "include", h) for h in ("rfm_hip.h", "rfm_neighbours.h", "rfm_audience.h")]
+    os.path.join(os.path.dirname(PKG_DIR), "include", h) for h in ("rfm_hip.h", "rfm_neighbours.h", "rfm_audience.h", "rfm_diverse.h")]
 
 RFM_OK, RFM_ERR_BAD_ARG, RFM_ERR_HIP, RFM_ERR_NO_DEVICE, RFM_ERR_INTERNAL = range(5)
 MF_MAX_MODELS = 1024  # RFM_MF_MAX_MODELS
@@ -274,6 +274,13 @@ AUDIENCE_SIGNATURES = {
     "rfm_pair_order_by_item": SIGNATURES["rfm_pair_order"],
 }
 
+# diversified re-ranking, the part that include/rfm_diverse.h declares.  select: ctx, candidate items and
+# scores, n_lists, depth, ld_c, R, n_items, n_factors, ld_R, penalty, trade_off, k, the four outputs
+DIVERSE_SIGNATURES = {
+    "rfm_diverse_select": [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _i64, _i32, _i64, _vp, _f64, _i32, _vp, _vp, _vp, _vp],
+    "rfm_diverse_geometry": [_vp, _i64, _i32, _i32, _i64, _i32, _vp],
+}
+
 
 def exported_symbols() -> List[str]:
     return list(SIGNATURES)
@@ -305,7 +312,7 @@ def load():
         lib = C.CDLL(path)
     except OSError as exc:
         raise RfmError(f"cannot load {path}: {exc}") from exc
-    for name, argtypes in {**SIGNATURES, **NEIGHBOUR_SIGNATURES, **AUDIENCE_SIGNATURES}.items():
+    for name, argtypes in {**SIGNATURES, **NEIGHBOUR_SIGNATURES, **AUDIENCE_SIGNATURES, **DIVERSE_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError = header/library mismatch
         fn.argtypes = argtypes
         fn.restype = _i32

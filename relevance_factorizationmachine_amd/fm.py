@@ -552,6 +552,20 @@ class FactorizationMachines(PointwiseBaseRecommender):
 
         return rec.rank_catalogue(*rec.operands(self, sides, new_users=new_users), depth, users, exclude)
 
+    def recommend_diverse(self, sides, k: int, depth=None, trade_off=0.5, users=None, exclude=None, metric="cosine",
+                          item_penalty=None, new_users=None):
+        """``k`` (1..64) of each user's ``depth`` best items of ``sides`` (default ``min(n_items, max(64,
+        4 k))``, at most 1 024), chosen greedily by Maximal Marginal Relevance: ``(items int32 [n, k],
+        scores float64 [n, k], values float64 [n, k])`` in the order chosen.  A pick maximises
+        ``trade_off * score - item_penalty[item] - (1 - trade_off) * max similarity to the picks before
+        it``, the similarity the cosine (``metric="dot"``: the dot product) of the item vectors ``b_i``;
+        ``trade_off=1`` without a penalty is ``recommend(k)``.  An item without entries has no
+        direction: its similarity to anything counts as 0.  Short rows pad with item -1 / NaN
+        (recommend.diverse)."""
+        from . import recommend as rec
+
+        return rec.diverse(self, sides, k, depth, trade_off, users, exclude, metric, item_penalty, new_users)
+
     # the item -> users direction (DESIGN.md 8 N23).  new_items: the FoldedColumns of fold_in_items
     # stand in for the item side -- ``items`` and the item axis of ``exclude`` then index the folded
     # rows; new_users as above; the model is not touched.  ``exclude`` is recommend()'s, by user id

@@ -458,6 +458,18 @@ class LogisticMatrixFactorization(PointwiseBaseRecommender):
 
         return rec.rank_catalogue(*rec.operands(self, new_users=new_users), depth, users, exclude)
 
+    def recommend_diverse(self, k: int, depth=None, trade_off=0.5, users=None, exclude=None, metric="cosine",
+                          item_penalty=None, new_users=None):
+        """``k`` (1..64) of each user's ``depth`` best items (default ``min(n_items, max(64, 4 k))``, at
+        most 1 024), chosen greedily by Maximal Marginal Relevance: ``(items int32 [n, k], scores
+        float64 [n, k], values float64 [n, k])`` in the order chosen.  A pick maximises ``trade_off *
+        score - item_penalty[item] - (1 - trade_off) * max similarity to the picks before it``, the
+        similarity the cosine (``metric="dot"``: the dot product) of rows of ``Q``; ``trade_off=1``
+        without a penalty is ``recommend(k)``.  Short rows pad with item -1 / NaN (recommend.diverse)."""
+        from . import recommend as rec
+
+        return rec.diverse(self, None, k, depth, trade_off, users, exclude, metric, item_penalty, new_users)
+
     # the item -> users direction (DESIGN.md 8 N23).  new_items: the FoldedRows of fold_in_items stand
     # in for Q, b_i -- ``items`` and the item axis of ``exclude`` then index the folded rows; new_users
     # as above; the model is not touched.  ``exclude`` is the matrix recommend() takes, by user id

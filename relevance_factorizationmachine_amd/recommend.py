@@ -23,6 +23,8 @@ each other by cosine or dot product, under the same order, with the value itself
 ``topk_users`` / ``rank_users`` / ``rank_audience`` are ``topk`` / ``rank_items`` /
 ``rank_catalogue`` for "this item, which users?": the same pair has the same logit, bit for bit, in
 both directions, ties go to the higher USER index, and ``exclude`` stays the matrix by user id.
+``diverse`` / ``diversify`` re-rank: ``k`` of each user's ``depth`` most relevant items,
+chosen greedily by Maximal Marginal Relevance against the rows of the item table.
 """
 from __future__ import annotations
 
@@ -455,13 +457,24 @@ def rank_catalogue(rt: Runtime, A, LU, B, LI, c, n_factors: int, depth: int, use
     columns are ``topk``'s bytes, and ``rank_items`` of the r-th returned item is r.
     ``workspace_bytes``: device memory for the logits of a block of users (``order_workspace_bytes``;
     default: the preferred size, at most ``ORDER_WORKSPACE_BYTES``); the result does not depend on it."""
+    items, scores, n_ranked = rank_catalogue_device(rt, A, LU, B, LI, c, n_factors, depth, users, exclude,
+                                                    workspace_bytes)
+    rt.sync()
+    return items.cpu().numpy(), scores.cpu().numpy(), n_ranked.cpu().numpy()
+
+
+def rank_catalogue_device(rt: Runtime, A, LU, B, LI, c, n_factors: int, depth: int, users=None, exclude=None,
+                          workspace_bytes: Optional[int] = None):
+    """``rank_catalogue`` left on the device: its checks, its ``rfm_pair_order`` call and its workspace
+    rule, and the three results as device tensors ``(items [n_sel, depth], scores [n_sel, depth],
+    n_ranked [n_sel])`` on the runtime's stream, without a host wait -- what ``diverse`` selects from."""
     torch = __import__("torch")
     ops = Operands(rt, A, LU, B, LI, c, n_factors)
     depth = _depth(depth)
     ids, n_sel = _users(rt, users, ops.n_users)
     excl = _exclusions(rt, _host_exclusions(exclude, ops.n_users, ops.n_items))
     if n_sel == 0:
-        return np.zeros((0, depth), np.int32), np.zeros((0, depth), np.float64), np.zeros(0, np.int32)
+        return rt.empty((0, depth), torch.int32), rt.empty((0, depth), torch.float64), rt.empty((0,), torch.int32)
     least, preferred = order_workspace_bytes(n_sel, ops.n_items, depth)
     if workspace_bytes is None:
         workspace_bytes = max(least, min(preferred, ORDER_WORKSPACE_BYTES))
@@ -474,8 +487,7 @@ def rank_catalogue(rt: Runtime, A, LU, B, LI, c, n_factors: int, depth: int, use
     n_ranked = rt.empty((n_sel,), torch.int32)
     _lib.check(rt.lib.rfm_pair_order(*ops.pair_args(ids, n_sel), *excl_args(excl), depth, ws.data_ptr(),
                                      workspace_bytes, items.data_ptr(), scores.data_ptr(), n_ranked.data_ptr()))
-    rt.sync()
-    return items.cpu().numpy(), scores.cpu().numpy(), n_ranked.cpu().numpy()
+    return items, scores, n_ranked
 
 
 # ---------------------------------------------------------------------------
@@ -733,3 +745,103 @@ def similar(model, side: str, k: int, ids=None, metric="cosine", exclude=None, i
     else:
         R = (model.P, model.Q)[item].dev
     return neighbours(rt, R, kf, *request, queries, side + "s")
+
+
+# ---------------------------------------------------------------------------
+# diversified re-ranking
+# ---------------------------------------------------------------------------
+MAX_DIVERSE_DEPTH = 1024
+
+
+def check_diverse(n_items: int, k, depth=None, trade_off=0.5, metric="cosine", item_penalty=None):
+    """The checks of ``diverse`` that need no device -> ``(k, depth, trade_off, penalty float64
+    [n_items] or None)``.  ``depth`` None: ``min(n_items, max(64, 4 k))``; an explicit depth is clamped
+    to ``n_items`` (``rank_catalogue``'s ``depth >= n_items`` is the full ordering) and must not
+    exceed ``MAX_DIVERSE_DEPTH`` after that."""
+    n_items = int(n_items)
+    if not is_int(k) or not 1 <= k <= MAX_K:
+        raise ValueError(f"k={k!r} outside 1..{MAX_K}")
+    k = int(k)
+    depth = min(n_items, max(64, 4 * k)) if depth is None else min(_depth(depth), n_items)
+    if depth > MAX_DIVERSE_DEPTH:
+        raise ValueError(f"depth={depth}: at most {MAX_DIVERSE_DEPTH} candidates are re-ranked")
+    if k > depth:
+        raise ValueError(f"k={k} picks from depth={depth} candidates")
+    try:
+        lam = float(trade_off)
+    except (TypeError, ValueError):
+        raise ValueError(f"trade_off must be a number in [0, 1], got {trade_off!r}") from None
+    if not 0.0 <= lam <= 1.0:  # (false for a NaN)
+        raise ValueError(f"trade_off={lam} outside [0, 1]")
+    if metric not in METRICS:
+        raise ValueError(f"metric {metric!r} is neither 'cosine' nor 'dot'")
+    penalty = None
+    if item_penalty is not None:
+        penalty = np.ascontiguousarray(item_penalty, dtype=np.float64)
+        if penalty.shape != (n_items,):
+            raise ValueError(f"item_penalty has shape {penalty.shape}, expected {(n_items,)}")
+        if np.isnan(penalty).any():
+            raise ValueError("item_penalty holds a NaN")
+    return k, depth, lam, penalty
+
+
+def diversify(rt: Runtime, cand_items, cand_scores, R, n_factors: int, k: int, trade_off: float, item_penalty=None):
+    """Greedy MMR among each row's candidates, one ``rfm_diverse_select`` launch: device tensors in
+    (``cand_items`` int32 and ``cand_scores`` float64 ``[n_lists, depth]``, the item rows ``R [n_items,
+    k or kpad]``, ``item_penalty`` float64 ``[n_items]`` or None), four host arrays out --
+    ``(items int32, scores float64, values float64, pos int32)``, each ``[n_lists, k]``: the chosen
+    items in the order they were chosen, their scores as given, the MMR value each was chosen at and
+    its position among the candidates; a row that runs out of eligible candidates pads with item -1 /
+    NaN / NaN / pos -1.  The arithmetic is the one include/rfm_diverse.h states."""
+    torch = __import__("torch")
+    R, kf = _table(R, n_factors), int(n_factors)
+    if (cand_items.dim() != 2 or cand_items.shape != cand_scores.shape or cand_items.dtype != torch.int32
+            or cand_scores.dtype != torch.float64 or not cand_items.is_contiguous() or not cand_scores.is_contiguous()):
+        raise ValueError("candidates must be contiguous [n_lists, depth] tensors, items int32 and scores float64")
+    n_lists, depth = (int(v) for v in cand_items.shape)
+    if item_penalty is not None and (item_penalty.dtype != torch.float64 or tuple(item_penalty.shape) != (R.shape[0],)
+                                     or not item_penalty.is_contiguous()):
+        raise ValueError(f"item_penalty must be a float64 tensor of {int(R.shape[0])} items")
+    if n_lists == 0:
+        none = np.zeros((0, int(k)))
+        return none.astype(np.int32), none, none.copy(), none.astype(np.int32)
+    items, pos = rt.empty((n_lists, int(k)), torch.int32), rt.empty((n_lists, int(k)), torch.int32)
+    scores, values = rt.empty((n_lists, int(k)), torch.float64), rt.empty((n_lists, int(k)), torch.float64)
+    _lib.check(rt.lib.rfm_diverse_select(rt.ctx, cand_items.data_ptr(), cand_scores.data_ptr(), n_lists, depth, depth,
+                                         R.data_ptr(), int(R.shape[0]), kf, int(R.shape[1]),
+                                         None if item_penalty is None else item_penalty.data_ptr(), float(trade_off),
+                                         int(k), items.data_ptr(), scores.data_ptr(), values.data_ptr(),
+                                         pos.data_ptr()))
+    rt.sync()
+    return items.cpu().numpy(), scores.cpu().numpy(), values.cpu().numpy(), pos.cpu().numpy()
+
+
+def diverse(model, sides, k, depth=None, trade_off=0.5, users=None, exclude=None, metric="cosine",
+            item_penalty=None, new_users=None):
+    """``recommend_diverse`` of both model classes: ``(items, scores, values)`` of ``diversify`` on each
+    user's ``depth`` most relevant items (the device ranking of ``rank_catalogue``) and the item table
+    -- the rows of ``Q`` (MF) or the item side sums ``b_i`` of ``sides`` (FM), through ``normalised``
+    for ``metric="cosine"``, as they are for ``"dot"``.  ``new_users``: folded users, as in the other
+    forward calls; the candidates change, the item table does not.  Every argument is checked before
+    the first launch.
+
+    ``trade_off=1`` without a penalty leaves nothing to trade against relevance, and the call is ``topk``:
+    ``recommend(k)``'s lists, the values the scores.  The selection itself would agree wherever the
+    scores in play are distinct doubles; it ranks by the PROBABILITY, which saturates to exactly 1.0 /
+    0.0 where the logits still differ (the reason ``topk`` ranks by logit), and equal values go by item
+    id.  At any other ``trade_off`` such saturated candidates do tie in relevance and go by id."""
+    n_users, n_items = catalogue_shape(model, sides)
+    if new_users is not None:
+        n_users = int(folded_queries(model, "user", new_users).shape[0])
+    k, depth, lam, penalty = check_diverse(n_items, k, depth, trade_off, metric, item_penalty)
+    if users is not None:
+        _id_array(users, "users", n_users)
+    _host_exclusions(exclude, n_users, n_items)
+    ops = operands(model, sides, new_users=new_users)
+    rt, kf = ops.rt, ops.n_factors
+    if lam == 1.0 and penalty is None:
+        items, scores = topk(*ops, k, users, exclude)
+        return items, scores, scores.copy()
+    cand_items, cand_scores, _ = rank_catalogue_device(*ops, depth, users, exclude)
+    R = normalised(rt, ops.B, kf)[0] if metric == "cosine" else ops.B  # (B is [n_items, kpad] already)
+    return diversify(rt, cand_items, cand_scores, R, kf, k, lam, None if penalty is None else rt.upload(penalty))[:3]
